@@ -7,6 +7,11 @@ With N GPUs the frame's 8x8-pixel camera tiles are dealt round-robin to the rank
 torch.distributed.run) and one RCCL gather per frame brings every rank's tile-packed rgba+depth to rank 0, which scatters the
 tiles into the image: total work is fixed, so this is strong scaling. Inputs (model, camera) are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times --steps frames and prints the headline. --full adds everything else the benchmark
+measures or checks, each outside the timed region: one frame at a time and into host memory, the roofline, the exact-march
+and sharded-share probes, the CPU baseline with the PSNR against the oracle, the training and frequency.json probes, and
+(N > 1) the gathered frame against a single-GPU render. --dump-outputs DIR writes the frame of the last timed step.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -40,10 +45,25 @@ GATHER_PEAK_LANE_LOADS = 1.92  # per clock and CU (profiles/r2_gather_probe.txt,
 # ngp_set_schedule: refill_min, skip_steps, go_min, max_stall, k_busy, k_drain, block_jumps, share (defaults of csrc/ngp_host.h)
 DEFAULT_SCHEDULE = (64, 4, 32, 1, 1, 4, 1, 1)
 EXACT_MARCH = (64, 4, 32, 1, 1, 4, 0, 1)  # block_jumps = 0: empty space is walked voxel by voxel like the reference -- its exact sample sets
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs stays under 64 MB, file headers included
 
 
 def pkg(sub):
     return importlib.import_module(PKG + "." + sub)
+
+
+def dump_outputs(out_dir, rgba, depth):
+    """What the timed path hands its caller for one frame: rgba.npy (H, W, 4) and depth.npy (H, W), float32. A frame
+    larger than DUMP_MAX_BYTES (1080p is 41.5 MB) is cut to a fixed, seeded sample of pixels: rgba (n, 4), depth (n,)."""
+    rgba = rgba.detach().cpu().numpy().astype(np.float32)
+    depth = depth.detach().cpu().numpy().astype(np.float32)
+    if rgba.nbytes + depth.nbytes > DUMP_MAX_BYTES:
+        n_px = depth.size
+        idx = np.sort(np.random.default_rng(0).choice(n_px, DUMP_MAX_BYTES // 20, replace=False))
+        rgba, depth = rgba.reshape(n_px, 4)[idx], depth.reshape(n_px)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgba.npy"), rgba)
+    np.save(os.path.join(out_dir, "depth.npy"), depth)
 
 
 def cpu_baseline(scene_dict, scene_mod, gpu_ctx=None, native=None):
@@ -138,6 +158,55 @@ def pmc_evidence():
     return out
 
 
+def roofline(per_rank, solo):
+    """The roofline block of --full: rank 0's render_nerf_fused launch priced against the unit ceilings, with the counters
+    of the committed profile passes (pmc_evidence)."""
+    # dominant kernel: render_nerf_fused on rank 0 (one launch per step). Its duration for the roofline is the HIP-event time
+    # of launches issued one at a time (N = 1); with N > 1 the device-clock duration of the timed region's launches stands in.
+    k_ms_timed = float(per_rank[0, :, 5].mean())  # first wave in .. last wave out on the chip's 100 MHz clock, timed region
+    if solo:
+        k_ms, k_rays, k_samples = solo["kernel_ms"], solo["n_rays"], solo["n_samples"]
+    else:
+        k_ms, k_rays, k_samples = k_ms_timed, float(per_rank[0, :, 0].mean()), float(per_rank[0, :, 2].mean())
+    algo_bytes = k_samples * BYTES_PER_SAMPLE + k_rays * BYTES_PER_RAY
+    achieved = algo_bytes / (k_ms * 1e-3) / 1e9
+    ev = pmc_evidence()
+    mfma_tflops = k_samples * FLOP_PER_SAMPLE / (k_ms * 1e-3) / 1e12
+    # which unit binds, by the counters of the committed profile passes of this command (fractions of each unit's ceiling):
+    # "ta" = texture-address / vector-L1 path (lane-loads per clock and CU against the measured all-hit ceiling), "valu" = issue
+    # slots of the vector ALU, "hbm" = HBM-side bytes (FETCH_SIZE x 2 + WRITE_SIZE) against 8 TB/s, "mfma" = matrix pipe
+    util = {}
+    if ev.get("lane_loads_per_clk_per_cu") is not None:
+        util["ta"] = ev["lane_loads_per_clk_per_cu"] / GATHER_PEAK_LANE_LOADS
+    if ev.get("valu_issue_util") is not None:
+        util["valu"] = ev["valu_issue_util"]
+    if ev.get("mfma_pipe_util") is not None:
+        util["mfma"] = ev["mfma_pipe_util"]
+    if ev.get("traffic"):
+        util["hbm"] = ev["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+    bound = max(util, key=util.get) if util else "ta"
+    return {
+        "bound": bound,
+        "unit_utilisation_from_counters": {k: round(v, 3) for k, v in util.items()},
+        "achieved": round(achieved, 2),
+        "peak": round(GATHER_PEAK_GBS, 1),
+        "unit": "GB/s",
+        "frac": round(achieved / GATHER_PEAK_GBS, 5),
+        "traffic": ev.get("traffic"),
+        "kernel": "render_nerf_fused",
+        "kernel_ms": round(k_ms, 4),
+        "kernel_ms_how": ("HIP events around launches issued one at a time (%d frames after the timed region)" % solo["n"]) if solo else "device clock, timed region (launches of consecutive frames overlap)",
+        "kernel_ms_timed_region_device_clock": round(k_ms_timed, 4),
+        "algorithmic_bytes_per_launch": int(algo_bytes),
+        "peak_is": "`achieved` / `peak` / `frac` price the algorithmic gather bytes against the measured L1 gather ceiling for 8-byte lane-loads (tools/micro/gather_probe.hip, profiles/r2_gather_probe.txt): 1.92 lane-loads/clk/CU x 8 B x 256 CUs x 2.4 GHz; `bound` names the unit the counters show closest to ITS ceiling",
+        "hbm_algorithmic_frac": round(achieved / HBM_PEAK_GBS, 5),  # SURVEY 8(d)'s figure: algorithmic bytes against the 8 TB/s HBM peak
+        "hbm_traffic_frac": round(ev["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if ev.get("traffic") else None,
+        "mfma_tflops": round(mfma_tflops, 3),
+        "mfma_frac": round(mfma_tflops / MFMA_PEAK_TFLOPS, 5),
+        "counters": ev,
+    }
+
+
 def frequency_probe(native, scene_mod):
     """SURVEY 8 a-19, reported beside the headline (never part of `value`): the same 1080p camera over the same occupancy with
     the configs/nerf/frequency.json network (Frequency encodings, MLPs 256 x 7 + 256 x 1; 434176 MACs per sample, 42x base.json's).
@@ -203,14 +272,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-training-probe", action="store_true")
-    ap.add_argument("--no-extra-probes", action="store_true", help="skip the exact-march and sharded-share measurements (counter passes: every launch of the run is then a full frame of the default schedule)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other measurement and check (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame as DIR/rgba.npy and DIR/depth.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the PSNR against the oracle")
+    ap.add_argument("--no-training-probe", action="store_true", help="with --full: skip the training and frequency.json probes")
+    ap.add_argument("--no-extra-probes", action="store_true", help="with --full: skip the exact-march and sharded-share measurements")
     ap.add_argument("--width", type=int, default=WIDTH)
     ap.add_argument("--height", type=int, default=HEIGHT)
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("NGP_BENCH_INFLIGHT", "0")),
                     help="frames in flight (streams / buffer sets); 0 = 2 on one or two GPUs, 6 beyond (a rank's share of a frame is short: tools/shard_probe.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -282,20 +355,22 @@ def main():
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        frame = step(i)
     fence()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *frame)  # rank 0 holds the assembled frame
 
     # ---- outside the timed region (N = 1): one frame at a time, for the kernel's own duration and the latency of a single frame
     # (in the timed region two launches overlap in their drain, so a per-launch HIP-event time there includes the wait for CUs),
     # and the host-buffer entry point ngp_render (what pyngp's Testbed.render returns: render + device-to-host copy)
     timed_hist = ctx.render_history(min(args.steps, 256))
     solo = None
-    if world == 1 and args.steps > 0:
+    if args.full and world == 1 and args.steps > 0:
         n_solo = min(args.steps, 16)
         rgba, depth = outs[0]
         for i in range(2):
@@ -335,7 +410,7 @@ def main():
 
     exact_ms = None
     shares = None
-    if world == 1 and args.steps > 0 and not args.no_extra_probes:
+    if args.full and world == 1 and args.steps > 0 and not args.no_extra_probes:
         # the benchmarked schedule leaves empty 4^3 / 16^3 blocks in one step; with block_jumps = 0 the march is the reference's, sample for sample
         ctx.set_schedule(*EXACT_MARCH)
         exact_ms = in_flight_ms(opts, min(args.steps, 16), len(streams), outs)
@@ -351,7 +426,7 @@ def main():
 
     # outside the timed region: the frame the ranks assembled must be the frame one GPU renders alone
     gather_diff = None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         last = args.steps - 1
         img_g, depth_g = gatherers[last % len(streams)].img.view(h, w, 4), gatherers[last % len(streams)].depth.view(h, w)
         solo_rgba = torch.zeros((h, w, 4), dtype=torch.float32, device=dev)
@@ -376,50 +451,6 @@ def main():
         value = n_rays / (dt / args.steps) / 1e6
         samples_per_frame = per_rank[:, :, 2].sum(0).mean()
         hits_per_frame = per_rank[:, :, 1].sum(0).mean()
-        # dominant kernel: render_nerf_fused on rank 0 (one launch per step). Its duration for the roofline is the HIP-event time
-        # of launches issued one at a time (N = 1); with N > 1 the device-clock duration of the timed region's launches stands in.
-        k_ms_timed = float(per_rank[0, :, 5].mean())  # first wave in .. last wave out on the chip's 100 MHz clock, timed region
-        if solo:
-            k_ms, k_rays, k_samples = solo["kernel_ms"], solo["n_rays"], solo["n_samples"]
-        else:
-            k_ms, k_rays, k_samples = k_ms_timed, float(per_rank[0, :, 0].mean()), float(per_rank[0, :, 2].mean())
-        algo_bytes = k_samples * BYTES_PER_SAMPLE + k_rays * BYTES_PER_RAY
-        achieved = algo_bytes / (k_ms * 1e-3) / 1e9
-        ev = pmc_evidence()
-        mfma_tflops = k_samples * FLOP_PER_SAMPLE / (k_ms * 1e-3) / 1e12
-        # which unit binds, by the counters of the committed profile passes of this command (fractions of each unit's ceiling):
-        # "ta" = texture-address / vector-L1 path (lane-loads per clock and CU against the measured all-hit ceiling), "valu" = issue
-        # slots of the vector ALU, "hbm" = HBM-side bytes (FETCH_SIZE x 2 + WRITE_SIZE) against 8 TB/s, "mfma" = matrix pipe
-        util = {}
-        if ev.get("lane_loads_per_clk_per_cu") is not None:
-            util["ta"] = ev["lane_loads_per_clk_per_cu"] / GATHER_PEAK_LANE_LOADS
-        if ev.get("valu_issue_util") is not None:
-            util["valu"] = ev["valu_issue_util"]
-        if ev.get("mfma_pipe_util") is not None:
-            util["mfma"] = ev["mfma_pipe_util"]
-        if ev.get("traffic"):
-            util["hbm"] = ev["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        bound = max(util, key=util.get) if util else "ta"
-        roof = {
-            "bound": bound,
-            "unit_utilisation_from_counters": {k: round(v, 3) for k, v in util.items()},
-            "achieved": round(achieved, 2),
-            "peak": round(GATHER_PEAK_GBS, 1),
-            "unit": "GB/s",
-            "frac": round(achieved / GATHER_PEAK_GBS, 5),
-            "traffic": ev.get("traffic"),
-            "kernel": "render_nerf_fused",
-            "kernel_ms": round(k_ms, 4),
-            "kernel_ms_how": ("HIP events around launches issued one at a time (%d frames after the timed region)" % solo["n"]) if solo else "device clock, timed region (launches of consecutive frames overlap)",
-            "kernel_ms_timed_region_device_clock": round(k_ms_timed, 4),
-            "algorithmic_bytes_per_launch": int(algo_bytes),
-            "peak_is": "`achieved` / `peak` / `frac` price the algorithmic gather bytes against the measured L1 gather ceiling for 8-byte lane-loads (tools/micro/gather_probe.hip, profiles/r2_gather_probe.txt): 1.92 lane-loads/clk/CU x 8 B x 256 CUs x 2.4 GHz; `bound` names the unit the counters show closest to ITS ceiling",
-            "hbm_algorithmic_frac": round(achieved / HBM_PEAK_GBS, 5),  # SURVEY 8(d)'s figure: algorithmic bytes against the 8 TB/s HBM peak
-            "hbm_traffic_frac": round(ev["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if ev.get("traffic") else None,
-            "mfma_tflops": round(mfma_tflops, 3),
-            "mfma_frac": round(mfma_tflops / MFMA_PEAK_TFLOPS, 5),
-            "counters": ev,
-        }
         out = {
             "metric": "Mrays/s @1080p NeRF inference (Lego snapshot); PSNR vs reference",
             "value": round(value, 3),
@@ -443,8 +474,9 @@ def main():
                 "tile_sharding": f"8x8 tiles round-robin over {world} rank(s)" + (", gather of tile-packed rgba+depth to rank 0 per frame (RCCL send/recv)" if world > 1 else ""),
                 "frames_in_flight": len(streams),
             },
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline(per_rank, solo)
         if solo:
             out["single_frame_ms"] = round(solo["frame_s"] * 1e3, 4)          # one frame at a time, image left in HBM
             out["single_frame_mrays"] = round(n_rays / solo["frame_s"] / 1e6, 2)
@@ -459,9 +491,9 @@ def main():
             out["sharded_share_speedup_bound"] = {k: round(ms / v["in_flight_ms"], 2) for k, v in shares.items()}  # this run's ms_per_step over a rank's share: compute side only
         if gather_diff is not None:
             out["gathered_frame_max_abs_diff_vs_single_gpu"] = gather_diff  # rank 0's check of the assembled frame, outside the timed region
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sc, scene_mod, ctx, native)
-        if world == 1 and not args.no_training_probe:
+        if args.full and world == 1 and not args.no_training_probe:
             out["training"] = training_probe(native, scene_mod, ctx)
             out["frequency_json"] = frequency_probe(native, scene_mod)
         print(json.dumps(out), flush=True)

@@ -5,13 +5,14 @@ import ctypes as C
 import gzip
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
 
-REF = "/root/reference"
+FOX = os.path.join(ROOT, "tests", "golden", "fox")
 
 
 def test_library_exports_every_declared_symbol(native):
@@ -92,19 +93,41 @@ def test_transforms_json(tmp_path, native, scene_mod):
     ctx.close()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference mount not present (GPU box)")
-def test_reference_datasets_load(native):
-    """The reference's own data files (SURVEY 8c 'usable inputs'): fox keeps the 50 frames whose images exist."""
+def _png_rgb(w, h, value):
+    import struct
+    import zlib
+
+    def chunk(tag, body):
+        return struct.pack(">I", len(body)) + tag + body + struct.pack(">I", zlib.crc32(tag + body) & 0xFFFFFFFF)
+
+    rows = (b"\0" + bytes([value]) * (3 * w)) * h
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows)) + chunk(b"IEND", b"")
+
+
+def test_reference_datasets_load(tmp_path, native):
+    """The reference's own data files (SURVEY 8c 'usable inputs'): fox (tests/golden/fox/, its photographs downscaled by 2 with the
+    pixel-unit intrinsics scaled to match) keeps the 50 frames whose images exist. A second dataset (perspective lens, aabb_scale 1, an explicit
+    offset; written here, NeRF-synthetic style) then replaces it."""
+    fox = tmp_path / "fox"  # the reference's layout: one transforms.json beside images/ (the committed copy adds the train / test split)
+    os.makedirs(fox)
+    shutil.copy(os.path.join(FOX, "transforms.json"), fox)
+    os.symlink(os.path.join(FOX, "images"), fox / "images")
     ctx = native.Context(-1)
-    ctx.load_training_data(os.path.join(REF, "data/nerf/fox"))
+    ctx.load_training_data(str(fox))
     assert ctx.n_training_views() == 50
     assert ctx.dataset_info()["aabb_scale"] == 4
     v = ctx.training_view(0)
-    assert v["resolution"].tolist() == [1080, 1920] and abs(v["focal_length"][0] - 1375.52) < 1e-2
+    assert v["resolution"].tolist() == [540, 960] and abs(v["focal_length"][0] - 1375.52 / 2) < 1e-2
     assert np.allclose(v["principal_point"], [554.558 / 1080, 965.268 / 1920], atol=1e-6)
     # read_lens (src/nerf_loader.cu:175-240): fox carries OpenCV distortion coefficients
     assert v["lens_mode"] == native.LENS_OPENCV and np.allclose(v["lens_params"][:4], [0.0578421, -0.0805099, -0.000980296, 0.00015575], rtol=1e-6)
-    ctx.load_training_data(os.path.join(REF, "data/test3/images/transforms_train.json"))
+    os.makedirs(tmp_path / "images")
+    frames = []
+    for i in range(150):
+        (tmp_path / "images" / f"r_{i}.png").write_bytes(_png_rgb(8, 6, i))
+        frames.append({"file_path": f"./images/r_{i}", "transform_matrix": np.eye(4).tolist()})
+    (tmp_path / "transforms_train.json").write_text(json.dumps({"camera_angle_x": 0.6911, "aabb_scale": 1, "offset": [0.5, 0.5, 0.0], "frames": frames}))
+    ctx.load_training_data(str(tmp_path / "transforms_train.json"))
     assert ctx.n_training_views() == 150
     assert ctx.training_view(3)["lens_mode"] == native.LENS_PERSPECTIVE
     info = ctx.dataset_info()
