@@ -17,18 +17,47 @@
 
 namespace ngp {
 
+// threads per workgroup of every fused kernel. Waves share rays inside a workgroup (knob 7), so a larger one balances better: for the
+// benchmark's kernel (render_nerf_fused_unit_plain), 768 (one 12-wave workgroup per CU) renders one 1080p frame at a time 2 % faster, but
+// such a workgroup holds its CU until its last wave is done, and overlapped frames / a rank's share lose 2-10 %; 384 or 512 leave SIMDs
+// half empty (wave placement). Measured, 256 stays.
 constexpr int BLOCK = 256;
 
-// UNIT: unit-cube scenes (aabb_scale 1 => one cascade, cone angle 0 => fixed step sqrt(3)/1024; load_nerf_post,
+// The variants of the fused kernel: each one states how it differs from FusedGeneric.
+// probe: fed by the probe ray fans instead of the camera
+// prof: diagnostic build -- section stamps (1) and, in addition, stamps inside the network section (2)
+// unit: unit-cube scenes (aabb_scale 1 => one cascade, cone angle 0 => fixed step sqrt(3)/1024; load_nerf_post,
 // src/testbed_nerf.cu:2729-2736). The instantiation folds away the cascade climb, the mip arithmetic and both
 // exponential-stepping branches; the arithmetic that remains is the same expression for expression.
-// OUTSIDE: the render box may reach beyond the occupancy grid (geometry mode, a hand-set render box)
-// PLAIN: static pinhole camera, no depth of field, no environment map (FrameParams::plain, decided by the host)
-// NORMALS: ERenderMode::Normals -- every sample's colour is the unit vector opposite to the density's input gradient (one backward
+// mips: cascades whose block summaries sit in LDS
+// outside: the render box may reach beyond the occupancy grid (geometry mode, a hand-set render box)
+// rgb_mid: the network heads, as mlp_pass takes them (nerf_device.h; -2: linear.json, whose density head has no hidden layer either)
+// plain: static pinhole camera, no depth of field, no environment map (FrameParams::plain, decided by the host)
+// normals: ERenderMode::Normals -- every sample's colour is the unit vector opposite to the density's input gradient (one backward
 // pass through the density head and the encoding per sample, density_gradient_pass); an instantiation of its own, so that no other
 // kernel carries its registers
-template <bool PROBE, int PROF = 0, bool UNIT = false, int MIPS = (UNIT ? 1 : (int)NERF_CASCADES), bool OUTSIDE = true, int RGB_MID = 1, bool PLAIN = false, bool NORMALS = false, int FB = BLOCK>
+struct FusedGeneric {
+	static constexpr bool probe = false, unit = false, outside = true, plain = false, normals = false;
+	static constexpr int prof = 0, mips = (int)NERF_CASCADES, rgb_mid = 1;
+};
+struct FusedUnit : FusedGeneric { static constexpr bool unit = true; static constexpr int mips = 1; };
+struct FusedUnitPlain : FusedUnit { static constexpr bool plain = true; };
+struct FusedC5 : FusedGeneric { static constexpr bool outside = false; static constexpr int mips = 4; };
+struct FusedC5Plain : FusedC5 { static constexpr bool plain = true; };
+struct FusedMid0 : FusedGeneric { static constexpr int rgb_mid = 0; };
+struct FusedMid2 : FusedGeneric { static constexpr int rgb_mid = 2; };
+struct FusedLinRgb : FusedGeneric { static constexpr int rgb_mid = -1; };
+struct FusedLin : FusedGeneric { static constexpr int rgb_mid = -2; };
+struct FusedNormals : FusedGeneric { static constexpr bool normals = true; };
+struct FusedProf : FusedGeneric { static constexpr int prof = 1; };
+struct FusedUnitPlainProf : FusedUnitPlain { static constexpr int prof = 1; };
+struct FusedUnitPlainProf2 : FusedUnitPlain { static constexpr int prof = 2; };
+struct FusedProbe : FusedGeneric { static constexpr bool probe = true; };
+
+template <class V>
 NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const FrameParams& F, const ProbeParams& P) {
+	constexpr bool PROBE = V::probe, UNIT = V::unit, OUTSIDE = V::outside, PLAIN = V::plain, NORMALS = V::normals;
+	constexpr int PROF = V::prof, MIPS = V::mips, RGB_MID = V::rgb_mid;
 	const uint32_t max_cascade = UNIT ? 0u : M.max_cascade;
 	const float cone_angle = UNIT ? 0.0f : M.cone_angle;
 	const Stepping stepping = make_stepping(cone_angle); // (wave-uniform: the exponential stepping's constants, formed once)
@@ -36,11 +65,11 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	__shared__ LevelInfo s_lv[N_LEVELS];
 	__shared__ uint32_t s_coarse[MIPS * COARSE_WORDS_PER_MIP]; // 4 KB per cascade: empty-space summary of the occupancy grid, cascades 0 .. MIPS - 1 (outer ones: M.coarse)
 	__shared__ uint32_t s_coarse16[(UNIT ? 1 : (int)NERF_CASCADES) * 16];
-	__shared__ uint2 s_sh[FB * 4]; // per ray slot: 16 fp16 SH coefficients of its direction, written once per ray
+	__shared__ uint2 s_sh[BLOCK * 4]; // per ray slot: 16 fp16 SH coefficients of its direction, written once per ray
 	constexpr int SLOTS = 64; // a wave's sample list: 4 network passes of 16
-	__shared__ float4 s_samp[FB / 64 * SLOTS]; // samples that wait for the network, in emission order: warped position, warped dt
-	__shared__ uint2 s_res[FB / 64 * SLOTS];   // .x = the lane that owns the sample; after the pass: the network's 4 fp16 outputs (rgb, density)
-	__shared__ float4 s_nrm[NORMALS ? FB / 64 * SLOTS : 1]; // Normals: d logit / d warped position and the logit
+	__shared__ float4 s_samp[BLOCK / 64 * SLOTS]; // samples that wait for the network, in emission order: warped position, warped dt
+	__shared__ uint2 s_res[BLOCK / 64 * SLOTS];   // .x = the lane that owns the sample; after the pass: the network's 4 fp16 outputs (rgb, density)
+	__shared__ float4 s_nrm[NORMALS ? BLOCK / 64 * SLOTS : 1]; // Normals: d logit / d warped position and the logit
 	// Ray sharing inside a workgroup (knob 7): a wave that has run out of work asks through s_xstate, a busy wave hands it every second
 	// one of its live rays (16 at most at a time) through s_xray (16 words per ray; the SH coefficients go straight into the receiver's s_sh rows), so the last
 	// tiles of a frame -- or a small frame's heavy tiles -- are finished by four waves instead of one.
@@ -52,13 +81,13 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	if (threadIdx.x == 0) {
 		s_xstate = 0u;
 		s_xcount = 0u;
-		s_active = FB / 64;
+		s_active = BLOCK / 64;
 	}
 	unsigned long long t_entry = 0, rt_entry = 0; // diagnostic build: the wave's arrival, before the workgroup stages weights and occupancy summaries
 	if (PROF) { t_entry = stamp(); rt_entry = realtime(); }
-	for (int i = threadIdx.x; i < n_frags_for(RGB_MID) * 64; i += FB) s_w[i] = M.wfrags[i];
+	for (int i = threadIdx.x; i < n_frags_for(RGB_MID) * 64; i += BLOCK) s_w[i] = M.wfrags[i];
 	if (threadIdx.x < N_LEVELS) s_lv[threadIdx.x] = M.levels[threadIdx.x];
-	for (uint32_t i = threadIdx.x; i < (max_cascade + 1 < (uint32_t)MIPS ? max_cascade + 1 : (uint32_t)MIPS) * COARSE_WORDS_PER_MIP; i += FB) s_coarse[i] = M.coarse[i];
+	for (uint32_t i = threadIdx.x; i < (max_cascade + 1 < (uint32_t)MIPS ? max_cascade + 1 : (uint32_t)MIPS) * COARSE_WORDS_PER_MIP; i += BLOCK) s_coarse[i] = M.coarse[i];
 	if (threadIdx.x < (UNIT ? 1 : (int)NERF_CASCADES) * 16) s_coarse16[threadIdx.x] = M.coarse[NERF_CASCADES * COARSE_WORDS_PER_MIP + threadIdx.x];
 	__syncthreads();
 
@@ -653,77 +682,37 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	finish_launch(F, lane, n_alive_init, n_hit, n_samples);
 }
 
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false>(M, C, F, P);
-}
-#ifndef NGP_UNIT_NONPLAIN_WAVES
-#define NGP_UNIT_NONPLAIN_WAVES 3
-#endif
-__global__ __launch_bounds__(BLOCK, NGP_UNIT_NONPLAIN_WAVES) void render_nerf_fused_unit(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, true>(M, C, F, P);
-}
+// the camera kernels: name, waves per SIMD they are built for (= workgroups per CU: a workgroup has one wave on each SIMD), variant
+#define NGP_FUSED_KERNEL(NAME, WAVES, V) \
+	__global__ __launch_bounds__(BLOCK, WAVES) void NAME(const ModelParams M, const CameraParams C, const FrameParams F) { \
+		ProbeParams P{}; \
+		fused_body<V>(M, C, F, P); \
+	}
+NGP_FUSED_KERNEL(render_nerf_fused, 2, FusedGeneric)
+NGP_FUSED_KERNEL(render_nerf_fused_unit, 3, FusedUnit)
 // the same for a static pinhole camera without depth of field or environment map -- the frame a benchmark or a screenshot renders
-// threads per workgroup of the benchmark instantiation. Waves share rays inside a workgroup (knob 7), so a larger one balances better:
-// 768 (one 12-wave workgroup per CU) renders one 1080p frame at a time 2 % faster, but such a workgroup holds its CU until its last
-// wave is done, and overlapped frames / a rank's share lose 2-10 %; 384 or 512 leave SIMDs half empty (wave placement). Measured, 256 stays.
-constexpr int FB_UNIT_PLAIN = BLOCK;
-__global__ __launch_bounds__(FB_UNIT_PLAIN, 3) void render_nerf_fused_unit_plain(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 0, true, 1, true, 1, true, false, FB_UNIT_PLAIN>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 3) void render_nerf_fused_c5_plain(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 0, false, 4, false, 1, true>(M, C, F, P);
-}
+NGP_FUSED_KERNEL(render_nerf_fused_unit_plain, 3, FusedUnitPlain)
+NGP_FUSED_KERNEL(render_nerf_fused_c5_plain, 3, FusedC5Plain)
 // scenes of up to 5 cascades (aabb_scale <= 16: fox, garden) rendered inside their occupancy grid: the block summaries of four cascades in
 // LDS (16 KB instead of 32; the fifth cascade's 4 KB table is read through the vector L1) leave room for a third workgroup per CU
-__global__ __launch_bounds__(BLOCK, 3) void render_nerf_fused_c5(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 0, false, 4, false>(M, C, F, P);
-}
+NGP_FUSED_KERNEL(render_nerf_fused_c5, 3, FusedC5)
 // rgb heads with 1 or 3 hidden layers (configs/nerf/base_1layer.json, base_3layer.json): the general kernel with no / two 64x64 layers
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_mid0(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, false, (int)NERF_CASCADES, true, 0>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_mid2(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, false, (int)NERF_CASCADES, true, 2>(M, C, F, P);
-}
+NGP_FUSED_KERNEL(render_nerf_fused_mid0, 2, FusedMid0)
+NGP_FUSED_KERNEL(render_nerf_fused_mid2, 2, FusedMid2)
 // heads without a hidden layer: configs/nerf/base_0layer.json (the rgb head is one matrix) and linear.json (both are)
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_lin_rgb(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, false, (int)NERF_CASCADES, true, -1>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_lin(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, false, (int)NERF_CASCADES, true, -2>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_normals(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, false, false, (int)NERF_CASCADES, true, 1, false, true>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 2) void render_nerf_fused_prof(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 1>(M, C, F, P);
-}
+NGP_FUSED_KERNEL(render_nerf_fused_lin_rgb, 2, FusedLinRgb)
+NGP_FUSED_KERNEL(render_nerf_fused_lin, 2, FusedLin)
+NGP_FUSED_KERNEL(render_nerf_fused_normals, 2, FusedNormals)
+NGP_FUSED_KERNEL(render_nerf_fused_prof, 2, FusedProf)
 // the stamped twins of the kernel a benchmark frame runs (unit scene, static pinhole camera), at its occupancy: section stamps (1) and,
 // in addition, stamps inside the network section (2: they serialise gather wait and MFMA chain, so that build's totals are an upper bound)
-__global__ __launch_bounds__(BLOCK, 3) void render_nerf_fused_unit_plain_prof(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 1, true, 1, true, 1, true>(M, C, F, P);
-}
-__global__ __launch_bounds__(BLOCK, 3) void render_nerf_fused_unit_plain_prof2(const ModelParams M, const CameraParams C, const FrameParams F) {
-	ProbeParams P{};
-	fused_body<false, 2, true, 1, true, 1, true>(M, C, F, P);
-}
+NGP_FUSED_KERNEL(render_nerf_fused_unit_plain_prof, 3, FusedUnitPlainProf)
+NGP_FUSED_KERNEL(render_nerf_fused_unit_plain_prof2, 3, FusedUnitPlainProf2)
 
 // the same machinery fed by the probe ray fans instead of the camera (Testbed::computeEnvmap*, testbed.h:709-743)
 __global__ __launch_bounds__(BLOCK, 2) void trace_probe_fused(const ModelParams M, const FrameParams F, const ProbeParams P) {
 	CameraParams C{};
-	fused_body<true>(M, C, F, P);
+	fused_body<FusedProbe>(M, C, F, P);
 }
 
 // probe texture: texel = mean of its rays' shaded RGBA, summed in increasing ray index (mode 3: one texture per probe of the grid)
@@ -1135,71 +1124,74 @@ __global__ void accumulate_tonemap_kernel(uint32_t n_pixels, const float4* __res
 // Persistent grids are sized to what is resident at once (workgroups per CU from the occupancy query): a workgroup
 // that only starts when another one has drained would begin its rays late and stretch the frame by a ray lifetime.
 template <typename K>
-static int resident_blocks_per_cu(K kernel, int threads = BLOCK) {
+static int resident_blocks_per_cu(K kernel) {
 	int n = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess || n < 1) n = 1;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, BLOCK, 0) != hipSuccess || n < 1) n = 1;
 	return n;
 }
 // the persistent grid of a frame: what is resident, but no more waves than tiles
-static int grid_blocks(const FrameParams& F, int resident, int threads = BLOCK) {
-	const int waves = threads / 64, needed = (int)((F.n_local_tiles + waves - 1) / waves); // one tile per wave at least
+static int grid_blocks(const FrameParams& F, int resident) {
+	const int waves = BLOCK / 64, needed = (int)((F.n_local_tiles + waves - 1) / waves); // one tile per wave at least
 	return resident > needed ? (needed > 0 ? needed : 1) : resident;
 }
-static FrameParams with_grid(const FrameParams& F, int n_blocks, int threads = BLOCK) {
+static FrameParams with_grid(const FrameParams& F, int n_blocks) {
 	FrameParams G = F;
-	G.n_waves = (uint32_t)n_blocks * (threads / 64);
+	G.n_waves = (uint32_t)n_blocks * (BLOCK / 64);
 	return G;
 }
+// the network heads as mlp_pass<RGB_MID> takes them: rgb_mid, or -2 for a head pair without hidden layers (configs/nerf/linear.json)
+static int head_kind(const ModelParams& M) { return M.rgb_mid < 0 ? (M.density_linear ? -2 : -1) : M.rgb_mid; }
+
+// the kernel launch_render_nerf runs for a frame (RK_WIDE: configs/nerf/frequency.json, wide_kernels.hip)
+enum RenderKernel { RK_GENERIC, RK_UNIT, RK_UNIT_PLAIN, RK_C5, RK_C5_PLAIN, RK_PROF, RK_UNIT_PLAIN_PROF, RK_UNIT_PLAIN_PROF2,
+                    RK_MID0, RK_MID2, RK_LIN_RGB, RK_LIN, RK_NORMALS, RK_COUNT, RK_WIDE = RK_COUNT };
+static RenderKernel select_render_kernel(const ModelParams& M, const CameraParams& C, const FrameParams& F) {
+	if (M.wide.width) return RK_WIDE;
+	if (F.render_mode == 7) return RK_NORMALS; // ERenderMode::Normals: the density head only, whatever the rgb head
+	switch (head_kind(M)) { // the base_0layer / base_1layer / base_3layer / linear heads: one general kernel each
+	case -2: return RK_LIN;
+	case -1: return RK_LIN_RGB;
+	case 0: return RK_MID0;
+	case 2: return RK_MID2;
+	}
+	const bool unit = M.max_cascade == 0 && M.cone_angle <= 1e-5f;
+	const bool c5 = !unit && M.max_cascade < 5 && !F.outside_possible;
+	const bool plain = C.lens_mode == 0 && C.aperture_size == 0.0f && !C.moving && !F.envmap;
+	if (F.prof) return unit && plain ? (F.prof_level >= 2 ? RK_UNIT_PLAIN_PROF2 : RK_UNIT_PLAIN_PROF) : RK_PROF;
+	if (unit) return plain ? RK_UNIT_PLAIN : RK_UNIT;
+	if (c5) return plain ? RK_C5_PLAIN : RK_C5;
+	return RK_GENERIC;
+}
+// per kernel: whether the grid clamps of launch_render_nerf apply to it (the base head's kernels: the ones measured for them)
+static const struct { void (*kernel)(ModelParams, CameraParams, FrameParams); bool clamped; } RENDER_KERNELS[RK_COUNT] = {
+	{render_nerf_fused, true}, {render_nerf_fused_unit, true}, {render_nerf_fused_unit_plain, true}, {render_nerf_fused_c5, true},
+	{render_nerf_fused_c5_plain, true}, {render_nerf_fused_prof, true}, {render_nerf_fused_unit_plain_prof, true},
+	{render_nerf_fused_unit_plain_prof2, true}, {render_nerf_fused_mid0, false}, {render_nerf_fused_mid2, false},
+	{render_nerf_fused_lin_rgb, false}, {render_nerf_fused_lin, false}, {render_nerf_fused_normals, false}};
 void launch_render_nerf_wide(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream);
 void launch_trace_probe_wide(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream) {
-	if (M.wide.width) return launch_render_nerf_wide(M, C, F, n_cus, stream); // configs/nerf/frequency.json: wide_kernels.hip
-	const bool unit = M.max_cascade == 0 && M.cone_angle <= 1e-5f;
-	const bool c5 = !unit && M.max_cascade < 5 && !F.outside_possible;
-	if (F.render_mode == 7) { // ERenderMode::Normals: the density head only, whatever the rgb head
-		static const int per_cu_normals = resident_blocks_per_cu(render_nerf_fused_normals);
-		const int nb = grid_blocks(F, n_cus * per_cu_normals);
-		const FrameParams G = with_grid(F, nb);
-		hipLaunchKernelGGL(render_nerf_fused_normals, dim3(nb), dim3(BLOCK), 0, stream, M, C, G);
-		return;
+	const RenderKernel k = select_render_kernel(M, C, F);
+	if (k == RK_WIDE) return launch_render_nerf_wide(M, C, F, n_cus, stream);
+	static const struct PerCu { int v[RK_COUNT]; } resident = []() {
+		PerCu r;
+		for (int i = 0; i < RK_COUNT; ++i) r.v[i] = resident_blocks_per_cu(RENDER_KERNELS[i].kernel);
+		return r;
+	}();
+	int per_cu = resident.v[k];
+	if (RENDER_KERNELS[k].clamped) {
+		// a rank of a sharded frame leaves a third of every CU to the collective's kernels and to the next frame's launch
+		// (measured on one GPU with two frames in flight: 2 per CU is as fast as 3 from N = 2 on, tools/shard_probe.py)
+		static const int shard_per_cu = []() { const char* e = getenv("NGP_SHARD_BLOCKS_PER_CU"); int v = e ? atoi(e) : 2; return v >= 1 && v <= 8 ? v : 2; }(); // experiments: tools/shard_probe.py
+		if (F.shard_count > 1 && per_cu > shard_per_cu) per_cu = shard_per_cu;
+		// a frame of fewer than ~2 tiles per resident wave (below ~800 x 450) is faster on two workgroups per CU as well, alone (512 x 288: 0.81 -> 0.72 ms,
+		// 800 x 450: 0.89 -> 0.84) and with frames in flight (-1..6 %); from 960 x 540 on the third workgroup pays (profiles/r3_small_frame.txt)
+		if (F.shard_count <= 1 && F.n_local_tiles <= 6144u && per_cu > 2) per_cu = 2;
+		if (const char* e = getenv("NGP_BLOCKS_PER_CU")) { int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; } // experiments only
 	}
-	if (M.rgb_mid != 1) { // the base_0layer / base_1layer / base_3layer / linear heads: one general kernel each
-		static const int per_cu_mid0 = resident_blocks_per_cu(render_nerf_fused_mid0), per_cu_mid2 = resident_blocks_per_cu(render_nerf_fused_mid2),
-		                 per_cu_lin_rgb = resident_blocks_per_cu(render_nerf_fused_lin_rgb), per_cu_lin = resident_blocks_per_cu(render_nerf_fused_lin);
-		const int nb = grid_blocks(F, n_cus * (M.rgb_mid == 0 ? per_cu_mid0 : M.rgb_mid == 2 ? per_cu_mid2 : M.density_linear ? per_cu_lin : per_cu_lin_rgb));
-		const FrameParams G = with_grid(F, nb);
-		if (M.rgb_mid == 0) hipLaunchKernelGGL(render_nerf_fused_mid0, dim3(nb), dim3(BLOCK), 0, stream, M, C, G);
-		else if (M.rgb_mid < 0 && M.density_linear) hipLaunchKernelGGL(render_nerf_fused_lin, dim3(nb), dim3(BLOCK), 0, stream, M, C, G);
-		else if (M.rgb_mid < 0) hipLaunchKernelGGL(render_nerf_fused_lin_rgb, dim3(nb), dim3(BLOCK), 0, stream, M, C, G);
-		else hipLaunchKernelGGL(render_nerf_fused_mid2, dim3(nb), dim3(BLOCK), 0, stream, M, C, G);
-		return;
-	}
-	static const int per_cu_generic = resident_blocks_per_cu(render_nerf_fused), per_cu_unit = resident_blocks_per_cu(render_nerf_fused_unit),
-	                 per_cu_prof = resident_blocks_per_cu(render_nerf_fused_prof), per_cu_c5 = resident_blocks_per_cu(render_nerf_fused_c5),
-	                 per_cu_unit_plain_prof = resident_blocks_per_cu(render_nerf_fused_unit_plain_prof), per_cu_unit_plain_prof2 = resident_blocks_per_cu(render_nerf_fused_unit_plain_prof2),
-	                 per_cu_unit_plain = resident_blocks_per_cu(render_nerf_fused_unit_plain, FB_UNIT_PLAIN), per_cu_c5_plain = resident_blocks_per_cu(render_nerf_fused_c5_plain);
-	const bool plain = C.lens_mode == 0 && C.aperture_size == 0.0f && !C.moving && !F.envmap;
-	int per_cu = F.prof ? (unit && plain ? (F.prof_level >= 2 ? per_cu_unit_plain_prof2 : per_cu_unit_plain_prof) : per_cu_prof) : unit ? (plain ? per_cu_unit_plain : per_cu_unit) : c5 ? (plain ? per_cu_c5_plain : per_cu_c5) : per_cu_generic;
-	// a rank of a sharded frame leaves a third of every CU to the collective's kernels and to the next frame's launch
-	// (measured on one GPU with two frames in flight: 2 per CU is as fast as 3 from N = 2 on, tools/shard_probe.py)
-	static const int shard_per_cu = []() { const char* e = getenv("NGP_SHARD_BLOCKS_PER_CU"); int v = e ? atoi(e) : 2; return v >= 1 && v <= 8 ? v : 2; }(); // experiments: tools/shard_probe.py
-	if (F.shard_count > 1 && per_cu > shard_per_cu) per_cu = shard_per_cu;
-	// a frame of fewer than ~2 tiles per resident wave (below ~800 x 450) is faster on two workgroups per CU as well, alone (512 x 288: 0.81 -> 0.72 ms,
-	// 800 x 450: 0.89 -> 0.84) and with frames in flight (-1..6 %); from 960 x 540 on the third workgroup pays (profiles/r3_small_frame.txt)
-	if (F.shard_count <= 1 && F.n_local_tiles <= 6144u && per_cu > 2) per_cu = 2;
-	if (const char* e = getenv("NGP_BLOCKS_PER_CU")) { int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; } // experiments only
-	const int threads = (!F.prof && unit && plain) ? FB_UNIT_PLAIN : BLOCK;
-	if (F.shard_count > 1 && threads != BLOCK) per_cu = per_cu * threads > 2 * BLOCK ? ((2 * BLOCK) / threads > 0 ? (2 * BLOCK) / threads : 1) : per_cu; // (a rank's share: two thirds of the CU, as above)
-	const int n_blocks = grid_blocks(F, n_cus * per_cu, threads);
-	const FrameParams G = with_grid(F, n_blocks, threads);
-	if (F.prof && unit && plain && F.prof_level >= 2) hipLaunchKernelGGL(render_nerf_fused_unit_plain_prof2, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else if (F.prof && unit && plain) hipLaunchKernelGGL(render_nerf_fused_unit_plain_prof, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else if (F.prof) hipLaunchKernelGGL(render_nerf_fused_prof, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else if (unit && plain) hipLaunchKernelGGL(render_nerf_fused_unit_plain, dim3(n_blocks), dim3(FB_UNIT_PLAIN), 0, stream, M, C, G);
-	else if (unit) hipLaunchKernelGGL(render_nerf_fused_unit, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else if (c5 && plain) hipLaunchKernelGGL(render_nerf_fused_c5_plain, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else if (c5) hipLaunchKernelGGL(render_nerf_fused_c5, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
-	else hipLaunchKernelGGL(render_nerf_fused, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
+	const int n_blocks = grid_blocks(F, n_cus * per_cu);
+	const FrameParams G = with_grid(F, n_blocks);
+	hipLaunchKernelGGL(RENDER_KERNELS[k].kernel, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
 }
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream) {
 	if (M.wide.width) return launch_trace_probe_wide(M, F, P, n_cus, stream);
@@ -1231,12 +1223,15 @@ void launch_grid_encode(const ModelParams& M, uint32_t n, const float* pos01, ui
 	hipLaunchKernelGGL(grid_encode_kernel, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, out);
 }
 void launch_network_inference(const ModelParams& M, uint32_t n, const float* pos01, const float* dir01, uint16_t* out, hipStream_t stream) {
-	uint32_t n_waves = (n + 63) / 64;
-	if (M.rgb_mid < 0 && M.density_linear) hipLaunchKernelGGL(network_inference_kernel<-2>, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
-	else if (M.rgb_mid < 0) hipLaunchKernelGGL(network_inference_kernel<-1>, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
-	else if (M.rgb_mid == 0) hipLaunchKernelGGL(network_inference_kernel<0>, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
-	else if (M.rgb_mid == 2) hipLaunchKernelGGL(network_inference_kernel<2>, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
-	else hipLaunchKernelGGL(network_inference_kernel<1>, dim3((n_waves + 3) / 4), dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
+	const uint32_t n_waves = (n + 63) / 64;
+	const dim3 grid((n_waves + 3) / 4);
+	switch (head_kind(M)) {
+	case -2: hipLaunchKernelGGL(network_inference_kernel<-2>, grid, dim3(BLOCK), 0, stream, M, n, pos01, dir01, out); break;
+	case -1: hipLaunchKernelGGL(network_inference_kernel<-1>, grid, dim3(BLOCK), 0, stream, M, n, pos01, dir01, out); break;
+	case 0: hipLaunchKernelGGL(network_inference_kernel<0>, grid, dim3(BLOCK), 0, stream, M, n, pos01, dir01, out); break;
+	case 2: hipLaunchKernelGGL(network_inference_kernel<2>, grid, dim3(BLOCK), 0, stream, M, n, pos01, dir01, out); break;
+	default: hipLaunchKernelGGL(network_inference_kernel<1>, grid, dim3(BLOCK), 0, stream, M, n, pos01, dir01, out);
+	}
 }
 void launch_build_normals_fragments(uint4* wfrags, hipStream_t stream) {
 	hipLaunchKernelGGL(build_normals_fragments_kernel, dim3(1), dim3(256), 0, stream, (uint16_t*)wfrags);

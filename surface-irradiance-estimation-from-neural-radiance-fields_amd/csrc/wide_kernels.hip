@@ -188,10 +188,7 @@ NGP_DEV uint2 pack4(float a, float b, float c, float d, bool relu) {
 // exchanged). The barriers inside the network wait for LDS traffic only (s_waitcnt lgkmcnt(0) + s_barrier): a __syncthreads()
 // would also drain the outstanding global loads, i.e. the stream.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#ifndef WIDE_RING
-#define WIDE_RING (WIDE_MFMA16 ? 2 : 3) // (a K block of the 16x16x32 form is 32 wide: one block ahead is the same 512 MFMA cycles as two of the 32x32x16 form)
-#endif
-constexpr int RING = WIDE_RING, AHEAD = RING - 1; // stages of the weight ring, K-blocks it runs ahead
+constexpr int RING = 3, AHEAD = RING - 1; // stages of the weight ring, K-blocks it runs ahead
 NGP_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 NGP_DEV half8 as_half8(u32x4 u) { return __builtin_bit_cast(half8, u); }
 
@@ -208,89 +205,6 @@ NGP_DEV void ring_preload(u32x4 (&ar)[RING][MT], LayerFrags L) {
 			if (m < L.mt) ar[st][m] = *(const u32x4*)(L.base + ((size_t)m * L.nkb + st) * 64);
 }
 
-#if WIDE_MFMA16
-// ---- the GEMMs on v_mfma_f32_16x16x32_f16. MT counts 16-neuron tiles of a wave (4 for 256 neurons), NKB 32-wide K blocks.
-// A fragment: lane (r = lane & 15, h = lane >> 4) holds W[16 m + r][32 kb + 8 h ..]; B: lane (c, h) reads X[16 t + c][32 kb + 8 h ..]
-// (one ds_read_b128); D: lane (c, h) holds neurons 16 m + 4 h .. + 3 of sample 16 t + c -- four packed halves, one 8-byte LDS write.
-// A wave owns 16 MT neurons and all eight 16-sample tiles: MT x 8 accumulator tiles of 4 registers (128 for MT = 4, as before). The
-// B operands of half a K block (four sample tiles) are read while the MFMAs of the other half run.
-typedef float floatx4w __attribute__((ext_vector_type(4)));
-NGP_DEV floatx4w mfma16w(half8 a, half8 b, floatx4w c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-template <int MT, int NKB>
-NGP_DEV void wide_hidden_layer(half_t* X, u32x4 (&ar)[RING][MT], const uint4* __restrict__ wf, int wave, int lane, LayerFrags next) {
-	const int c = lane & 15, h = lane >> 4;
-	const floatx4w zero = {0.f, 0.f, 0.f, 0.f};
-	floatx4w acc[MT][8];
-	const half_t* col = X + c * XS + 8 * h;
-	// B operands: two sample tiles at a time, read while the MFMAs of the previous pair run (MT x 2 MFMAs = 128 cycles for MT = 4: a
-	// ds_read_b128's latency); a quarter of a K block in flight instead of a whole one keeps the loop inside 256 registers
-	half8 b[2][2];
-	b[0][0] = *(const half8*)col;
-	b[0][1] = *(const half8*)(col + 16 * XS);
-#pragma unroll
-	for (int kb = 0; kb < NKB; ++kb) {
-		if (kb + AHEAD < NKB) {
-#pragma unroll
-			for (int m = 0; m < MT; ++m) ar[(kb + AHEAD) % RING][m] = *(const u32x4*)(wf + ((size_t)m * NKB + kb + AHEAD) * 64);
-		}
-#pragma unroll
-		for (int q = 0; q < 4; ++q) { // sample tiles 2q, 2q + 1
-			const int nq = (q + 1) & 3, nkb = q == 3 ? kb + 1 : kb;
-			if (nkb < NKB) {
-				b[(q + 1) & 1][0] = *(const half8*)(col + 16 * (2 * nq) * XS + 32 * nkb);
-				b[(q + 1) & 1][1] = *(const half8*)(col + 16 * (2 * nq + 1) * XS + 32 * nkb);
-			}
-			__builtin_amdgcn_sched_barrier(0); // (the scheduler would sink the reads next to their use)
-			const bool last = kb == NKB - 1 && q == 3;
-			if (last) lds_barrier(); // every wave has read the layer's input: the in-place writes may start under the last MFMAs (see the 32x32x16 form)
-#pragma unroll
-			for (int t = 0; t < 2; ++t)
-#pragma unroll
-				for (int m = 0; m < MT; ++m) acc[m][2 * q + t] = mfma16w(as_half8(ar[kb % RING][m]), b[q & 1][t], kb == 0 ? zero : acc[m][2 * q + t]);
-			if (!last) __builtin_amdgcn_sched_barrier(0);
-		}
-	}
-	ring_preload<MT>(ar, next);
-#pragma unroll
-	for (int t = 0; t < 8; ++t) {
-		half_t* row = X + (16 * t + c) * XS + 16 * (wave * MT) + 4 * h;
-#pragma unroll
-		for (int m = 0; m < MT; ++m) *(uint2*)(row + 16 * m) = pack4(acc[m][t][0], acc[m][t][1], acc[m][t][2], acc[m][t][3], true);
-	}
-	lds_barrier();
-}
-
-// An output layer (at most 16 neurons, no activation): wave w computes sample tiles 2w and 2w + 1; fragments in ar[.][0].
-// Returned: acc[t'] = outputs 4h .. 4h + 3 of sample 16 (2 wave + t') + c
-struct OutTiles {
-	floatx4w t[2];
-};
-template <int MT, int NKB>
-NGP_DEV OutTiles wide_out_layer(const half_t* X, u32x4 (&ar)[RING][MT], const uint4* __restrict__ wf, int wave, int lane, LayerFrags next) {
-	const int c = lane & 15, h = lane >> 4;
-	const floatx4w zero = {0.f, 0.f, 0.f, 0.f};
-	OutTiles acc;
-	acc.t[0] = acc.t[1] = zero;
-	const half_t* col = X + (32 * wave + c) * XS + 8 * h;
-	half8 b[2][2];
-	b[0][0] = *(const half8*)col;
-	b[0][1] = *(const half8*)(col + 16 * XS);
-#pragma unroll
-	for (int kb = 0; kb < NKB; ++kb) {
-		if (kb + AHEAD < NKB) ar[(kb + AHEAD) % RING][0] = *(const u32x4*)(wf + (size_t)(kb + AHEAD) * 64);
-		if (kb + 1 < NKB) {
-			b[(kb + 1) & 1][0] = *(const half8*)(col + 32 * (kb + 1));
-			b[(kb + 1) & 1][1] = *(const half8*)(col + 16 * XS + 32 * (kb + 1));
-		}
-		__builtin_amdgcn_sched_barrier(0);
-		acc.t[0] = mfma16w(as_half8(ar[kb % RING][0]), b[kb & 1][0], acc.t[0]);
-		acc.t[1] = mfma16w(as_half8(ar[kb % RING][0]), b[kb & 1][1], acc.t[1]);
-		__builtin_amdgcn_sched_barrier(0);
-	}
-	ring_preload<MT>(ar, next);
-	return acc;
-}
-#else
 // One hidden layer, in place: X[:, 0 .. 128 MT) <- ReLU(W X[:, 0 .. 16 NKB)); ring stages 0..2 hold (or await) K-blocks 0..2.
 // MODE (ERenderMode::Normals, the density network's backward pass on the same GEMM): 0 = forward; 1 = forward, and bit (row, neuron) of `mask`
 // (ROWS x 32 bytes) records which outputs are positive; 2 = a TRANSPOSED layer of the backward pass: no ReLU, outputs whose mask bit is
@@ -390,8 +304,6 @@ NGP_DEV floatx16 wide_out_layer(const half_t* X, u32x4 (&ar)[RING][MT], const ui
 	return acc;
 }
 
-#endif
-
 struct WideOut {
 	half_t r, g, b, sigma;
 	float gx, gy, gz; // ERenderMode::Normals only: d logit / d warped position
@@ -425,7 +337,6 @@ template <int MT>
 NGP_DEV WideOut wide_network(const WideModel& W, WideShared& S, int tid, u32x4 (&ar)[RING][MT], int my_row, unsigned long long* pr = nullptr) {
 	const int wave = tid >> 6, lane = tid & 63;
 	const int n = lane & 31, h = lane >> 5;
-	(void)n; (void)h;
 	const int row_id = tid & (ROWS - 1), part = tid >> 7;
 	const uint32_t n_layers = W.n_hidden_density + W.n_hidden_rgb + 2u;
 	WideOut o;
@@ -434,33 +345,19 @@ NGP_DEV WideOut wide_network(const WideModel& W, WideShared& S, int tid, u32x4 (
 		const bool density_out = l == W.n_hidden_density, rgb_out = l + 1u == n_layers;
 		const LayerFrags cur = layer_frags<MT>(W, l, wave, lane), next = layer_frags<MT>(W, l + 1u, wave, lane);
 		if (!density_out && !rgb_out) {
-#if WIDE_MFMA16
-			if (cur.nkb == K256) wide_hidden_layer<MT, K256>(S.x, ar, cur.base, wave, lane, next);
-			else wide_hidden_layer<MT, K128>(S.x, ar, cur.base, wave, lane, next);
-#else
 			if (cur.nkb == K256) wide_hidden_layer<MT, K256>(S.x, ar, cur.base, wave, lane, next, pr);
 			else wide_hidden_layer<MT, K128>(S.x, ar, cur.base, wave, lane, next, pr);
-#endif
 			continue;
 		}
-#if WIDE_MFMA16
-		const OutTiles acc = cur.nkb == K256 ? wide_out_layer<MT, K256>(S.x, ar, cur.base, wave, lane, next) : wide_out_layer<MT, K128>(S.x, ar, cur.base, wave, lane, next);
-#else
 		unsigned long long ts0 = 0;
 		if (pr) ts0 = stamp();
 		const floatx16 acc = cur.nkb == K256 ? wide_out_layer<MT, K256>(S.x, ar, cur.base, wave, lane, next) : wide_out_layer<MT, K128>(S.x, ar, cur.base, wave, lane, next);
 		if (pr) { asm volatile("" :: "v"(acc[0])); pr[15] += stamp() - ts0; }
-#endif
 		if (density_out) {
 			// the 16 density outputs become columns 0..15 of the rgb network's input (rows of this wave's own tile: no other wave reads them now)
-#if WIDE_MFMA16
-#pragma unroll
-			for (int q = 0; q < 2; ++q) *(uint2*)(S.x + (32 * wave + 16 * q + (lane & 15)) * XS + 4 * (lane >> 4)) = pack4(acc.t[q][0], acc.t[q][1], acc.t[q][2], acc.t[q][3], false);
-#else
 			half_t* orow = S.x + (32 * wave + n) * XS + 4 * h;
 #pragma unroll
 			for (int q = 0; q < 2; ++q) *(uint2*)(orow + 8 * q) = pack4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3], false);
-#endif
 			lds_barrier();
 			// [density out | direction encoding | ones up to the network's input alignment | zeros up to the next layer's K]; two threads per row
 			half_t* row = S.x + row_id * XS;
@@ -478,14 +375,7 @@ NGP_DEV WideOut wide_network(const WideModel& W, WideShared& S, int tid, u32x4 (
 			}
 			lds_barrier();
 		} else {
-#if WIDE_MFMA16
-			if ((lane >> 4) == 0) {
-#pragma unroll
-				for (int q = 0; q < 2; ++q) *(uint2*)row_meta(S, 32 * wave + 16 * q + (lane & 15)) = pack4(acc.t[q][0], acc.t[q][1], acc.t[q][2], 0.f, false);
-			}
-#else
 			if (h == 0) *(uint2*)row_meta(S, 32 * wave + n) = pack4(acc[0], acc[1], acc[2], 0.f, false);
-#endif
 			lds_barrier();
 			if (my_row >= 0) {
 				union { uint2 u; half_t hh[4]; } r;
@@ -497,7 +387,6 @@ NGP_DEV WideOut wide_network(const WideModel& W, WideShared& S, int tid, u32x4 (
 	return o;
 }
 
-#if !WIDE_MFMA16
 template <int MT>
 NGP_DEV LayerFrags layer_frags_t(const WideModel& W, int l, int wave, int lane) {
 	LayerFrags L;
@@ -597,7 +486,6 @@ NGP_DEV WideOut wide_density_gradient(const WideModel& W, WideShared& S, uint8_t
 	}
 	return o;
 }
-#endif
 
 NGP_DEV void encode_direction(const WideModel& W, WideShared& S, int slot, f3 d) {
 	const float dx = (d.x + 1.0f) * 0.5f, dy = (d.y + 1.0f) * 0.5f, dz = (d.z + 1.0f) * 0.5f;
@@ -866,11 +754,7 @@ NGP_DEV void wide_body(const ModelParams& M, const CameraParams& C, const FrameP
 		lds_barrier();
 		if (prof) lap2(13);
 		if (prof) { lap(3); S.prof[5] += 1ull; S.prof[7] += (unsigned long long)(n_ready < ROWS ? n_ready : ROWS); }
-#if WIDE_MFMA16
-		const WideOut o = wide_network<MT>(W, S, tid, ar, my_row, prof ? S.prof : nullptr);
-#else
 		const WideOut o = NORMALS ? wide_density_gradient<MT>(W, S, s_mask, tid, ar, my_row) : wide_network<MT>(W, S, tid, ar, my_row, prof ? S.prof : nullptr);
-#endif
 		if (prof) { lap(2); t2 = t0; }
 
 		// ---- K6: composite_kernel_nerf (:569-726)
@@ -947,7 +831,6 @@ NGP_WIDE_KERNEL void trace_probe_wide128(const ModelParams M, const FrameParams 
 	wide_body<true, 32 / WIDE_TILE_M>(M, C, F, P);
 }
 
-#if !WIDE_MFMA16
 // ERenderMode::Normals: the density network's backward pass per round; 32 KB of masks beside the activations = one workgroup per CU
 NGP_WIDE_KERNEL_1 void render_nerf_wide256_normals(const ModelParams M, const CameraParams C, const FrameParams F) {
 	ProbeParams P{};
@@ -957,7 +840,6 @@ NGP_WIDE_KERNEL_1 void render_nerf_wide128_normals(const ModelParams M, const Ca
 	ProbeParams P{};
 	wide_body<false, 32 / WIDE_TILE_M, true>(M, C, F, P);
 }
-#endif
 
 // NerfNetwork::inference on explicit inputs (ngp_network_inference): 128 samples per workgroup round; GRADIENT: the density logit's input
 // gradient instead (ngp_density_gradient: 3 floats per sample into `out`)
@@ -984,11 +866,7 @@ NGP_DEV void wide_inference_body(const ModelParams& M, uint32_t n, const float* 
 		lds_barrier();
 		encode_positions(W, S, tid);
 		lds_barrier();
-#if WIDE_MFMA16
-		const WideOut o = wide_network<MT>(W, S, tid, ar, (run && part == 0) ? row : -1);
-#else
 		const WideOut o = GRADIENT ? wide_density_gradient<MT>(W, S, s_mask, tid, ar, (run && part == 0) ? row : -1) : wide_network<MT>(W, S, tid, ar, (run && part == 0) ? row : -1);
-#endif
 		if (run && part == 0) {
 			if (GRADIENT) {
 				float* og = (float*)out + 3 * (size_t)i;
@@ -1008,14 +886,12 @@ NGP_WIDE_KERNEL void network_inference_wide256(const ModelParams M, uint32_t n, 
 NGP_WIDE_KERNEL void network_inference_wide128(const ModelParams M, uint32_t n, const float* __restrict__ pos01, const float* __restrict__ dir01, uint16_t* __restrict__ out) {
 	wide_inference_body<32 / WIDE_TILE_M>(M, n, pos01, dir01, out);
 }
-#if !WIDE_MFMA16
 NGP_WIDE_KERNEL_1 void density_gradient_wide256(const ModelParams M, uint32_t n, const float* __restrict__ pos01, float* __restrict__ out) {
 	wide_inference_body<64 / WIDE_TILE_M, true>(M, n, pos01, pos01, (uint16_t*)out);
 }
 NGP_WIDE_KERNEL_1 void density_gradient_wide128(const ModelParams M, uint32_t n, const float* __restrict__ pos01, float* __restrict__ out) {
 	wide_inference_body<32 / WIDE_TILE_M, true>(M, n, pos01, pos01, (uint16_t*)out);
 }
-#endif
 // the position encoding alone (ngp_grid_encode's counterpart for this architecture): n x enc_dims halves
 __global__ void frequency_encode_kernel(const ModelParams M, uint32_t n, const float* __restrict__ pos01, uint16_t* __restrict__ out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1033,6 +909,15 @@ static int wide_blocks_per_cu(K kernel) {
 	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, WBLOCK, 0) != hipSuccess || n < 1) n = 1;
 	return n;
 }
+// A kernel family comes in pairs: [0] for 256 neurons, [1] for 128. A persistent one carries its workgroups per CU.
+static int wide_pick(const ModelParams& M) { return M.wide.width == 256 ? 0 : 1; }
+template <typename K>
+struct WideResident {
+	K kernel;
+	int per_cu;
+};
+template <typename K>
+static WideResident<K> wide_resident(K kernel) { return {kernel, wide_blocks_per_cu(kernel)}; }
 // The round's schedule (FrameParams::tune as this kernel reads it; of ngp_set_schedule's knobs only block_jumps applies here):
 // [1] voxel steps a marching slot may take per round, [2] run the network once this many samples wait (of the 128 a round takes) ...
 // [3] ... or after this many extra march rounds. WIDE_TUNE="steps,go,stall" overrides the defaults (experiments).
@@ -1049,6 +934,7 @@ static void wide_schedule(FrameParams& G) {
 	G.tune[2] = t.v[1];
 	G.tune[3] = t.v[2];
 }
+// the persistent grid of a frame, and the frame's parameters for it
 static int wide_blocks(const FrameParams& F, int n_cus, int per_cu) {
 	if (const char* e = getenv("NGP_BLOCKS_PER_CU")) { int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; } // experiments only
 	int n_blocks = n_cus * per_cu;
@@ -1056,53 +942,40 @@ static int wide_blocks(const FrameParams& F, int n_cus, int per_cu) {
 	if (n_blocks > needed) n_blocks = needed > 0 ? needed : 1;
 	return n_blocks;
 }
-void launch_render_nerf_wide(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream) {
-#if !WIDE_MFMA16
-	if (F.render_mode == 7) { // ERenderMode::Normals
-		static const int per_cu256n = wide_blocks_per_cu(render_nerf_wide256_normals), per_cu128n = wide_blocks_per_cu(render_nerf_wide128_normals);
-		const int nb = wide_blocks(F, n_cus, M.wide.width == 256 ? per_cu256n : per_cu128n);
-		FrameParams G = F;
-		G.n_waves = (uint32_t)nb * (WBLOCK / 64);
-		wide_schedule(G);
-		if (M.wide.width == 256) hipLaunchKernelGGL(render_nerf_wide256_normals, dim3(nb), dim3(WBLOCK), 0, stream, M, C, G);
-		else hipLaunchKernelGGL(render_nerf_wide128_normals, dim3(nb), dim3(WBLOCK), 0, stream, M, C, G);
-		return;
-	}
-#endif
-	static const int per_cu256 = wide_blocks_per_cu(render_nerf_wide256), per_cu128 = wide_blocks_per_cu(render_nerf_wide128);
-	const int n_blocks = wide_blocks(F, n_cus, M.wide.width == 256 ? per_cu256 : per_cu128);
+static FrameParams wide_frame(const FrameParams& F, int n_blocks) {
 	FrameParams G = F;
 	G.n_waves = (uint32_t)n_blocks * (WBLOCK / 64);
 	wide_schedule(G);
-	if (M.wide.width == 256) hipLaunchKernelGGL(render_nerf_wide256, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, C, G);
-	else hipLaunchKernelGGL(render_nerf_wide128, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, C, G);
+	return G;
+}
+void launch_render_nerf_wide(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream) {
+	typedef WideResident<decltype(&render_nerf_wide256)> R;
+	static const R pairs[2][2] = {{wide_resident(render_nerf_wide256), wide_resident(render_nerf_wide128)},
+	                              {wide_resident(render_nerf_wide256_normals), wide_resident(render_nerf_wide128_normals)}}; // [ERenderMode::Normals]
+	const R& k = pairs[F.render_mode == 7][wide_pick(M)];
+	const int n_blocks = wide_blocks(F, n_cus, k.per_cu);
+	hipLaunchKernelGGL(k.kernel, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, C, wide_frame(F, n_blocks));
 }
 void launch_trace_probe_wide(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream) {
-	static const int per_cu256 = wide_blocks_per_cu(trace_probe_wide256), per_cu128 = wide_blocks_per_cu(trace_probe_wide128);
-	const int n_blocks = wide_blocks(F, n_cus, M.wide.width == 256 ? per_cu256 : per_cu128);
-	FrameParams G = F;
-	G.n_waves = (uint32_t)n_blocks * (WBLOCK / 64);
-	wide_schedule(G);
-	if (M.wide.width == 256) hipLaunchKernelGGL(trace_probe_wide256, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, G, P);
-	else hipLaunchKernelGGL(trace_probe_wide128, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, G, P);
+	typedef WideResident<decltype(&trace_probe_wide256)> R;
+	static const R pair[2] = {wide_resident(trace_probe_wide256), wide_resident(trace_probe_wide128)};
+	const R& k = pair[wide_pick(M)];
+	const int n_blocks = wide_blocks(F, n_cus, k.per_cu);
+	hipLaunchKernelGGL(k.kernel, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, wide_frame(F, n_blocks), P);
 }
 void launch_network_inference_wide(const ModelParams& M, uint32_t n, const float* pos01, const float* dir01, uint16_t* out, int n_cus, hipStream_t stream) {
 	if (n == 0) return;
+	static const decltype(&network_inference_wide256) pair[2] = {network_inference_wide256, network_inference_wide128};
 	int n_blocks = (int)((n + ROWS - 1) / ROWS);
 	if (n_blocks > 2 * n_cus) n_blocks = 2 * n_cus;
-	if (M.wide.width == 256) hipLaunchKernelGGL(network_inference_wide256, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, dir01, out);
-	else hipLaunchKernelGGL(network_inference_wide128, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, dir01, out);
+	hipLaunchKernelGGL(pair[wide_pick(M)], dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, dir01, out);
 }
 void launch_density_gradient_wide(const ModelParams& M, uint32_t n, const float* pos01, float* out, int n_cus, hipStream_t stream) {
 	if (n == 0) return;
-#if !WIDE_MFMA16
+	static const decltype(&density_gradient_wide256) pair[2] = {density_gradient_wide256, density_gradient_wide128};
 	int n_blocks = (int)((n + ROWS - 1) / ROWS);
 	if (n_blocks > n_cus) n_blocks = n_cus;
-	if (M.wide.width == 256) hipLaunchKernelGGL(density_gradient_wide256, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, out);
-	else hipLaunchKernelGGL(density_gradient_wide128, dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, out);
-#else
-	fprintf(stderr, "[ngp] the density gradient of the wide architecture is not built in the WIDE_MFMA16 experiment\n");
-#endif
+	hipLaunchKernelGGL(pair[wide_pick(M)], dim3(n_blocks), dim3(WBLOCK), 0, stream, M, n, pos01, out);
 }
 void launch_frequency_encode(const ModelParams& M, uint32_t n, const float* pos01, uint16_t* out, hipStream_t stream) {
 	if (n == 0) return;
