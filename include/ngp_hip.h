@@ -424,6 +424,47 @@ NGP_API int ngp_train_apply(ngp_ctx* ctx);
 /* current training parameters (fp32 master copy) and their Ema (fp16 -> fp32), n_params each, nullable */
 NGP_API int ngp_get_training_params(ngp_ctx* ctx, float* params_out, float* ema_out);
 
+
+/* --- marching cubes: Testbed::compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh (python_api.cu; scripts/run.py
+ * --save_mesh). The reference's marching_cubes.cu is not part of this project's sources: what upstream instant-ngp does is marked
+ * (upstream); the rest is this project's own contract.
+ * Lattice: res3 = (rx, ry, rz), each in [2, 1024], at most 2^30 points. aabb6 = min xyz, max xyz in ngp space (NULL: the render aabb),
+ * finite and max > min on every axis. Point (i, j, k) sits at p = R^T (aabb.min + (aabb.max - aabb.min) * (i, j, k) / (res - 1)), R the
+ * render aabb's to_local (generate_grid_samples_nerf_uniform, upstream), and holds the ACTIVATED density network_to_density(logit,
+ * density_activation) of the density head at warp_position(p, scene aabb); fp32, index i + rx (j + ry k). Grid models (every head the
+ * loader serves) and Frequency / Identity models.
+ * Vertices: a lattice point is inside when density > thresh (strictly); each lattice edge whose ends differ gets exactly one vertex at
+ * t = (thresh - d0) / (d1 - d0) (fp32) along it, placed by the lattice formula at (i, j, k) + t e_axis. Vertex order: the linear index
+ * of the edge's lower end (x fastest), then axis x < y < z; no atomics decide it, the output is bit-identical from run to run.
+ * Triangles: a 256-case table generated by one stated rule (csrc/mc_table.h) whose face decisions depend on the face's corners alone,
+ * so a smooth closed surface gives a watertight mesh; at most 5 per cell. Order: linear cell index (x fastest), then table order.
+ * uint32 indices; the counter-clockwise normal points from the dense side to the empty side.
+ * Normals: -grad sigma / |grad sigma| at the vertex from the density-gradient stage behind NGP_RENDER_NORMALS; (0, 0, 0) where the
+ * gradient is zero or not finite. Upstream derives them from the mesh's 1-ring instead.
+ * Colours: sigmoid of the rgb logits of the full network at the vertex, direction normalize(p - 0.5) (upstream
+ * generate_nerf_network_inputs_from_positions' outward choice), through the ngp_network_inference path of the model.
+ * Files (ngp_save_marching_cubes_mesh): by extension, .obj or .ply (anything else is refused); positions in dataset space
+ * (p - offset) / scale per axis, no axis permutation (save_mesh(..., nerf_scale, nerf_offset), upstream).
+ *   OBJ: "v x y z r g b" (positions %.9g, colours %.3f), "vn nx ny nz", "f a//a b//b c//c" (1-based).
+ *   PLY: ASCII; x y z nx ny nz float, red green blue uchar, "property list uchar int vertex_index". Both keep the winding above
+ *   (upstream's PLY writes the indices reversed).
+ *   A mesh of a caller's lattice has neither: "v x y z" / "f a b c", and x y z alone in the PLY.
+ * Refused with a message: a host-only context ("no HIP device"), no model, a resolution out of range, an empty or non-finite aabb,
+ * a non-finite thresh. */
+/* the lattice alone, host out[rx * ry * rz] (a stage entry for tests) */
+NGP_API int ngp_density_on_grid(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float* out);
+/* marching cubes on a lattice the caller supplies (host density[rx * ry * rz], laid out as above); the mesh is kept in the context and has
+ * no normals or colours */
+NGP_API int ngp_marching_cubes(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float thresh, const float* density, uint32_t* n_verts, uint32_t* n_tris);
+/* the whole pipeline: lattice, marching cubes, normals, colours; the mesh is kept in the context */
+NGP_API int ngp_compute_marching_cubes_mesh(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float thresh, uint32_t* n_verts, uint32_t* n_tris);
+/* the kept mesh, ngp space: V, N, C n_verts x 3 floats, F n_tris x 3; each pointer nullable. N or C of a caller-lattice mesh is refused. */
+NGP_API int ngp_get_marching_cubes_mesh(ngp_ctx* ctx, float* V, float* N, float* C, uint32_t* F);
+NGP_API int ngp_save_marching_cubes_mesh(ngp_ctx* ctx, const char* path);
+/* device time (HIP events) of the last ngp_compute_marching_cubes_mesh, ms: lattice, marching cubes (count, scan, read-back of the two
+ * totals, emit), normals + colours. No counterpart in the reference; tools/mc_rate.py reads it. */
+NGP_API int ngp_get_marching_cubes_timings(ngp_ctx* ctx, float* ms3);
+
 #ifdef __cplusplus
 }
 #endif

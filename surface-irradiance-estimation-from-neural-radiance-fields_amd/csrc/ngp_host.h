@@ -2,6 +2,7 @@
 #pragma once
 
 #include "../../include/ngp_hip.h"
+#include "mc_table.h"
 #include "minijson.h"
 #include "ngp_kernels.h"
 #include "pcg32.h"
@@ -57,6 +58,15 @@ void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t strea
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
 void launch_irradiance_lookup(const IrradianceMap& I, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 void launch_trace_mesh_rays(const MeshSceneParams& S, uint32_t n, float* positions, float* directions, hipStream_t stream);
+
+// marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
+// scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.
+void launch_mc_density(const ModelParams& M, const McLattice& L, float* d_out, float* d_scratch_pos, uint16_t* d_scratch_net, uint32_t chunk, int n_cus, hipStream_t stream);
+uint32_t mc_n_blocks(uint32_t n_points); // blocks of the count / emit kernels = entries of the block-offset array
+void launch_mc_count_scan(const McGrid& G, uint2* d_blocks, unsigned long long* d_totals, hipStream_t stream);
+void launch_mc_emit(const McGrid& G, const McLattice& L, const uint2* d_blocks, uint32_t* d_vofs, uint32_t* d_vmask, float* d_V, uint32_t* d_F, hipStream_t stream);
+void launch_mc_vertex_inputs(const ModelParams& M, uint32_t n, const float* d_V, float* d_pos01, float* d_dir01, hipStream_t stream);
+void launch_mc_vertex_attributes(const ModelParams& M, uint32_t n, const float* d_grad, const uint16_t* d_net, float* d_N, float* d_C, hipStream_t stream);
 
 // kernel launchers, train_kernels.hip
 void launch_train_generate_samples(const ModelParams& M, const TrainStepParams& P, const TrainImage* images, const TrainBatch& B, hipStream_t stream);
@@ -280,6 +290,12 @@ struct ngp_ctx {
 	uint64_t n_multi_frames = 0;
 	bool last_was_multi = false; // the last frame was rendered over all devices (ngp_get_render_stats sums the shares)
 	bool streams_mixed = false; // frames were issued on more than one stream since the last device-wide wait
+
+	// ---- the last marching-cubes mesh (ngp_mc.cpp), ngp space; N / C empty for a mesh of a caller's lattice
+	std::vector<float> mc_V, mc_N, mc_C;
+	std::vector<uint32_t> mc_F;
+	bool mc_valid = false, mc_attrs = false;
+	float mc_ms[3] = {0.f, 0.f, 0.f}; // device time of the last ngp_compute_marching_cubes_mesh: lattice, marching cubes, normals + colours
 
 	// ---- training (ngp_train.cpp)
 	ngp::TrainState* train = nullptr;

@@ -74,7 +74,8 @@ std::string read_text(const std::string& path) {
 void usage() {
 	std::cout << "ngp_hip_main [files...] [--scene PATH] [--snapshot|--load_snapshot PATH] [--width W] [--height H] [--spp N]\n"
 	             "             [--screenshot OUT.png] [--screenshot_transforms T.json --screenshot_dir DIR] [--render_mode Shade|ShadeEnvMap|ShadeGridEnvMap|AO|Positions|Depth]\n"
-	             "             [--exposure E] [--n_steps N] [--save_snapshot OUT.ingp] [--network CONFIG.json] [--no-gui] [--no-train] [--version]\n"
+	             "             [--exposure E] [--n_steps N] [--save_snapshot OUT.ingp] [--network CONFIG.json]\n"
+	             "             [--save_mesh OUT.obj|OUT.ply [--marching_cubes_res N] [--marching_cubes_density_thresh T]] [--no-gui] [--no-train] [--version]\n"
 	             "             [--video_camera_path PATH.json --video_output DIR/%04d.png [--video_n_seconds S] [--video_fps F] [--video_spp N]]\n";
 }
 
@@ -83,6 +84,9 @@ void usage() {
 int main(int argc, char** argv) {
 	try {
 		std::vector<std::string> files;
+		std::string save_mesh;          // scripts/run.py --save_mesh, --marching_cubes_res (256), --marching_cubes_density_thresh (2.5)
+		int mc_res = 256;
+		float mc_thresh = 2.5f;
 		std::string scene, snapshot, screenshot, shot_transforms, shot_dir, render_mode = "Shade", save_snapshot, network, video_path, video_output = "video_%04d.png";
 		int width = 1920, height = 1080, spp = 1, n_steps = -1, video_seconds = 1, video_fps = 60, video_spp = 8;
 		bool no_train = false;
@@ -107,6 +111,9 @@ int main(int argc, char** argv) {
 			else if (a == "--exposure") exposure = (float)std::atof(val().c_str());
 			else if (a == "--n_steps") n_steps = std::atoi(val().c_str()); // scripts/run.py:66
 			else if (a == "--save_snapshot") save_snapshot = val();       // scripts/run.py:37
+			else if (a == "--save_mesh") save_mesh = val();
+			else if (a == "--marching_cubes_res") mc_res = std::atoi(val().c_str());
+			else if (a == "--marching_cubes_density_thresh") mc_thresh = (float)std::atof(val().c_str());
 			else if (a == "--network" || a == "--config" || a == "-n" || a == "-c") network = val(); // src/main.cu:96-101
 			else if (a == "--video_camera_path") video_path = val();   // scripts/run.py:46-54, 304-337 (frames only: no ffmpeg here)
 			else if (a == "--video_output") video_output = val();
@@ -144,6 +151,11 @@ int main(int argc, char** argv) {
 		if (!save_snapshot.empty()) {
 			testbed.save_snapshot(save_snapshot, false);
 			std::cerr << "wrote " << save_snapshot << "\n";
+		}
+		if (!save_mesh.empty()) { // scripts/run.py:210-215
+			std::cerr << "Generating mesh via marching cubes and saving to " << save_mesh << ". Resolution=[" << mc_res << "," << mc_res << "," << mc_res
+			          << "], Density Threshold=" << mc_thresh << "\n";
+			testbed.compute_and_save_marching_cubes_mesh(save_mesh, {(uint32_t)mc_res, (uint32_t)mc_res, (uint32_t)mc_res}, nullptr, mc_thresh);
 		}
 		if (render_mode == "Shade") testbed.m_render_mode = ngp::ERenderMode::Shade;
 		else if (render_mode == "ShadeGridEnvMap") testbed.m_render_mode = ngp::ERenderMode::ShadeGridEnvMap;
@@ -196,7 +208,7 @@ int main(int argc, char** argv) {
 			write_png(screenshot, img, width, height, exposure);
 			std::cerr << "wrote " << screenshot << "\n";
 		} else {
-			if (save_snapshot.empty() && video_path.empty()) std::cerr << "nothing to do: give --screenshot, --screenshot_transforms or --n_steps with --save_snapshot (this build has no window)\n";
+			if (save_snapshot.empty() && video_path.empty() && save_mesh.empty()) std::cerr << "nothing to do: give --screenshot, --screenshot_transforms or --n_steps with --save_snapshot (this build has no window)\n";
 		}
 		return 0;
 	} catch (const std::exception& e) {

@@ -27,6 +27,14 @@ static py::array_t<float> from_colmajor(const std::array<float, 12>& m) {
 	return a;
 }
 
+// a bounding box argument: None, or (min3, max3) as any sequence of 6 floats / 2 x 3 array
+static std::vector<float> aabb6_arg(const py::object& o) {
+	if (o.is_none()) return {};
+	py::array_t<float, py::array::c_style | py::array::forcecast> a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(o);
+	if (!a || a.size() != 6) throw std::runtime_error("aabb: None or (min xyz, max xyz)");
+	return std::vector<float>(a.data(), a.data() + 6);
+}
+
 PYBIND11_MODULE(pyngp, m) {
 	m.doc() = "MI355X-native NeRF renderer and trainer behind the instant-ngp Testbed API";
 	py::enum_<ETestbedMode>(m, "TestbedMode")
@@ -153,7 +161,30 @@ PYBIND11_MODULE(pyngp, m) {
 		.def("load_camera_path", &Testbed::load_camera_path, py::arg("path"), "Load a camera path")
 		.def("set_camera_from_time", &Testbed::set_camera_from_time, py::arg("t"), "place the camera on the loaded path, t in [0, 1]")
 		.def_readwrite("camera_smoothing", &Testbed::m_camera_smoothing)
-		.def("compute_and_save_marching_cubes_mesh", [](Testbed&, py::args, py::kwargs) { throw std::runtime_error("marching cubes is outside the MI355X renderer's scope (SURVEY section 2)"); })
+		.def("compute_marching_cubes_mesh", [](Testbed& t, const std::array<uint32_t, 3>& res, py::object aabb, float thresh) {
+			const std::vector<float> box = aabb6_arg(aabb);
+			Testbed::MarchingCubesMesh m;
+			{
+				py::gil_scoped_release nogil;
+				m = t.compute_marching_cubes_mesh(res, box.empty() ? nullptr : box.data(), thresh);
+			}
+			auto rows = [](const auto& v) {
+				using T = typename std::decay_t<decltype(v)>::value_type;
+				py::array_t<T> a({(py::ssize_t)(v.size() / 3), (py::ssize_t)3});
+				if (!v.empty()) memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+				return a;
+			};
+			py::dict d;
+			d["V"] = rows(m.V); d["N"] = rows(m.N); d["C"] = rows(m.C); d["F"] = rows(m.F);
+			return d;
+		}, py::arg("resolution") = std::array<uint32_t, 3>{256, 256, 256}, py::arg("aabb") = py::none(), py::arg("thresh") = 2.5f,
+		   "Marching cubes of the density: {'V', 'N', 'C', 'F'} in ngp space (aabb: None = the render aabb, or (min, max))")
+		.def("compute_and_save_marching_cubes_mesh", [](Testbed& t, const std::string& filename, const std::array<uint32_t, 3>& res, py::object aabb, float thresh, bool uvs) {
+			const std::vector<float> box = aabb6_arg(aabb);
+			py::gil_scoped_release nogil;
+			t.compute_and_save_marching_cubes_mesh(filename, res, box.empty() ? nullptr : box.data(), thresh, uvs);
+		}, py::arg("filename"), py::arg("resolution") = std::array<uint32_t, 3>{256, 256, 256}, py::arg("aabb") = py::none(), py::arg("thresh") = 2.5f,
+		   py::arg("generate_uvs_for_obj_file") = false, "Marching cubes of the density, saved as .obj or .ply in dataset space")
 		.def("frame", &Testbed::frame, py::call_guard<py::gil_scoped_release>(), "Process a single frame: one training step when shall_train is set (headless, nothing is drawn).")
 		.def("train", &Testbed::train, py::call_guard<py::gil_scoped_release>(), "Perform a single training step with a specified batch size.")
 		.def("reset", &Testbed::reset_network, py::arg("reset_density_grid") = true, "Reset training.")

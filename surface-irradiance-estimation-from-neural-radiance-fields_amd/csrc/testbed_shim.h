@@ -238,6 +238,30 @@ public:
 		m_testbed_mode = ETestbedMode::Geometry;
 	}
 
+	// Testbed::compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh (python_api.cu; scripts/run.py --save_mesh; contract in
+	// include/ngp_hip.h). aabb6: min xyz, max xyz in ngp space, nullptr = the render aabb. V, N, C, F in ngp space.
+	struct MarchingCubesMesh {
+		std::vector<float> V, N, C;
+		std::vector<uint32_t> F;
+	};
+	MarchingCubesMesh compute_marching_cubes_mesh(const std::array<uint32_t, 3>& res = {256, 256, 256}, const float* aabb6 = nullptr, float thresh = 2.5f) {
+		uint32_t nv = 0, nt = 0;
+		check(ngp_compute_marching_cubes_mesh(m_ctx, res.data(), aabb6, thresh, &nv, &nt));
+		MarchingCubesMesh m;
+		m.V.resize((size_t)nv * 3); m.N.resize((size_t)nv * 3); m.C.resize((size_t)nv * 3); m.F.resize((size_t)nt * 3);
+		check(ngp_get_marching_cubes_mesh(m_ctx, m.V.data(), m.N.data(), m.C.data(), m.F.data()));
+		return m;
+	}
+	void compute_and_save_marching_cubes_mesh(const std::string& filename, const std::array<uint32_t, 3>& res = {256, 256, 256}, const float* aabb6 = nullptr, float thresh = 2.5f,
+	                                          bool generate_uvs_for_obj_file = false) {
+		if (generate_uvs_for_obj_file) throw std::runtime_error("generate_uvs_for_obj_file: UV unwrapping is not implemented in this build");
+		auto ends = [&](const char* e) { size_t n = strlen(e); return filename.size() >= n && strcasecmp(filename.c_str() + filename.size() - n, e) == 0; };
+		if (!ends(".obj") && !ends(".ply")) throw std::runtime_error("marching cubes: the mesh file must end in .obj or .ply");
+		uint32_t nv = 0, nt = 0;
+		check(ngp_compute_marching_cubes_mesh(m_ctx, res.data(), aabb6, thresh, &nv, &nt));
+		check(ngp_save_marching_cubes_mesh(m_ctx, filename.c_str()));
+	}
+
 	// ---- camera path (include/neural-graphics-primitives/camera_path.h, src/camera_path.cu:30-160, src/testbed.cu:3724-3740)
 	struct CameraKeyframe {
 		std::array<float, 4> R{0.f, 0.f, 0.f, 1.f}; // quaternion x, y, z, w

@@ -177,6 +177,12 @@ def load_library():
     L.ngp_network_inference.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.ngp_density_gradient.argtypes = [vp, C.c_uint32, vp, vp]
     L.ngp_get_density_bitfield.argtypes = [vp, vp, vp]
+    L.ngp_density_on_grid.argtypes = [vp, vp, vp, vp]
+    L.ngp_marching_cubes.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp]
+    L.ngp_compute_marching_cubes_mesh.argtypes = [vp, vp, vp, C.c_float, vp, vp]
+    L.ngp_get_marching_cubes_mesh.argtypes = [vp, vp, vp, vp, vp]
+    L.ngp_save_marching_cubes_mesh.argtypes = [vp, C.c_char_p]
+    L.ngp_get_marching_cubes_timings.argtypes = [vp, vp]
     L.ngp_init_rays.argtypes = [vp, C.POINTER(Camera), vp]
     L.ngp_load_scene.argtypes = [vp, C.c_char_p]
     L.ngp_add_mesh.argtypes = [vp, vp, C.c_uint32, vp]
@@ -614,6 +620,55 @@ class Context:
         out = np.zeros((pos01.shape[0], 4), np.uint16)
         self._check(self.L.ngp_network_inference(self.h, pos01.shape[0], _p(pos01), _p(dir01), _p(out)))
         return out.view(np.float16)
+
+    # ---- marching cubes (contract: include/ngp_hip.h). res: one int or three; aabb: None (the render aabb) or (min3, max3) in ngp space
+    @staticmethod
+    def _mc_args(res, aabb):
+        r = np.asarray([res] * 3 if np.isscalar(res) else res, np.uint32)
+        if r.shape != (3,):
+            raise ValueError("resolution: one value or three")
+        a = None if aabb is None else np.ascontiguousarray(np.asarray(aabb, np.float32).reshape(6))
+        return r, a
+
+    def density_on_grid(self, res, aabb=None):
+        """the activated density on the lattice: float32 (rz, ry, rx)"""
+        r, a = self._mc_args(res, aabb)
+        out = np.zeros((int(r[2]), int(r[1]), int(r[0])), np.float32)
+        self._check(self.L.ngp_density_on_grid(self.h, _p(r), _p(a) if a is not None else None, _p(out)))
+        return out
+
+    def _mc_mesh(self, nv, nt, attrs):
+        V = np.zeros((nv, 3), np.float32)
+        F = np.zeros((nt, 3), np.uint32)
+        N = np.zeros((nv, 3), np.float32) if attrs else None
+        Cc = np.zeros((nv, 3), np.float32) if attrs else None
+        self._check(self.L.ngp_get_marching_cubes_mesh(self.h, _p(V), _p(N) if attrs else None, _p(Cc) if attrs else None, _p(F)))
+        return {"V": V, "N": N, "C": Cc, "F": F}
+
+    def marching_cubes(self, density, thresh, aabb=None):
+        """marching cubes on a caller's lattice (float32 (rz, ry, rx)): {"V", "F"} in ngp space"""
+        d = np.ascontiguousarray(density, np.float32)
+        r, a = self._mc_args(d.shape[::-1], aabb)
+        nv, nt = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.ngp_marching_cubes(self.h, _p(r), _p(a) if a is not None else None, float(thresh), _p(d), C.addressof(nv), C.addressof(nt)))
+        m = self._mc_mesh(nv.value, nt.value, False)
+        return {"V": m["V"], "F": m["F"]}
+
+    def compute_marching_cubes_mesh(self, res=256, aabb=None, thresh=2.5):
+        """lattice + marching cubes + normals + colours: {"V", "N", "C", "F"} in ngp space"""
+        r, a = self._mc_args(res, aabb)
+        nv, nt = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.ngp_compute_marching_cubes_mesh(self.h, _p(r), _p(a) if a is not None else None, float(thresh), C.addressof(nv), C.addressof(nt)))
+        return self._mc_mesh(nv.value, nt.value, True)
+
+    def save_marching_cubes_mesh(self, path):
+        self._check(self.L.ngp_save_marching_cubes_mesh(self.h, os.fsencode(path)))
+
+    def marching_cubes_timings(self):
+        """device ms of the last compute_marching_cubes_mesh: lattice, marching cubes, normals + colours"""
+        ms = np.zeros(3, np.float32)
+        self._check(self.L.ngp_get_marching_cubes_timings(self.h, _p(ms)))
+        return [float(x) for x in ms]
 
     def density_bitfield(self):
         bf = np.zeros(128 ** 3 // 8 * 8, np.uint8)
