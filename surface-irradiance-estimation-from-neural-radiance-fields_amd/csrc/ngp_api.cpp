@@ -305,24 +305,15 @@ WideShapes wide_shapes(const ngp_model_desc& d) {
 
 void free_model(ngp_ctx* ctx) {
 	ngp::free_training(ctx);
-	if (ctx->d_params) (void)hipFree(ctx->d_params);
-	if (ctx->d_xgrid) (void)hipFree(ctx->d_xgrid);
-	ctx->d_xgrid = nullptr;
-	if (ctx->d_wfrags) (void)hipFree(ctx->d_wfrags);
-	if (ctx->d_bitfield) (void)hipFree(ctx->d_bitfield);
-	if (ctx->d_coarse) (void)hipFree(ctx->d_coarse);
-	ctx->d_coarse = nullptr;
-	if (ctx->d_density_f16) (void)hipFree(ctx->d_density_f16);
-	if (ctx->d_density_f32) (void)hipFree(ctx->d_density_f32);
-	if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-	if (ctx->d_density_tmp) (void)hipFree(ctx->d_density_tmp);
-	ctx->d_density_tmp = nullptr;
-	ctx->d_params = nullptr;
-	ctx->d_wfrags = nullptr;
-	ctx->d_bitfield = nullptr;
-	ctx->d_density_f16 = nullptr;
-	ctx->d_density_f32 = nullptr;
-	ctx->d_partial = nullptr;
+	ctx->d_params.reset();
+	ctx->d_xgrid.reset();
+	ctx->d_wfrags.reset();
+	ctx->d_bitfield.reset();
+	ctx->d_coarse.reset();
+	ctx->d_density_f16.reset();
+	ctx->d_density_f32.reset();
+	ctx->d_density_tmp.reset();
+	ctx->d_partial.reset();
 	ctx->model_loaded = false;
 }
 
@@ -430,18 +421,15 @@ void set_model_impl(ngp_ctx* ctx, const ngp_model_desc& d) {
 			WM.out_row0_offset = (uint32_t)(frags.size() / 8);
 			frags.insert(frags.end(), D, D + d.n_neurons); // (D now points at the output layer: row 0 = the density logit's weights)
 		}
-		NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_wfrags, frags.size() * sizeof(uint16_t)));
-		NGP_HIP_CHECK(hipMemcpy(ctx->d_wfrags, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-		WM.frags = ctx->d_wfrags;
+		ctx->d_wfrags.upload((const uint4*)frags.data(), frags.size() / 8);
+		WM.frags = ctx->d_wfrags.get();
 	} else {
 	// grid table
-	NGP_HIP_CHECK(hipMalloc(&ctx->d_params, ng * sizeof(uint16_t)));
-	NGP_HIP_CHECK(hipMemcpy(ctx->d_params, ctx->params.data() + nd + nr, ng * sizeof(uint16_t), hipMemcpyHostToDevice));
+	ctx->d_params.upload(ctx->params.data() + nd + nr, ng);
 	{
 		std::vector<uint64_t> table;
 		build_xor_layout(M.levels, d.n_levels, ctx->params.data() + nd + nr, table);
-		NGP_HIP_CHECK(hipMalloc(&ctx->d_xgrid, table.size() * sizeof(uint64_t)));
-		NGP_HIP_CHECK(hipMemcpy(ctx->d_xgrid, table.data(), table.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+		ctx->d_xgrid.upload(table.data(), table.size());
 		if (table.size() * sizeof(uint64_t) > 0x7FFFFFFFull || ng * sizeof(uint16_t) > 0x7FFFFFFFull) throw std::runtime_error("hash grid too large for 31-bit buffer-load offsets");
 		M.xgrid_bytes = (uint32_t)(table.size() * sizeof(uint64_t));
 		M.grid_bytes = (uint32_t)(ng * sizeof(uint16_t));
@@ -466,34 +454,32 @@ void set_model_impl(ngp_ctx* ctx, const ngp_model_desc& d) {
 	}
 	M.rgb_mid = rgb_mid;
 	M.density_linear = d.n_hidden_density == 0 ? 1u : 0u;
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_wfrags, frags.size() * sizeof(uint16_t)));
-	NGP_HIP_CHECK(hipMemcpy(ctx->d_wfrags, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-	launch_build_normals_fragments(ctx->d_wfrags, ctx->stream);
+	ctx->d_wfrags.upload((const uint4*)frags.data(), frags.size() / 8);
+	launch_build_normals_fragments(ctx->d_wfrags.get(), ctx->stream);
 	}
 	// occupancy: fp16 grid -> fp32 -> bitfield + mips on the device (K8/K9)
 	const size_t bitfield_bytes = (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES;
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_bitfield, bitfield_bytes));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_density_f32, n_grid_expected * sizeof(float)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_partial, 256 * sizeof(double)));
+	ctx->d_bitfield.reset(bitfield_bytes);
+	ctx->d_density_f32.reset(n_grid_expected);
+	ctx->d_partial.reset(256);
 	if (d.n_density_grid) {
-		NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_density_f16, d.n_density_grid * sizeof(uint16_t)));
-		NGP_HIP_CHECK(hipMemcpy(ctx->d_density_f16, ctx->density_grid.data(), d.n_density_grid * sizeof(uint16_t), hipMemcpyHostToDevice));
+		ctx->d_density_f16.upload(ctx->density_grid.data(), d.n_density_grid);
 	} else {
 		// a snapshot whose grid was never populated renders as empty space (testbed.cu:5348-5351)
-		NGP_HIP_CHECK(hipMemset(ctx->d_density_f32, 0, n_grid_expected * sizeof(float)));
+		NGP_HIP_CHECK(hipMemset(ctx->d_density_f32.get(), 0, n_grid_expected * sizeof(float)));
 	}
-	launch_density_grid_to_bitfield(ctx->d_density_f16, (uint32_t)d.n_density_grid, max_cascade, ctx->d_density_f32, ctx->d_partial, ctx->d_bitfield,
+	launch_density_grid_to_bitfield(ctx->d_density_f16.get(), (uint32_t)d.n_density_grid, max_cascade, ctx->d_density_f32.get(), ctx->d_partial.get(), ctx->d_bitfield.get(),
 	                                &ctx->bitfield_mean, ctx->stream);
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_coarse, ((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16) * sizeof(uint32_t)));
-	launch_coarse_occupancy(ctx->d_bitfield, ctx->d_coarse, ctx->stream);
+	ctx->d_coarse.reset((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16);
+	launch_coarse_occupancy(ctx->d_bitfield.get(), ctx->d_coarse.get(), ctx->stream);
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	NGP_HIP_CHECK(hipGetLastError());
 
-	M.grid = (const uint2*)ctx->d_params;
-	M.xgrid = (const char*)ctx->d_xgrid;
-	M.coarse = ctx->d_coarse;
-	M.wfrags = wide ? nullptr : ctx->d_wfrags;
-	M.bitfield = ctx->d_bitfield;
+	M.grid = (const uint2*)ctx->d_params.get();
+	M.xgrid = (const char*)ctx->d_xgrid.get();
+	M.coarse = ctx->d_coarse.get();
+	M.wfrags = wide ? nullptr : ctx->d_wfrags.get();
+	M.bitfield = ctx->d_bitfield.get();
 	for (int i = 0; i < 3; ++i) {
 		M.aabb_min[i] = d.aabb_min[i];
 		M.aabb_diag[i] = d.aabb_max[i] - d.aabb_min[i];
@@ -603,7 +589,7 @@ void dataset_from_json(const mj::Value& j, Dataset& ds) { // json_binding.h:121-
 	const int64_t n_images = j.at("n_images").integer();
 	if (n_images < 0 || !j.at("xforms").is_array() || (uint64_t)n_images != j.at("xforms").size()) throw std::runtime_error("snapshot dataset: n_images does not match the list of camera transforms");
 	size_t n = (size_t)n_images;
-	ds.views.assign(n, TrainingView{});
+	ds.views = std::vector<TrainingView>(n); // (value-initialised: TrainingView{} each)
 	for (size_t i = 0; i < n; ++i) {
 		TrainingView& v = ds.views[i];
 		v.principal_point[0] = v.principal_point[1] = 0.5f;
@@ -639,7 +625,8 @@ void dataset_from_json(const mj::Value& j, Dataset& ds) { // json_binding.h:121-
 	ds.n_extra_learnable_dims = to_int(j.value("n_extra_learnable_dims", 0.0));
 }
 
-mj::Value dataset_to_json(const Dataset& ds) { // json_binding.h:94-119
+// the dataset as the snapshot describes it: with the model's aabb_scale and, unless the dataset sets one, the model's render box
+mj::Value dataset_to_json(const Dataset& ds, int32_t aabb_scale, const float* render_aabb_min, const float* render_aabb_max) { // json_binding.h:94-119
 	mj::Value j = mj::Value::make_object();
 	j["n_images"] = mj::Value::make_uint(ds.views.size());
 	mj::Value paths = mj::Value::make_array(), metadata = mj::Value::make_array(), xforms = mj::Value::make_array();
@@ -665,8 +652,8 @@ mj::Value dataset_to_json(const Dataset& ds) { // json_binding.h:94-119
 	j["metadata"] = metadata;
 	j["xforms"] = xforms;
 	mj::Value ra = mj::Value::make_object();
-	ra["min"] = write_vec(ds.render_aabb_min, 3);
-	ra["max"] = write_vec(ds.render_aabb_max, 3);
+	ra["min"] = write_vec(render_aabb_min, 3);
+	ra["max"] = write_vec(render_aabb_max, 3);
 	j["render_aabb"] = ra;
 	j["render_aabb_to_local"] = write_mat(ds.render_aabb_to_local, 3, 3);
 	j["up"] = write_vec(ds.up, 3);
@@ -676,7 +663,7 @@ mj::Value dataset_to_json(const Dataset& ds) { // json_binding.h:94-119
 	er.push(mj::Value::make_int(0));
 	j["envmap_resolution"] = er;
 	j["scale"] = mj::Value::make_float(ds.scale);
-	j["aabb_scale"] = mj::Value::make_int(ds.aabb_scale);
+	j["aabb_scale"] = mj::Value::make_int(aabb_scale);
 	j["from_mitsuba"] = mj::Value::make_bool(ds.from_mitsuba);
 	j["is_hdr"] = mj::Value::make_bool(ds.is_hdr);
 	j["wants_importance_sampling"] = mj::Value::make_bool(true);
@@ -839,10 +826,8 @@ void load_snapshot_value(ngp_ctx* ctx, mj::Value root) {
 
 	set_model_impl(ctx, d);
 
-	for (auto& v : ctx->dataset.views) // training images of the dataset being replaced
-		if (v.d_pixels) (void)hipFree(v.d_pixels);
 	if (ctx->train) ctx->train->images_dirty = true;
-	ctx->dataset = ds;
+	ctx->dataset = std::move(ds); // (frees the training images of the dataset being replaced)
 	ctx->has_snapshot_camera = false;
 	{ // src/testbed.cu:5395-5418
 		ngp_session_state& st = ctx->session;
@@ -852,7 +837,7 @@ void load_snapshot_value(ngp_ctx* ctx, mj::Value root) {
 		st.sun_dir[0] = st.sun_dir[1] = st.sun_dir[2] = 0.57735026f;
 		st.up_dir[1] = 1.f;
 		st.camera_scale = 1.5f;
-		memcpy(st.up_dir, ds.up, sizeof(st.up_dir));
+		memcpy(st.up_dir, ctx->dataset.up, sizeof(st.up_dir));
 		if (snap.contains("background_color")) read_vec(snap.at("background_color"), st.background_color, 4);
 		st.exposure = (float)snap.value("exposure", 0.0);
 		if (snap.contains("sun_dir")) read_vec(snap.at("sun_dir"), st.sun_dir, 3);
@@ -1085,10 +1070,8 @@ void load_training_data_impl(ngp_ctx* ctx, const std::string& path) {
 			ds.views.push_back(std::move(v));
 		}
 	}
-	for (auto& v : ctx->dataset.views) // training images of the dataset being replaced
-		if (v.d_pixels) (void)hipFree(v.d_pixels);
 	if (ctx->train) ctx->train->images_dirty = true;
-	ctx->dataset = std::move(ds);
+	ctx->dataset = std::move(ds); // (frees the training images of the dataset being replaced)
 	ctx->data_path = path;
 }
 
@@ -1119,26 +1102,21 @@ void schedule_from_env(ngp_ctx* ctx) {
 
 void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	if (!ctx->d_sync) {
-		NGP_HIP_CHECK(hipMalloc(&ctx->d_sync, ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY));
-		NGP_HIP_CHECK(hipMemset(ctx->d_sync, 0, ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY));
+		ctx->d_sync.reset(ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY);
+		NGP_HIP_CHECK(hipMemset(ctx->d_sync.get(), 0, ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY));
 		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-			NGP_HIP_CHECK(hipEventCreate(&ctx->ev_frame0[i]));
-			NGP_HIP_CHECK(hipEventCreate(&ctx->ev_frame1[i]));
-			NGP_HIP_CHECK(hipEventCreate(&ctx->ev_kern0[i]));
-			NGP_HIP_CHECK(hipEventCreate(&ctx->ev_kern1[i]));
+			ctx->ev_frame0[i] = new_event();
+			ctx->ev_frame1[i] = new_event();
+			ctx->ev_kern0[i] = new_event();
+			ctx->ev_kern1[i] = new_event();
 		}
 	}
-	if (n_pixels <= ctx->n_pixels_alloc) return;
-	if (ctx->d_frame) (void)hipFree(ctx->d_frame);
-	if (ctx->d_depth) (void)hipFree(ctx->d_depth);
-	if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-	if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
-	ctx->n_pixels_alloc = 0;
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_frame, n_pixels * sizeof(float4)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_depth, n_pixels * sizeof(float)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_accum, n_pixels * sizeof(float4)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_rgba, n_pixels * sizeof(float4)));
-	ctx->n_pixels_alloc = n_pixels;
+	if (n_pixels <= ctx->d_rgba.size()) return;
+	ctx->d_frame.reset(), ctx->d_depth.reset(), ctx->d_accum.reset(), ctx->d_rgba.reset(); // all four go before the new ones come
+	ctx->d_frame.reset(n_pixels);
+	ctx->d_depth.reset(n_pixels);
+	ctx->d_accum.reset(n_pixels);
+	ctx->d_rgba.reset(n_pixels);
 }
 
 CameraParams make_camera_params(const ngp_camera& cam, uint32_t spp_index) {
@@ -1170,7 +1148,7 @@ CameraParams make_camera_params(const ngp_camera& cam, uint32_t spp_index) {
 
 // Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
 void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba_out, float* d_depth_out, hipStream_t stream) {
-	if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); rendering needs an MI355X -- there is no CPU fallback");
+	require_device(ctx, "rendering needs an MI355X");
 	if (!ctx->model_loaded && !(opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty())) throw std::runtime_error("No network available."); // testbed.cu:4735-4738
 	ngp::sync_inference_model(ctx);
 	if (cam.width <= 0 || cam.height <= 0 || cam.width > 65536 || cam.height > 65536) throw std::runtime_error("invalid render resolution"); // (tile counts stay inside 32 bits)
@@ -1189,8 +1167,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	const int spp = opts.spp > 0 ? opts.spp : 1;
 
 	FrameParams F{};
-	F.frame_buffer = ctx->d_frame;
-	F.depth_buffer = d_depth_out ? d_depth_out : ctx->d_depth;
+	F.frame_buffer = ctx->d_frame.get();
+	F.depth_buffer = d_depth_out ? d_depth_out : ctx->d_depth.get();
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
 	// in an unsynchronised loop of short frames, may still be running: two live launches on one slot would deal tiles twice and zero
@@ -1211,17 +1189,17 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	F.prof = nullptr;
 	memcpy(F.tune, ctx->tune, sizeof(F.tune));
 	if (getenv("NGP_PROFILE_SECTIONS")) { // diagnostic: per-section cycle sums of the fused kernel, printed by ngp_get_render_stats
-		if (!ctx->d_prof) NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_prof, 1024));
-		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_prof, 0, 1024, stream));
-		F.prof = ctx->d_prof;
+		if (!ctx->d_prof) ctx->d_prof.reset(128);
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_prof.get(), 0, 1024, stream));
+		F.prof = ctx->d_prof.get();
 		F.prof_level = atoi(getenv("NGP_PROFILE_SECTIONS"));
 		if (const char* e = getenv("NGP_PROFILE_TRACE")) { // timelines of every stride-th working wave (tools/wave_trace.py)
 			const int stride = atoi(e);
 			if (stride > 0) {
 				const size_t words = 16 + (size_t)ngp_ctx::TRACE_WAVES * 16 + (size_t)ngp_ctx::TRACE_WAVES * ngp_ctx::TRACE_ITERS * 16;
-				if (!ctx->d_trace) NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_trace, words * sizeof(uint32_t)));
-				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_trace, 0, words * sizeof(uint32_t), stream));
-				F.trace = ctx->d_trace;
+				if (!ctx->d_trace) ctx->d_trace.reset(words);
+				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_trace.get(), 0, words * sizeof(uint32_t), stream));
+				F.trace = ctx->d_trace.get();
 				F.trace_stride = (uint32_t)stride;
 				F.trace_cap_waves = ngp_ctx::TRACE_WAVES;
 				F.trace_cap_iters = ngp_ctx::TRACE_ITERS;
@@ -1253,7 +1231,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	F.exposure_scale = powf(2.0f, opts.exposure);
 	if (ctx->d_bg_envmap) {
 		if (geometry) throw std::runtime_error("an environment map applies to NeRF mode (in the reference the Geometry-mode NeRF pass would paint it over the meshes, src/testbed_geometry_training.cu:1993-1995): clear it with ngp_set_envmap(ctx, 0, 0, NULL)");
-		F.envmap = ctx->d_bg_envmap;
+		F.envmap = ctx->d_bg_envmap.get();
 		F.env_w = ctx->bg_env_w;
 		F.env_h = ctx->bg_env_h;
 	}
@@ -1283,7 +1261,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	for (int s = 0; s < spp && !F.direct; ++s) {
 		CameraParams C = make_camera_params(cam, cam.spp_index + (uint32_t)s);
 		// CudaRenderBufferView::clear (src/render_buffer.cu:603-607)
-		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_frame, 0, n_pixels * sizeof(float4), stream));
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_frame.get(), 0, n_pixels * sizeof(float4), stream));
 		NGP_HIP_CHECK(hipMemsetAsync(F.depth_buffer, 0, n_pixels * sizeof(float), stream));
 		F.add_results = s > 0 ? 1 : 0; // the call's counters are the sums over its samples per pixel
 		const bool last = s == spp - 1;
@@ -1296,13 +1274,13 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 				if (!ctx->d_irradiance || ctx->env_probe.mode != 3) throw std::runtime_error("render_mode ShadeGridEnvMap needs ngp_compute_envmap_grid first");
 				I = ngp::irradiance_map_of(ctx);
 			}
-			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, C, ctx->d_frame, F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
 		if (ctx->model_loaded) launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
 		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
-		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame, ctx->d_accum, (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
+		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame.get(), ctx->d_accum.get(), (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
 	}
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
 	NGP_HIP_CHECK(hipGetLastError());
@@ -1326,7 +1304,7 @@ void update_density_grid_device(ngp_ctx* ctx, float decay, uint32_t n_uniform, u
 	hipStream_t stream = ctx->stream;
 	ensure_frame_buffers(ctx, 0);
 	order_after_frames(ctx, stream); // frames in flight on ANY stream read the bitfield and its summaries: the refresh waits for them on the device
-	if (!ctx->d_density_tmp) NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_density_tmp, (size_t)n_elements * sizeof(float)));
+	if (!ctx->d_density_tmp) ctx->d_density_tmp.reset(n_elements);
 	Pcg32 rng;
 	rng.state = ctx->grid_rng_state;
 	rng.inc = ctx->grid_rng_inc;
@@ -1336,38 +1314,32 @@ void update_density_grid_device(ngp_ctx* ctx, float decay, uint32_t n_uniform, u
 			if (ctx->grid_updates < 256) nu = NERF_GRID_N_CELLS * n_cascades;
 			else nu = nn = NERF_GRID_N_CELLS / 4 * n_cascades;
 		}
-		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_density_tmp, 0, (size_t)n_elements * sizeof(float), stream));
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_density_tmp.get(), 0, (size_t)n_elements * sizeof(float), stream));
 		if (ctx->M.wide.width) { // a network without a hash grid: positions -> NerfNetwork::inference (wide_kernels.hip) -> splat
 			const size_t n_max = std::max(nu, nn);
-			if (n_max > ctx->grid_scratch_samples) {
-				if (ctx->d_grid_scratch) (void)hipFree(ctx->d_grid_scratch);
-				ctx->d_grid_scratch = nullptr;
-				ctx->grid_scratch_samples = 0;
-				NGP_HIP_CHECK(hipMalloc(&ctx->d_grid_scratch, n_max * 24));
-				ctx->grid_scratch_samples = n_max;
-			}
-			float* d_pos = (float*)ctx->d_grid_scratch;
-			uint32_t* d_cell = (uint32_t*)((char*)ctx->d_grid_scratch + n_max * 12);
-			uint16_t* d_out = (uint16_t*)((char*)ctx->d_grid_scratch + n_max * 16);
-			launch_density_grid_update_wide(ctx->M, nu, rng, ctx->grid_ema_step, n_cascades, -0.01f, ctx->d_density_f32, ctx->d_density_tmp, d_pos, d_cell, d_out, ctx->n_cus, stream);
+			if (n_max * 24 > ctx->d_grid_scratch.size()) ctx->d_grid_scratch.reset(n_max * 24);
+			float* d_pos = (float*)ctx->d_grid_scratch.get();
+			uint32_t* d_cell = (uint32_t*)(ctx->d_grid_scratch.get() + n_max * 12);
+			uint16_t* d_out = (uint16_t*)(ctx->d_grid_scratch.get() + n_max * 16);
+			launch_density_grid_update_wide(ctx->M, nu, rng, ctx->grid_ema_step, n_cascades, -0.01f, ctx->d_density_f32.get(), ctx->d_density_tmp.get(), d_pos, d_cell, d_out, ctx->n_cus, stream);
 			rng.advance();
-			launch_density_grid_update_wide(ctx->M, nn, rng, ctx->grid_ema_step, n_cascades, 0.01f, ctx->d_density_f32, ctx->d_density_tmp, d_pos, d_cell, d_out, ctx->n_cus, stream);
+			launch_density_grid_update_wide(ctx->M, nn, rng, ctx->grid_ema_step, n_cascades, 0.01f, ctx->d_density_f32.get(), ctx->d_density_tmp.get(), d_pos, d_cell, d_out, ctx->n_cus, stream);
 			rng.advance();
 		} else {
-			launch_density_grid_update(ctx->M, nu, rng, ctx->grid_ema_step, n_cascades, -0.01f, ctx->d_density_f32, ctx->d_density_tmp, stream);
+			launch_density_grid_update(ctx->M, nu, rng, ctx->grid_ema_step, n_cascades, -0.01f, ctx->d_density_f32.get(), ctx->d_density_tmp.get(), stream);
 			rng.advance();
-			launch_density_grid_update(ctx->M, nn, rng, ctx->grid_ema_step, n_cascades, 0.01f /* NERF_MIN_OPTICAL_THICKNESS */, ctx->d_density_f32, ctx->d_density_tmp, stream);
+			launch_density_grid_update(ctx->M, nn, rng, ctx->grid_ema_step, n_cascades, 0.01f /* NERF_MIN_OPTICAL_THICKNESS */, ctx->d_density_f32.get(), ctx->d_density_tmp.get(), stream);
 			rng.advance();
 		}
-		launch_density_grid_ema(n_elements, decay, ctx->d_density_f32, ctx->d_density_tmp, stream);
+		launch_density_grid_ema(n_elements, decay, ctx->d_density_f32.get(), ctx->d_density_tmp.get(), stream);
 		++ctx->grid_ema_step;
 		++ctx->grid_updates;
 	}
 	ctx->grid_rng_state = rng.state;
 	ctx->grid_rng_inc = rng.inc;
 	// update_density_grid_mean_and_bitfield (:2863-2880) + the block summaries the march reads
-	launch_density_grid_to_bitfield(nullptr, 0, ctx->max_cascade, ctx->d_density_f32, ctx->d_partial, ctx->d_bitfield, &ctx->bitfield_mean, stream);
-	launch_coarse_occupancy(ctx->d_bitfield, ctx->d_coarse, stream);
+	launch_density_grid_to_bitfield(nullptr, 0, ctx->max_cascade, ctx->d_density_f32.get(), ctx->d_partial.get(), ctx->d_bitfield.get(), &ctx->bitfield_mean, stream);
+	launch_coarse_occupancy(ctx->d_bitfield.get(), ctx->d_coarse.get(), stream);
 	mark_model_updated(ctx, stream);
 	ctx->density_grid_host_dirty = true;
 	++ctx->grid_generation;
@@ -1377,7 +1349,7 @@ void refresh_density_grid_host(ngp_ctx* ctx) {
 	if (!ctx->density_grid_host_dirty || ctx->device < 0 || !ctx->model_loaded) return;
 	const uint32_t n_elements = NERF_GRID_N_CELLS * (ctx->max_cascade + 1);
 	std::vector<float> grid(n_elements);
-	NGP_HIP_CHECK(hipMemcpyAsync(grid.data(), ctx->d_density_f32, (size_t)n_elements * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	NGP_HIP_CHECK(hipMemcpyAsync(grid.data(), ctx->d_density_f32.get(), (size_t)n_elements * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	NGP_HIP_CHECK(hipGetLastError());
 	ctx->density_grid.resize(n_elements);
@@ -1408,61 +1380,34 @@ ngp_ctx* ngp_create(int device) {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return nullptr;
 	if (hipSetDevice(device) != hipSuccess) return nullptr;
-	ngp_ctx* ctx = new ngp_ctx();
+	std::unique_ptr<ngp_ctx> ctx(new ngp_ctx());
 	ctx->device = device;
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->n_cus = prop.multiProcessorCount;
-	if (hipStreamCreate(&ctx->stream) != hipSuccess) {
-		delete ctx;
+	try {
+		ctx->stream = new_stream();
+	} catch (const std::exception&) {
 		return nullptr;
 	}
 	try {
-		schedule_from_env(ctx);
+		schedule_from_env(ctx.get());
 	} catch (const std::exception& e) {
 		fprintf(stderr, "ngp_create: %s\n", e.what());
-		(void)hipStreamDestroy(ctx->stream);
-		delete ctx;
 		return nullptr;
 	}
-	return ctx;
+	return ctx.release();
 }
 
+// peers first; then every owner of the context releases its resources on the owning device, after the last frame
 void ngp_destroy(ngp_ctx* ctx) {
 	if (!ctx) return;
 	for (ngp_ctx* p : ctx->peers) ngp_destroy(p);
 	ctx->peers.clear();
-	if (ctx->device >= 0) ngp::free_multi_buffers(ctx);
-	if (ctx->device < 0) { delete ctx->train; delete ctx; return; }
-	(void)hipSetDevice(ctx->device);
-	if (ctx->last_stream) (void)hipStreamSynchronize(ctx->last_stream);
-	free_model(ctx);
-	delete ctx->train;
-	for (auto& v : ctx->dataset.views)
-		if (v.d_pixels) (void)hipFree(v.d_pixels);
-	for (auto& m : ctx->meshes) {
-		if (m.d_tris) (void)hipFree(m.d_tris);
-		if (m.d_nodes) (void)hipFree(m.d_nodes);
+	if (ctx->device >= 0) {
+		(void)hipSetDevice(ctx->device);
+		if (ctx->last_stream) (void)hipStreamSynchronize(ctx->last_stream);
+		free_model(ctx);
 	}
-	if (ctx->d_meshrefs) (void)hipFree(ctx->d_meshrefs);
-	if (ctx->d_envmap) (void)hipFree(ctx->d_envmap);
-	if (ctx->d_irradiance) (void)hipFree(ctx->d_irradiance);
-	if (ctx->d_bg_envmap) (void)hipFree(ctx->d_bg_envmap);
-	if (ctx->d_frame) (void)hipFree(ctx->d_frame);
-	if (ctx->d_depth) (void)hipFree(ctx->d_depth);
-	if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-	if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
-	if (ctx->d_sync) (void)hipFree(ctx->d_sync);
-	if (ctx->d_trace) (void)hipFree(ctx->d_trace);
-	if (ctx->d_grid_scratch) (void)hipFree(ctx->d_grid_scratch);
-	for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-		if (ctx->ev_frame0[i]) (void)hipEventDestroy(ctx->ev_frame0[i]);
-		if (ctx->ev_frame1[i]) (void)hipEventDestroy(ctx->ev_frame1[i]);
-		if (ctx->ev_kern0[i]) (void)hipEventDestroy(ctx->ev_kern0[i]);
-		if (ctx->ev_kern1[i]) (void)hipEventDestroy(ctx->ev_kern1[i]);
-	}
-	if (ctx->ev_model) (void)hipEventDestroy(ctx->ev_model);
-	if (ctx->ev_synced) (void)hipEventDestroy(ctx->ev_synced);
-	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
 
@@ -1580,12 +1525,8 @@ int ngp_save_snapshot_file(ngp_ctx* ctx, const char* path, int compress) {
 		rgbc["measured_batch_size"] = mj::Value::make_uint(0);
 		rgbc["measured_batch_size_before_compaction"] = mj::Value::make_uint(0);
 		nerf["rgb"] = rgbc;
-		Dataset ds = ctx->dataset;
-		ds.aabb_scale = (int)d.aabb_scale;
-		if (!ds.has_render_aabb) {
-			for (int i = 0; i < 3; ++i) { ds.render_aabb_min[i] = d.render_aabb_min[i]; ds.render_aabb_max[i] = d.render_aabb_max[i]; }
-		}
-		nerf["dataset"] = dataset_to_json(ds);
+		const Dataset& ds = ctx->dataset;
+		nerf["dataset"] = dataset_to_json(ds, (int)d.aabb_scale, ds.has_render_aabb ? ds.render_aabb_min : d.render_aabb_min, ds.has_render_aabb ? ds.render_aabb_max : d.render_aabb_max);
 		snap["nerf"] = nerf;
 		snap["training_step"] = mj::Value::make_uint(0);
 		snap["loss"] = mj::Value::make_float(0.0);
@@ -1748,7 +1689,7 @@ int ngp_render(ngp_ctx* ctx, const ngp_camera* cam, const ngp_render_opts* opts,
 		if (cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536) throw std::runtime_error("invalid render resolution");
 		if (!rgba_out) throw std::runtime_error("null argument");
 		if (opts->packed_output) throw std::runtime_error("packed_output is for ngp_render_device (GPU-resident tiles); ngp_render returns images");
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); rendering needs an MI355X -- there is no CPU fallback");
+		require_device(ctx, "rendering needs an MI355X");
 		const size_t n_pixels = (size_t)cam->width * cam->height;
 		ensure_frame_buffers(ctx, n_pixels);
 		// A destination from ngp_host_alloc is page-locked AND mapped into the device's address space: the image is write-only for
@@ -1757,12 +1698,12 @@ int ngp_render(ngp_ctx* ctx, const ngp_camera* cam, const ngp_render_opts* opts,
 		// copy engine 0.8 ms after a 2.4 ms render. NGP_HOST_DIRECT=0 restores render-then-copy (A/B measurements).
 		static const bool host_direct = []() { const char* e = getenv("NGP_HOST_DIRECT"); return !e || atoi(e) != 0; }();
 		float4* d_image = host_direct ? (float4*)pinned_device_alias(rgba_out, n_pixels * sizeof(float4)) : nullptr;
-		float4* d_target = d_image ? d_image : ctx->d_rgba;
-		if (!ctx->peers.empty() && opts->shard_count <= 1) ngp::render_frames_multi(ctx, *cam, *opts, d_target, ctx->d_depth, ctx->stream);
+		float4* d_target = d_image ? d_image : ctx->d_rgba.get();
+		if (!ctx->peers.empty() && opts->shard_count <= 1) ngp::render_frames_multi(ctx, *cam, *opts, d_target, ctx->d_depth.get(), ctx->stream);
 		else render_frames(ctx, *cam, *opts, d_target, nullptr, ctx->stream);
 		// (otherwise: one DMA at the link's rate into page-locked memory, a staged copy into ordinary memory)
-		if (!d_image) NGP_HIP_CHECK(hipMemcpyAsync(rgba_out, ctx->d_rgba, n_pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-		if (depth_out) NGP_HIP_CHECK(hipMemcpyAsync(depth_out, ctx->d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		if (!d_image) NGP_HIP_CHECK(hipMemcpyAsync(rgba_out, ctx->d_rgba.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+		if (depth_out) NGP_HIP_CHECK(hipMemcpyAsync(depth_out, ctx->d_depth.get(), n_pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
 }
@@ -1848,7 +1789,7 @@ void ngp_host_free(void* p) {
 static void read_history_slot(ngp_ctx* ctx, uint64_t call, ngp_render_stats* out) {
 	const int slot = (int)(call % ngp_ctx::HISTORY);
 	unsigned long long c[4];
-	NGP_HIP_CHECK(hipMemcpy(c, (char*)ctx->d_sync + ngp_ctx::SLOT_BYTES * (size_t)slot + 32, sizeof(c), hipMemcpyDeviceToHost)); // the slot's results (ngp_ctx::bind_slot)
+	NGP_HIP_CHECK(hipMemcpy(c, ctx->d_sync.get() + ngp_ctx::SLOT_BYTES * (size_t)slot + 32, sizeof(c), hipMemcpyDeviceToHost)); // the slot's results (ngp_ctx::bind_slot)
 	out->kernel_device_ms = (float)((double)c[3] * 1e-5); // 100 MHz ticks
 	out->n_rays = ctx->hist_n_rays[slot];
 	out->n_rays_alive_after_init = c[0];
@@ -1867,18 +1808,17 @@ int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {
 		if (ctx->last_was_multi) { // a frame over several devices: totals over the devices' shares, the slowest share's times
 			for (ngp_ctx* p : ctx->peers) {
 				ngp_render_stats s{};
-				NGP_HIP_CHECK(hipSetDevice(p->device));
+				DeviceGuard g(p->device);
 				if (ngp_get_render_stats(p, &s) != 0) throw std::runtime_error(p->error);
 				out->n_rays += s.n_rays; out->n_rays_alive_after_init += s.n_rays_alive_after_init; out->n_rays_hit += s.n_rays_hit; out->n_samples += s.n_samples;
 				out->kernel_ms = std::max(out->kernel_ms, s.kernel_ms);
 				out->frame_ms = std::max(out->frame_ms, s.frame_ms);
 				out->kernel_device_ms = std::max(out->kernel_device_ms, s.kernel_device_ms);
 			}
-			NGP_HIP_CHECK(hipSetDevice(ctx->device));
 		}
 		if (ctx->d_prof && getenv("NGP_PROFILE_SECTIONS")) {
 			unsigned long long p[128];
-			NGP_HIP_CHECK(hipMemcpy(p, ctx->d_prof, sizeof(p), hipMemcpyDeviceToHost));
+			NGP_HIP_CHECK(hipMemcpy(p, ctx->d_prof.get(), sizeof(p), hipMemcpyDeviceToHost));
 			{ // wave timeline on the 100 MHz chip clock: when the tile queue ran dry, when the last wave left
 				const double us = 0.01, t_first = (double)(~p[8]);
 				fprintf(stderr, "[ngp timeline] kernel %.1f us | queue empty seen first at %.1f us, last at %.1f us | wave exits per 0.1 ms:", ((double)p[9] - t_first) * us,
@@ -1905,7 +1845,7 @@ int ngp_get_profile_trace(ngp_ctx* ctx, uint32_t* out, uint64_t n_words, uint32_
 		if (cap_iters) *cap_iters = ngp_ctx::TRACE_ITERS;
 		if (!out) return;
 		NGP_HIP_CHECK(hipDeviceSynchronize());
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_trace, std::min<size_t>(words, (size_t)n_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_trace.get(), std::min<size_t>(words, (size_t)n_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	});
 }
 
@@ -1929,81 +1869,63 @@ int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out) {
 
 int ngp_grid_encode(ngp_ctx* ctx, uint32_t n, const float* pos01, uint16_t* out_fp16) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
 		if (n == 0) return;
 		if (!pos01 || !out_fp16) throw std::runtime_error("null argument");
-		float* d_pos = nullptr;
-		uint16_t* d_out = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_pos, (size_t)n * 3 * sizeof(float)));
+		DevArray<float> d_pos;
+		d_pos.upload(pos01, (size_t)n * 3);
 		const size_t width = ctx->M.wide.width ? ctx->M.wide.enc_dims : 32; // the position encoding's (padded) width
-		NGP_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)n * width * sizeof(uint16_t)));
-		NGP_HIP_CHECK(hipMemcpy(d_pos, pos01, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		if (ctx->M.wide.width) launch_frequency_encode(ctx->M, n, d_pos, d_out, ctx->stream);
-		else launch_grid_encode(ctx->M, n, d_pos, d_out, ctx->stream);
+		DevArray<uint16_t> d_out((size_t)n * width);
+		if (ctx->M.wide.width) launch_frequency_encode(ctx->M, n, d_pos.get(), d_out.get(), ctx->stream);
+		else launch_grid_encode(ctx->M, n, d_pos.get(), d_out.get(), ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		NGP_HIP_CHECK(hipMemcpy(out_fp16, d_out, (size_t)n * width * sizeof(uint16_t), hipMemcpyDeviceToHost));
-		(void)hipFree(d_pos);
-		(void)hipFree(d_out);
+		NGP_HIP_CHECK(hipMemcpy(out_fp16, d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
 
 int ngp_density_gradient(ngp_ctx* ctx, uint32_t n, const float* pos01, float* out_grad) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		if (ctx->M.wide.width && (!ctx->M.wide.layers_t[0].n_mtiles || ctx->M.wide.enc_dims > ctx->M.wide.width))
 			throw std::runtime_error("the density gradient of a Frequency / Identity-encoding model: implemented for up to 8 hidden density layers and an encoding no wider than the network");
 		ngp::sync_inference_model(ctx);
 		if (n == 0) return;
 		if (!pos01 || !out_grad) throw std::runtime_error("null argument");
-		float *d_pos = nullptr, *d_out = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_pos, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMemcpy(d_pos, pos01, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		if (ctx->M.wide.width) launch_density_gradient_wide(ctx->M, n, d_pos, d_out, ctx->n_cus, ctx->stream);
-		else launch_density_gradient(ctx->M, n, d_pos, d_out, ctx->stream);
+		DevArray<float> d_pos, d_out((size_t)n * 3);
+		d_pos.upload(pos01, (size_t)n * 3);
+		if (ctx->M.wide.width) launch_density_gradient_wide(ctx->M, n, d_pos.get(), d_out.get(), ctx->n_cus, ctx->stream);
+		else launch_density_gradient(ctx->M, n, d_pos.get(), d_out.get(), ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		NGP_HIP_CHECK(hipMemcpy(out_grad, d_out, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-		(void)hipFree(d_pos);
-		(void)hipFree(d_out);
+		NGP_HIP_CHECK(hipMemcpy(out_grad, d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
 
 int ngp_network_inference(ngp_ctx* ctx, uint32_t n, const float* pos01, const float* dir01, uint16_t* out_fp16) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
 		if (n == 0) return;
 		if (!pos01 || !dir01 || !out_fp16) throw std::runtime_error("null argument");
-		float *d_pos = nullptr, *d_dir = nullptr;
-		uint16_t* d_out = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_pos, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_dir, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)n * 4 * sizeof(uint16_t)));
-		NGP_HIP_CHECK(hipMemcpy(d_pos, pos01, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		NGP_HIP_CHECK(hipMemcpy(d_dir, dir01, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		if (ctx->M.wide.width) launch_network_inference_wide(ctx->M, n, d_pos, d_dir, d_out, ctx->n_cus, ctx->stream);
-		else launch_network_inference(ctx->M, n, d_pos, d_dir, d_out, ctx->stream);
+		DevArray<float> d_pos, d_dir;
+		DevArray<uint16_t> d_out((size_t)n * 4);
+		d_pos.upload(pos01, (size_t)n * 3);
+		d_dir.upload(dir01, (size_t)n * 3);
+		if (ctx->M.wide.width) launch_network_inference_wide(ctx->M, n, d_pos.get(), d_dir.get(), d_out.get(), ctx->n_cus, ctx->stream);
+		else launch_network_inference(ctx->M, n, d_pos.get(), d_dir.get(), d_out.get(), ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		NGP_HIP_CHECK(hipMemcpy(out_fp16, d_out, (size_t)n * 4 * sizeof(uint16_t), hipMemcpyDeviceToHost));
-		(void)hipFree(d_pos);
-		(void)hipFree(d_dir);
-		(void)hipFree(d_out);
+		NGP_HIP_CHECK(hipMemcpy(out_fp16, d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
 
 int ngp_get_density_bitfield(ngp_ctx* ctx, uint8_t* out, float* out_mean) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
-		if (out) NGP_HIP_CHECK(hipMemcpy(out, ctx->d_bitfield, (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES, hipMemcpyDeviceToHost));
+		if (out) NGP_HIP_CHECK(hipMemcpy(out, ctx->d_bitfield.get(), (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES, hipMemcpyDeviceToHost));
 		if (out_mean) *out_mean = ctx->bitfield_mean;
 	});
 }
@@ -2030,19 +1952,17 @@ int ngp_set_envmap(ngp_ctx* ctx, int32_t width, int32_t height, const float* rgb
 	return guarded(ctx, [&] {
 		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only)");
 		NGP_HIP_CHECK(hipDeviceSynchronize()); // frames in flight read the map
-		if (ctx->d_bg_envmap) (void)hipFree(ctx->d_bg_envmap);
-		ctx->d_bg_envmap = nullptr;
+		ctx->d_bg_envmap.reset();
 		ctx->bg_env_w = ctx->bg_env_h = 0;
 		if (!rgba || width <= 0 || height <= 0) return;
 		if ((int64_t)width * height > (1ll << 28)) throw std::runtime_error("environment map too large");
-		NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_bg_envmap, (size_t)width * height * sizeof(float4)));
-		NGP_HIP_CHECK(hipMemcpy(ctx->d_bg_envmap, rgba, (size_t)width * height * sizeof(float4), hipMemcpyHostToDevice));
+		ctx->d_bg_envmap.upload((const float4*)rgba, (size_t)width * height);
 		ctx->bg_env_w = width;
 		ctx->bg_env_h = height;
 		for (ngp_ctx* p : ctx->peers) { // the replicas of a multi-device context see the same background
+			DeviceGuard g(p->device);
 			if (ngp_set_envmap(p, width, height, rgba) != 0) throw std::runtime_error(p->error);
 		}
-		NGP_HIP_CHECK(hipSetDevice(ctx->device));
 	});
 }
 
@@ -2058,8 +1978,7 @@ int ngp_set_cone_angle_constant(ngp_ctx* ctx, float cone_angle_constant) {
 
 int ngp_update_density_grid(ngp_ctx* ctx, float decay, uint32_t n_uniform, uint32_t n_nonuniform, uint32_t n_iterations) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
 		ngp::update_density_grid_device(ctx, decay, n_uniform, n_nonuniform, n_iterations);
 		ngp::refresh_density_grid_host(ctx);
@@ -2068,29 +1987,24 @@ int ngp_update_density_grid(ngp_ctx* ctx, float decay, uint32_t n_uniform, uint3
 
 int ngp_get_density_grid(ngp_ctx* ctx, float* out, uint64_t n) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
 		const uint64_t n_elements = (uint64_t)NERF_GRID_N_CELLS * (ctx->max_cascade + 1);
 		if (!out || n != n_elements) throw std::runtime_error("density grid holds " + std::to_string(n_elements) + " values");
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_density_f32, n_elements * sizeof(float), hipMemcpyDeviceToHost));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_density_f32.get(), n_elements * sizeof(float), hipMemcpyDeviceToHost));
 	});
 }
 
 int ngp_init_rays(ngp_ctx* ctx, const ngp_camera* cam, void* payloads_out) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-		if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+		require_model(ctx);
 		ngp::sync_inference_model(ctx);
 		if (!cam || !payloads_out) throw std::runtime_error("null argument");
-		const size_t n = (size_t)cam->width * cam->height;
-		NerfPayload* d_p = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_p, n * sizeof(NerfPayload)));
+		DevArray<NerfPayload> d_p((size_t)cam->width * cam->height);
 		CameraParams C = make_camera_params(*cam, cam->spp_index);
-		launch_init_rays(ctx->M, C, d_p, ctx->stream);
+		launch_init_rays(ctx->M, C, d_p.get(), ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		NGP_HIP_CHECK(hipMemcpy(payloads_out, d_p, n * sizeof(NerfPayload), hipMemcpyDeviceToHost));
-		(void)hipFree(d_p);
+		NGP_HIP_CHECK(hipMemcpy(payloads_out, d_p.get(), d_p.bytes(), hipMemcpyDeviceToHost));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }

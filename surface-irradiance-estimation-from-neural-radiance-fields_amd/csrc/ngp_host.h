@@ -13,10 +13,12 @@
 #include <array>
 #include <cstdlib>
 #include <fstream>
+#include <memory>
 #include <sstream>
 #include <sys/stat.h>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace ngp {
@@ -26,6 +28,94 @@ namespace ngp {
 		hipError_t _e = (expr);                                                                                    \
 		if (_e != hipSuccess) throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(_e));   \
 	} while (0)
+
+// ------------------------------------------------------------------------------------------------ owners of HIP resources
+// Move-only. An empty owner makes no HIP call, so host-only contexts (ngp_create(-1)) never touch the runtime.
+template <typename T, bool Pinned = false>
+class HipArray { // n elements of device memory, or of page-locked host memory
+public:
+	HipArray() = default;
+	explicit HipArray(size_t n) { reset(n); }
+	HipArray(HipArray&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+	HipArray& operator=(HipArray&& o) noexcept {
+		if (this != &o) {
+			reset();
+			std::swap(p_, o.p_);
+			std::swap(n_, o.n_);
+		}
+		return *this;
+	}
+	~HipArray() { reset(); }
+	// frees the old allocation before it makes the new one (peak memory of a regrow = the new size)
+	void reset(size_t n = 0) {
+		if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+		p_ = nullptr;
+		n_ = 0;
+		if (!n) return;
+		if (Pinned) NGP_HIP_CHECK(hipHostMalloc((void**)&p_, n * sizeof(T), hipHostMallocDefault));
+		else NGP_HIP_CHECK(hipMalloc((void**)&p_, n * sizeof(T)));
+		n_ = n;
+	}
+	void upload(const T* src, size_t n) { // reset(n) + a synchronous copy from the host
+		reset(n);
+		if (n) NGP_HIP_CHECK(hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice));
+	}
+	T* get() const { return p_; }
+	size_t size() const { return n_; }
+	size_t bytes() const { return n_ * sizeof(T); }
+	explicit operator bool() const { return p_ != nullptr; }
+
+private:
+	T* p_ = nullptr;
+	size_t n_ = 0;
+};
+template <typename T> using DevArray = HipArray<T>;
+template <typename T> using PinnedArray = HipArray<T, true>;
+
+template <typename H, hipError_t (*Destroy)(H)>
+class HipHandle { // an event or a stream; converts to the raw handle for the runtime's calls
+public:
+	HipHandle() = default;
+	explicit HipHandle(H h) : h_(h) {}
+	HipHandle(HipHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+	HipHandle& operator=(HipHandle&& o) noexcept {
+		if (this != &o) {
+			if (h_) (void)Destroy(h_);
+			h_ = o.h_;
+			o.h_ = nullptr;
+		}
+		return *this;
+	}
+	~HipHandle() {
+		if (h_) (void)Destroy(h_);
+	}
+	operator H() const { return h_; }
+
+private:
+	H h_ = nullptr;
+};
+using Event = HipHandle<hipEvent_t, hipEventDestroy>;
+using Stream = HipHandle<hipStream_t, hipStreamDestroy>;
+inline Event new_event(unsigned flags = hipEventDefault) {
+	hipEvent_t e = nullptr;
+	NGP_HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+	return Event(e);
+}
+inline Stream new_stream(unsigned flags = hipStreamDefault) {
+	hipStream_t s = nullptr;
+	NGP_HIP_CHECK(hipStreamCreateWithFlags(&s, flags));
+	return Stream(s);
+}
+
+// makes `device` current for a scope; the previous device is current again when it ends, on a throw as well
+struct DeviceGuard {
+	int prev = 0;
+	explicit DeviceGuard(int dev) {
+		(void)hipGetDevice(&prev);
+		NGP_HIP_CHECK(hipSetDevice(dev));
+	}
+	~DeviceGuard() { (void)hipSetDevice(prev); }
+};
 
 // kernel launchers, nerf_kernels.hip
 void launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream);
@@ -89,8 +179,8 @@ struct HostMesh { // MeshData (mesh.h:18-24) after load_mesh
 	std::vector<TriangleBvhNode> nodes;
 	float bmin[3], bmax[3];
 	float center[3];
-	Triangle* d_tris = nullptr;
-	TriangleBvhNode* d_nodes = nullptr;
+	DevArray<Triangle> d_tris; // (a peer's replica holds these alone: the host vectors stay empty, ngp_mesh.cpp sync_peer_geometry)
+	DevArray<TriangleBvhNode> d_nodes;
 };
 
 // NerfDataset subset (nerf_loader.h:60-170): what rendering and the harness read
@@ -104,7 +194,7 @@ struct TrainingView {
 	std::string path;
 	std::string abs_path; // the image file the loader resolved (extension probing, nerf_loader.cu), may not exist
 	bool white_transparent = false, black_transparent = false; // transforms.json flags (NSVF-style data), src/nerf_loader.cu:462-468
-	void* d_pixels = nullptr; // training image on the device (ngp_set_training_image), RGBA
+	DevArray<uint8_t> d_pixels; // training image on the device (ngp_set_training_image), RGBA
 	int32_t image_type = 0;   // ngp_image_type
 };
 struct Dataset {
@@ -126,41 +216,45 @@ struct Dataset {
 struct TrainState {
 	ngp_training_opts opts{};
 	uint32_t n_params = 0, n_matrix = 0;
-	float* d_weights_fp32 = nullptr;   // Trainer::m_params_full_precision
-	uint16_t* d_weights = nullptr;     // m_params (fp16, what the training kernels read; tcnn order: density MLP, rgb MLP, grid)
-	uint16_t* d_weights_ema = nullptr; // Ema's m_weights_ema = the inference parameters
-	float* d_ema_tmp = nullptr;
-	float* d_grad = nullptr;           // fp32, cleared by the optimizer kernel
-	float* d_m1 = nullptr;
-	float* d_m2 = nullptr;
-	uint32_t* d_steps = nullptr;
-	uint4* d_tfrags = nullptr;         // MFMA fragments of the training parameters (forward + transposed)
-	uint2* d_kfrags = nullptr;
-	uint4* d_tfrags_inference = nullptr;
-	uint2* d_kfrags_inference = nullptr;
-	TrainImage* d_images = nullptr;
+	DevArray<float> d_weights_fp32;      // Trainer::m_params_full_precision
+	DevArray<uint16_t> d_weights;        // m_params (fp16, what the training kernels read; tcnn order: density MLP, rgb MLP, grid)
+	DevArray<uint16_t> d_weights_ema;    // Ema's m_weights_ema = the inference parameters
+	DevArray<float> d_ema_tmp;
+	DevArray<float> d_grad;              // fp32, cleared by the optimizer kernel
+	DevArray<float> d_m1;
+	DevArray<float> d_m2;
+	DevArray<uint32_t> d_steps;
+	DevArray<uint4> d_tfrags;            // MFMA fragments of the training parameters (forward + transposed)
+	DevArray<uint2> d_kfrags;
+	DevArray<uint4> d_tfrags_inference;
+	DevArray<uint2> d_kfrags_inference;
+	DevArray<TrainImage> d_images;
 	uint32_t n_images = 0;
 	bool images_dirty = true;
-	TrainBatch B{}; // the step in flight: gen[cur]'s buffers + the shared ones
+	TrainBatch B{}; // the step in flight, a view: gen[cur]'s buffers + the shared ones below
+	DevArray<uint16_t> mlp_out;
+	DevArray<float> coords_compacted;
+	DevArray<uint16_t> dloss;
+	DevArray<float> loss;
 	// sample generation only reads the images, the occupancy bitfield and the step's rng: step N+1's runs on a second
 	// stream beside step N's backward pass, into the other of two buffer sets
 	struct GenSet {
-		uint32_t* counters = nullptr;
-		uint32_t* ray_indices = nullptr;
-		float* rays = nullptr;
-		uint32_t* numsteps = nullptr;
-		float* coords = nullptr;
+		DevArray<uint32_t> counters;
+		DevArray<uint32_t> ray_indices;
+		DevArray<float> rays;
+		DevArray<uint32_t> numsteps;
+		DevArray<float> coords;
 		uint32_t cap_rays = 0, cap_samples = 0;
 	} gen[2];
 	int cur = 0;
 	bool pregenerated = false; // gen[cur ^ 1] holds the next step's samples (ev_gen marks them complete)
 	TrainStepParams pre_P{};
-	hipStream_t stream2 = nullptr;
-	hipEvent_t ev_gen = nullptr, ev_loss = nullptr;
-	uint32_t* h_counters = nullptr; // pinned: counters[4] + loss sum
+	Stream stream2;
+	Event ev_gen, ev_loss;
+	PinnedArray<uint32_t> h_counters; // counters[4] + loss sum
 	uint32_t cap_loss = 0, cap_out = 0, cap_target = 0;
-	float* d_loss_sum = nullptr;
-	float* d_partials = nullptr; // per-block weight-gradient sums of train_backward_kernel
+	DevArray<float> d_loss_sum;
+	DevArray<float> d_partials; // per-block weight-gradient sums of train_backward_kernel
 	// NerfCounters + Testbed members
 	uint32_t training_step = 0;
 	uint32_t rays_per_batch = 1u << 12;
@@ -181,7 +275,7 @@ struct ngp_ctx {
 	int device = 0;
 	int n_cus = 256;
 	std::string error;
-	hipStream_t stream = nullptr;
+	ngp::Stream stream;
 
 	// ---- model
 	bool model_loaded = false; // uploaded to the device
@@ -190,17 +284,17 @@ struct ngp_ctx {
 	std::vector<uint16_t> params;
 	std::vector<uint16_t> density_grid;
 	uint32_t max_cascade = 0;
-	void* d_params = nullptr;
-	void* d_xgrid = nullptr; // the grid table again, in the xor layout (ngp_api.cpp build_xor_layout)
-	uint4* d_wfrags = nullptr;
-	uint8_t* d_bitfield = nullptr;
-	uint32_t* d_coarse = nullptr;
-	float* d_density_tmp = nullptr; // density_grid_tmp of update_density_grid_nerf
+	ngp::DevArray<uint16_t> d_params; // the grid table, tcnn order
+	ngp::DevArray<uint64_t> d_xgrid;  // the grid table again, in the xor layout (ngp_api.cpp build_xor_layout)
+	ngp::DevArray<uint4> d_wfrags;
+	ngp::DevArray<uint8_t> d_bitfield;
+	ngp::DevArray<uint32_t> d_coarse;
+	ngp::DevArray<float> d_density_tmp; // density_grid_tmp of update_density_grid_nerf
 	uint64_t grid_rng_state = 0, grid_rng_inc = 0; // m_nerf.training.density_grid_rng
 	uint32_t grid_ema_step = 0, grid_updates = 0;
-	uint16_t* d_density_f16 = nullptr;
-	float* d_density_f32 = nullptr;
-	double* d_partial = nullptr;
+	ngp::DevArray<uint16_t> d_density_f16;
+	ngp::DevArray<float> d_density_f32;
+	ngp::DevArray<double> d_partial;
 	float bitfield_mean = 0.f;
 	ngp::ModelParams M{};
 
@@ -218,33 +312,32 @@ struct ngp_ctx {
 
 	// ---- geometry mode
 	std::vector<ngp::HostMesh> meshes;
-	ngp::MeshRef* d_meshrefs = nullptr;
+	ngp::DevArray<ngp::MeshRef> d_meshrefs;
 	ngp::MeshSceneParams mesh_scene{};
 	ngp::MeshShadeParams shade{{0.57735026f, 0.57735026f, 0.57735026f}, {0.f, 1.f, 0.f}, 0.f, 0.f, 1.f, 0.5f, 0.f, 0.f, 0.f, {0.8f, 0.8f, 0.8f}, {0.f, 0.f, 0.f}};
 
 	// ---- irradiance probe texture(s) (m_envmap_tex / gridSize, testbed.h:949-950) and E(n) tabulated at their texels
-	float4* d_envmap = nullptr;
-	float4* d_irradiance = nullptr;
+	ngp::DevArray<float4> d_envmap;
+	ngp::DevArray<float4> d_irradiance;
 	uint32_t env_n_theta = 0, env_n_phi = 0;
 	ngp::ProbeParams env_probe{}; // what was traced: mode, shell position(s), grid
 
 	// ---- environment map behind the NeRF (m_envmap.inference_view(), testbed.h:1297-1316)
-	float4* d_bg_envmap = nullptr;
+	ngp::DevArray<float4> d_bg_envmap;
 	int32_t bg_env_w = 0, bg_env_h = 0;
 
 	// ---- frame
-	size_t n_pixels_alloc = 0;
-	float4* d_frame = nullptr;
-	float* d_depth = nullptr;
-	float4* d_accum = nullptr;
-	float4* d_rgba = nullptr;
+	ngp::DevArray<float4> d_frame; // (d_rgba, allocated last, holds the size of all four)
+	ngp::DevArray<float> d_depth;
+	ngp::DevArray<float4> d_accum;
+	ngp::DevArray<float4> d_rgba;
 	// a ring of per-call slots of 80 B: accumulators [alive, hit, samples], {tile queue, exited waves}, results [alive, hit, samples, device ticks], start stamp.
 	// Zeroed once; every launch's last wave leaves its slot's first four words zero again (nerf_kernels.hip fused_body)
 	static constexpr int HISTORY = 256;
 	static constexpr size_t SLOT_BYTES = 128;
-	void* d_sync = nullptr;
+	ngp::DevArray<char> d_sync;
 	void bind_slot(ngp::FrameParams& F, int slot) const {
-		unsigned long long* w = (unsigned long long*)((char*)d_sync + SLOT_BYTES * (size_t)slot);
+		unsigned long long* w = (unsigned long long*)(d_sync.get() + SLOT_BYTES * (size_t)slot);
 		F.counters = w;
 		F.queue = (uint32_t*)(w + 3);
 		F.done = F.queue + 1;
@@ -253,7 +346,7 @@ struct ngp_ctx {
 		static const bool xcd_queues = []() { const char* e = getenv("NGP_XCD_QUEUES"); return !e || atoi(e) != 0; }(); // 0: one queue (A/B)
 		F.xqueue = xcd_queues ? (uint32_t*)(w + 9) : nullptr; // bytes 72..103 of the 128-byte slot
 	}
-	hipEvent_t ev_frame0[HISTORY] = {}, ev_frame1[HISTORY] = {}, ev_kern0[HISTORY] = {}, ev_kern1[HISTORY] = {};
+	ngp::Event ev_frame0[HISTORY], ev_frame1[HISTORY], ev_kern0[HISTORY], ev_kern1[HISTORY];
 	uint64_t hist_n_rays[HISTORY] = {};
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
@@ -262,13 +355,12 @@ struct ngp_ctx {
 	// since the previous update (ngp::order_after_frames: device-side waits on the frames' end events), does its work, and records
 	// ev_model; every later frame orders its stream behind ev_model (ngp::order_after_model).
 	uint64_t fenced_calls = 0;        // frames [0, fenced_calls) are already ordered before the last update
-	hipEvent_t ev_model = nullptr;    // end of the last update of the render model / occupancy grid on this device
+	ngp::Event ev_model;              // end of the last update of the render model / occupancy grid on this device
 	bool ev_model_valid = false;
-	hipEvent_t ev_synced = nullptr;   // peer: its copies out of the primary's buffers are done
-	unsigned long long* d_prof = nullptr;
-	void* d_grid_scratch = nullptr; // occupancy-grid refresh of a Frequency-encoding model: positions, cells, network outputs of a batch of samples
-	size_t grid_scratch_samples = 0;
-	uint32_t* d_trace = nullptr; // wave timelines of the diagnostic build (NGP_PROFILE_TRACE)
+	ngp::Event ev_synced;             // peer: its copies out of the primary's buffers are done
+	ngp::DevArray<unsigned long long> d_prof;
+	ngp::DevArray<char> d_grid_scratch; // occupancy-grid refresh of a Frequency-encoding model: positions, cells, network outputs of a batch of samples (24 B each)
+	ngp::DevArray<uint32_t> d_trace; // wave timelines of the diagnostic build (NGP_PROFILE_TRACE)
 	static constexpr uint32_t TRACE_WAVES = 64, TRACE_ITERS = 1024;
 	int32_t tune[8] = {64, 4, 32, 1, 1, 4, 1, 1}; // FrameParams::tune; changed only through validate_schedule (ngp_api.cpp)
 
@@ -280,13 +372,11 @@ struct ngp_ctx {
 	uint64_t params_generation = 0, synced_params_generation = 0;       // the inference parameters followed a training step
 	uint64_t mesh_generation = 0, synced_mesh_generation = 0;           // the mesh list / BVHs changed (Geometry mode)
 	uint64_t probe_generation = 0, synced_probe_generation = 0;         // the irradiance probe textures were (re)computed
-	float4* d_pack_rgba = nullptr;   // this device's tiles of the current frame, tile-packed
-	float* d_pack_depth = nullptr;
-	size_t pack_alloc = 0;
-	float4* d_gather_rgba = nullptr; // primary: [device][slots * 64]
-	float* d_gather_depth = nullptr;
-	size_t gather_alloc = 0;
-	hipEvent_t ev_pack = nullptr, ev_unpacked = nullptr;
+	ngp::DevArray<float4> d_pack_rgba;   // this device's tiles of the current frame, tile-packed
+	ngp::DevArray<float> d_pack_depth;   // (allocated last: its size is that of both)
+	ngp::DevArray<float4> d_gather_rgba; // primary: [device][slots * 64]
+	ngp::DevArray<float> d_gather_depth; // (allocated last: its size is that of both)
+	ngp::Event ev_pack, ev_unpacked;
 	uint64_t n_multi_frames = 0;
 	bool last_was_multi = false; // the last frame was rendered over all devices (ngp_get_render_stats sums the shares)
 	bool streams_mixed = false; // frames were issued on more than one stream since the last device-wide wait
@@ -298,12 +388,22 @@ struct ngp_ctx {
 	float mc_ms[3] = {0.f, 0.f, 0.f}; // device time of the last ngp_compute_marching_cubes_mesh: lattice, marching cubes, normals + colours
 
 	// ---- training (ngp_train.cpp)
-	ngp::TrainState* train = nullptr;
+	std::unique_ptr<ngp::TrainState> train;
 	bool density_grid_host_dirty = false; // ctx->density_grid lags d_density_f32
 };
 
 namespace ngp {
 // ------------------------------------------------------------------------------------------------ helpers
+// Preconditions of the entry points that run on the GPU. The messages reach callers (ngp_last_error); `needs` says what cannot run.
+inline void require_device(const ngp_ctx* ctx, const char* needs = nullptr) {
+	if (ctx->device < 0)
+		throw std::runtime_error(std::string("this context has no HIP device (host-only); ") + (needs ? std::string(needs) + " -- " : std::string()) + "there is no CPU fallback");
+}
+inline void require_model(const ngp_ctx* ctx, const char* needs = nullptr) {
+	require_device(ctx, needs);
+	if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+}
+
 template <typename F>
 inline int guarded(ngp_ctx* ctx, F&& f) {
 	if (!ctx) return -1;
@@ -352,7 +452,7 @@ inline void order_after_frames(ngp_ctx* ctx, hipStream_t stream) {
 	ctx->fenced_calls = ctx->n_calls;
 }
 inline void mark_model_updated(ngp_ctx* ctx, hipStream_t stream) {
-	if (!ctx->ev_model) NGP_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_model, hipEventDisableTiming));
+	if (!ctx->ev_model) ctx->ev_model = new_event(hipEventDisableTiming);
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_model, stream));
 	ctx->ev_model_valid = true;
 }
@@ -376,12 +476,11 @@ void ensure_sync_buffers(ngp_ctx* ctx);
 void render_frames_on(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
 void ensure_frame_buffers_for(ngp_ctx* ctx, size_t n_pixels);
 void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
-void free_multi_buffers(ngp_ctx* ctx);
 // ngp_mesh.cpp: Geometry mode on an auxiliary device -- the primary's meshes (BVHs as built), shading parameters and irradiance tables
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer);
 inline IrradianceMap irradiance_map_of(const ngp_ctx* ctx) {
 	IrradianceMap I{};
-	I.irradiance = ctx->d_irradiance;
+	I.irradiance = ctx->d_irradiance.get();
 	I.n_theta = ctx->env_n_theta;
 	I.n_phi = ctx->env_n_phi;
 	if (ctx->env_probe.mode == 3) {

@@ -5,33 +5,15 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <memory>
 
 using namespace ngp;
 
 namespace {
 
-// device buffers of one call
-struct DevBuf {
-	void* p = nullptr;
-	explicit DevBuf(size_t bytes) { NGP_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 4)); }
-	~DevBuf() { (void)hipFree(p); }
-	DevBuf(const DevBuf&) = delete;
-	DevBuf& operator=(const DevBuf&) = delete;
-	template <class T> T* as() const { return (T*)p; }
-};
+// device buffers of one call; never empty, so that an empty mesh still passes valid pointers
+template <class T> DevArray<T> scratch(size_t n) { return DevArray<T>(n ? n : 1); }
 
-struct Events {
-	hipEvent_t e[4] = {};
-	Events() { for (auto& x : e) NGP_HIP_CHECK(hipEventCreate(&x)); }
-	~Events() { for (auto& x : e) (void)hipEventDestroy(x); }
-};
-
-void require_device(const ngp_ctx* ctx);
-void require_device_and_model(ngp_ctx* ctx) {
-	require_device(ctx);
-	if (!ctx->model_loaded) throw std::runtime_error("No network available.");
-}
+constexpr const char* NEEDS = "marching cubes runs on the GPU";
 
 McLattice make_lattice(const ngp_ctx* ctx, const uint32_t* res3, const float* aabb6) {
 	if (!res3) throw std::runtime_error("null argument");
@@ -54,10 +36,6 @@ McLattice make_lattice(const ngp_ctx* ctx, const uint32_t* res3, const float* aa
 	return L;
 }
 
-void require_device(const ngp_ctx* ctx) {
-	if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); marching cubes runs on the GPU -- there is no CPU fallback");
-}
-
 void check_thresh(float thresh) {
 	if (!std::isfinite(thresh)) throw std::runtime_error("marching cubes: thresh must be finite");
 }
@@ -73,8 +51,9 @@ void density_on_grid(ngp_ctx* ctx, const McLattice& L, float* d_out) {
 		launch_mc_density(ctx->M, L, d_out, nullptr, nullptr, 0, ctx->n_cus, ctx->stream);
 	} else {
 		const uint32_t chunk = std::min<uint32_t>(n, 1u << 22);
-		DevBuf pos((size_t)chunk * 3 * sizeof(float)), net((size_t)chunk * 4 * sizeof(uint16_t));
-		launch_mc_density(ctx->M, L, d_out, pos.as<float>(), net.as<uint16_t>(), chunk, ctx->n_cus, ctx->stream);
+		auto pos = scratch<float>((size_t)chunk * 3);
+		auto net = scratch<uint16_t>((size_t)chunk * 4);
+		launch_mc_density(ctx->M, L, d_out, pos.get(), net.get(), chunk, ctx->n_cus, ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (the scratch goes out of scope)
 	}
 	NGP_HIP_CHECK(hipGetLastError());
@@ -84,25 +63,28 @@ void density_on_grid(ngp_ctx* ctx, const McLattice& L, float* d_out) {
 // in between); after_emit (nullable) is recorded behind the emit kernels
 struct DevMesh {
 	uint32_t nv = 0, nt = 0;
-	std::unique_ptr<DevBuf> V, F;
+	DevArray<float> V;
+	DevArray<uint32_t> F;
 };
 DevMesh marching_cubes(ngp_ctx* ctx, const McLattice& L, const float* d_density, float thresh, hipEvent_t after_emit = nullptr) {
 	const uint32_t n = n_points(L);
 	const McGrid G{d_density, L.res[0], L.res[1], L.res[2], n, thresh};
 	const uint32_t nb = mc_n_blocks(n);
-	DevBuf blocks((size_t)nb * sizeof(uint2)), totals(2 * sizeof(unsigned long long));
-	launch_mc_count_scan(G, blocks.as<uint2>(), totals.as<unsigned long long>(), ctx->stream);
+	auto blocks = scratch<uint2>(nb);
+	auto totals = scratch<unsigned long long>(2);
+	launch_mc_count_scan(G, blocks.get(), totals.get(), ctx->stream);
 	unsigned long long tot[2] = {0, 0};
-	NGP_HIP_CHECK(hipMemcpyAsync(tot, totals.p, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
+	NGP_HIP_CHECK(hipMemcpyAsync(tot, totals.get(), sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	if (tot[0] > 0xffffffffull || tot[1] > 0xffffffffull / 3) throw std::runtime_error("marching cubes: the mesh would exceed 32-bit indices; lower the resolution");
 	DevMesh m;
 	m.nv = (uint32_t)tot[0];
 	m.nt = (uint32_t)tot[1];
-	DevBuf vofs(padded(n) * sizeof(uint32_t)), vmask(padded(n));
-	m.V.reset(new DevBuf((size_t)m.nv * 3 * sizeof(float)));
-	m.F.reset(new DevBuf((size_t)m.nt * 3 * sizeof(uint32_t)));
-	launch_mc_emit(G, L, blocks.as<uint2>(), vofs.as<uint32_t>(), vmask.as<uint32_t>(), m.V->as<float>(), m.F->as<uint32_t>(), ctx->stream);
+	auto vofs = scratch<uint32_t>(padded(n));
+	auto vmask = scratch<uint32_t>(padded(n) / 4);
+	m.V = scratch<float>((size_t)m.nv * 3);
+	m.F = scratch<uint32_t>((size_t)m.nt * 3);
+	launch_mc_emit(G, L, blocks.get(), vofs.get(), vmask.get(), m.V.get(), m.F.get(), ctx->stream);
 	NGP_HIP_CHECK(hipGetLastError());
 	if (after_emit) NGP_HIP_CHECK(hipEventRecord(after_emit, ctx->stream));
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (vofs / vmask go out of scope)
@@ -112,8 +94,8 @@ DevMesh marching_cubes(ngp_ctx* ctx, const McLattice& L, const float* d_density,
 void read_back(ngp_ctx* ctx, const DevMesh& m) {
 	ctx->mc_V.resize((size_t)m.nv * 3);
 	ctx->mc_F.resize((size_t)m.nt * 3);
-	NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_V.data(), m.V->p, ctx->mc_V.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_F.data(), m.F->p, ctx->mc_F.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_V.data(), m.V.get(), ctx->mc_V.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_F.data(), m.F.get(), ctx->mc_F.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
@@ -135,30 +117,30 @@ extern "C" {
 
 int ngp_density_on_grid(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float* out) {
 	return guarded(ctx, [&] {
-		require_device_and_model(ctx);
+		require_model(ctx, NEEDS);
 		const McLattice L = make_lattice(ctx, res3, aabb6);
 		if (!out) throw std::runtime_error("null argument");
 		ngp::sync_inference_model(ctx);
 		const uint32_t n = n_points(L);
-		DevBuf d(padded(n) * sizeof(float));
-		density_on_grid(ctx, L, d.as<float>());
-		NGP_HIP_CHECK(hipMemcpyAsync(out, d.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		auto d = scratch<float>(padded(n));
+		density_on_grid(ctx, L, d.get());
+		NGP_HIP_CHECK(hipMemcpyAsync(out, d.get(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	});
 }
 
 int ngp_marching_cubes(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float thresh, const float* density, uint32_t* n_verts, uint32_t* n_tris) {
 	return guarded(ctx, [&] {
-		require_device_and_model(ctx);
+		require_model(ctx, NEEDS);
 		const McLattice L = make_lattice(ctx, res3, aabb6);
 		check_thresh(thresh);
 		if (!density) throw std::runtime_error("null argument");
 		clear_mesh(ctx);
 		const uint32_t n = n_points(L);
-		DevBuf d(padded(n) * sizeof(float));
-		NGP_HIP_CHECK(hipMemsetAsync(d.p, 0, padded(n) * sizeof(float), ctx->stream));
-		NGP_HIP_CHECK(hipMemcpyAsync(d.p, density, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-		read_back(ctx, marching_cubes(ctx, L, d.as<float>(), thresh));
+		auto d = scratch<float>(padded(n));
+		NGP_HIP_CHECK(hipMemsetAsync(d.get(), 0, d.bytes(), ctx->stream));
+		NGP_HIP_CHECK(hipMemcpyAsync(d.get(), density, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+		read_back(ctx, marching_cubes(ctx, L, d.get(), thresh));
 		ctx->mc_valid = true;
 		if (n_verts) *n_verts = (uint32_t)(ctx->mc_V.size() / 3);
 		if (n_tris) *n_tris = (uint32_t)(ctx->mc_F.size() / 3);
@@ -167,7 +149,7 @@ int ngp_marching_cubes(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, f
 
 int ngp_compute_marching_cubes_mesh(ngp_ctx* ctx, const uint32_t* res3, const float* aabb6, float thresh, uint32_t* n_verts, uint32_t* n_tris) {
 	return guarded(ctx, [&] {
-		require_device_and_model(ctx);
+		require_model(ctx, NEEDS);
 		const McLattice L = make_lattice(ctx, res3, aabb6);
 		check_thresh(thresh);
 		if (ctx->M.wide.width && (!ctx->M.wide.layers_t[0].n_mtiles || ctx->M.wide.enc_dims > ctx->M.wide.width))
@@ -175,36 +157,37 @@ int ngp_compute_marching_cubes_mesh(ngp_ctx* ctx, const uint32_t* res3, const fl
 		clear_mesh(ctx);
 		ngp::sync_inference_model(ctx);
 		const uint32_t n = n_points(L);
-		Events ev;
-		DevBuf d(padded(n) * sizeof(float));
-		NGP_HIP_CHECK(hipEventRecord(ev.e[0], ctx->stream));
-		density_on_grid(ctx, L, d.as<float>());
-		NGP_HIP_CHECK(hipEventRecord(ev.e[1], ctx->stream));
-		const DevMesh mesh = marching_cubes(ctx, L, d.as<float>(), thresh, ev.e[2]);
+		const Event ev[4] = {new_event(), new_event(), new_event(), new_event()};
+		auto d = scratch<float>(padded(n));
+		NGP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
+		density_on_grid(ctx, L, d.get());
+		NGP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
+		const DevMesh mesh = marching_cubes(ctx, L, d.get(), thresh, ev[2]);
 		const uint32_t nv = mesh.nv;
-		DevBuf pos((size_t)nv * 3 * sizeof(float)), dir((size_t)nv * 3 * sizeof(float)), grad((size_t)nv * 3 * sizeof(float));
-		DevBuf net((size_t)nv * 4 * sizeof(uint16_t)), N((size_t)nv * 3 * sizeof(float)), C((size_t)nv * 3 * sizeof(float));
+		auto pos = scratch<float>((size_t)nv * 3), dir = scratch<float>((size_t)nv * 3), grad = scratch<float>((size_t)nv * 3);
+		auto net = scratch<uint16_t>((size_t)nv * 4);
+		auto N = scratch<float>((size_t)nv * 3), C = scratch<float>((size_t)nv * 3);
 		if (nv) {
-			launch_mc_vertex_inputs(ctx->M, nv, mesh.V->as<float>(), pos.as<float>(), dir.as<float>(), ctx->stream);
+			launch_mc_vertex_inputs(ctx->M, nv, mesh.V.get(), pos.get(), dir.get(), ctx->stream);
 			if (ctx->M.wide.width) {
-				launch_density_gradient_wide(ctx->M, nv, pos.as<float>(), grad.as<float>(), ctx->n_cus, ctx->stream);
-				launch_network_inference_wide(ctx->M, nv, pos.as<float>(), dir.as<float>(), net.as<uint16_t>(), ctx->n_cus, ctx->stream);
+				launch_density_gradient_wide(ctx->M, nv, pos.get(), grad.get(), ctx->n_cus, ctx->stream);
+				launch_network_inference_wide(ctx->M, nv, pos.get(), dir.get(), net.get(), ctx->n_cus, ctx->stream);
 			} else {
-				launch_density_gradient(ctx->M, nv, pos.as<float>(), grad.as<float>(), ctx->stream);
-				launch_network_inference(ctx->M, nv, pos.as<float>(), dir.as<float>(), net.as<uint16_t>(), ctx->stream);
+				launch_density_gradient(ctx->M, nv, pos.get(), grad.get(), ctx->stream);
+				launch_network_inference(ctx->M, nv, pos.get(), dir.get(), net.get(), ctx->stream);
 			}
-			launch_mc_vertex_attributes(ctx->M, nv, grad.as<float>(), net.as<uint16_t>(), N.as<float>(), C.as<float>(), ctx->stream);
+			launch_mc_vertex_attributes(ctx->M, nv, grad.get(), net.get(), N.get(), C.get(), ctx->stream);
 			NGP_HIP_CHECK(hipGetLastError());
 		}
-		NGP_HIP_CHECK(hipEventRecord(ev.e[3], ctx->stream));
+		NGP_HIP_CHECK(hipEventRecord(ev[3], ctx->stream));
 		read_back(ctx, mesh);
 		ctx->mc_N.resize((size_t)nv * 3);
 		ctx->mc_C.resize((size_t)nv * 3);
-		NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_N.data(), N.p, ctx->mc_N.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-		NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_C.data(), C.p, ctx->mc_C.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_N.data(), N.get(), ctx->mc_N.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		NGP_HIP_CHECK(hipMemcpyAsync(ctx->mc_C.data(), C.get(), ctx->mc_C.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		// lattice; marching cubes (count, scan, the read-back of the two totals, emit); normals + colours. The host copies of the mesh follow.
-		for (int s = 0; s < 3; ++s) NGP_HIP_CHECK(hipEventElapsedTime(&ctx->mc_ms[s], ev.e[s], ev.e[s + 1]));
+		for (int s = 0; s < 3; ++s) NGP_HIP_CHECK(hipEventElapsedTime(&ctx->mc_ms[s], ev[s], ev[s + 1]));
 		ctx->mc_valid = ctx->mc_attrs = true;
 		if (n_verts) *n_verts = nv;
 		if (n_tris) *n_tris = (uint32_t)(ctx->mc_F.size() / 3);
@@ -213,7 +196,7 @@ int ngp_compute_marching_cubes_mesh(ngp_ctx* ctx, const uint32_t* res3, const fl
 
 int ngp_get_marching_cubes_mesh(ngp_ctx* ctx, float* V, float* N, float* C, uint32_t* F) {
 	return guarded(ctx, [&] {
-		require_device(ctx);
+		require_device(ctx, NEEDS);
 		if (!ctx->mc_valid) throw std::runtime_error("no marching-cubes mesh has been computed");
 		if ((N || C) && !ctx->mc_attrs) throw std::runtime_error("a mesh of a caller's lattice (ngp_marching_cubes) has no normals or colours");
 		if (V) memcpy(V, ctx->mc_V.data(), ctx->mc_V.size() * sizeof(float));
@@ -225,7 +208,7 @@ int ngp_get_marching_cubes_mesh(ngp_ctx* ctx, float* V, float* N, float* C, uint
 
 int ngp_get_marching_cubes_timings(ngp_ctx* ctx, float* ms3) {
 	return guarded(ctx, [&] {
-		require_device(ctx);
+		require_device(ctx, NEEDS);
 		if (!ms3) throw std::runtime_error("null argument");
 		memcpy(ms3, ctx->mc_ms, sizeof(ctx->mc_ms));
 	});
@@ -233,7 +216,7 @@ int ngp_get_marching_cubes_timings(ngp_ctx* ctx, float* ms3) {
 
 int ngp_save_marching_cubes_mesh(ngp_ctx* ctx, const char* path) {
 	return guarded(ctx, [&] {
-		require_device(ctx);
+		require_device(ctx, NEEDS);
 		if (!path) throw std::runtime_error("null argument");
 		const std::string p(path);
 		const bool obj = ends_with_ci(p, ".obj"), ply = ends_with_ci(p, ".ply");

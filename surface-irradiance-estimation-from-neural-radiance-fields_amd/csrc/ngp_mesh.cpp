@@ -104,20 +104,10 @@ void build_bvh4(std::vector<Triangle>& triangles, uint32_t n_primitives_per_leaf
 	}
 }
 
-void free_mesh_device(HostMesh& m) {
-	if (m.d_tris) (void)hipFree(m.d_tris);
-	if (m.d_nodes) (void)hipFree(m.d_nodes);
-	m.d_tris = nullptr;
-	m.d_nodes = nullptr;
-}
-
 // after any change of the mesh list: scene AABB (load_scene :3183-3189) and the device-side MeshRef table
 void rebuild_scene(ngp_ctx* ctx) {
 	++ctx->mesh_generation;
-	if (ctx->d_meshrefs) {
-		(void)hipFree(ctx->d_meshrefs);
-		ctx->d_meshrefs = nullptr;
-	}
+	ctx->d_meshrefs.reset();
 	ctx->mesh_scene = MeshSceneParams{};
 	if (ctx->meshes.empty()) return;
 	V3 lo = ld(ctx->meshes[0].bmin), hi = ld(ctx->meshes[0].bmax);
@@ -133,21 +123,18 @@ void rebuild_scene(ngp_ctx* ctx) {
 	for (size_t i = 0; i < refs.size(); ++i) {
 		HostMesh& m = ctx->meshes[i];
 		if (!m.d_tris) {
-			NGP_HIP_CHECK(hipMalloc((void**)&m.d_tris, m.tris.size() * sizeof(Triangle)));
-			NGP_HIP_CHECK(hipMemcpy(m.d_tris, m.tris.data(), m.tris.size() * sizeof(Triangle), hipMemcpyHostToDevice));
-			NGP_HIP_CHECK(hipMalloc((void**)&m.d_nodes, m.nodes.size() * sizeof(TriangleBvhNode)));
-			NGP_HIP_CHECK(hipMemcpy(m.d_nodes, m.nodes.data(), m.nodes.size() * sizeof(TriangleBvhNode), hipMemcpyHostToDevice));
+			m.d_tris.upload(m.tris.data(), m.tris.size());
+			m.d_nodes.upload(m.nodes.data(), m.nodes.size());
 		}
-		refs[i].nodes = m.d_nodes;
-		refs[i].tris = m.d_tris;
+		refs[i].nodes = m.d_nodes.get();
+		refs[i].tris = m.d_tris.get();
 		memcpy(refs[i].bmin, m.bmin, sizeof(m.bmin));
 		memcpy(refs[i].bmax, m.bmax, sizeof(m.bmax));
-		refs[i].n_tris = (uint32_t)m.tris.size();
-		refs[i].n_nodes = (uint32_t)m.nodes.size();
+		refs[i].n_tris = (uint32_t)m.d_tris.size();
+		refs[i].n_nodes = (uint32_t)m.d_nodes.size();
 	}
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_meshrefs, refs.size() * sizeof(MeshRef)));
-	NGP_HIP_CHECK(hipMemcpy(ctx->d_meshrefs, refs.data(), refs.size() * sizeof(MeshRef), hipMemcpyHostToDevice));
-	ctx->mesh_scene.meshes = ctx->d_meshrefs;
+	ctx->d_meshrefs.upload(refs.data(), refs.size());
+	ctx->mesh_scene.meshes = ctx->d_meshrefs.get();
 }
 
 // Testbed::load_mesh (:2786-2866): normalise into the unit cube around `center`, build the BVH
@@ -261,7 +248,6 @@ extern "C" {
 
 int ngp_clear_meshes(ngp_ctx* ctx) {
 	return guarded(ctx, [&] {
-		for (auto& m : ctx->meshes) free_mesh_device(m);
 		ctx->meshes.clear();
 		rebuild_scene(ctx);
 	});
@@ -285,7 +271,6 @@ int ngp_load_scene(ngp_ctx* ctx, const char* json_path) {
 		if (!json.is_object() || json.size() == 0) throw std::runtime_error("Geometry file must contain an array of geometry metadata.");
 		const mj::Value& geometries = json.at("geometry");
 		const std::string base = parent_dir(json_path);
-		for (auto& m : ctx->meshes) free_mesh_device(m);
 		ctx->meshes.clear();
 		for (const mj::Value& g : geometries.arr) {
 			std::string path = g.at("path").str();
@@ -336,22 +321,17 @@ int ngp_set_geometry_opts(ngp_ctx* ctx, const ngp_geometry_opts* o) {
 
 int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* directions) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
+		require_device(ctx);
 		if (ctx->meshes.empty()) throw std::runtime_error("no meshes loaded");
 		if (n == 0) return;
 		if (!positions || !directions) throw std::runtime_error("null argument");
-		float *d_p = nullptr, *d_d = nullptr;
-		const size_t bytes = (size_t)n * 3 * sizeof(float);
-		NGP_HIP_CHECK(hipMalloc((void**)&d_p, bytes));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_d, bytes));
-		NGP_HIP_CHECK(hipMemcpy(d_p, positions, bytes, hipMemcpyHostToDevice));
-		NGP_HIP_CHECK(hipMemcpy(d_d, directions, bytes, hipMemcpyHostToDevice));
-		launch_trace_mesh_rays(ctx->mesh_scene, n, d_p, d_d, ctx->stream);
+		DevArray<float> d_p, d_d;
+		d_p.upload(positions, (size_t)n * 3);
+		d_d.upload(directions, (size_t)n * 3);
+		launch_trace_mesh_rays(ctx->mesh_scene, n, d_p.get(), d_d.get(), ctx->stream);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		NGP_HIP_CHECK(hipMemcpy(positions, d_p, bytes, hipMemcpyDeviceToHost));
-		NGP_HIP_CHECK(hipMemcpy(directions, d_d, bytes, hipMemcpyDeviceToHost));
-		(void)hipFree(d_p);
-		(void)hipFree(d_d);
+		NGP_HIP_CHECK(hipMemcpy(positions, d_p.get(), d_p.bytes(), hipMemcpyDeviceToHost));
+		NGP_HIP_CHECK(hipMemcpy(directions, d_d.get(), d_d.bytes(), hipMemcpyDeviceToHost));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
@@ -362,8 +342,7 @@ namespace {
 // trace the fan(s) described by P in ONE persistent launch, reduce to the probe texture(s), tabulate E(n) at the texel directions
 void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	using namespace ngp;
-	if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-	if (!ctx->model_loaded) throw std::runtime_error("No network available.");
+	require_model(ctx);
 	ngp::sync_inference_model(ctx);
 	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error("irradiance probes are built for the configs/nerf/base.json rgb head (2 hidden layers)");
 	ensure_sync_buffers(ctx);
@@ -374,12 +353,11 @@ void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	if (n_rays64 > (1ull << 28)) throw std::runtime_error("probe too large");
 	P.n_rays = (uint32_t)n_rays64;
 	const uint32_t n_texels = P.n_theta * P.n_phi * n_probes;
-	NGP_HIP_CHECK(hipMalloc((void**)&P.ray_rgba, (size_t)P.n_rays * sizeof(float4)));
-	if (ctx->d_envmap) (void)hipFree(ctx->d_envmap);
-	if (ctx->d_irradiance) (void)hipFree(ctx->d_irradiance);
-	ctx->d_envmap = ctx->d_irradiance = nullptr;
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_envmap, (size_t)n_texels * sizeof(float4)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_irradiance, (size_t)n_texels * sizeof(float4)));
+	DevArray<float4> ray_rgba(P.n_rays);
+	P.ray_rgba = ray_rgba.get();
+	ctx->d_envmap.reset(), ctx->d_irradiance.reset();
+	ctx->d_envmap.reset(n_texels);
+	ctx->d_irradiance.reset(n_texels);
 	hipStream_t stream = ctx->stream;
 	if (ctx->last_stream && ctx->last_stream != stream) NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
@@ -404,16 +382,15 @@ void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	}
 	launch_trace_probe(M, F, P, ctx->n_cus, stream);
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
-	launch_probe_reduce(P, ctx->d_envmap, stream);
-	launch_irradiance(P, ctx->d_envmap, n_texels, nullptr, ctx->d_irradiance, stream);
+	launch_probe_reduce(P, ctx->d_envmap.get(), stream);
+	launch_irradiance(P, ctx->d_envmap.get(), n_texels, nullptr, ctx->d_irradiance.get(), stream);
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
 	ctx->hist_n_rays[slot] = P.n_rays;
 	ctx->last_stream = stream;
 	++ctx->n_calls;
 	NGP_HIP_CHECK(hipStreamSynchronize(stream));
 	NGP_HIP_CHECK(hipGetLastError());
-	(void)hipFree(P.ray_rgba);
-	P.ray_rgba = nullptr;
+	P.ray_rgba = nullptr; // (ray_rgba goes out of scope)
 	++ctx->probe_generation;
 	ctx->env_probe = P;
 	ctx->env_n_theta = P.n_theta;
@@ -436,7 +413,7 @@ int ngp_compute_envmap(ngp_ctx* ctx, const ngp_probe_desc* d, float* rgba_out) {
 		P.n_origin = d->mode == NGP_PROBE_MULTI_CENTER ? d->n_origin : 1u;
 		for (int i = 0; i < 3; ++i) P.origin[i] = d->origin[i];
 		compute_probes(ctx, P, d->min_transmittance);
-		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap, env_texels(ctx) * sizeof(float4), hipMemcpyDeviceToHost));
+		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap.get(), env_texels(ctx) * sizeof(float4), hipMemcpyDeviceToHost));
 	});
 }
 
@@ -453,7 +430,7 @@ int ngp_compute_envmap_grid(ngp_ctx* ctx, const ngp_probe_grid_desc* d, float* r
 		P.grid_y = d->grid_y;
 		P.shell_radius = d->shell_radius;
 		compute_probes(ctx, P, d->min_transmittance);
-		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap, env_texels(ctx) * sizeof(float4), hipMemcpyDeviceToHost));
+		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap.get(), env_texels(ctx) * sizeof(float4), hipMemcpyDeviceToHost));
 	});
 }
 
@@ -463,8 +440,8 @@ int ngp_get_envmap(ngp_ctx* ctx, uint32_t* n_theta, uint32_t* n_phi, float* rgba
 		if (n_theta) *n_theta = ctx->env_n_theta;
 		if (n_phi) *n_phi = ctx->env_n_phi;
 		const size_t bytes = env_texels(ctx) * sizeof(float4); // a grid returns grid_x * grid_y textures back to back (ngp_get_envmap_grid tells how many)
-		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap, bytes, hipMemcpyDeviceToHost));
-		if (irradiance_rgba_out) NGP_HIP_CHECK(hipMemcpy(irradiance_rgba_out, ctx->d_irradiance, bytes, hipMemcpyDeviceToHost));
+		if (rgba_out) NGP_HIP_CHECK(hipMemcpy(rgba_out, ctx->d_envmap.get(), bytes, hipMemcpyDeviceToHost));
+		if (irradiance_rgba_out) NGP_HIP_CHECK(hipMemcpy(irradiance_rgba_out, ctx->d_irradiance.get(), bytes, hipMemcpyDeviceToHost));
 	});
 }
 
@@ -507,15 +484,11 @@ int ngp_irradiance(ngp_ctx* ctx, uint32_t n, const float* normals, float* rgb_ou
 		if (ctx->env_probe.mode == 3) throw std::runtime_error("the probe texture is a grid: use ngp_irradiance_at (position + normal)");
 		if (n == 0) return;
 		if (!normals || !rgb_out) throw std::runtime_error("null argument");
-		float* d_n = nullptr;
-		float4* d_o = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_n, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_o, (size_t)n * sizeof(float4)));
-		NGP_HIP_CHECK(hipMemcpy(d_n, normals, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		launch_irradiance(ctx->env_probe, ctx->d_envmap, n, d_n, d_o, ctx->stream);
-		download_rgb(ctx, d_o, n, rgb_out);
-		(void)hipFree(d_n);
-		(void)hipFree(d_o);
+		DevArray<float> d_n;
+		d_n.upload(normals, (size_t)n * 3);
+		DevArray<float4> d_o(n);
+		launch_irradiance(ctx->env_probe, ctx->d_envmap.get(), n, d_n.get(), d_o.get(), ctx->stream);
+		download_rgb(ctx, d_o.get(), n, rgb_out);
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
@@ -525,18 +498,12 @@ int ngp_irradiance_at(ngp_ctx* ctx, uint32_t n, const float* positions, const fl
 		if (!ctx->d_irradiance) throw std::runtime_error("no probe texture: call ngp_compute_envmap / ngp_compute_envmap_grid first");
 		if (n == 0) return;
 		if (!positions || !normals || !rgb_out) throw std::runtime_error("null argument");
-		float *d_p = nullptr, *d_n = nullptr;
-		float4* d_o = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_p, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_n, (size_t)n * 3 * sizeof(float)));
-		NGP_HIP_CHECK(hipMalloc((void**)&d_o, (size_t)n * sizeof(float4)));
-		NGP_HIP_CHECK(hipMemcpy(d_p, positions, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		NGP_HIP_CHECK(hipMemcpy(d_n, normals, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
-		launch_irradiance_lookup(ngp::irradiance_map_of(ctx), n, d_p, d_n, d_o, ctx->stream);
-		download_rgb(ctx, d_o, n, rgb_out);
-		(void)hipFree(d_p);
-		(void)hipFree(d_n);
-		(void)hipFree(d_o);
+		DevArray<float> d_p, d_n;
+		d_p.upload(positions, (size_t)n * 3);
+		d_n.upload(normals, (size_t)n * 3);
+		DevArray<float4> d_o(n);
+		launch_irradiance_lookup(ngp::irradiance_map_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
+		download_rgb(ctx, d_o.get(), n, rgb_out);
 		NGP_HIP_CHECK(hipGetLastError());
 	});
 }
@@ -550,36 +517,33 @@ namespace ngp {
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->shade = primary->shade;
 	if (peer->synced_mesh_generation != primary->mesh_generation) {
-		NGP_HIP_CHECK(hipSetDevice(peer->device));
+		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)
-		for (auto& m : peer->meshes) free_mesh_device(m);
 		peer->meshes.clear();
-		for (const HostMesh& m : primary->meshes) {
+		for (const HostMesh& m : primary->meshes) { // uploaded from the primary's host copies; the replica keeps none
 			HostMesh c;
-			c.tris = m.tris;
-			c.nodes = m.nodes;
 			memcpy(c.bmin, m.bmin, sizeof(c.bmin));
 			memcpy(c.bmax, m.bmax, sizeof(c.bmax));
 			memcpy(c.center, m.center, sizeof(c.center));
+			c.d_tris.upload(m.tris.data(), m.tris.size());
+			c.d_nodes.upload(m.nodes.data(), m.nodes.size());
 			peer->meshes.push_back(std::move(c));
 		}
 		rebuild_scene(peer);
 		peer->synced_mesh_generation = primary->mesh_generation;
-		NGP_HIP_CHECK(hipSetDevice(primary->device));
 	}
 	if (peer->synced_probe_generation != primary->probe_generation && primary->d_irradiance) {
 		const size_t texels = (size_t)primary->env_n_theta * primary->env_n_phi * (primary->env_probe.mode == 3 ? (size_t)primary->env_probe.grid_x * primary->env_probe.grid_y : 1u);
-		NGP_HIP_CHECK(hipSetDevice(peer->device));
-		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream));
-		if (peer->d_envmap) (void)hipFree(peer->d_envmap);
-		if (peer->d_irradiance) (void)hipFree(peer->d_irradiance);
-		peer->d_envmap = peer->d_irradiance = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&peer->d_envmap, texels * sizeof(float4)));
-		NGP_HIP_CHECK(hipMalloc((void**)&peer->d_irradiance, texels * sizeof(float4)));
-		NGP_HIP_CHECK(hipSetDevice(primary->device));
+		{
+			DeviceGuard g(peer->device);
+			NGP_HIP_CHECK(hipStreamSynchronize(peer->stream));
+			peer->d_envmap.reset(), peer->d_irradiance.reset();
+			peer->d_envmap.reset(texels);
+			peer->d_irradiance.reset(texels);
+		}
 		NGP_HIP_CHECK(hipStreamSynchronize(primary->stream)); // compute_probes ends synchronised; a no-op in practice
-		NGP_HIP_CHECK(hipMemcpyPeer(peer->d_envmap, peer->device, primary->d_envmap, primary->device, texels * sizeof(float4)));
-		NGP_HIP_CHECK(hipMemcpyPeer(peer->d_irradiance, peer->device, primary->d_irradiance, primary->device, texels * sizeof(float4)));
+		NGP_HIP_CHECK(hipMemcpyPeer(peer->d_envmap.get(), peer->device, primary->d_envmap.get(), primary->device, texels * sizeof(float4)));
+		NGP_HIP_CHECK(hipMemcpyPeer(peer->d_irradiance.get(), peer->device, primary->d_irradiance.get(), primary->device, texels * sizeof(float4)));
 		peer->env_probe = primary->env_probe;
 		peer->env_n_theta = primary->env_n_theta;
 		peer->env_n_phi = primary->env_n_phi;

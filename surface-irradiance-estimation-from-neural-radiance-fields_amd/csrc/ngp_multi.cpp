@@ -16,15 +16,6 @@ void launch_unpack_tiles(const float4* gathered_rgba, const float* gathered_dept
                          hipStream_t stream);
 
 namespace {
-struct DeviceGuard {
-	int prev = 0;
-	explicit DeviceGuard(int dev) {
-		(void)hipGetDevice(&prev);
-		NGP_HIP_CHECK(hipSetDevice(dev));
-	}
-	~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 // sync_device (src/testbed.cu:5523-5563): a device whose replica lags the primary's gets what changed, device to device
 // where the shapes stand (parameters after training steps, the occupancy grid after a refresh: the reference's
 // cudaMemcpyPeerAsync of params + bitfield, :5542-5555), through the host descriptor when the model itself was replaced
@@ -64,9 +55,9 @@ void sync_peer_model(ngp_ctx* primary, ngp_ctx* peer) {
 	order_after_frames(peer, s); // (frames a caller put on another stream of the peer, if any)
 	if (grid) {
 		const size_t n_cells = (size_t)NERF_GRID_N_CELLS * (primary->max_cascade + 1);
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_bitfield, peer->device, primary->d_bitfield, primary->device, (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES, s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_coarse, peer->device, primary->d_coarse, primary->device, ((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16) * sizeof(uint32_t), s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_density_f32, peer->device, primary->d_density_f32, primary->device, n_cells * sizeof(float), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_bitfield.get(), peer->device, primary->d_bitfield.get(), primary->device, (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES, s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_coarse.get(), peer->device, primary->d_coarse.get(), primary->device, ((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16) * sizeof(uint32_t), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_density_f32.get(), peer->device, primary->d_density_f32.get(), primary->device, n_cells * sizeof(float), s));
 		peer->bitfield_mean = primary->bitfield_mean;
 		peer->grid_rng_state = primary->grid_rng_state;
 		peer->grid_rng_inc = primary->grid_rng_inc;
@@ -75,13 +66,13 @@ void sync_peer_model(ngp_ctx* primary, ngp_ctx* peer) {
 		peer->synced_grid_generation = primary->grid_generation;
 	}
 	if (params) {
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_params, peer->device, primary->d_params, primary->device, primary->M.grid_bytes, s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_xgrid, peer->device, primary->d_xgrid, primary->device, primary->M.xgrid_bytes, s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_wfrags, peer->device, primary->d_wfrags, primary->device, (size_t)(N_FRAGS_MAX + N_NORMALS_FRAGS) * 64 * sizeof(uint4), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_params.get(), peer->device, primary->d_params.get(), primary->device, primary->M.grid_bytes, s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_xgrid.get(), peer->device, primary->d_xgrid.get(), primary->device, primary->M.xgrid_bytes, s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_wfrags.get(), peer->device, primary->d_wfrags.get(), primary->device, (size_t)(N_FRAGS_MAX + N_NORMALS_FRAGS) * 64 * sizeof(uint4), s));
 		peer->synced_params_generation = primary->params_generation;
 	}
 	mark_model_updated(peer, s); // the peer's frames read the new tables
-	if (!peer->ev_synced) NGP_HIP_CHECK(hipEventCreateWithFlags(&peer->ev_synced, hipEventDisableTiming));
+	if (!peer->ev_synced) peer->ev_synced = new_event(hipEventDisableTiming);
 	NGP_HIP_CHECK(hipEventRecord(peer->ev_synced, s));
 	{
 		DeviceGuard gp(primary->device);
@@ -89,29 +80,28 @@ void sync_peer_model(ngp_ctx* primary, ngp_ctx* peer) {
 	}
 }
 
+// colour + depth of n pixels; both go before the new ones come, the second one's size stands for both
+void ensure_pair(DevArray<float4>& rgba, DevArray<float>& depth, size_t n) {
+	if (n <= depth.size()) return;
+	rgba.reset(), depth.reset();
+	rgba.reset(n);
+	depth.reset(n);
+}
+
+void enable_peer_access(int dev, int peer) {
+	try {
+		DeviceGuard g(dev);
+		(void)hipDeviceEnablePeerAccess(peer, 0);
+	} catch (const std::exception&) { // (the device cannot be made current: peer access stays off)
+	}
+	(void)hipGetLastError(); // "already enabled" is fine
+}
+
 void ensure_pack_buffers(ngp_ctx* ctx, size_t n_pixels_packed) {
-	if (n_pixels_packed <= ctx->pack_alloc) return;
-	if (ctx->d_pack_rgba) (void)hipFree(ctx->d_pack_rgba);
-	if (ctx->d_pack_depth) (void)hipFree(ctx->d_pack_depth);
-	ctx->pack_alloc = 0;
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_pack_rgba, n_pixels_packed * sizeof(float4)));
-	NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_pack_depth, n_pixels_packed * sizeof(float)));
-	ctx->pack_alloc = n_pixels_packed;
-	if (!ctx->ev_pack) NGP_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
+	ensure_pair(ctx->d_pack_rgba, ctx->d_pack_depth, n_pixels_packed);
+	if (!ctx->ev_pack) ctx->ev_pack = new_event(hipEventDisableTiming);
 }
 } // namespace
-
-void free_multi_buffers(ngp_ctx* ctx) {
-	if (ctx->d_pack_rgba) (void)hipFree(ctx->d_pack_rgba);
-	if (ctx->d_pack_depth) (void)hipFree(ctx->d_pack_depth);
-	if (ctx->d_gather_rgba) (void)hipFree(ctx->d_gather_rgba);
-	if (ctx->d_gather_depth) (void)hipFree(ctx->d_gather_depth);
-	if (ctx->ev_pack) (void)hipEventDestroy(ctx->ev_pack);
-	ctx->d_pack_rgba = ctx->d_gather_rgba = nullptr;
-	ctx->d_pack_depth = ctx->d_gather_depth = nullptr;
-	ctx->ev_pack = nullptr;
-	ctx->pack_alloc = ctx->gather_alloc = 0;
-}
 
 // One frame over every device of a multi-device context; the assembled image lands in d_rgba / d_depth (device 0), enqueued
 // on `stream` of device 0. Nothing here waits for the GPUs.
@@ -123,15 +113,8 @@ void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_o
 	const size_t packed = (size_t)n_slots * 64;
 	{ // the primary's landing zone for everybody's tiles
 		DeviceGuard g(ctx->device);
-		if (packed * n_dev > ctx->gather_alloc) {
-			if (ctx->d_gather_rgba) (void)hipFree(ctx->d_gather_rgba);
-			if (ctx->d_gather_depth) (void)hipFree(ctx->d_gather_depth);
-			ctx->gather_alloc = 0;
-			NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_gather_rgba, packed * n_dev * sizeof(float4)));
-			NGP_HIP_CHECK(hipMalloc((void**)&ctx->d_gather_depth, packed * n_dev * sizeof(float)));
-			ctx->gather_alloc = packed * n_dev;
-		}
-		if (!ctx->ev_pack) NGP_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
+		ensure_pair(ctx->d_gather_rgba, ctx->d_gather_depth, packed * n_dev);
+		if (!ctx->ev_pack) ctx->ev_pack = new_event(hipEventDisableTiming);
 		// the landing zone is rewritten by every frame: the previous frame's unpack (on `stream` or another stream of this device) must be done with it
 		if (ctx->n_multi_frames > 0) NGP_HIP_CHECK(hipStreamWaitEvent(stream, ctx->ev_unpacked, 0));
 		NGP_HIP_CHECK(hipEventRecord(ctx->ev_pack, stream)); // "the landing zone is free as of here"
@@ -157,21 +140,21 @@ void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_o
 		o.shard_count = n_dev;
 		o.packed_output = 1;
 		if (i > 0) NGP_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_pack, 0)); // do not push into a landing zone the previous frame still reads
-		render_frames_on(dev, cam, o, dev->d_pack_rgba, dev->d_pack_depth, s);
+		render_frames_on(dev, cam, o, dev->d_pack_rgba.get(), dev->d_pack_depth.get(), s);
 		// push this device's tiles to the primary: one peer copy each for colour and depth (5.2 MB per GPU at 1080p / 8 GPUs), on the
 		// rendering device's stream so that it follows the kernel without a host round trip
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(ctx->d_gather_rgba + packed * i, ctx->device, dev->d_pack_rgba, dev->device, packed * sizeof(float4), s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(ctx->d_gather_depth + packed * i, ctx->device, dev->d_pack_depth, dev->device, packed * sizeof(float), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(ctx->d_gather_rgba.get() + packed * i, ctx->device, dev->d_pack_rgba.get(), dev->device, packed * sizeof(float4), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(ctx->d_gather_depth.get() + packed * i, ctx->device, dev->d_pack_depth.get(), dev->device, packed * sizeof(float), s));
 		if (i > 0) NGP_HIP_CHECK(hipEventRecord(dev->ev_pack, s));
 	}
 	DeviceGuard g(ctx->device);
 	for (ngp_ctx* p : ctx->peers) NGP_HIP_CHECK(hipStreamWaitEvent(stream, p->ev_pack, 0));
 	if (!d_depth) {
 		ensure_frame_buffers_for(ctx, (size_t)cam.width * cam.height);
-		d_depth = ctx->d_depth;
+		d_depth = ctx->d_depth.get();
 	}
-	launch_unpack_tiles(ctx->d_gather_rgba, ctx->d_gather_depth, n_dev, n_slots, cam.width, cam.height, d_rgba, d_depth, stream);
-	if (!ctx->ev_unpacked) NGP_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_unpacked, hipEventDisableTiming));
+	launch_unpack_tiles(ctx->d_gather_rgba.get(), ctx->d_gather_depth.get(), n_dev, n_slots, cam.width, cam.height, d_rgba, d_depth, stream);
+	if (!ctx->ev_unpacked) ctx->ev_unpacked = new_event(hipEventDisableTiming);
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_unpacked, stream));
 	++ctx->n_multi_frames;
 	ctx->last_was_multi = true;
@@ -199,11 +182,8 @@ ngp_ctx* ngp_create_multi(const int* devices, int n_devices) {
 			int can = 0;
 			(void)hipDeviceCanAccessPeer(&can, devices[0], devices[i]);
 			if (can) {
-				(void)hipSetDevice(devices[0]);
-				(void)hipDeviceEnablePeerAccess(devices[i], 0);
-				(void)hipSetDevice(devices[i]);
-				(void)hipDeviceEnablePeerAccess(devices[0], 0);
-				(void)hipGetLastError(); // "already enabled" is fine
+				ngp::enable_peer_access(devices[0], devices[i]);
+				ngp::enable_peer_access(devices[i], devices[0]);
 			}
 		}
 	}

@@ -16,11 +16,6 @@ constexpr uint32_t BATCH_SIZE_GRANULARITY = 128; // tcnn
 
 uint32_t next_multiple(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
-void require_device_model(ngp_ctx* ctx) {
-	if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
-	if (!ctx->model_loaded) throw std::runtime_error("No network available.");
-}
-
 void default_opts(ngp_training_opts& o) {
 	memset(&o, 0, sizeof(o));
 	o.struct_size = sizeof(o);
@@ -44,31 +39,21 @@ void default_opts(ngp_training_opts& o) {
 	o.color_space = 1; // EColorSpace::SRGB
 }
 
-template <typename T>
-void dev_alloc(T*& p, size_t n) {
-	NGP_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
-}
-template <typename T>
-void dev_free(T*& p) {
-	if (p) (void)hipFree((void*)p);
-	p = nullptr;
-}
-
 ModelParams training_model(const ngp_ctx* ctx) {
 	ModelParams M = ctx->M;
 	const TrainState& T = *ctx->train;
-	M.grid = (const uint2*)(T.d_weights + T.n_matrix);
+	M.grid = (const uint2*)(T.d_weights.get() + T.n_matrix);
 	M.xgrid = nullptr; // training kernels read the tcnn-order table only
-	M.wfrags = T.d_tfrags;
+	M.wfrags = T.d_tfrags.get();
 	return M;
 }
 
 // Trainer construction: parameters from the current model (ctx->params), optimizer state zeroed
 TrainState& ensure_training(ngp_ctx* ctx) {
-	require_device_model(ctx);
+	require_model(ctx);
 	if (ctx->M.wide.width) throw std::runtime_error("training is built for the configs/nerf/base.json network; a Frequency-encoding model (configs/nerf/frequency.json) is inference only");
 	if (ctx->train && ctx->train->d_weights) return *ctx->train;
-	if (!ctx->train) ctx->train = new TrainState();
+	if (!ctx->train) ctx->train = std::make_unique<TrainState>();
 	if (ctx->train->opts.struct_size == 0) default_opts(ctx->train->opts);
 	TrainState& T = *ctx->train;
 	const ngp_model_desc& d = ctx->desc;
@@ -78,22 +63,22 @@ TrainState& ensure_training(ngp_ctx* ctx) {
 	T.n_matrix = (uint32_t)(d.n_params - ng);
 	if (T.n_matrix != 10240u) throw std::runtime_error("training is built for the configs/nerf/base.json network (10240 matrix weights)");
 	const size_t n = T.n_params;
-	dev_alloc(T.d_weights_fp32, n);
-	dev_alloc(T.d_weights, n);
-	dev_alloc(T.d_weights_ema, n);
-	dev_alloc(T.d_ema_tmp, n);
-	dev_alloc(T.d_grad, n);
-	dev_alloc(T.d_m1, n);
-	dev_alloc(T.d_m2, n);
-	dev_alloc(T.d_steps, n);
-	dev_alloc(T.d_tfrags, (size_t)N_TFRAGS * 64);
-	dev_alloc(T.d_kfrags, (size_t)N_KFRAGS * 64);
-	dev_alloc(T.d_tfrags_inference, (size_t)N_TFRAGS * 64);
-	dev_alloc(T.d_kfrags_inference, (size_t)N_KFRAGS * 64);
-	dev_alloc(T.d_loss_sum, 1);
-	dev_alloc(T.d_partials, train_backward_partials_floats(ctx->n_cus));
-	NGP_HIP_CHECK(hipMemcpy(T.d_weights, ctx->params.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
-	NGP_HIP_CHECK(hipMemcpy(T.d_weights_ema, ctx->params.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+	T.d_weights_fp32.reset(n);
+	T.d_weights.reset(n);
+	T.d_weights_ema.reset(n);
+	T.d_ema_tmp.reset(n);
+	T.d_grad.reset(n);
+	T.d_m1.reset(n);
+	T.d_m2.reset(n);
+	T.d_steps.reset(n);
+	T.d_tfrags.reset((size_t)N_TFRAGS * 64);
+	T.d_kfrags.reset((size_t)N_KFRAGS * 64);
+	T.d_tfrags_inference.reset((size_t)N_TFRAGS * 64);
+	T.d_kfrags_inference.reset((size_t)N_KFRAGS * 64);
+	T.d_loss_sum.reset(1);
+	T.d_partials.reset(train_backward_partials_floats(ctx->n_cus));
+	NGP_HIP_CHECK(hipMemcpy(T.d_weights.get(), ctx->params.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+	NGP_HIP_CHECK(hipMemcpy(T.d_weights_ema.get(), ctx->params.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
 	{
 		std::vector<float> w(n);
 		for (size_t i = 0; i < n; ++i) {
@@ -112,14 +97,14 @@ TrainState& ensure_training(ngp_ctx* ctx) {
 			else bits = sign | ((exp + 112u) << 23) | (man << 13);
 			memcpy(&w[i], &bits, 4);
 		}
-		NGP_HIP_CHECK(hipMemcpy(T.d_weights_fp32, w.data(), n * sizeof(float), hipMemcpyHostToDevice));
-		NGP_HIP_CHECK(hipMemcpy(T.d_ema_tmp, w.data(), n * sizeof(float), hipMemcpyHostToDevice));
+		NGP_HIP_CHECK(hipMemcpy(T.d_weights_fp32.get(), w.data(), n * sizeof(float), hipMemcpyHostToDevice));
+		NGP_HIP_CHECK(hipMemcpy(T.d_ema_tmp.get(), w.data(), n * sizeof(float), hipMemcpyHostToDevice));
 	}
-	NGP_HIP_CHECK(hipMemset(T.d_grad, 0, n * sizeof(float)));
-	NGP_HIP_CHECK(hipMemset(T.d_m1, 0, n * sizeof(float)));
-	NGP_HIP_CHECK(hipMemset(T.d_m2, 0, n * sizeof(float)));
-	NGP_HIP_CHECK(hipMemset(T.d_steps, 0, n * sizeof(uint32_t)));
-	launch_train_build_fragments(T.d_weights, T.d_tfrags, T.d_kfrags, ctx->stream);
+	NGP_HIP_CHECK(hipMemset(T.d_grad.get(), 0, n * sizeof(float)));
+	NGP_HIP_CHECK(hipMemset(T.d_m1.get(), 0, n * sizeof(float)));
+	NGP_HIP_CHECK(hipMemset(T.d_m2.get(), 0, n * sizeof(float)));
+	NGP_HIP_CHECK(hipMemset(T.d_steps.get(), 0, n * sizeof(uint32_t)));
+	launch_train_build_fragments(T.d_weights.get(), T.d_tfrags.get(), T.d_kfrags.get(), ctx->stream);
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	T.rng.seed(1337u); // m_rng = default_rng_t{m_seed}; the density-grid generator took its first draw (set_model_impl)
 	(void)T.rng.next_uint();
@@ -140,7 +125,7 @@ void upload_images(ngp_ctx* ctx, TrainState& T) {
 	for (const TrainingView& v : ctx->dataset.views) {
 		if (!v.d_pixels) continue; // views without pixels take no part (n_images_for_training counts loaded images)
 		TrainImage im{};
-		im.pixels = v.d_pixels;
+		im.pixels = v.d_pixels.get();
 		im.type = v.image_type;
 		im.res[0] = v.resolution[0]; im.res[1] = v.resolution[1];
 		im.focal[0] = v.focal_length[0]; im.focal[1] = v.focal_length[1];
@@ -151,54 +136,58 @@ void upload_images(ngp_ctx* ctx, TrainState& T) {
 		meta.push_back(im);
 	}
 	if (meta.empty()) throw std::runtime_error("No training data available."); // Testbed::train, src/testbed.cu:4365-4369
-	dev_free(T.d_images);
-	dev_alloc(T.d_images, meta.size());
-	NGP_HIP_CHECK(hipMemcpy(T.d_images, meta.data(), meta.size() * sizeof(TrainImage), hipMemcpyHostToDevice));
+	T.d_images.upload(meta.data(), meta.size());
 	T.n_images = (uint32_t)meta.size();
 	T.images_dirty = false;
 }
 
 void ensure_gen_set(TrainState::GenSet& G, uint32_t n_rays, uint32_t max_samples) {
-	if (!G.counters) dev_alloc(G.counters, 4);
+	if (!G.counters) G.counters.reset(4);
 	if (n_rays > G.cap_rays) {
-		dev_free(G.ray_indices); dev_free(G.rays); dev_free(G.numsteps);
+		G.cap_rays = 0;
+		G.ray_indices.reset(), G.rays.reset(), G.numsteps.reset();
+		G.ray_indices.reset(n_rays);
+		G.rays.reset((size_t)n_rays * 6);
+		G.numsteps.reset((size_t)n_rays * 2);
 		G.cap_rays = n_rays;
-		dev_alloc(G.ray_indices, n_rays);
-		dev_alloc(G.rays, (size_t)n_rays * 6);
-		dev_alloc(G.numsteps, (size_t)n_rays * 2);
 	}
 	if (max_samples > G.cap_samples) {
-		dev_free(G.coords);
+		G.cap_samples = 0;
+		G.coords.reset(((size_t)max_samples + 64) * TRAIN_COORD_FLOATS);
 		G.cap_samples = max_samples;
-		dev_alloc(G.coords, ((size_t)max_samples + 64) * TRAIN_COORD_FLOATS);
 	}
 }
 void ensure_workspace(ngp_ctx* ctx, TrainState& T, uint32_t n_rays, uint32_t max_samples, uint32_t target) {
 	TrainBatch& B = T.B;
 	if (!T.stream2) {
-		NGP_HIP_CHECK(hipStreamCreateWithFlags(&T.stream2, hipStreamNonBlocking));
-		NGP_HIP_CHECK(hipEventCreateWithFlags(&T.ev_gen, hipEventDisableTiming));
-		NGP_HIP_CHECK(hipEventCreateWithFlags(&T.ev_loss, hipEventDisableTiming));
-		NGP_HIP_CHECK(hipHostMalloc((void**)&T.h_counters, 8 * sizeof(uint32_t)));
+		T.stream2 = new_stream(hipStreamNonBlocking);
+		T.ev_gen = new_event(hipEventDisableTiming);
+		T.ev_loss = new_event(hipEventDisableTiming);
+		T.h_counters.reset(8);
 	}
 	if (n_rays > T.cap_loss) { // read by the previous step's loss kernels only: complete (the host waited for ev_loss)
-		dev_free(B.loss);
+		T.cap_loss = 0;
+		T.loss.reset(n_rays);
+		B.loss = T.loss.get();
 		T.cap_loss = n_rays;
-		dev_alloc(B.loss, n_rays);
 	}
 	if (max_samples > T.cap_out) {
-		dev_free(B.mlp_out);
+		T.cap_out = 0;
+		T.mlp_out.reset(((size_t)max_samples + 64) * 4);
+		B.mlp_out = T.mlp_out.get();
 		T.cap_out = max_samples;
-		dev_alloc(B.mlp_out, ((size_t)max_samples + 64) * 4);
 	}
 	if (target > T.cap_target) {
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // a backward pass may still read the old buffers
-		dev_free(B.coords_compacted); dev_free(B.dloss);
+		T.cap_target = 0;
+		T.coords_compacted.reset(), T.dloss.reset();
+		T.coords_compacted.reset(((size_t)target + 64) * TRAIN_COORD_FLOATS);
+		T.dloss.reset(((size_t)target + 64) * 4);
+		NGP_HIP_CHECK(hipMemset(T.coords_compacted.get(), 0, T.coords_compacted.bytes()));
+		NGP_HIP_CHECK(hipMemset(T.dloss.get(), 0, T.dloss.bytes()));
+		B.coords_compacted = T.coords_compacted.get();
+		B.dloss = T.dloss.get();
 		T.cap_target = target;
-		dev_alloc(B.coords_compacted, ((size_t)target + 64) * TRAIN_COORD_FLOATS);
-		dev_alloc(B.dloss, ((size_t)target + 64) * 4);
-		NGP_HIP_CHECK(hipMemset(B.coords_compacted, 0, ((size_t)target + 64) * TRAIN_COORD_FLOATS * sizeof(float)));
-		NGP_HIP_CHECK(hipMemset(B.dloss, 0, ((size_t)target + 64) * 4 * sizeof(uint16_t)));
 	}
 }
 
@@ -235,20 +224,21 @@ TrainStepParams step_params(const ngp_ctx* ctx, const TrainState& T, uint32_t ta
 	return P;
 }
 
-TrainBatch gen_batch(const TrainState::GenSet& G) {
-	TrainBatch B{};
-	B.counters = G.counters;
-	B.ray_indices = G.ray_indices;
-	B.rays = G.rays;
-	B.numsteps = G.numsteps;
-	B.coords = G.coords;
-	return B;
+// B's view of a generation set (the shared buffers stay as they are)
+void bind_gen_set(TrainBatch& B, const TrainState::GenSet& G) {
+	B.counters = G.counters.get();
+	B.ray_indices = G.ray_indices.get();
+	B.rays = G.rays.get();
+	B.numsteps = G.numsteps.get();
+	B.coords = G.coords.get();
 }
 void launch_generate(ngp_ctx* ctx, TrainState& T, int set, const TrainStepParams& P, hipStream_t stream) {
 	TrainState::GenSet& G = T.gen[set];
 	ensure_gen_set(G, P.n_rays, P.max_samples);
-	NGP_HIP_CHECK(hipMemsetAsync(G.counters, 0, 4 * sizeof(uint32_t), stream));
-	launch_train_generate_samples(training_model(ctx), P, T.d_images, gen_batch(G), stream);
+	NGP_HIP_CHECK(hipMemsetAsync(G.counters.get(), 0, 4 * sizeof(uint32_t), stream));
+	TrainBatch B{};
+	bind_gen_set(B, G);
+	launch_train_generate_samples(training_model(ctx), P, T.d_images.get(), B, stream);
 }
 
 // generate_training_samples_nerf + inference + compute_loss_kernel_train_nerf of train_nerf_step
@@ -271,20 +261,15 @@ void prepare_batch(ngp_ctx* ctx, TrainState& T, uint32_t target_batch, bool get_
 	T.pregenerated = false;
 	if (T.training_step == 0) T.n_rays_total = 0;
 	T.n_rays_total += P.n_rays;
-	const TrainState::GenSet& G = T.gen[T.cur];
-	T.B.counters = G.counters;
-	T.B.ray_indices = G.ray_indices;
-	T.B.rays = G.rays;
-	T.B.numsteps = G.numsteps;
-	T.B.coords = G.coords;
+	bind_gen_set(T.B, T.gen[T.cur]);
 	const ModelParams M = training_model(ctx);
 	NGP_HIP_CHECK(hipMemsetAsync(T.B.loss, 0, (size_t)P.n_rays * sizeof(float), stream));
-	launch_train_inference(M, T.d_tfrags, T.B.counters, P.max_samples, T.B.coords, T.B.mlp_out, ctx->n_cus, stream);
-	launch_train_loss(M, P, T.d_images, T.B, stream);
+	launch_train_inference(M, T.d_tfrags.get(), T.B.counters, P.max_samples, T.B.coords, T.B.mlp_out, ctx->n_cus, stream);
+	launch_train_loss(M, P, T.d_images.get(), T.B, stream);
 	// what the host needs to plan the next step, as soon as the loss kernel is through
-	if (get_loss_scalar) launch_train_loss_sum(T.B.loss, P.n_rays, T.d_loss_sum, stream);
-	NGP_HIP_CHECK(hipMemcpyAsync(T.h_counters, T.B.counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-	if (get_loss_scalar) NGP_HIP_CHECK(hipMemcpyAsync(T.h_counters + 4, T.d_loss_sum, sizeof(float), hipMemcpyDeviceToHost, stream));
+	if (get_loss_scalar) launch_train_loss_sum(T.B.loss, P.n_rays, T.d_loss_sum.get(), stream);
+	NGP_HIP_CHECK(hipMemcpyAsync(T.h_counters.get(), T.B.counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+	if (get_loss_scalar) NGP_HIP_CHECK(hipMemcpyAsync(T.h_counters.get() + 4, T.d_loss_sum.get(), sizeof(float), hipMemcpyDeviceToHost, stream));
 	NGP_HIP_CHECK(hipEventRecord(T.ev_loss, stream));
 	T.last_step = P;
 	T.batch_ready = true;
@@ -292,7 +277,7 @@ void prepare_batch(ngp_ctx* ctx, TrainState& T, uint32_t target_batch, bool get_
 
 void backward(ngp_ctx* ctx, TrainState& T, uint32_t target_batch) {
 	if (!T.batch_ready) throw std::runtime_error("no training batch prepared");
-	launch_train_backward(training_model(ctx), T.d_tfrags, T.d_kfrags, T.B.counters, target_batch, T.B.coords_compacted, T.B.dloss, T.d_grad, T.n_matrix, T.d_partials, ctx->n_cus, ctx->stream);
+	launch_train_backward(training_model(ctx), T.d_tfrags.get(), T.d_kfrags.get(), T.B.counters, target_batch, T.B.coords_compacted, T.B.dloss, T.d_grad.get(), T.n_matrix, T.d_partials.get(), ctx->n_cus, ctx->stream);
 }
 
 // m_trainer->optimizer_step (:3002): ExponentialDecay > Adam > Ema, then the fragments of the new weights. Asynchronous.
@@ -314,8 +299,8 @@ void launch_optimizer(ngp_ctx* ctx, TrainState& T) {
 	A.ema_decay = T.opts.ema_decay;
 	A.ema_debias_old = 1.0f - std::pow(T.opts.ema_decay, (float)(T.optimizer_step - 1));
 	A.ema_debias_new = 1.0f / (1.0f - std::pow(T.opts.ema_decay, (float)T.optimizer_step));
-	launch_train_optimizer(A, T.d_weights_fp32, T.d_weights, T.d_grad, T.d_m1, T.d_m2, T.d_steps, T.d_ema_tmp, ema ? T.d_weights_ema : nullptr, stream);
-	launch_train_build_fragments(T.d_weights, T.d_tfrags, T.d_kfrags, stream);
+	launch_train_optimizer(A, T.d_weights_fp32.get(), T.d_weights.get(), T.d_grad.get(), T.d_m1.get(), T.d_m2.get(), T.d_steps.get(), T.d_ema_tmp.get(), ema ? T.d_weights_ema.get() : nullptr, stream);
+	launch_train_build_fragments(T.d_weights.get(), T.d_tfrags.get(), T.d_kfrags.get(), stream);
 	if (T.opts.decay_interval > 0 && T.optimizer_step >= T.opts.decay_start && (T.optimizer_step - T.opts.decay_start) % T.opts.decay_interval == 0) T.lr_factor *= T.opts.decay_base;
 	T.inference_dirty = true;
 	T.host_params_dirty = true;
@@ -326,9 +311,9 @@ void launch_optimizer(ngp_ctx* ctx, TrainState& T) {
 // the backward pass and the optimizer keep running
 float finish_step(TrainState& T, uint32_t target_batch, bool get_loss_scalar) {
 	NGP_HIP_CHECK(hipEventSynchronize(T.ev_loss));
-	const uint32_t* counters = T.h_counters;
+	const uint32_t* counters = T.h_counters.get();
 	float loss_sum = 0.f;
-	memcpy(&loss_sum, T.h_counters + 4, sizeof(float));
+	memcpy(&loss_sum, T.h_counters.get() + 4, sizeof(float));
 	++T.training_step;
 	T.rng.advance();
 	T.measured_batch_size = 0;
@@ -412,19 +397,9 @@ bool probe_image_size(const std::string& path, int& width, int& height) {
 
 void free_training(ngp_ctx* ctx) {
 	if (!ctx->train) return;
-	TrainState& T = *ctx->train;
-	dev_free(T.d_weights_fp32); dev_free(T.d_weights); dev_free(T.d_weights_ema); dev_free(T.d_ema_tmp); dev_free(T.d_grad); dev_free(T.d_m1); dev_free(T.d_m2);
-	dev_free(T.d_steps); dev_free(T.d_tfrags); dev_free(T.d_kfrags); dev_free(T.d_tfrags_inference); dev_free(T.d_kfrags_inference); dev_free(T.d_images); dev_free(T.d_loss_sum); dev_free(T.d_partials);
-	if (T.stream2) (void)hipStreamSynchronize(T.stream2);
-	for (auto& G : T.gen) { dev_free(G.counters); dev_free(G.ray_indices); dev_free(G.rays); dev_free(G.numsteps); dev_free(G.coords); }
-	dev_free(T.B.mlp_out); dev_free(T.B.coords_compacted); dev_free(T.B.dloss); dev_free(T.B.loss);
-	if (T.stream2) (void)hipStreamDestroy(T.stream2);
-	if (T.ev_gen) (void)hipEventDestroy(T.ev_gen);
-	if (T.ev_loss) (void)hipEventDestroy(T.ev_loss);
-	if (T.h_counters) (void)hipHostFree(T.h_counters);
-	const ngp_training_opts keep = T.opts; // settings outlive a model (they belong to the Testbed, not to the network)
-	delete ctx->train;
-	ctx->train = new TrainState();
+	if (ctx->train->stream2) (void)hipStreamSynchronize(ctx->train->stream2);
+	const ngp_training_opts keep = ctx->train->opts; // settings outlive a model (they belong to the Testbed, not to the network)
+	ctx->train = std::make_unique<TrainState>();
 	ctx->train->opts = keep;
 }
 
@@ -436,13 +411,13 @@ void sync_inference_model(ngp_ctx* ctx) {
 	hipStream_t stream = ctx->stream;
 	ensure_sync_buffers(ctx);
 	order_after_frames(ctx, stream); // frames in flight on any stream read the tables: the update waits for them on the device, the host does not
-	const uint16_t* src = T.opts.ema_decay > 0.f ? T.d_weights_ema : T.d_weights;
+	const uint16_t* src = T.opts.ema_decay > 0.f ? T.d_weights_ema.get() : T.d_weights.get();
 	const size_t ng = (size_t)T.n_params - T.n_matrix;
-	NGP_HIP_CHECK(hipMemcpyAsync(ctx->d_params, src + T.n_matrix, ng * sizeof(uint16_t), hipMemcpyDeviceToDevice, stream));
-	launch_train_xor_layout(ctx->M, (const uint2*)ctx->d_params, (char*)ctx->d_xgrid, stream);
-	launch_train_build_fragments(src, T.d_tfrags_inference, T.d_kfrags_inference, stream);
-	NGP_HIP_CHECK(hipMemcpyAsync(ctx->d_wfrags, T.d_tfrags_inference, (size_t)N_FRAGS * 64 * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
-	launch_build_normals_fragments(ctx->d_wfrags, stream);
+	NGP_HIP_CHECK(hipMemcpyAsync(ctx->d_params.get(), src + T.n_matrix, ng * sizeof(uint16_t), hipMemcpyDeviceToDevice, stream));
+	launch_train_xor_layout(ctx->M, (const uint2*)ctx->d_params.get(), (char*)ctx->d_xgrid.get(), stream);
+	launch_train_build_fragments(src, T.d_tfrags_inference.get(), T.d_kfrags_inference.get(), stream);
+	NGP_HIP_CHECK(hipMemcpyAsync(ctx->d_wfrags.get(), T.d_tfrags_inference.get(), (size_t)N_FRAGS * 64 * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
+	launch_build_normals_fragments(ctx->d_wfrags.get(), stream);
 	mark_model_updated(ctx, stream); // (frames issued from here on wait for it: order_after_model in render_frames)
 	NGP_HIP_CHECK(hipGetLastError());
 	T.inference_dirty = false;
@@ -454,7 +429,7 @@ void sync_host_params(ngp_ctx* ctx) {
 	if (!ctx->train || !ctx->train->host_params_dirty || ctx->device < 0 || !ctx->train->d_weights) return;
 	TrainState& T = *ctx->train;
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-	NGP_HIP_CHECK(hipMemcpy(ctx->params.data(), T.d_weights, (size_t)T.n_params * sizeof(uint16_t), hipMemcpyDeviceToHost));
+	NGP_HIP_CHECK(hipMemcpy(ctx->params.data(), T.d_weights.get(), (size_t)T.n_params * sizeof(uint16_t), hipMemcpyDeviceToHost));
 	T.host_params_dirty = false;
 }
 
@@ -472,7 +447,7 @@ int ngp_set_training_opts(ngp_ctx* ctx, const ngp_training_opts* opts) {
 		if (opts->loss_type < 0 || opts->loss_type > NGP_LOSS_RELATIVE_L2) throw std::runtime_error("unknown loss type");
 		if (!(opts->learning_rate > 0.f) || !(opts->beta1 >= 0.f && opts->beta1 < 1.f) || !(opts->beta2 >= 0.f && opts->beta2 < 1.f) || !(opts->ema_decay >= 0.f && opts->ema_decay < 1.f))
 			throw std::runtime_error("invalid optimizer settings");
-		if (!ctx->train) ctx->train = new TrainState();
+		if (!ctx->train) ctx->train = std::make_unique<TrainState>();
 		ctx->train->opts = *opts;
 		if (ctx->have_desc) ctx->desc.linear_colors = opts->linear_colors; // m_nerf.training.linear_colors is one setting for training and shade_kernel_nerf
 	});
@@ -547,16 +522,13 @@ int ngp_reset_network(ngp_ctx* ctx, uint32_t log2_hashmap_size, uint64_t seed) {
 
 int ngp_set_training_image(ngp_ctx* ctx, int view, int32_t width, int32_t height, const void* rgba, int32_t image_type) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
+		require_device(ctx);
 		if (view < 0 || (size_t)view >= ctx->dataset.views.size()) throw std::runtime_error("NerfDataset::set_training_image: invalid frame index");
 		if (!rgba || width <= 0 || height <= 0) throw std::runtime_error("image should be (H,W,C) where C=4");
 		if (image_type != NGP_IMAGE_BYTE && image_type != NGP_IMAGE_FLOAT) throw std::runtime_error("unknown image type in set_training_image");
 		TrainingView& v = ctx->dataset.views[(size_t)view];
 		const size_t bytes = (size_t)width * height * (image_type == NGP_IMAGE_BYTE ? 4 : 16);
-		if (v.d_pixels) (void)hipFree(v.d_pixels);
-		v.d_pixels = nullptr;
-		NGP_HIP_CHECK(hipMalloc(&v.d_pixels, bytes));
-		NGP_HIP_CHECK(hipMemcpy(v.d_pixels, rgba, bytes, hipMemcpyHostToDevice));
+		v.d_pixels.upload((const uint8_t*)rgba, bytes);
 		if (v.resolution[0] != width || v.resolution[1] != height) {
 			// intrinsics follow the pixel grid (the loader scales them with the image it finds)
 			const float sx = (float)width / (float)v.resolution[0], sy = (float)height / (float)v.resolution[1];
@@ -592,7 +564,7 @@ int ngp_decode_image(const void* bytes, size_t n_bytes, int32_t* width, int32_t*
 
 int ngp_load_training_images(ngp_ctx* ctx, int32_t* n_loaded_out) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
+		require_device(ctx);
 		int n_loaded = 0;
 		std::string first_problem;
 		for (size_t i = 0; i < ctx->dataset.views.size(); ++i) {
@@ -644,22 +616,20 @@ int ngp_load_training_images(ngp_ctx* ctx, int32_t* n_loaded_out) {
 int ngp_render_ground_truth(ngp_ctx* ctx, int view, int32_t width, int32_t height, const float* background_rgba, float exposure, int32_t color_space, int32_t to_srgb,
                             int32_t fov_axis, float zoom, float* rgba_out) {
 	return guarded(ctx, [&] {
-		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only); there is no CPU fallback");
+		require_device(ctx);
 		if (view < 0 || (size_t)view >= ctx->dataset.views.size()) throw std::runtime_error("Invalid training view.");
 		const TrainingView& v = ctx->dataset.views[(size_t)view];
 		if (!v.d_pixels) throw std::runtime_error("training view " + std::to_string(view) + " has no image (ngp_load_training_images / ngp_set_training_image)");
 		if (width <= 0 || height <= 0 || !rgba_out || !background_rgba || !(zoom > 0.f) || (fov_axis != 0 && fov_axis != 1)) throw std::runtime_error("invalid ground-truth render arguments");
 		TrainImage im{};
-		im.pixels = v.d_pixels;
+		im.pixels = v.d_pixels.get();
 		im.type = v.image_type;
 		im.res[0] = v.resolution[0]; im.res[1] = v.resolution[1];
 		ensure_sync_buffers(ctx);
-		float4* d_out = nullptr;
-		NGP_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)width * height * sizeof(float4)));
-		launch_overlay_image(width, height, exposure, background_rgba, im, color_space, to_srgb, fov_axis, zoom, d_out, ctx->stream);
-		hipError_t e = hipMemcpyAsync(rgba_out, d_out, (size_t)width * height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream);
+		DevArray<float4> d_out((size_t)width * height);
+		launch_overlay_image(width, height, exposure, background_rgba, im, color_space, to_srgb, fov_axis, zoom, d_out.get(), ctx->stream);
+		hipError_t e = hipMemcpyAsync(rgba_out, d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost, ctx->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-		(void)hipFree(d_out);
 		NGP_HIP_CHECK(e);
 		NGP_HIP_CHECK(hipGetLastError());
 	});
@@ -727,11 +697,11 @@ int ngp_train_prepare_batch(ngp_ctx* ctx, uint32_t batch_size, uint32_t* counter
 int ngp_train_gradients(ngp_ctx* ctx, uint32_t batch_size, float* grad_out) {
 	return guarded(ctx, [&] {
 		TrainState& T = ensure_training(ctx);
-		NGP_HIP_CHECK(hipMemsetAsync(T.d_grad, 0, (size_t)T.n_params * sizeof(float), ctx->stream));
+		NGP_HIP_CHECK(hipMemsetAsync(T.d_grad.get(), 0, (size_t)T.n_params * sizeof(float), ctx->stream));
 		backward(ctx, T, batch_size);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		NGP_HIP_CHECK(hipGetLastError());
-		if (grad_out) NGP_HIP_CHECK(hipMemcpy(grad_out, T.d_grad, (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
+		if (grad_out) NGP_HIP_CHECK(hipMemcpy(grad_out, T.d_grad.get(), (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
 	});
 }
 
@@ -750,8 +720,8 @@ int ngp_get_training_params(ngp_ctx* ctx, float* params_out, float* ema_out) {
 	return guarded(ctx, [&] {
 		TrainState& T = ensure_training(ctx);
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		if (params_out) NGP_HIP_CHECK(hipMemcpy(params_out, T.d_weights_fp32, (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
-		if (ema_out) NGP_HIP_CHECK(hipMemcpy(ema_out, T.d_ema_tmp, (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
+		if (params_out) NGP_HIP_CHECK(hipMemcpy(params_out, T.d_weights_fp32.get(), (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
+		if (ema_out) NGP_HIP_CHECK(hipMemcpy(ema_out, T.d_ema_tmp.get(), (size_t)T.n_params * sizeof(float), hipMemcpyDeviceToHost));
 	});
 }
 

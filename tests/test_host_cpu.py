@@ -5,6 +5,7 @@ import ctypes as C
 import gzip
 import json
 import os
+import re
 import shutil
 
 import numpy as np
@@ -45,6 +46,21 @@ def test_no_cpu_fallback(native):
             if f.endswith((".py", ".cpp", ".h", ".hip")):
                 txt = open(os.path.join(root, f), errors="ignore").read()
                 assert "liboracle" not in txt and "import oracle" not in txt and "orc_" not in txt, f
+
+
+def test_hip_resources_have_owners():
+    # device memory, events, streams and pinned memory are made and released only by the owning types of ngp_host.h; the
+    # one exception is the page-locked pool behind ngp_host_alloc / ngp_host_free
+    csrc = os.path.join(ROOT, pkg("native").__name__.split(".")[0], "csrc")
+    calls = re.compile(r"\b(hipMalloc\w*|hipFree\w*|hipEventCreate\w*|hipEventDestroy|hipStreamCreate\w*|hipStreamDestroy|hipHostMalloc|hipHostFree)\b")
+    pool = re.compile(r"^(void\* ngp_host_alloc|void ngp_host_free)\(.*?^}$", re.S | re.M)
+    found = []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".cpp"):
+            txt = open(os.path.join(csrc, f)).read()
+            assert f != "ngp_api.cpp" or len(pool.findall(txt)) == 2, "ngp_host_alloc / ngp_host_free not found"
+            found += [f"{f}: {m}" for m in calls.findall(pool.sub("", txt))]
+    assert not found, found
 
 
 def _write_transforms(tmp_path, **extra):
