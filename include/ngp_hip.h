@@ -346,6 +346,54 @@ NGP_API int ngp_get_envmap_grid(ngp_ctx* ctx, ngp_probe_grid_desc* desc_out, flo
 /* the lookup mesh shading does, at explicit surface points: positions / normals n x 3 -> rgb n x 3 (one probe: position unused) */
 NGP_API int ngp_irradiance_at(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, float* rgb_out);
 
+/* --- traced irradiance: E(p, n) = integral of L(p, w) max(0, n.w) dw estimated at the point itself by tracing the NeRF, L cut off where
+ * an inserted mesh blocks the ray. The probes above read E from tables traced elsewhere; this is the quantity they approximate. No
+ * counterpart in the reference: this project's own contract. All three entries run on the context's primary device and serve the models
+ * the probes serve (grid models with base.json's heads, the Frequency architecture); anything else is refused with a message naming them.
+ * A host-only context is refused ("no HIP device").
+ *
+ * ngp_trace_nerf_rays: the caller's rays through the NeRF with the probe tracer's semantics. Host arrays; positions in ngp space.
+ *   Directions are normalised by the library and t is measured along the unit direction. A non-finite origin, or a zero or non-finite
+ *   direction, or a NaN in t_range is refused with a message. t_range NULL: t_min = 0, t_max = +inf.
+ *   Render box: the model's render box, or the inflated mesh-scene box while meshes are loaded (as for the probes).
+ *   Start: t_start = max(t_min, entry), entry = 0 for an origin inside the box, else the box entry distance + 1e-6 (as for camera rays).
+ *   A ray that misses the box (or has it behind its origin) or has t_start >= t_max is dead and returns zeros. As for probe rays there is
+ *   no start jitter and no K2 advance, and the march gives up after 200 skip iterations without a sample.
+ *   End: the march stops when the next sample position would be at t >= t_max, when it leaves the box, or at min_transmittance
+ *   (<= 0 selects 0.01); a ray cut at t_max is shaded like one that left the box.
+ *   Output: rgba_out n x 4, linear premultiplied RGBA, converted with the probe rule (an sRGB-trained network is linearised); no
+ *   background. depth_out (nullable, n): the tracer's accumulated depth, for these rays the distance d.(pos - origin) of the sample of
+ *   largest weight (what orc_trace_payloads returns with a camera at the origin looking along d); 0 where the ray was not shaded
+ *   (alpha <= 0.001, which also leaves its rgba zero). ngp_get_render_stats reports the call like a probe launch.
+ *   Large n is traced in chunks of a fixed size (2^21 rays); every ray is traced on its own, so results do not depend on it. */
+NGP_API int ngp_trace_nerf_rays(ngp_ctx* ctx, uint32_t n, const float* origins /* n x 3 */, const float* directions /* n x 3 */,
+                                const float* t_range /* nullable, n x 2: t_min, t_max */, float min_transmittance, float* rgba_out /* n x 4 */,
+                                float* depth_out /* nullable, n */);
+typedef struct ngp_irradiance_trace_desc {
+	uint32_t n_u, n_v;        /* K = n_u * n_v directions per point, each at least 1; n * K <= 2^28 */
+	float offset;             /* origin = p + offset * normalize(n), ngp units (e.g. 1e-4; finite and >= 0) */
+	float min_transmittance;  /* as in ngp_trace_nerf_rays */
+	int32_t occlude_by_meshes;
+} ngp_irradiance_trace_desc;
+/* ngp_irradiance_rays (a stage entry for tests): the hemisphere rays of n points, generated on the GPU. Point i's ray k has index
+ *   i K + k, k = u + n_u v. With n^ = normalize(n_i) (a zero or non-finite normal, or a non-finite position, is refused):
+ *   stratum centre a = (u + 0.5) / n_u, b = (v + 0.5) / n_v; local direction (Malley's method, cosine-weighted)
+ *   (sqrt(a) cos 2 pi b, sqrt(a) sin 2 pi b, sqrt(1 - a)); world direction d = local_frame(n^) * local (compute_local_frame,
+ *   random_val.cuh), normalised; origin p_i + offset n^. t_max: with occlude_by_meshes the distance to the closest triangle hit over ALL
+ *   loaded meshes (the minimum of the per-mesh BVH4 closest hit, within its 100-unit range; unlike ngp_trace_mesh_rays, which follows the
+ *   reference and only looks at the mesh whose box is entered first); +inf without meshes, without a hit or with occlusion off.
+ *   Outputs origins_out / directions_out n K x 3, t_max_out n K. */
+NGP_API int ngp_irradiance_rays(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc,
+                                float* origins_out, float* directions_out, float* t_max_out);
+/* ngp_irradiance_traced: the estimate. The generator's rays go through ngp_trace_nerf_rays' tracer (t_min = 0, t_max as generated) and a
+ *   reduction writes per point out n x 4: rgb = (pi / K) sum_k rgb_k, the cosine-weighted estimator (a constant radiance L gives pi L),
+ *   and w = the fraction of the point's K rays that no mesh blocks (1 without occlusion). A blocked ray still contributes the NeRF
+ *   radiance in front of its hit; a mesh adds no radiance of its own (no interreflection). The sum runs in a fixed order (one wave per
+ *   point, lane-strided, then a butterfly; no atomics), so the result is bit-identical from run to run and does not depend on how many
+ *   points one call carries. Limits and refusals as for ngp_irradiance_rays; no model is refused too. */
+NGP_API int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc,
+                                  float* out /* n x 4 */);
+
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),
  * Testbed::train_nerf / train_nerf_step (src/testbed_nerf.cu:2949-3431), training_prep_nerf (:3432-3446). The default

@@ -4,7 +4,7 @@
 // (src/testbed_geometry_training.cu:2202-2320, src/geometry_bvh.cu:646-676) with seven ray-state arrays in DRAM.
 // Primary hit, sun shadow ray and BRDF stay in registers; the only traffic is BVH nodes / triangles (cache resident)
 // and one frame/depth write per pixel. Software BVH4 traversal replaces OptiX (north_star: no OptiX).
-#include "nerf_device.h"
+#include "render_common.h"
 
 namespace ngp {
 
@@ -327,6 +327,116 @@ void launch_irradiance_lookup(const IrradianceMap& I, uint32_t n, const float* p
 }
 void launch_trace_mesh_rays(const MeshSceneParams& S, uint32_t n, float* positions, float* directions, hipStream_t stream) {
 	hipLaunchKernelGGL(trace_mesh_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, n, positions, directions);
+}
+
+
+// ---- traced irradiance (ngp_trace_nerf_rays, ngp_irradiance_rays, ngp_irradiance_traced; contract in include/ngp_hip.h).
+// The ray list feeds the probe tracer (ProbeParams mode PROBE_RAY_LIST); generator, BVH and reduction stay out of the fused kernel.
+
+// t[i] = (t_min, t_max) -> (t_start, t_max): t_start = max(t_min, the render box's entry distance + 1e-6 as for camera rays, 0 for an
+// origin inside the box); a ray that misses the box is dead (t_start = t_max). normalize: the caller's directions are normalised first.
+__global__ void ray_list_prep_kernel(const ModelParams M, uint32_t n, const float* __restrict__ o, float* __restrict__ d, float2* __restrict__ t, int normalize) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const f3 org = ld3(o + 3 * (size_t)i);
+	f3 dir = ld3(d + 3 * (size_t)i);
+	if (normalize) {
+		dir = normalize3(dir);
+		d[3 * (size_t)i] = dir.x; d[3 * (size_t)i + 1] = dir.y; d[3 * (size_t)i + 2] = dir.z;
+	}
+	float2 tt = t[i];
+	float entry = 0.0f;
+	bool miss = false;
+	if (!raabb_contains(M, org)) {
+		const float e = aabb_ray_entry(M.raabb_min, M.raabb_max, m3_mulv(M.r2l, org), m3_mulv(M.r2l, dir));
+		miss = !(e > 0.0f && e < 3.402823466e+38f); // (a box behind the origin has a slab overlap at negative t)
+		entry = e + 1e-6f;
+	}
+	tt.x = miss ? tt.y : fmaxf(tt.x, entry);
+	t[i] = tt;
+}
+
+// hemisphere rays of ngp_irradiance_rays: ray r = r0 + i of the request is ray k = r % K of point r / K, k = u + n_u v, stratum centre
+// (a, b) = ((u + .5) / n_u, (v + .5) / n_v), Malley's cosine-weighted direction local_frame(n) (sqrt(a) cos 2 pi b, sqrt(a) sin 2 pi b,
+// sqrt(1 - a)); origin p + offset n; t = (0, the closest triangle hit over all meshes, +inf without one). positions / normals hold the
+// points from r0 / K on.
+__global__ void irradiance_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, float offset, unsigned long long r0, uint32_t n,
+                                       const float* __restrict__ positions, const float* __restrict__ normals, float* __restrict__ o_out,
+                                       float* __restrict__ d_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const unsigned long long K = (unsigned long long)n_u * n_v, r = r0 + i, pt = r / K, pl = pt - r0 / K;
+	const uint32_t k = (uint32_t)(r - pt * K), u = k % n_u, v = k / n_u;
+	const f3 nrm = normalize3(ld3(normals + 3 * pl));
+	const float a = ((float)u + 0.5f) / (float)n_u, b = ((float)v + 0.5f) / (float)n_v;
+	const float sa = sqrtf(a), phi = 2.0f * 3.14159265358979323846f * b;
+	float frame[9];
+	local_frame(nrm, frame);
+	const f3 dir = normalize3(m3_mulv(frame, mk3(sa * cosf(phi), sa * sinf(phi), sqrtf(1.0f - a))));
+	const f3 org = add3(ld3(positions + 3 * pl), scale3(nrm, offset));
+	float t_max = __builtin_huge_valf();
+	if (occlude) {
+		for (uint32_t m = 0; m < S.n_meshes; ++m) {
+			int idx;
+			float t;
+			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
+			if (idx > -1 && t < t_max) t_max = t;
+		}
+	}
+	o_out[3 * (size_t)i] = org.x; o_out[3 * (size_t)i + 1] = org.y; o_out[3 * (size_t)i + 2] = org.z;
+	d_out[3 * (size_t)i] = dir.x; d_out[3 * (size_t)i + 1] = dir.y; d_out[3 * (size_t)i + 2] = dir.z;
+	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// one wave per point: the sum of its rays' rgb among rays [r0, r0 + n) of the request, lane-strided then a butterfly (a fixed order, no
+// atomics), and the count of rays no mesh blocks. A point whose rays span several chunks (K > the chunk) adds the chunks' sums in chunk
+// order in part[0]; its last chunk writes out = ((pi / K) sum rgb, unblocked / K). out holds the points from r0 / K on.
+__global__ void irradiance_reduce_kernel(uint32_t K, unsigned long long r0, uint32_t n, const float4* __restrict__ rgba, const float2* __restrict__ t,
+                                         float4* __restrict__ part, float4* __restrict__ out) {
+	const unsigned long long pt = r0 / K + (blockIdx.x * blockDim.x + threadIdx.x) / 64u;
+	const int lane = threadIdx.x & 63;
+	const unsigned long long lo_p = pt * K, hi_p = lo_p + K, r1 = r0 + n;
+	if (lo_p >= r1) return; // (wave-uniform)
+	const unsigned long long lo = lo_p > r0 ? lo_p : r0, hi = hi_p < r1 ? hi_p : r1;
+	float sr = 0.f, sg = 0.f, sb = 0.f;
+	uint32_t c = 0;
+	for (unsigned long long r = lo + lane; r < hi; r += 64u) {
+		const float4 x = rgba[r - r0];
+		sr += x.x; sg += x.y; sb += x.z;
+		c += t[r - r0].y == __builtin_huge_valf() ? 1u : 0u;
+	}
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) {
+		sr += __shfl_xor(sr, m);
+		sg += __shfl_xor(sg, m);
+		sb += __shfl_xor(sb, m);
+		c += __shfl_xor(c, m);
+	}
+	if (lane != 0) return;
+	if (lo != lo_p) { // not the point's first chunk
+		const float4 p = part[0];
+		sr = p.x + sr; sg = p.y + sg; sb = p.z + sb; c += __float_as_uint(p.w);
+	}
+	if (hi == hi_p) {
+		const float scale = 3.14159265358979323846f / (float)K;
+		out[pt - r0 / K] = make_float4(sr * scale, sg * scale, sb * scale, (float)((double)c / (double)K));
+	} else {
+		part[0] = make_float4(sr, sg, sb, __uint_as_float(c));
+	}
+}
+
+void launch_ray_list_prep(const ModelParams& M, uint32_t n, const float* o, float* d, float2* t, bool normalize, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(ray_list_prep_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, M, n, o, d, t, normalize ? 1 : 0);
+}
+void launch_irradiance_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, float offset, uint64_t r0, uint32_t n, const float* positions,
+                            const float* normals, float* o, float* d, float2* t, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, offset, (unsigned long long)r0, n,
+	                          positions, normals, o, d, t);
+}
+void launch_irradiance_reduce(uint32_t K, uint64_t r0, uint32_t n, const float4* rgba, const float2* t, float4* part, float4* out, hipStream_t stream) {
+	if (!n) return;
+	const uint64_t n_pts = (r0 + n - 1) / K - r0 / K + 1; // points the chunk touches
+	hipLaunchKernelGGL(irradiance_reduce_kernel, dim3((unsigned)((n_pts + 3) / 4)), dim3(256), 0, stream, K, (unsigned long long)r0, n, rgba, t, part, out);
 }
 
 } // namespace ngp

@@ -118,6 +118,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	Accum acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 	uint32_t step = 1;
 	uint32_t skip_i = 1;
+	float t_max = 0.f; // probe rays: the end of the march (init_probe_ray)
 	bool counted = false;
 	// A ray may have several samples in the wave's list at once (emitted this round, not yet through the network): n_pend of them,
 	// their slots packed 8 bits each in emission order. left_box: the ray has run out of the render box behind its last waiting sample.
@@ -239,8 +240,8 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				if (PROBE) {
 					uint32_t q = tile * 64u + slot;
 					if (take && q < P.n_rays) {
-						init_probe_ray(P, q, ray);
-						fresh = true;
+						init_probe_ray(P, q, ray, t_max);
+						fresh = ray.alive; // (a ray-list ray may miss the box)
 					}
 				} else if (take) {
 					uint32_t x = (tile % F.tiles_x) * 8u + (slot & 7u);
@@ -351,6 +352,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			const f3 pos = add3(ray.o, scale3(ray.d, ray.t));
 			bool out = ray.t >= MAX_DEPTH || !raabb_contains(M, pos);
 			if (PROBE && skip_i >= 200) out = true; // the 200-iteration variant of trace_mesh (:497-534)
+			if (PROBE && ray.t >= t_max) out = true; // a ray-list ray's t_max: what it gathered is shaded, as at the box exit
 			const bool inside = marching && !out;
 			uint32_t mip = 0, empty = 1u;
 			if (inside) {
@@ -605,7 +607,8 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 					o.h[3] = (half_t)g.w;
 				}
 				const f3 pos = add3(amin, mul3(mk3(a.x, a.y, a.z), adiag)); // unwarp_position
-				const float sdepth = dot3(cam_fwd, sub3(pos, cam_pos));
+				const float sdepth = PROBE ? dot3(ray.d, sub3(pos, ray.o)) // probe rays: the distance along the ray
+				                          : dot3(cam_fwd, sub3(pos, cam_pos));
 				float T = 1.0f - acc.a;
 				float dt = unwarp_dt(a.w);
 				float alpha = 1.0f - fast_exp(-network_to_density((float)o.h[3], M.density_act) * dt);

@@ -148,6 +148,10 @@ void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t strea
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
 void launch_irradiance_lookup(const IrradianceMap& I, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 void launch_trace_mesh_rays(const MeshSceneParams& S, uint32_t n, float* positions, float* directions, hipStream_t stream);
+void launch_ray_list_prep(const ModelParams& M, uint32_t n, const float* o, float* d, float2* t, bool normalize, hipStream_t stream);
+void launch_irradiance_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, float offset, uint64_t r0, uint32_t n, const float* positions,
+                            const float* normals, float* o, float* d, float2* t, hipStream_t stream);
+void launch_irradiance_reduce(uint32_t K, uint64_t r0, uint32_t n, const float4* rgba, const float2* t, float4* part, float4* out, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
 // scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.

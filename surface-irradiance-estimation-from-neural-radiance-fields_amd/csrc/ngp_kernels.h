@@ -170,7 +170,8 @@ struct FrameParams {
 
 // ---- irradiance probes
 struct ProbeParams {
-	int32_t mode; // 0 centre fan (K10), 1 shell position looking inward (K11), 2 Halton-jittered centres (K12), 3 a grid_x x grid_y lattice of K11 probes
+	int32_t mode; // 0 centre fan (K10), 1 shell position looking inward (K11), 2 Halton-jittered centres (K12), 3 a grid_x x grid_y lattice of K11 probes,
+	              // 4 a list of caller rays (PROBE_RAY_LIST)
 	uint32_t n_theta, n_phi, n_origin;
 	float origin[3];
 	float center[3]; // render_aabb.center()
@@ -178,7 +179,14 @@ struct ProbeParams {
 	float4* ray_rgba; // one shaded RGBA per probe ray (zero when the ray saw nothing)
 	uint32_t grid_x, grid_y; // mode 3: probe g = i + grid_x * j sits at center + shell_radius * cylindrical_to_dir_nerf((i + .5) / grid_x, (j + .5) / grid_y)
 	float shell_radius;
+	// mode 4: ray q starts at ray_o[q] + ray_t[q].x ray_d[q] (ray_d unit, ray_t[q].x past the render box entry) and stops before a
+	// sample at t >= ray_t[q].y; a ray with ray_t[q].x >= ray_t[q].y is dead. ray_depth (nullable): the shaded rays' accumulated depth
+	const float* ray_o;
+	const float* ray_d;
+	const float2* ray_t;
+	float* ray_depth;
 };
+constexpr int32_t PROBE_RAY_LIST = 4;
 
 // ---- geometry mode (meshes)
 struct Triangle { // triangle.cuh:163 -- 36 B

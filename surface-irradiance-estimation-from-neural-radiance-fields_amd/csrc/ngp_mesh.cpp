@@ -340,12 +340,28 @@ int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* direc
 // ------------------------------------------------------------------------------------------------ irradiance probes
 namespace {
 // trace the fan(s) described by P in ONE persistent launch, reduce to the probe texture(s), tabulate E(n) at the texel directions
-void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
-	using namespace ngp;
+// the models the probe tracer serves: base.json's heads and the Frequency architecture (`what` names the caller's work in the refusal)
+void require_probe_model(ngp_ctx* ctx, const char* what) {
 	require_model(ctx);
 	ngp::sync_inference_model(ctx);
-	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error("irradiance probes are built for the configs/nerf/base.json rgb head (2 hidden layers)");
+	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error(std::string(what) + " are built for the configs/nerf/base.json rgb head (2 hidden layers)");
 	ensure_sync_buffers(ctx);
+}
+// the model as probe rays see it: in Geometry mode load_scene made the inflated mesh box the render box (testbed_geometry_training.cu:3185-3189)
+ngp::ModelParams probe_model(const ngp_ctx* ctx) {
+	ngp::ModelParams M = ctx->M;
+	if (!ctx->meshes.empty()) {
+		for (int i = 0; i < 3; ++i) { M.raabb_min[i] = ctx->mesh_scene.scene_min[i]; M.raabb_max[i] = ctx->mesh_scene.scene_max[i]; }
+		const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+		memcpy(M.r2l, ident, sizeof(ident));
+		M.r2l_identity = 1u;
+	}
+	return M;
+}
+
+void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
+	using namespace ngp;
+	require_probe_model(ctx, "irradiance probes");
 	for (int i = 0; i < 3; ++i) P.center[i] = 0.5f * (ctx->M.raabb_max[i] + ctx->M.raabb_min[i]); // render_aabb.center()
 	const uint32_t no = P.mode == NGP_PROBE_MULTI_CENTER ? P.n_origin : 1u;
 	const uint32_t n_probes = P.mode == 3 ? P.grid_x * P.grid_y : 1u;
@@ -373,14 +389,7 @@ void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot], stream));
 	NGP_HIP_CHECK(hipMemsetAsync(P.ray_rgba, 0, (size_t)P.n_rays * sizeof(float4), stream));
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
-	ModelParams M = ctx->M;
-	if (!ctx->meshes.empty()) { // Geometry mode: load_scene made the inflated mesh box the render box (testbed_geometry_training.cu:3185-3189); the shell positions lie inside it
-		for (int i = 0; i < 3; ++i) { M.raabb_min[i] = ctx->mesh_scene.scene_min[i]; M.raabb_max[i] = ctx->mesh_scene.scene_max[i]; }
-		const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-		memcpy(M.r2l, ident, sizeof(ident));
-		M.r2l_identity = 1u;
-	}
-	launch_trace_probe(M, F, P, ctx->n_cus, stream);
+	launch_trace_probe(probe_model(ctx), F, P, ctx->n_cus, stream); // (Geometry mode: the shell positions lie inside the mesh box)
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
 	launch_probe_reduce(P, ctx->d_envmap.get(), stream);
 	launch_irradiance(P, ctx->d_envmap.get(), n_texels, nullptr, ctx->d_irradiance.get(), stream);
@@ -505,6 +514,212 @@ int ngp_irradiance_at(ngp_ctx* ctx, uint32_t n, const float* positions, const fl
 		launch_irradiance_lookup(ngp::irradiance_map_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
 		download_rgb(ctx, d_o.get(), n, rgb_out);
 		NGP_HIP_CHECK(hipGetLastError());
+	});
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------ traced irradiance
+namespace {
+// rays per tracer launch: bounds the ray-list workspace (48 B a ray). Every ray is traced on its own, so chunking changes no result.
+constexpr uint32_t RAY_CHUNK = 1u << 21;
+constexpr uint64_t MAX_TRACED_RAYS = 1ull << 28;
+
+bool finite3(const float* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+bool nonzero3(const float* p) { return p[0] != 0.0f || p[1] != 0.0f || p[2] != 0.0f; }
+
+// the launches of one call of a ray-list entry: one history slot, reported by ngp_get_render_stats like a probe launch (the chunks'
+// counters and device ticks add up; kernel_ms spans the first chunk's trace to the last one's)
+class RayListTrace {
+public:
+	RayListTrace(ngp_ctx* ctx, uint64_t n_rays, float min_transmittance) : ctx_(ctx), n_rays_(n_rays) {
+		stream_ = ctx->stream;
+		if (ctx->last_stream && ctx->last_stream != stream_) NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		slot_ = (int)(ctx->n_calls % ngp_ctx::HISTORY);
+		if (ctx->n_calls >= (uint64_t)ngp_ctx::HISTORY) NGP_HIP_CHECK(hipStreamWaitEvent(stream_, ctx->ev_frame1[slot_], 0));
+		ctx->bind_slot(F_, slot_);
+		F_.shard_index = 0;
+		F_.shard_count = 1;
+		F_.min_transmittance = min_transmittance > 0.f ? min_transmittance : 0.01f;
+		F_.linear_colors = ctx->desc.linear_colors;
+		memcpy(F_.tune, ctx->tune, sizeof(F_.tune));
+		M_ = probe_model(ctx);
+		NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot_], stream_));
+	}
+	const ngp::ModelParams& model() const { return M_; }
+	// n rays of P (ray_o, ray_d, ray_t prepared; ray_rgba and ray_depth are cleared here)
+	void trace(ngp::ProbeParams P, uint32_t n) {
+		P.mode = ngp::PROBE_RAY_LIST;
+		P.n_rays = n;
+		NGP_HIP_CHECK(hipMemsetAsync(P.ray_rgba, 0, (size_t)n * sizeof(float4), stream_));
+		if (P.ray_depth) NGP_HIP_CHECK(hipMemsetAsync(P.ray_depth, 0, (size_t)n * sizeof(float), stream_));
+		if (!traced_) NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern0[slot_], stream_));
+		F_.n_local_tiles = (n + 63) / 64;
+		F_.add_results = traced_ ? 1 : 0;
+		launch_trace_probe(M_, F_, P, ctx_->n_cus, stream_);
+		NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern1[slot_], stream_));
+		traced_ = true;
+	}
+	void finish() {
+		if (!traced_) {
+			NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern0[slot_], stream_));
+			NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern1[slot_], stream_));
+		}
+		NGP_HIP_CHECK(hipEventRecord(ctx_->ev_frame1[slot_], stream_));
+		ctx_->hist_n_rays[slot_] = n_rays_;
+		ctx_->last_stream = stream_;
+		++ctx_->n_calls;
+		NGP_HIP_CHECK(hipStreamSynchronize(stream_));
+		NGP_HIP_CHECK(hipGetLastError());
+	}
+
+private:
+	ngp_ctx* ctx_;
+	uint64_t n_rays_;
+	hipStream_t stream_;
+	int slot_ = 0;
+	bool traced_ = false;
+	ngp::FrameParams F_{};
+	ngp::ModelParams M_{};
+};
+
+void download(ngp_ctx* ctx, void* dst, const void* src, size_t bytes) {
+	NGP_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+void upload(ngp_ctx* ctx, void* dst, const void* src, size_t bytes) {
+	NGP_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+}
+
+// the points' checks shared by ngp_irradiance_rays and ngp_irradiance_traced; returns K
+uint32_t check_irradiance_request(uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* d) {
+	if (!d) throw std::runtime_error("null argument");
+	if (d->n_u == 0 || d->n_v == 0) throw std::runtime_error("invalid irradiance descriptor: n_u and n_v must be at least 1");
+	if (!std::isfinite(d->offset) || d->offset < 0.0f) throw std::runtime_error("invalid irradiance descriptor: offset must be finite and >= 0");
+	const uint64_t K = (uint64_t)d->n_u * d->n_v;
+	if (K * n > MAX_TRACED_RAYS) throw std::runtime_error("irradiance request too large: n * n_u * n_v > 2^28 rays");
+	if (n && (!positions || !normals)) throw std::runtime_error("null argument");
+	for (uint32_t i = 0; i < n; ++i) {
+		if (!finite3(positions + 3 * (size_t)i)) throw std::runtime_error("position " + std::to_string(i) + " is not finite");
+		if (!finite3(normals + 3 * (size_t)i) || !nonzero3(normals + 3 * (size_t)i)) throw std::runtime_error("normal " + std::to_string(i) + " is zero or not finite");
+	}
+	return (uint32_t)K;
+}
+
+// the chunks of an irradiance request: whole points while K <= RAY_CHUNK, else RAY_CHUNK-ray pieces of one point. f(r0, n_rays).
+template <typename F>
+void for_each_irradiance_chunk(uint32_t n, uint32_t K, F&& f) {
+	if (K <= RAY_CHUNK) {
+		const uint32_t per = RAY_CHUNK / K;
+		for (uint32_t p = 0; p < n; p += per) f((uint64_t)p * K, (std::min(per, n - p)) * K);
+	} else {
+		for (uint32_t p = 0; p < n; ++p)
+			for (uint32_t k = 0; k < K; k += RAY_CHUNK) f((uint64_t)p * K + k, std::min(RAY_CHUNK, K - k));
+	}
+}
+
+// the generator for rays [r0, r0 + m) of the request into o, d, t (the chunk's points are uploaded from the host arrays first)
+void generate_irradiance_rays(ngp_ctx* ctx, const ngp_irradiance_trace_desc* d, uint32_t K, const float* positions, const float* normals, uint64_t r0, uint32_t m,
+                              DevArray<float>& pts, float* o, float* dir, float2* t) {
+	const uint64_t p0 = r0 / K, p1 = (r0 + m - 1) / K + 1;
+	upload(ctx, pts.get(), positions + 3 * p0, (size_t)(p1 - p0) * 3 * sizeof(float));
+	upload(ctx, pts.get() + pts.size() / 2, normals + 3 * p0, (size_t)(p1 - p0) * 3 * sizeof(float));
+	ngp::launch_irradiance_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, d->offset, r0, m, pts.get(), pts.get() + pts.size() / 2, o, dir, t,
+	                            ctx->stream);
+}
+} // namespace
+
+extern "C" {
+
+int ngp_trace_nerf_rays(ngp_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* t_range, float min_transmittance, float* rgba_out,
+                        float* depth_out) {
+	return guarded(ctx, [&] {
+		require_probe_model(ctx, "traced rays");
+		if (n == 0) return;
+		if (!origins || !directions || !rgba_out) throw std::runtime_error("null argument");
+		for (uint32_t i = 0; i < n; ++i) {
+			if (!finite3(origins + 3 * (size_t)i)) throw std::runtime_error("origin " + std::to_string(i) + " is not finite");
+			if (!finite3(directions + 3 * (size_t)i) || !nonzero3(directions + 3 * (size_t)i)) throw std::runtime_error("direction " + std::to_string(i) + " is zero or not finite");
+			if (t_range && (std::isnan(t_range[2 * (size_t)i]) || std::isnan(t_range[2 * (size_t)i + 1]))) throw std::runtime_error("t_range " + std::to_string(i) + " is NaN");
+		}
+		const uint32_t cap = std::min(n, RAY_CHUNK);
+		DevArray<float> o(3 * (size_t)cap), dir(3 * (size_t)cap), depth(depth_out ? cap : 0);
+		DevArray<float2> t(cap);
+		DevArray<float4> rgba(cap);
+		std::vector<float2> t_host(cap);
+		RayListTrace tr(ctx, n, min_transmittance);
+		for (uint32_t r0 = 0; r0 < n; r0 += cap) {
+			const uint32_t m = std::min(cap, n - r0);
+			upload(ctx, o.get(), origins + 3 * (size_t)r0, (size_t)m * 3 * sizeof(float));
+			upload(ctx, dir.get(), directions + 3 * (size_t)r0, (size_t)m * 3 * sizeof(float));
+			for (uint32_t i = 0; i < m; ++i)
+				t_host[i] = t_range ? make_float2(t_range[2 * (size_t)(r0 + i)], t_range[2 * (size_t)(r0 + i) + 1]) : make_float2(0.0f, std::numeric_limits<float>::infinity());
+			upload(ctx, t.get(), t_host.data(), (size_t)m * sizeof(float2));
+			ngp::launch_ray_list_prep(tr.model(), m, o.get(), dir.get(), t.get(), true, ctx->stream);
+			ngp::ProbeParams P{};
+			P.ray_o = o.get();
+			P.ray_d = dir.get();
+			P.ray_t = t.get();
+			P.ray_rgba = rgba.get();
+			P.ray_depth = depth.get();
+			tr.trace(P, m);
+			download(ctx, rgba_out + 4 * (size_t)r0, rgba.get(), (size_t)m * sizeof(float4)); // (the stream stays in order: the next chunk's uploads wait here)
+			if (depth_out) download(ctx, depth_out + r0, depth.get(), (size_t)m * sizeof(float));
+		}
+		tr.finish();
+	});
+}
+
+int ngp_irradiance_rays(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc, float* origins_out,
+                        float* directions_out, float* t_max_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		const uint32_t K = check_irradiance_request(n, positions, normals, desc);
+		if (n == 0) return;
+		if (!origins_out || !directions_out || !t_max_out) throw std::runtime_error("null argument");
+		const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+		DevArray<float> pts(6 * (size_t)std::min<uint64_t>(n, cap)), o(3 * (size_t)cap), dir(3 * (size_t)cap);
+		DevArray<float2> t(cap);
+		std::vector<float2> t_host(cap);
+		for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) {
+			generate_irradiance_rays(ctx, desc, K, positions, normals, r0, m, pts, o.get(), dir.get(), t.get());
+			download(ctx, origins_out + 3 * r0, o.get(), (size_t)m * 3 * sizeof(float));
+			download(ctx, directions_out + 3 * r0, dir.get(), (size_t)m * 3 * sizeof(float));
+			download(ctx, t_host.data(), t.get(), (size_t)m * sizeof(float2));
+			for (uint32_t i = 0; i < m; ++i) t_max_out[r0 + i] = t_host[i].y;
+		});
+		NGP_HIP_CHECK(hipGetLastError());
+	});
+}
+
+int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc, float* out) {
+	return guarded(ctx, [&] {
+		require_probe_model(ctx, "traced irradiance estimates");
+		const uint32_t K = check_irradiance_request(n, positions, normals, desc);
+		if (n == 0) return;
+		if (!out) throw std::runtime_error("null argument");
+		const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+		const uint32_t cap_pts = (uint32_t)std::min<uint64_t>(n, cap);
+		DevArray<float> pts(6 * (size_t)cap_pts), o(3 * (size_t)cap), dir(3 * (size_t)cap);
+		DevArray<float2> t(cap);
+		DevArray<float4> rgba(cap), part(1), E(cap_pts);
+		RayListTrace tr(ctx, (uint64_t)n * K, desc->min_transmittance);
+		for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) {
+			generate_irradiance_rays(ctx, desc, K, positions, normals, r0, m, pts, o.get(), dir.get(), t.get());
+			ngp::launch_ray_list_prep(tr.model(), m, o.get(), dir.get(), t.get(), false, ctx->stream);
+			ngp::ProbeParams P{};
+			P.ray_o = o.get();
+			P.ray_d = dir.get();
+			P.ray_t = t.get();
+			P.ray_rgba = rgba.get();
+			tr.trace(P, m);
+			ngp::launch_irradiance_reduce(K, r0, m, rgba.get(), t.get(), part.get(), E.get(), ctx->stream);
+			if ((r0 + m) % K == 0) { // the chunk ends a point: its points [r0 / K, (r0 + m) / K) are complete
+				const uint64_t p0 = r0 / K, p1 = (r0 + m) / K;
+				download(ctx, out + 4 * p0, E.get(), (size_t)(p1 - p0) * sizeof(float4));
+			}
+		});
+		tr.finish();
 	});
 }
 

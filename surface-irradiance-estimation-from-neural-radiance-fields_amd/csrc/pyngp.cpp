@@ -185,6 +185,22 @@ PYBIND11_MODULE(pyngp, m) {
 			t.compute_and_save_marching_cubes_mesh(filename, res, box.empty() ? nullptr : box.data(), thresh, uvs);
 		}, py::arg("filename"), py::arg("resolution") = std::array<uint32_t, 3>{256, 256, 256}, py::arg("aabb") = py::none(), py::arg("thresh") = 2.5f,
 		   py::arg("generate_uvs_for_obj_file") = false, "Marching cubes of the density, saved as .obj or .ply in dataset space")
+		.def("compute_irradiance_at_points", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions,
+		                                        py::array_t<float, py::array::c_style | py::array::forcecast> normals, uint32_t n_u, uint32_t n_v, float offset,
+		                                        bool occlude_by_meshes) {
+			if (positions.ndim() != 2 || positions.shape(1) != 3 || normals.ndim() != 2 || normals.shape(1) != 3 || positions.shape(0) != normals.shape(0))
+				throw std::runtime_error("positions and normals: (n, 3) each");
+			const uint32_t n = (uint32_t)positions.shape(0);
+			std::vector<float> e;
+			{
+				py::gil_scoped_release nogil;
+				e = t.compute_irradiance_at_points(positions.data(), normals.data(), n, n_u, n_v, offset, occlude_by_meshes);
+			}
+			py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)4});
+			if (n) memcpy(a.mutable_data(), e.data(), e.size() * sizeof(float));
+			return a;
+		}, py::arg("positions"), py::arg("normals"), py::arg("n_u") = 16, py::arg("n_v") = 16, py::arg("offset") = 1e-4f, py::arg("occlude_by_meshes") = true,
+		   "This project's own: the irradiance traced at surface points through the NeRF, (n, 4) = rgb, fraction of rays no mesh blocks")
 		.def("frame", &Testbed::frame, py::call_guard<py::gil_scoped_release>(), "Process a single frame: one training step when shall_train is set (headless, nothing is drawn).")
 		.def("train", &Testbed::train, py::call_guard<py::gil_scoped_release>(), "Perform a single training step with a specified batch size.")
 		.def("reset", &Testbed::reset_network, py::arg("reset_density_grid") = true, "Reset training.")

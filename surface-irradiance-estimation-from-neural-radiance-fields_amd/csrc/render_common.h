@@ -67,6 +67,7 @@ NGP_DEV bool shade_ray(const FrameParams& F, const ProbeParams& P, f3 bg_linear,
 	}
 	if (PROBE) {
 		P.ray_rgba[idx] = make_float4(r, g, b, a);
+		if (P.ray_depth) P.ray_depth[idx] = acc.depth;
 		return true;
 	}
 	if (F.direct) { // the frame buffer would hold zeros (tmp + 0 * (1 - a) == tmp) or the environment map's value for this ray
@@ -126,7 +127,20 @@ NGP_DEV f3 probe_grid_origin(const float* center, uint32_t grid_x, uint32_t grid
 	f3 dir = cylindrical_to_dir_nerf(((float)i + 0.5f) / (float)grid_x, ((float)j + 0.5f) / (float)grid_y);
 	return add3(mk3(center[0], center[1], center[2]), scale3(dir, shell_radius));
 }
-NGP_DEV void init_probe_ray(const ProbeParams& P, uint32_t q, RayState& r) {
+// t_max: where the ray's march stops (+inf but for the ray list). A ray-list ray may come out dead (r.alive false).
+NGP_DEV void init_probe_ray(const ProbeParams& P, uint32_t q, RayState& r, float& t_max) {
+	r.idx = q;
+	r.out = q;
+	if (P.mode == PROBE_RAY_LIST) {
+		const float2 tt = P.ray_t[q];
+		r.o = mk3(P.ray_o[3 * (size_t)q], P.ray_o[3 * (size_t)q + 1], P.ray_o[3 * (size_t)q + 2]);
+		r.d = mk3(P.ray_d[3 * (size_t)q], P.ray_d[3 * (size_t)q + 1], P.ray_d[3 * (size_t)q + 2]);
+		r.t = tt.x;
+		t_max = tt.y;
+		r.alive = tt.x < tt.y;
+		return;
+	}
+	t_max = __builtin_huge_valf();
 	const uint32_t no = P.mode == 2 ? P.n_origin : 1u;
 	const uint32_t w = P.n_theta * no;
 	const uint32_t per_probe = P.n_theta * P.n_phi * no * no;
@@ -151,8 +165,6 @@ NGP_DEV void init_probe_ray(const ProbeParams& P, uint32_t q, RayState& r) {
 	r.o = origin;
 	r.d = dir;
 	r.t = 0.0f;
-	r.idx = q;
-	r.out = q;
 	r.alive = true;
 }
 

@@ -505,6 +505,18 @@ public:
 		m_envmap_grid_ready = true;
 		m_envmap_ready = false;
 	}
+	// This project's own method (the reference declares nothing like it): E(p, n) traced at the points (ngp_irradiance_traced), n x 4 =
+	// rgb irradiance, fraction of rays no mesh blocks
+	std::vector<float> compute_irradiance_at_points(const float* positions, const float* normals, uint32_t n, uint32_t n_u = 16, uint32_t n_v = 16,
+	                                                float offset = 1e-4f, bool occlude_by_meshes = true) {
+		ngp_irradiance_trace_desc d{};
+		d.n_u = n_u; d.n_v = n_v; d.offset = offset;
+		d.min_transmittance = nerf.render_min_transmittance;
+		d.occlude_by_meshes = occlude_by_meshes ? 1 : 0;
+		std::vector<float> out((size_t)n * 4);
+		check(ngp_irradiance_traced(m_ctx, n, positions, normals, &d, out.data()));
+		return out;
+	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path
 	bool m_has_camera_end = false;

@@ -540,6 +540,7 @@ NGP_DEV void wide_body(const ModelParams& M, const CameraParams& C, const FrameP
 	f3 idir = mk3(0.f, 0.f, 0.f);
 	Accum acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 	uint32_t step = 1, skip_i = 1;
+	float t_max = 0.f; // probe rays: the end of the march (init_probe_ray)
 	bool ready = false, counted = false, finished = false, exhausted = false;
 	bool held = false; // ready, but the round's 128 rows went to others: first in line next round
 	float wx = 0.f, wy = 0.f, wz = 0.f, wdt = 0.f;
@@ -594,8 +595,8 @@ NGP_DEV void wide_body(const ModelParams& M, const CameraParams& C, const FrameP
 				if (PROBE) {
 					const uint32_t q = tile * 64u + slot;
 					if (take && q < P.n_rays) {
-						init_probe_ray(P, q, ray);
-						fresh = true;
+						init_probe_ray(P, q, ray, t_max);
+						fresh = ray.alive; // (a ray-list ray may miss the box)
 					}
 				} else if (take) {
 					const uint32_t x = (tile % F.tiles_x) * 8u + (slot & 7u);
@@ -653,6 +654,7 @@ NGP_DEV void wide_body(const ModelParams& M, const CameraParams& C, const FrameP
 				const f3 pos = add3(ray.o, scale3(ray.d, ray.t));
 				bool out = ray.t >= MAX_DEPTH || !raabb_contains(M, pos);
 				if (PROBE && skip_i >= 200) out = true;
+				if (PROBE && ray.t >= t_max) out = true; // a ray-list ray's t_max: what it gathered is shaded, as at the box exit
 				if (out) {
 					ray.alive = false;
 					finished = true;
@@ -761,7 +763,8 @@ NGP_DEV void wide_body(const ModelParams& M, const CameraParams& C, const FrameP
 		if (run) {
 			ready = false;
 			const f3 pos = add3(amin, mul3(mk3(wx, wy, wz), adiag));
-			const float sdepth = dot3(cam_fwd, sub3(pos, cam_pos));
+			const float sdepth = PROBE ? dot3(ray.d, sub3(pos, ray.o)) // probe rays: the distance along the ray
+			                          : dot3(cam_fwd, sub3(pos, cam_pos));
 			const float T = 1.0f - acc.a;
 			const float dt = unwarp_dt(wdt);
 			const float alpha = 1.0f - fast_exp(-network_to_density((float)o.sigma, M.density_act) * dt);

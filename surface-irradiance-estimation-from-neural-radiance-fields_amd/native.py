@@ -85,6 +85,10 @@ class ProbeGridDesc(C.Structure):
                 ("min_transmittance", C.c_float)]
 
 
+class IrradianceTraceDesc(C.Structure):
+    _fields_ = [("n_u", C.c_uint32), ("n_v", C.c_uint32), ("offset", C.c_float), ("min_transmittance", C.c_float), ("occlude_by_meshes", C.c_int32)]
+
+
 MODE_NERF, MODE_GEOMETRY = 0, 1
 RENDER_SHADE, RENDER_SHADE_ENVMAP, RENDER_AO, RENDER_POSITIONS, RENDER_DEPTH, RENDER_COST, RENDER_SHADE_GRID_ENVMAP, RENDER_NORMALS = 0, 1, 2, 3, 4, 5, 6, 7
 PROBE_CENTER, PROBE_CENTER_OUTWARD, PROBE_MULTI_CENTER = 0, 1, 2
@@ -199,6 +203,9 @@ def load_library():
     L.ngp_compute_envmap_grid.argtypes = [vp, C.POINTER(ProbeGridDesc), vp]
     L.ngp_get_envmap_grid.argtypes = [vp, C.POINTER(ProbeGridDesc), vp]
     L.ngp_irradiance_at.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    L.ngp_trace_nerf_rays.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_float, vp, vp]
+    L.ngp_irradiance_rays.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(IrradianceTraceDesc), vp, vp, vp]
+    L.ngp_irradiance_traced.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(IrradianceTraceDesc), vp]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -595,6 +602,46 @@ class Context:
         nrm = np.ascontiguousarray(normals, np.float32)
         out = np.zeros((nrm.shape[0], 3), np.float32)
         self._check(self.L.ngp_irradiance_at(self.h, nrm.shape[0], _p(pos), _p(nrm), _p(out)))
+        return out
+
+    # ---------------------------------------------------------------- traced irradiance (contract: include/ngp_hip.h)
+    def trace_nerf_rays(self, origins, directions, t_range=None, min_transmittance=0.01):
+        """the caller's rays (ngp space, n x 3 each; t_range None or n x 2 (t_min, t_max)) through the NeRF: (rgba n x 4, depth n)"""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if d.shape != o.shape:
+            raise ValueError("origins and directions: n x 3 each")
+        t = None if t_range is None else np.ascontiguousarray(t_range, np.float32).reshape(o.shape[0], 2)
+        rgba = np.zeros((o.shape[0], 4), np.float32)
+        depth = np.zeros(o.shape[0], np.float32)
+        self._check(self.L.ngp_trace_nerf_rays(self.h, o.shape[0], _p(o), _p(d), _p(t) if t is not None else None, min_transmittance, _p(rgba), _p(depth)))
+        return rgba, depth
+
+    @staticmethod
+    def _irradiance_args(positions, normals, n_u, n_v, offset, occlude_by_meshes, min_transmittance):
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != n.shape:
+            raise ValueError("positions and normals: n x 3 each")
+        d = IrradianceTraceDesc()
+        d.n_u, d.n_v, d.offset, d.min_transmittance, d.occlude_by_meshes = n_u, n_v, offset, min_transmittance, int(bool(occlude_by_meshes))
+        return p, n, d
+
+    def irradiance_rays(self, positions, normals, n_u=16, n_v=16, offset=1e-4, occlude_by_meshes=True, min_transmittance=0.01):
+        """the generator's hemisphere rays: (origins (n, K, 3), directions (n, K, 3), t_max (n, K)), K = n_u n_v, k = u + n_u v"""
+        p, n, d = self._irradiance_args(positions, normals, n_u, n_v, offset, occlude_by_meshes, min_transmittance)
+        k = int(n_u) * int(n_v)
+        o = np.zeros((p.shape[0], k, 3), np.float32)
+        dr = np.zeros((p.shape[0], k, 3), np.float32)
+        t = np.zeros((p.shape[0], k), np.float32)
+        self._check(self.L.ngp_irradiance_rays(self.h, p.shape[0], _p(p), _p(n), C.byref(d), _p(o), _p(dr), _p(t)))
+        return o, dr, t
+
+    def irradiance_traced(self, positions, normals, n_u=16, n_v=16, offset=1e-4, occlude_by_meshes=True, min_transmittance=0.01):
+        """E(p, n) traced at the points: (n, 4) = rgb irradiance, fraction of rays no mesh blocks"""
+        p, n, d = self._irradiance_args(positions, normals, n_u, n_v, offset, occlude_by_meshes, min_transmittance)
+        out = np.zeros((p.shape[0], 4), np.float32)
+        self._check(self.L.ngp_irradiance_traced(self.h, p.shape[0], _p(p), _p(n), C.byref(d), _p(out)))
         return out
 
     # ---------------------------------------------------------------- stages
