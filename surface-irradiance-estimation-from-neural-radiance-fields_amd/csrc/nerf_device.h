@@ -772,7 +772,7 @@ NGP_DEV void store_features(const FeatureAcc& lo, const FeatureAcc& hi, half8& o
 
 // lane (h, c) of a 16-sample pass encodes levels h and h+4: B-fragment element j<4 is feature j of level h,
 // element j>=4 is feature j-4 of level h+4 (the K permutation n(s,h,j) = 32s + 16(j>>2) + 4h + (j&3) that the
-// host applied to every weight matrix, see ngp_api.cpp build_weight_fragments).
+// host applied to every weight matrix, see ngp_model.cpp emit_fragments).
 // The encode is split in two so that a wave can keep the gathers of two 16-sample passes (32 loads per lane) in
 // flight before it consumes either: issue computes the 16 addresses and starts the loads, finish forms the 16
 // trilinear weights (from the 6 cell fractions kept meanwhile) and accumulates.

@@ -1123,7 +1123,7 @@ __global__ void accumulate_tonemap_kernel(uint32_t n_pixels, const float4* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// launchers (called from ngp_api.cpp)
+// launchers (called from the ngp_*.cpp host files)
 // Persistent grids are sized to what is resident at once (workgroups per CU from the occupancy query): a workgroup
 // that only starts when another one has drained would begin its rays late and stretch the frame by a ray lifetime.
 template <typename K>

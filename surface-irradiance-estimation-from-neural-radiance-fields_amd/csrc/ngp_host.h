@@ -289,7 +289,7 @@ struct ngp_ctx {
 	std::vector<uint16_t> density_grid;
 	uint32_t max_cascade = 0;
 	ngp::DevArray<uint16_t> d_params; // the grid table, tcnn order
-	ngp::DevArray<uint64_t> d_xgrid;  // the grid table again, in the xor layout (ngp_api.cpp build_xor_layout)
+	ngp::DevArray<uint64_t> d_xgrid;  // the grid table again, in the xor layout (ngp_model.cpp build_xor_layout)
 	ngp::DevArray<uint4> d_wfrags;
 	ngp::DevArray<uint8_t> d_bitfield;
 	ngp::DevArray<uint32_t> d_coarse;
@@ -366,7 +366,7 @@ struct ngp_ctx {
 	ngp::DevArray<char> d_grid_scratch; // occupancy-grid refresh of a Frequency-encoding model: positions, cells, network outputs of a batch of samples (24 B each)
 	ngp::DevArray<uint32_t> d_trace; // wave timelines of the diagnostic build (NGP_PROFILE_TRACE)
 	static constexpr uint32_t TRACE_WAVES = 64, TRACE_ITERS = 1024;
-	int32_t tune[8] = {64, 4, 32, 1, 1, 4, 1, 1}; // FrameParams::tune; changed only through validate_schedule (ngp_api.cpp)
+	int32_t tune[8] = {64, 4, 32, 1, 1, 4, 1, 1}; // FrameParams::tune; changed only through validate_schedule (ngp_render.cpp)
 
 	// ---- several devices behind this context (ngp_multi.cpp): replicas on the auxiliary devices, tile gather at the primary
 	std::vector<ngp_ctx*> peers;  // owned; empty for a single-device context
@@ -464,21 +464,37 @@ inline void order_after_model(ngp_ctx* ctx, hipStream_t stream) {
 	if (ctx->ev_model_valid) NGP_HIP_CHECK(hipStreamWaitEvent(stream, ctx->ev_model, 0));
 }
 
-void load_snapshot_path(ngp_ctx* ctx, const std::string& path);
-void install_model(ngp_ctx* ctx, const ngp_model_desc& d); // set_model_impl of ngp_api.cpp
+// frame tiles of 8 x 8 pixels dealt round-robin to `count` shards: how many of them shard `index` renders
+inline uint32_t tile_share(int32_t width, int32_t height, uint32_t index, uint32_t count) {
+	const uint32_t tiles = (uint32_t)((width + 7) / 8) * (uint32_t)((height + 7) / 8);
+	return tiles > index ? (tiles - index + count - 1) / count : 0;
+}
+
+// numbers out of untrusted files: a double that does not fit the integer type must not reach the cast (undefined behaviour); out-of-range values
+// become ones that every later validation refuses
+inline uint32_t to_u32(double v) { return v >= 0.0 && v < 4294967296.0 ? (uint32_t)v : 0xffffffffu; }
+inline int to_int(double v) { return v > -2147483648.0 && v < 2147483648.0 ? (int)v : (v < 0.0 ? -2147483647 - 1 : 2147483647); }
+
+// ngp_model.cpp
+void set_model_impl(ngp_ctx* ctx, const ngp_model_desc& d); // validates the descriptor, then replaces the context's model
+void free_model(ngp_ctx* ctx);
 void update_density_grid_device(ngp_ctx* ctx, float decay, uint32_t n_uniform, uint32_t n_nonuniform, uint32_t n_iterations);
 void refresh_density_grid_host(ngp_ctx* ctx);
-uint16_t half_from_float(float f);
+// ngp_snapshot.cpp
+void load_snapshot_path(ngp_ctx* ctx, const std::string& path);
+uint16_t float_to_half(float f);
+void read_vec(const mj::Value& v, float* out, size_t n);
+// ngp_render.cpp
+void schedule_from_env(ngp_ctx* ctx);
+void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels); // (0: the per-call slots and events alone)
+CameraParams make_camera_params(const ngp_camera& cam, uint32_t spp_index);
+void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
 // ngp_train.cpp
 void free_training(ngp_ctx* ctx);
 bool probe_image_size(const std::string& path, int& width, int& height);
 void sync_inference_model(ngp_ctx* ctx); // render what has been trained (no-op when nothing changed)
 void sync_host_params(ngp_ctx* ctx);     // ctx->params <- training parameters, for snapshots
-
-void ensure_sync_buffers(ngp_ctx* ctx);
-// ngp_multi.cpp / ngp_api.cpp
-void render_frames_on(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
-void ensure_frame_buffers_for(ngp_ctx* ctx, size_t n_pixels);
+// ngp_multi.cpp
 void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
 // ngp_mesh.cpp: Geometry mode on an auxiliary device -- the primary's meshes (BVHs as built), shading parameters and irradiance tables
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer);

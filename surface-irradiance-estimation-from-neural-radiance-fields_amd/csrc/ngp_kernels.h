@@ -37,7 +37,7 @@ struct LevelInfo {
 	uint32_t hashed; // 1: spatial hash, 0: dense x + y*res + z*res^2
 	uint32_t mask;   // size-1 if size is a power of two, else 0
 	// xor layout (ModelParams::xgrid): byte offset of corner (x, y, z) = ((8x ^ y*mul_y8 ^ z*mul_z8) & mask8) | base8,
-	// valid while max(x, y, z) of the cell's low corner <= coord_max (always for hashed levels; see ngp_api.cpp
+	// valid while max(x, y, z) of the cell's low corner <= coord_max (always for hashed levels; see ngp_model.cpp
 	// build_xor_layout)
 	uint32_t coord_max;
 	uint32_t mul_y8, mul_z8, mask8, base8;

@@ -345,7 +345,7 @@ void require_probe_model(ngp_ctx* ctx, const char* what) {
 	require_model(ctx);
 	ngp::sync_inference_model(ctx);
 	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error(std::string(what) + " are built for the configs/nerf/base.json rgb head (2 hidden layers)");
-	ensure_sync_buffers(ctx);
+	ensure_frame_buffers(ctx, 0);
 }
 // the model as probe rays see it: in Geometry mode load_scene made the inflated mesh box the render box (testbed_geometry_training.cu:3185-3189)
 ngp::ModelParams probe_model(const ngp_ctx* ctx) {
@@ -377,7 +377,7 @@ void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	hipStream_t stream = ctx->stream;
 	if (ctx->last_stream && ctx->last_stream != stream) NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
-	if (ctx->n_calls >= (uint64_t)ngp_ctx::HISTORY) NGP_HIP_CHECK(hipStreamWaitEvent(stream, ctx->ev_frame1[slot], 0)); // the slot's previous launch (render_frames, ngp_api.cpp)
+	if (ctx->n_calls >= (uint64_t)ngp_ctx::HISTORY) NGP_HIP_CHECK(hipStreamWaitEvent(stream, ctx->ev_frame1[slot], 0)); // the slot's previous launch (render_frames, ngp_render.cpp)
 	FrameParams F{};
 	ctx->bind_slot(F, slot);
 	F.n_local_tiles = (P.n_rays + 63) / 64;

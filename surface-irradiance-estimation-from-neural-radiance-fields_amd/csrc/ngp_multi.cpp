@@ -31,10 +31,10 @@ void sync_peer_model(ngp_ctx* primary, ngp_ctx* peer) {
 		d.n_density_grid = primary->density_grid.size();
 		{
 			DeviceGuard g(peer->device);
-			install_model(peer, d);
+			set_model_impl(peer, d);
 		}
 		peer->synced_generation = primary->model_generation;
-		// (install_model derives the occupancy bits from the fp16 grid of the descriptor; if the primary has refreshed its grid since
+		// (set_model_impl derives the occupancy bits from the fp16 grid of the descriptor; if the primary has refreshed its grid since
 		// it was loaded, its fp32 grid is the truth -- copied below)
 		peer->synced_grid_generation = primary->grid_generation == 0 ? 0 : ~0ull;
 		peer->synced_params_generation = primary->params_generation == 0 ? 0 : ~0ull;
@@ -108,8 +108,7 @@ void ensure_pack_buffers(ngp_ctx* ctx, size_t n_pixels_packed) {
 void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream) {
 	if (opts.packed_output) throw std::runtime_error("packed_output addresses one shard: render it through a single-device context");
 	const uint32_t n_dev = 1u + (uint32_t)ctx->peers.size();
-	const uint32_t tiles = (uint32_t)((cam.width + 7) / 8) * (uint32_t)((cam.height + 7) / 8);
-	const uint32_t n_slots = (tiles + n_dev - 1) / n_dev; // tiles per device, rounded up: the stride of a device's block at the primary
+	const uint32_t n_slots = tile_share(cam.width, cam.height, 0, n_dev); // tiles per device, rounded up (device 0's share): the stride of a device's block at the primary
 	const size_t packed = (size_t)n_slots * 64;
 	{ // the primary's landing zone for everybody's tiles
 		DeviceGuard g(ctx->device);
@@ -140,7 +139,7 @@ void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_o
 		o.shard_count = n_dev;
 		o.packed_output = 1;
 		if (i > 0) NGP_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_pack, 0)); // do not push into a landing zone the previous frame still reads
-		render_frames_on(dev, cam, o, dev->d_pack_rgba.get(), dev->d_pack_depth.get(), s);
+		render_frames(dev, cam, o, dev->d_pack_rgba.get(), dev->d_pack_depth.get(), s);
 		// push this device's tiles to the primary: one peer copy each for colour and depth (5.2 MB per GPU at 1080p / 8 GPUs), on the
 		// rendering device's stream so that it follows the kernel without a host round trip
 		NGP_HIP_CHECK(hipMemcpyPeerAsync(ctx->d_gather_rgba.get() + packed * i, ctx->device, dev->d_pack_rgba.get(), dev->device, packed * sizeof(float4), s));
@@ -150,7 +149,7 @@ void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_o
 	DeviceGuard g(ctx->device);
 	for (ngp_ctx* p : ctx->peers) NGP_HIP_CHECK(hipStreamWaitEvent(stream, p->ev_pack, 0));
 	if (!d_depth) {
-		ensure_frame_buffers_for(ctx, (size_t)cam.width * cam.height);
+		ensure_frame_buffers(ctx, (size_t)cam.width * cam.height);
 		d_depth = ctx->d_depth.get();
 	}
 	launch_unpack_tiles(ctx->d_gather_rgba.get(), ctx->d_gather_depth.get(), n_dev, n_slots, cam.width, cam.height, d_rgba, d_depth, stream);

@@ -1,0 +1,510 @@
+// Frames: the per-frame constants, the scheduling knobs, the context's frame buffers and the issue of a frame's work on a
+// stream; page-locked host images; render statistics.
+#include "ngp_host.h"
+
+#include <map>
+#include <mutex>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+using namespace ngp;
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ sampling (host)
+// ld_random_pixel_offset (random_val.cuh:365-370) is a per-frame constant, so it is evaluated once on the host.
+// Sobol dimensions 0 and 1 need no table: dim 0 is a bit reversal, dim 1's direction numbers obey v[i] = v[i-1] ^ (v[i-1] >> 1).
+uint32_t reverse_bits32(uint32_t x) {
+	x = ((x & 0xaaaaaaaau) >> 1) | ((x & 0x55555555u) << 1);
+	x = ((x & 0xccccccccu) >> 2) | ((x & 0x33333333u) << 2);
+	x = ((x & 0xf0f0f0f0u) >> 4) | ((x & 0x0f0f0f0fu) << 4);
+	x = ((x & 0xff00ff00u) >> 8) | ((x & 0x00ff00ffu) << 8);
+	return (x >> 16) | (x << 16);
+}
+uint32_t lk_perm(uint32_t x, uint32_t seed) {
+	x += seed;
+	x ^= x * 0x6c50b47cu;
+	x ^= x * 0xb82f1e52u;
+	x ^= x * 0xc7afe638u;
+	x ^= x * 0x8d22f6e6u;
+	return x;
+}
+uint32_t nus2(uint32_t x, uint32_t seed) { return reverse_bits32(lk_perm(reverse_bits32(x), seed)); }
+uint32_t hash_combine(uint32_t seed, uint32_t v) { return seed ^ (v + (seed << 6) + (seed >> 2)); }
+uint32_t sobol_dim(uint32_t index, int dim) {
+	if (dim == 0) return reverse_bits32(index);
+	uint32_t v = 0x80000000u, X = 0;
+	for (int bit = 0; bit < 32; ++bit) {
+		if ((index >> bit) & 1u) X ^= v;
+		v ^= v >> 1;
+	}
+	return X;
+}
+void ld_random_val_2d(uint32_t index, uint32_t seed, float* out) {
+	index = nus2(index, seed);
+	for (int i = 0; i < 2; ++i) out[i] = (float)nus2(sobol_dim(index, i), hash_combine(seed, (uint32_t)i)) * 2.3283064365386963e-10f;
+}
+void ld_random_pixel_offset(uint32_t spp, float* out) {
+	float a[2], b[2];
+	ld_random_val_2d(0, 0xdeadbeefu, a);
+	ld_random_val_2d(spp, 0xdeadbeefu, b);
+	for (int i = 0; i < 2; ++i) {
+		float v = (0.5f - a[i]) + b[i];
+		out[i] = v - floorf(v);
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ frame
+// The scheduling knobs of the persistent render kernel (FrameParams::tune). They never change results except
+// block_jumps (0 = the reference's voxel-by-voxel walk through empty space), but values outside these ranges would
+// leave a wave spinning in fused_body's loop (a refill threshold above 64 never refills, zero march steps never
+// advance a ray): a GPU hang, not an error. Hence one gate for every way of setting them.
+void validate_schedule(const int32_t* t, int n) {
+	static const struct { const char* name; int lo, hi; } range[8] = {{"refill_min", 16, 64}, {"skip_steps", 1, 64},  {"go_min", 1, 64},      {"max_stall", 0, 64},
+	                                                                  {"k_busy", 1, 8},       {"k_drain", 1, 8},      {"block_jumps", 0, 1}, {"share", 0, 1}};
+	if (n < 0 || n > 8) throw std::runtime_error("schedule: at most 8 knobs");
+	for (int i = 0; i < n; ++i)
+		if (t[i] < range[i].lo || t[i] > range[i].hi)
+			throw std::runtime_error(std::string("schedule knob ") + range[i].name + " = " + std::to_string(t[i]) + " outside [" + std::to_string(range[i].lo) + ", " + std::to_string(range[i].hi) + "]");
+}
+
+uint32_t shard_count_of(const ngp_render_opts& opts) { return opts.shard_count ? opts.shard_count : 1u; }
+
+// What a frame of the render kernel needs beyond the camera (FrameParams), and the call's copy of the model (M arrives as ctx->M;
+// a Geometry-mode frame marches the NeRF inside the meshes' box). Enqueues the clears of the diagnostic buffers on `stream`.
+void make_frame_params(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float* d_depth_out, int slot, int spp, hipStream_t stream, FrameParams& F, ModelParams& M) {
+	const uint32_t shard_count = shard_count_of(opts);
+	F.frame_buffer = ctx->d_frame.get();
+	F.depth_buffer = d_depth_out ? d_depth_out : ctx->d_depth.get();
+	ctx->bind_slot(F, slot); // every call has its own queue word and counters: frames on different streams may overlap
+	if (shard_count > 1) F.xqueue = nullptr; // per-XCD bands pay for a whole frame (+1.4 %); a rank's interleaved share is too small for them (N = 4: -3 %, N = 8: -6 %)
+	F.tiles_x = (uint32_t)(cam.width + 7) / 8;
+	F.tiles_y = (uint32_t)(cam.height + 7) / 8;
+	F.shard_index = opts.shard_index;
+	F.shard_count = shard_count;
+	F.n_local_tiles = tile_share(cam.width, cam.height, opts.shard_index, shard_count);
+	F.min_transmittance = opts.min_transmittance;
+	F.linear_colors = ctx->desc.linear_colors;
+	F.packed = opts.packed_output ? 1 : 0;
+	F.prof = nullptr;
+	memcpy(F.tune, ctx->tune, sizeof(F.tune));
+	if (getenv("NGP_PROFILE_SECTIONS")) { // diagnostic: per-section cycle sums of the fused kernel, printed by ngp_get_render_stats
+		if (!ctx->d_prof) ctx->d_prof.reset(128);
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_prof.get(), 0, 1024, stream));
+		F.prof = ctx->d_prof.get();
+		F.prof_level = atoi(getenv("NGP_PROFILE_SECTIONS"));
+		if (const char* e = getenv("NGP_PROFILE_TRACE")) { // timelines of every stride-th working wave (tools/wave_trace.py)
+			const int stride = atoi(e);
+			if (stride > 0) {
+				const size_t words = 16 + (size_t)ngp_ctx::TRACE_WAVES * 16 + (size_t)ngp_ctx::TRACE_WAVES * ngp_ctx::TRACE_ITERS * 16;
+				if (!ctx->d_trace) ctx->d_trace.reset(words);
+				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_trace.get(), 0, words * sizeof(uint32_t), stream));
+				F.trace = ctx->d_trace.get();
+				F.trace_stride = (uint32_t)stride;
+				F.trace_cap_waves = ngp_ctx::TRACE_WAVES;
+				F.trace_cap_iters = ngp_ctx::TRACE_ITERS;
+			}
+		}
+	}
+	const bool geometry = opts.testbed_mode == NGP_MODE_GEOMETRY;
+	const bool have_meshes = geometry && !ctx->meshes.empty();
+	if (have_meshes && cam.has_matrix1 && memcmp(cam.matrix, cam.matrix1, sizeof(cam.matrix)) != 0) throw std::runtime_error("a moving camera (matrix1 / rolling shutter) renders NeRF mode");
+	F.depth_test = geometry ? 1 : 0; // shade_kernel_nerf_geometry
+	if (have_meshes) { // load_scene sets m_render_aabb to the inflated mesh bb (testbed_geometry_training.cu:3185-3189)
+		for (int i = 0; i < 3; ++i) { M.raabb_min[i] = ctx->mesh_scene.scene_min[i]; M.raabb_max[i] = ctx->mesh_scene.scene_max[i]; }
+		const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+		memcpy(M.r2l, ident, sizeof(ident));
+		M.r2l_identity = 1u;
+	}
+
+	// 1 spp and no mesh pass: the fused kernel writes finished pixels (clear + accumulate + tonemap folded in) straight
+	// into the caller's image -- one 32-byte memset and one launch per frame
+	// (a rank's share in image layout keeps the general path: the other ranks' pixels must read as an empty frame)
+	F.direct = (spp == 1 && !have_meshes && !geometry && (shard_count == 1 || opts.packed_output)) ? 1 : 0;
+	F.to_srgb = opts.to_srgb;
+	F.render_mode = opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ? NGP_RENDER_SHADE_ENVMAP : opts.render_mode; // (the NeRF pass treats both like Shade)
+	F.color_space = opts.color_space;
+	if (opts.color_space != 0 && opts.color_space != 1) throw std::runtime_error("color_space: 0 (Linear) or 1 (SRGB)");
+	F.depth_scale = opts.depth_scale != 0.f ? opts.depth_scale : 1.0f / 0.33f;
+	memcpy(F.background, opts.background, sizeof(F.background));
+	F.exposure_scale = powf(2.0f, opts.exposure);
+	if (ctx->d_bg_envmap) {
+		if (geometry) throw std::runtime_error("an environment map applies to NeRF mode (in the reference the Geometry-mode NeRF pass would paint it over the meshes, src/testbed_geometry_training.cu:1993-1995): clear it with ngp_set_envmap(ctx, 0, 0, NULL)");
+		F.envmap = ctx->d_bg_envmap.get();
+		F.env_w = ctx->bg_env_w;
+		F.env_h = ctx->bg_env_h;
+	}
+	{ // a render box inside the outermost cascade's cube never puts a ray outside the occupancy grid (kernel selection)
+		const float h = 0.5f * (float)(1u << M.max_cascade);
+		bool inside = M.r2l_identity != 0;
+		for (int i = 0; i < 3; ++i) inside = inside && M.raabb_min[i] >= 0.5f - h && M.raabb_max[i] <= 0.5f + h;
+		F.outside_possible = inside ? 0 : 1;
+	}
+}
+
+// what can be refused before anything is allocated or enqueued
+void validate_render_request(const ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts) {
+	if (cam.width <= 0 || cam.height <= 0 || cam.width > 65536 || cam.height > 65536) throw std::runtime_error("invalid render resolution"); // (tile counts stay inside 32 bits)
+	if (opts.render_mode < NGP_RENDER_SHADE || opts.render_mode > NGP_RENDER_NORMALS) throw std::runtime_error("render modes implemented: Shade, ShadeEnvMap, ShadeGridEnvMap, AO, Normals, Positions, Depth, Cost");
+	const bool gbuffer_mode = (opts.render_mode >= NGP_RENDER_AO && opts.render_mode <= NGP_RENDER_COST) || opts.render_mode == NGP_RENDER_NORMALS;
+	if (gbuffer_mode && opts.testbed_mode == NGP_MODE_GEOMETRY) throw std::runtime_error("the G-buffer render modes (AO, Normals, Positions, Depth, Cost) apply to NeRF mode");
+	if (opts.render_mode == NGP_RENDER_NORMALS && ctx->model_loaded && ctx->M.wide.width && (!ctx->M.wide.layers_t[0].n_mtiles || ctx->M.wide.enc_dims > ctx->M.wide.width))
+		throw std::runtime_error("render_mode Normals on a Frequency / Identity-encoding model: implemented for up to 8 hidden density layers and an encoding no wider than the network");
+	if (opts.shard_index >= shard_count_of(opts)) throw std::runtime_error("shard_index out of range");
+}
+
+} // namespace
+
+namespace ngp {
+// NGP_TUNE="refill_min,skip_steps,..." (experiments: tools/sweep_tune.sh): read ONCE, at context creation
+void schedule_from_env(ngp_ctx* ctx) {
+	const char* t = getenv("NGP_TUNE");
+	if (!t || !*t) return;
+	int32_t v[8];
+	memcpy(v, ctx->tune, sizeof(v));
+	int n = sscanf(t, "%d,%d,%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]);
+	if (n <= 0) throw std::runtime_error("NGP_TUNE: expected a comma-separated list of integers");
+	validate_schedule(v, n);
+	memcpy(ctx->tune, v, sizeof(v));
+}
+
+CameraParams make_camera_params(const ngp_camera& cam, uint32_t spp_index) {
+	CameraParams C{};
+	memcpy(C.m, cam.matrix, sizeof(C.m));
+	C.width = cam.width;
+	C.height = cam.height;
+	C.focal[0] = cam.focal_length[0];
+	C.focal[1] = cam.focal_length[1];
+	C.screen_center[0] = cam.screen_center[0];
+	C.screen_center[1] = cam.screen_center[1];
+	C.spp = spp_index;
+	C.near_distance = cam.near_distance;
+	if (cam.lens_mode < 0 || cam.lens_mode > NGP_LENS_EQUIRECTANGULAR) throw std::runtime_error("unknown lens mode (Perspective, OpenCV, FTheta, LatLong, OpenCVFisheye, Equirectangular)");
+	C.lens_mode = cam.lens_mode;
+	C.aperture_size = cam.focus_z < 0.f ? 0.f : cam.aperture_size; // plane_z < 0 switches the aperture off (src/testbed_nerf.cu:1462-1464)
+	C.focus_z = cam.focus_z;
+	if (C.aperture_size != 0.f && !(C.focus_z > 0.f)) throw std::runtime_error("depth of field needs a positive focus distance");
+	memcpy(C.lens_params, cam.lens_params, sizeof(C.lens_params));
+	// camera_matrix1 + rolling shutter: a frame is "moving" only when camera1 differs from camera0 or the per-pixel time is not the
+	// whole-frame constant the quaternion round trip would leave unchanged anyway
+	C.moving = cam.has_matrix1 && memcmp(cam.matrix, cam.matrix1, sizeof(cam.matrix)) != 0 ? 1 : 0;
+	memcpy(C.m1, cam.has_matrix1 ? cam.matrix1 : cam.matrix, sizeof(C.m1));
+	memcpy(C.rolling_shutter, cam.rolling_shutter, sizeof(C.rolling_shutter));
+	if (!cam.has_matrix1) { C.rolling_shutter[0] = C.rolling_shutter[1] = C.rolling_shutter[2] = 0.f; C.rolling_shutter[3] = 1.f; }
+	ld_random_pixel_offset(cam.snap_to_pixel_centers ? 0u : spp_index, C.pixel_offset);
+	return C;
+}
+
+void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->d_sync) {
+		ctx->d_sync.reset(ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY);
+		NGP_HIP_CHECK(hipMemset(ctx->d_sync.get(), 0, ngp_ctx::SLOT_BYTES * ngp_ctx::HISTORY));
+		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
+			ctx->ev_frame0[i] = new_event();
+			ctx->ev_frame1[i] = new_event();
+			ctx->ev_kern0[i] = new_event();
+			ctx->ev_kern1[i] = new_event();
+		}
+	}
+	if (n_pixels <= ctx->d_rgba.size()) return;
+	ctx->d_frame.reset(), ctx->d_depth.reset(), ctx->d_accum.reset(), ctx->d_rgba.reset(); // all four go before the new ones come
+	ctx->d_frame.reset(n_pixels);
+	ctx->d_depth.reset(n_pixels);
+	ctx->d_accum.reset(n_pixels);
+	ctx->d_rgba.reset(n_pixels);
+}
+
+// Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
+void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba_out, float* d_depth_out, hipStream_t stream) {
+	require_device(ctx, "rendering needs an MI355X");
+	if (!ctx->model_loaded && !(opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty())) throw std::runtime_error("No network available."); // testbed.cu:4735-4738
+	sync_inference_model(ctx);
+	validate_render_request(ctx, cam, opts);
+	// frame-buffer extent: the whole image, or only this shard's tiles in tile-packed order
+	const size_t n_pixels = opts.packed_output ? (size_t)tile_share(cam.width, cam.height, opts.shard_index, shard_count_of(opts)) * 64 : (size_t)cam.width * cam.height;
+	ensure_frame_buffers(ctx, n_pixels ? n_pixels : 1);
+	const int spp = opts.spp > 0 ? opts.spp : 1;
+	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
+	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
+	// in an unsynchronised loop of short frames, may still be running: two live launches on one slot would deal tiles twice and zero
+	// the slot under each other. Order this call's stream behind that frame's end (a device-side wait, no host stall; free when the
+	// old frame is long done, which is the usual case).
+	if (ctx->n_calls >= (uint64_t)ngp_ctx::HISTORY) NGP_HIP_CHECK(hipStreamWaitEvent(stream, ctx->ev_frame1[slot], 0));
+	FrameParams F{};
+	ModelParams M = ctx->M;
+	make_frame_params(ctx, cam, opts, d_depth_out, slot, spp, stream, F, M);
+	const bool have_meshes = opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty();
+
+	order_after_model(ctx, stream); // a training step / grid refresh / peer copy that updated what this frame reads (a device-side wait)
+	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot], stream));
+	if (F.direct) {
+		F.frame_buffer = d_rgba_out;
+		CameraParams C = make_camera_params(cam, cam.spp_index);
+		NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
+		launch_render_nerf(M, C, F, ctx->n_cus, stream);
+		NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
+	}
+	if (!F.direct && ctx->n_calls > 0 && (ctx->streams_mixed || (ctx->last_stream && ctx->last_stream != stream))) {
+		// the general path goes through the context's own frame / accumulate buffers: frames on other streams must have
+		// left them (only direct-output frames may overlap each other). Several may still be in flight, one event would
+		// not cover them all: wait for the device.
+		NGP_HIP_CHECK(hipDeviceSynchronize());
+		ctx->streams_mixed = false;
+	}
+	if (ctx->last_stream && ctx->last_stream != stream) ctx->streams_mixed = true;
+	for (int s = 0; s < spp && !F.direct; ++s) {
+		CameraParams C = make_camera_params(cam, cam.spp_index + (uint32_t)s);
+		// CudaRenderBufferView::clear (src/render_buffer.cu:603-607)
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_frame.get(), 0, n_pixels * sizeof(float4), stream));
+		NGP_HIP_CHECK(hipMemsetAsync(F.depth_buffer, 0, n_pixels * sizeof(float), stream));
+		F.add_results = s > 0 ? 1 : 0; // the call's counters are the sums over its samples per pixel
+		const bool last = s == spp - 1;
+		if (have_meshes) {
+			IrradianceMap I{};
+			if (opts.render_mode == NGP_RENDER_SHADE_ENVMAP) {
+				if (!ctx->d_irradiance || ctx->env_probe.mode == 3) throw std::runtime_error("render_mode ShadeEnvMap needs ngp_compute_envmap first");
+				I = irradiance_map_of(ctx);
+			} else if (opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP) {
+				if (!ctx->d_irradiance || ctx->env_probe.mode != 3) throw std::runtime_error("render_mode ShadeGridEnvMap needs ngp_compute_envmap_grid first");
+				I = irradiance_map_of(ctx);
+			}
+			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+		}
+		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
+		if (ctx->model_loaded) launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
+		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
+		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
+		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame.get(), ctx->d_accum.get(), (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
+	}
+	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
+	NGP_HIP_CHECK(hipGetLastError());
+	ctx->last_stream = stream;
+	ctx->hist_n_rays[slot] = (uint64_t)F.n_local_tiles * 64u * (uint64_t)spp;
+	ctx->last_was_multi = false;
+	++ctx->n_calls;
+}
+} // namespace ngp
+
+// ================================================================================================== C ABI
+extern "C" {
+
+// ---- page-locked host images. Testbed::render_to_cpu returns a fresh numpy array per call (src/python_api.cu:124-202); a
+// pageable destination makes the runtime stage the 33 MB of a 1080p frame through its own bounce buffers (1.7 ms, against
+// 2.1 ms of rendering). Buffers from this pool are pinned once and recycled by size, so a binding can hand out "fresh"
+// arrays that the copy engine writes directly.
+namespace {
+struct HostPool {
+	std::mutex mu;
+	std::multimap<size_t, void*> free_list;
+	std::map<void*, size_t> live;
+	~HostPool() { // (process exit: the runtime may already be gone; leave the pages to the OS)
+	}
+} g_host_pool;
+constexpr size_t HOST_POOL_KEEP = 8; // buffers kept for reuse per process
+
+// the device-side address of [host, host + bytes) if that range lies inside a live page-locked buffer of the pool, else nullptr
+void* pinned_device_alias(const void* host, size_t bytes) {
+	std::lock_guard<std::mutex> lock(g_host_pool.mu);
+	auto it = g_host_pool.live.upper_bound(const_cast<void*>(host));
+	if (it == g_host_pool.live.begin()) return nullptr;
+	--it;
+	const char* base = (const char*)it->first;
+	if (it->second == 0 || (const char*)host < base || (const char*)host + bytes > base + it->second) return nullptr;
+	void* dev = nullptr;
+	if (hipHostGetDevicePointer(&dev, it->first, 0) != hipSuccess || !dev) {
+		(void)hipGetLastError();
+		return nullptr;
+	}
+	return (char*)dev + ((const char*)host - base);
+}
+} // namespace
+
+void* ngp_host_alloc(size_t bytes) {
+	if (bytes == 0) return nullptr;
+	const size_t rounded = (bytes + 4095) & ~(size_t)4095;
+	{
+		std::lock_guard<std::mutex> lock(g_host_pool.mu);
+		auto it = g_host_pool.free_list.find(rounded);
+		if (it != g_host_pool.free_list.end()) {
+			void* p = it->second;
+			g_host_pool.free_list.erase(it);
+			g_host_pool.live[p] = rounded;
+			return p;
+		}
+	}
+	void* p = nullptr;
+	if (hipHostMalloc(&p, rounded, hipHostMallocDefault) != hipSuccess) { // no device / no pinned memory left: plain memory still works, only slower
+		(void)hipGetLastError();
+		p = aligned_alloc(4096, rounded);
+		if (!p) return nullptr;
+		std::lock_guard<std::mutex> lock(g_host_pool.mu);
+		g_host_pool.live[p] = 0; // 0: malloc'ed, never pooled
+		return p;
+	}
+	std::lock_guard<std::mutex> lock(g_host_pool.mu);
+	g_host_pool.live[p] = rounded;
+	return p;
+}
+
+void ngp_host_free(void* p) {
+	if (!p) return;
+	size_t size = 0;
+	bool release = false;
+	{
+		std::lock_guard<std::mutex> lock(g_host_pool.mu);
+		auto it = g_host_pool.live.find(p);
+		if (it == g_host_pool.live.end()) return; // not ours
+		size = it->second;
+		g_host_pool.live.erase(it);
+		if (size != 0 && g_host_pool.free_list.size() < HOST_POOL_KEEP) g_host_pool.free_list.emplace(size, p);
+		else release = true;
+	}
+	if (!release) return;
+	if (size == 0) free(p);
+	else (void)hipHostFree(p);
+}
+
+int ngp_render_device(ngp_ctx* ctx, const ngp_camera* cam, const ngp_render_opts* opts, void* d_rgba, void* d_depth, void* stream) {
+	return guarded(ctx, [&] {
+		if (!cam || !opts || !d_rgba) throw std::runtime_error("null argument");
+		if (!ctx->peers.empty() && opts->shard_count <= 1) { // a multi-device context: every device renders its tiles, device 0 assembles
+			ngp::render_frames_multi(ctx, *cam, *opts, (float4*)d_rgba, (float*)d_depth, stream ? (hipStream_t)stream : ctx->stream);
+			return;
+		}
+		render_frames(ctx, *cam, *opts, (float4*)d_rgba, (float*)d_depth, stream ? (hipStream_t)stream : ctx->stream);
+	});
+}
+
+uint32_t ngp_packed_tiles(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count) {
+	if (width <= 0 || height <= 0 || shard_count == 0 || shard_index >= shard_count) return 0;
+	return tile_share(width, height, shard_index, shard_count);
+}
+
+int ngp_render(ngp_ctx* ctx, const ngp_camera* cam, const ngp_render_opts* opts, float* rgba_out, float* depth_out) {
+	return guarded(ctx, [&] {
+		if (!cam || !opts) throw std::runtime_error("null argument");
+		if (cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536) throw std::runtime_error("invalid render resolution");
+		if (!rgba_out) throw std::runtime_error("null argument");
+		if (opts->packed_output) throw std::runtime_error("packed_output is for ngp_render_device (GPU-resident tiles); ngp_render returns images");
+		require_device(ctx, "rendering needs an MI355X");
+		const size_t n_pixels = (size_t)cam->width * cam->height;
+		ensure_frame_buffers(ctx, n_pixels);
+		// A destination from ngp_host_alloc is page-locked AND mapped into the device's address space: the image is write-only for
+		// every kernel that produces it (the fused kernel's direct output, accumulate + tonemap, the multi-device tile scatter), so
+		// they write it over the link while they run and no copy follows the frame -- the 33 MB of a 1080p frame would take the
+		// copy engine 0.8 ms after a 2.4 ms render. NGP_HOST_DIRECT=0 restores render-then-copy (A/B measurements).
+		static const bool host_direct = []() { const char* e = getenv("NGP_HOST_DIRECT"); return !e || atoi(e) != 0; }();
+		float4* d_image = host_direct ? (float4*)pinned_device_alias(rgba_out, n_pixels * sizeof(float4)) : nullptr;
+		float4* d_target = d_image ? d_image : ctx->d_rgba.get();
+		if (!ctx->peers.empty() && opts->shard_count <= 1) ngp::render_frames_multi(ctx, *cam, *opts, d_target, ctx->d_depth.get(), ctx->stream);
+		else render_frames(ctx, *cam, *opts, d_target, nullptr, ctx->stream);
+		// (otherwise: one DMA at the link's rate into page-locked memory, a staged copy into ordinary memory)
+		if (!d_image) NGP_HIP_CHECK(hipMemcpyAsync(rgba_out, ctx->d_rgba.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+		if (depth_out) NGP_HIP_CHECK(hipMemcpyAsync(depth_out, ctx->d_depth.get(), n_pixels * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	});
+}
+
+static void read_history_slot(ngp_ctx* ctx, uint64_t call, ngp_render_stats* out) {
+	const int slot = (int)(call % ngp_ctx::HISTORY);
+	unsigned long long c[4];
+	NGP_HIP_CHECK(hipMemcpy(c, ctx->d_sync.get() + ngp_ctx::SLOT_BYTES * (size_t)slot + 32, sizeof(c), hipMemcpyDeviceToHost)); // the slot's results (ngp_ctx::bind_slot)
+	out->kernel_device_ms = (float)((double)c[3] * 1e-5); // 100 MHz ticks
+	out->n_rays = ctx->hist_n_rays[slot];
+	out->n_rays_alive_after_init = c[0];
+	out->n_rays_hit = c[1];
+	out->n_samples = c[2];
+	NGP_HIP_CHECK(hipEventElapsedTime(&out->kernel_ms, ctx->ev_kern0[slot], ctx->ev_kern1[slot]));
+	NGP_HIP_CHECK(hipEventElapsedTime(&out->frame_ms, ctx->ev_frame0[slot], ctx->ev_frame1[slot]));
+}
+
+int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {
+	return guarded(ctx, [&] {
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls) throw std::runtime_error("nothing rendered yet");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		read_history_slot(ctx, ctx->n_calls - 1, out);
+		if (ctx->last_was_multi) { // a frame over several devices: totals over the devices' shares, the slowest share's times
+			for (ngp_ctx* p : ctx->peers) {
+				ngp_render_stats s{};
+				DeviceGuard g(p->device);
+				if (ngp_get_render_stats(p, &s) != 0) throw std::runtime_error(p->error);
+				out->n_rays += s.n_rays; out->n_rays_alive_after_init += s.n_rays_alive_after_init; out->n_rays_hit += s.n_rays_hit; out->n_samples += s.n_samples;
+				out->kernel_ms = std::max(out->kernel_ms, s.kernel_ms);
+				out->frame_ms = std::max(out->frame_ms, s.frame_ms);
+				out->kernel_device_ms = std::max(out->kernel_device_ms, s.kernel_device_ms);
+			}
+		}
+		if (ctx->d_prof && getenv("NGP_PROFILE_SECTIONS")) {
+			unsigned long long p[128];
+			NGP_HIP_CHECK(hipMemcpy(p, ctx->d_prof.get(), sizeof(p), hipMemcpyDeviceToHost));
+			{ // wave timeline on the 100 MHz chip clock: when the tile queue ran dry, when the last wave left
+				const double us = 0.01, t_first = (double)(~p[8]);
+				fprintf(stderr, "[ngp timeline] kernel %.1f us | queue empty seen first at %.1f us, last at %.1f us | wave exits per 0.1 ms:", ((double)p[9] - t_first) * us,
+				        ((double)(~p[10]) - t_first) * us, ((double)p[11] - t_first) * us);
+				for (int b = 0; b < 48; ++b) fprintf(stderr, " %llu", p[16 + b]);
+				fprintf(stderr, "\n[ngp skips] lane-steps that left an empty cell %llu, an empty 4^3 block %llu, an empty 16^3 block %llu\n", p[12], p[13], p[14]);
+			}
+			double tot = (double)(p[0] + p[1] + p[2] + p[3]);
+			fprintf(stderr, "[ngp profile] refill %.1f%% march %.1f%% network %.1f%% composite %.1f%% | wave-iterations %llu passes %llu | cycles/iter %.0f cycles/pass(network) %.0f | skip rounds %llu lane-steps %llu (%.1f lanes/round) cycles/round %.0f\n",
+			        100.0 * p[0] / tot, 100.0 * p[1] / tot, 100.0 * p[2] / tot, 100.0 * p[3] / tot, p[4], p[5], tot / (double)p[4], (double)p[2] / (double)p[5], p[6], p[7], (double)p[7] / (double)p[6], (double)p[1] / (double)p[6]);
+			if (ctx->M.wide.width && p[5]) // the wide kernel's finer sections (wide_kernels.hip), cycles per network round of one workgroup
+				fprintf(stderr, "[ngp wide profile] per network round: hidden layers %.0f (-) %.0f output layers %.0f | march loop %.0f decision %.0f rows+prefetch %.0f encode %.0f composite %.0f | rounds %llu network rounds %llu\n",
+				        (double)p[64] / p[5], (double)p[65] / p[5], (double)p[71] / p[5], (double)p[66] / p[5], (double)p[67] / p[5], (double)p[68] / p[5], (double)p[69] / p[5], (double)p[70] / p[5], p[4], p[5]);
+		}
+	});
+}
+
+// diagnostic (NGP_PROFILE_SECTIONS + NGP_PROFILE_TRACE): the wave timelines of the last frame; layout in csrc/ngp_kernels.h (FrameParams::trace)
+int ngp_get_profile_trace(ngp_ctx* ctx, uint32_t* out, uint64_t n_words, uint32_t* cap_waves, uint32_t* cap_iters) {
+	return guarded(ctx, [&] {
+		if (!ctx->d_trace) throw std::runtime_error("no wave trace: set NGP_PROFILE_SECTIONS=1|2 and NGP_PROFILE_TRACE=<stride> before rendering");
+		const size_t words = 16 + (size_t)ngp_ctx::TRACE_WAVES * 16 + (size_t)ngp_ctx::TRACE_WAVES * ngp_ctx::TRACE_ITERS * 16;
+		if (cap_waves) *cap_waves = ngp_ctx::TRACE_WAVES;
+		if (cap_iters) *cap_iters = ngp_ctx::TRACE_ITERS;
+		if (!out) return;
+		NGP_HIP_CHECK(hipDeviceSynchronize());
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_trace.get(), std::min<size_t>(words, (size_t)n_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_set_schedule(ngp_ctx* ctx, const int32_t* knobs, int n) {
+	return guarded(ctx, [&] {
+		if (!knobs) throw std::runtime_error("schedule: null");
+		validate_schedule(knobs, n);
+		if (ctx->last_stream) NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		for (int i = 0; i < n; ++i) ctx->tune[i] = knobs[i];
+	});
+}
+
+int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out) {
+	return guarded(ctx, [&] {
+		if (!out || n <= 0) throw std::runtime_error("invalid argument");
+		if ((uint64_t)n > ctx->n_calls || n > ngp_ctx::HISTORY) throw std::runtime_error("history holds fewer render calls than requested");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		for (int i = 0; i < n; ++i) read_history_slot(ctx, ctx->n_calls - (uint64_t)n + (uint64_t)i, &out[i]);
+	});
+}
+
+int ngp_set_envmap(ngp_ctx* ctx, int32_t width, int32_t height, const float* rgba) {
+	return guarded(ctx, [&] {
+		if (ctx->device < 0) throw std::runtime_error("this context has no HIP device (host-only)");
+		NGP_HIP_CHECK(hipDeviceSynchronize()); // frames in flight read the map
+		ctx->d_bg_envmap.reset();
+		ctx->bg_env_w = ctx->bg_env_h = 0;
+		if (!rgba || width <= 0 || height <= 0) return;
+		if ((int64_t)width * height > (1ll << 28)) throw std::runtime_error("environment map too large");
+		ctx->d_bg_envmap.upload((const float4*)rgba, (size_t)width * height);
+		ctx->bg_env_w = width;
+		ctx->bg_env_h = height;
+		for (ngp_ctx* p : ctx->peers) { // the replicas of a multi-device context see the same background
+			DeviceGuard g(p->device);
+			if (ngp_set_envmap(p, width, height, rgba) != 0) throw std::runtime_error(p->error);
+		}
+	});
+}
+
+} // extern "C"

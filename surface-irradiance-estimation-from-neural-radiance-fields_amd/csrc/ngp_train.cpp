@@ -409,7 +409,7 @@ void sync_inference_model(ngp_ctx* ctx) {
 	if (!ctx->train || !ctx->train->inference_dirty || ctx->device < 0 || !ctx->model_loaded) return;
 	TrainState& T = *ctx->train;
 	hipStream_t stream = ctx->stream;
-	ensure_sync_buffers(ctx);
+	ensure_frame_buffers(ctx, 0);
 	order_after_frames(ctx, stream); // frames in flight on any stream read the tables: the update waits for them on the device, the host does not
 	const uint16_t* src = T.opts.ema_decay > 0.f ? T.d_weights_ema.get() : T.d_weights.get();
 	const size_t ng = (size_t)T.n_params - T.n_matrix;
@@ -509,14 +509,14 @@ int ngp_reset_network(ngp_ctx* ctx, uint32_t log2_hashmap_size, uint64_t seed) {
 		size_t k = 0;
 		for (const auto& m : mats) {
 			const float scale = std::sqrt(6.0f / (float)(m.n_in + m.n_out));
-			for (uint32_t i = 0; i < m.n_out * m.n_in; ++i) params[k++] = half_from_float((rng.next_float() * 2.0f - 1.0f) * scale);
+			for (uint32_t i = 0; i < m.n_out * m.n_in; ++i) params[k++] = float_to_half((rng.next_float() * 2.0f - 1.0f) * scale);
 		}
-		for (; k < params.size(); ++k) params[k] = half_from_float((rng.next_float() * 2.0f - 1.0f) * 1e-4f);
+		for (; k < params.size(); ++k) params[k] = float_to_half((rng.next_float() * 2.0f - 1.0f) * 1e-4f);
 		d.params_fp16 = params.data();
 		d.n_params = params.size();
 		d.density_grid_fp16 = nullptr;
 		d.n_density_grid = 0;
-		install_model(ctx, d);
+		set_model_impl(ctx, d);
 	});
 }
 
@@ -625,7 +625,7 @@ int ngp_render_ground_truth(ngp_ctx* ctx, int view, int32_t width, int32_t heigh
 		im.pixels = v.d_pixels.get();
 		im.type = v.image_type;
 		im.res[0] = v.resolution[0]; im.res[1] = v.resolution[1];
-		ensure_sync_buffers(ctx);
+		ensure_frame_buffers(ctx, 0);
 		DevArray<float4> d_out((size_t)width * height);
 		launch_overlay_image(width, height, exposure, background_rgba, im, color_space, to_srgb, fov_axis, zoom, d_out.get(), ctx->stream);
 		hipError_t e = hipMemcpyAsync(rgba_out, d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost, ctx->stream);

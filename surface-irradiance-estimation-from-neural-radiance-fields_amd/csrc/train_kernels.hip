@@ -476,7 +476,7 @@ __global__ void train_rollover_kernel(uint32_t target_batch, const uint32_t* __r
 
 // ---------------------------------------------------------------------------------------------------------
 // MFMA fragments of the current parameters, on the device (the host forms the inference set once per model in
-// ngp_api.cpp emit_fragments; during training the weights change every step).
+// ngp_model.cpp emit_fragments; during training the weights change every step).
 // params: fp16 [W_D0 64x32 | W_D1 16x64 | W_R0 64x32 | W_R1 64x64 | W_R2 16x64], row-major [out][in].
 NGP_DEV uint16_t frag_element(const uint16_t* W, int n_in, bool transposed, int f_local, int n_ksteps, int l, int j) {
 	const int m = f_local / n_ksteps, s = f_local % n_ksteps;
@@ -945,7 +945,7 @@ __global__ void train_optimizer_kernel(const AdamParams A, float* __restrict__ w
 	}
 }
 
-// the xor layout of one level of a parameter table (ngp_api.cpp build_xor_layout), on the device: one thread per
+// the xor layout of one level of a parameter table (ngp_model.cpp build_xor_layout), on the device: one thread per
 // destination entry -- a copy for hashed levels, the padded lattice [0, res]^3 for dense ones
 __global__ void train_xor_layout_kernel(const LevelInfo L, const uint2* __restrict__ src, char* __restrict__ dst, uint32_t n) {
 	const uint32_t t = threadIdx.x + blockIdx.x * blockDim.x;

@@ -58,7 +58,7 @@ def test_hip_resources_have_owners():
     for f in sorted(os.listdir(csrc)):
         if f.endswith(".cpp"):
             txt = open(os.path.join(csrc, f)).read()
-            assert f != "ngp_api.cpp" or len(pool.findall(txt)) == 2, "ngp_host_alloc / ngp_host_free not found"
+            assert f != "ngp_render.cpp" or len(pool.findall(txt)) == 2, "ngp_host_alloc / ngp_host_free not found"
             found += [f"{f}: {m}" for m in calls.findall(pool.sub("", txt))]
     assert not found, found
 
@@ -728,6 +728,78 @@ def test_snapshot_loader_survives_mutated_snapshots(tmp_path, native):
     assert n_refused > 100 and n_ok > 20, (n_ok, n_refused)
     ctx.load_snapshot_bytes(blob)  # and the context still takes the intact file
     assert ctx.get_model().n_params == sc["params"].size
+    ctx.close()
+
+
+def _model_fields(ctx):
+    """Every field of ngp_get_model's descriptor; the two pointers replaced by the bytes they point at."""
+    d = ctx.get_model()
+    out = {}
+    for name, _ in d._fields_:
+        v = getattr(d, name)
+        out[name] = list(v) if hasattr(v, "__len__") else v
+    out["params_fp16"] = C.string_at(d.params_fp16, 2 * int(d.n_params))
+    out["density_grid_fp16"] = C.string_at(d.density_grid_fp16, 2 * int(d.n_density_grid))
+    return out
+
+
+def test_refused_snapshot_leaves_the_context_unchanged(tmp_path, native):
+    """A snapshot that is valid up to a field the loader reads late (background_color, camera.matrix, up_dir) is refused, and the
+    context still holds the model, session, camera and network config it held before: the file is parsed as a whole, then committed."""
+    import msgpack
+
+    def snapshot_file(name, scene_kw, background, cam_angle, zoom):
+        ctx = native.Context(-1)
+        ctx.set_model(pkg("synthetic").make_scene(**scene_kw))
+        st = native.SessionState()
+        st.background_color[:] = background
+        st.exposure = background[0] * 10
+        st.sun_dir[:] = [0.0, 0.6, 0.8]
+        st.up_dir[:] = [0.0, 0.0, 1.0]
+        st.camera_scale, st.aperture_size, st.autofocus_depth = 2.5, 0.04, 0.7
+        ctx.set_session_state(st, pkg("scene").orbit_camera(cam_angle), relative_focal_length=(zoom, zoom), fov_axis=0, screen_center=(0.45, 0.55), zoom=zoom)
+        p = str(tmp_path / name)
+        ctx.save_snapshot_file(p, compress=False)
+        ctx.close()
+        return p
+
+    def state(ctx):
+        st, cam = ctx.session_state(), ctx.snapshot_camera()
+        return ({n: (list(getattr(st, n)) if hasattr(getattr(st, n), "__len__") else getattr(st, n)) for n, _ in st._fields_},
+                {k: np.asarray(v).tolist() for k, v in cam.items()})
+
+    file_a = snapshot_file("a.msgpack", dict(aabb_scale=2, seed=5, log2_hashmap_size=8), [0.1, 0.2, 0.3, 0.5], 33.0, 1.5)
+    file_b = snapshot_file("b.msgpack", dict(aabb_scale=4, seed=6, log2_hashmap_size=9), [0.6, 0.5, 0.4, 1.0], 120.0, 2.0)
+    ctx = native.Context(-1)
+    ctx.load_snapshot_file(file_a)
+    model_a, state_a = _model_fields(ctx), state(ctx)
+    assert state_a[0]["valid"] == 1 and state_a[1]["zoom"] == 1.5
+    other = native.Context(-1)
+    other.load_snapshot_file(file_b)
+    model_b, state_b = _model_fields(other), state(other)
+    other.close()
+    assert model_b["n_params"] != model_a["n_params"] and model_b["aabb_scale"] != model_a["aabb_scale"] and model_b["log2_hashmap_size"] != model_a["log2_hashmap_size"]
+    assert state_b != state_a
+
+    root_b = msgpack.unpackb(open(file_b, "rb").read(), raw=False)
+    cam_b = root_b["snapshot"]["camera"]
+    assert len(root_b["snapshot"]["background_color"]) == 4 and [len(r) for r in cam_b["matrix"]] == [4, 4, 4]
+    late = {"background_color": dict(root_b["snapshot"], background_color=root_b["snapshot"]["background_color"][:3]),
+            "camera.matrix": dict(root_b["snapshot"], camera=dict(cam_b, matrix=[cam_b["matrix"][0], cam_b["matrix"][1][:3], cam_b["matrix"][2]])),
+            "up_dir": dict(root_b["snapshot"], up_dir="up")}
+    for what, snap in late.items():
+        with pytest.raises(RuntimeError):
+            ctx.load_snapshot_bytes(msgpack.packb(dict(root_b, snapshot=snap), use_bin_type=True))
+        assert _model_fields(ctx) == model_a, what
+        assert state(ctx) == state_a, what
+        p = str(tmp_path / "after.msgpack")
+        ctx.save_snapshot_file(p, compress=False)
+        fresh = native.Context(-1)
+        fresh.load_snapshot_file(p)
+        assert _model_fields(fresh) == model_a, what
+        fresh.close()
+    ctx.load_snapshot_file(file_b)
+    assert _model_fields(ctx) == model_b and state(ctx) == state_b
     ctx.close()
 
 

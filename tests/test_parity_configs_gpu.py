@@ -189,7 +189,7 @@ def test_aabb_scale_128_scene_eight_cascades(gpu_ctx, oracle, native, scene_mod,
     assert scene_128["max_cascade"] == 7
     # per_level_scale is exactly 4 here (the upstream rule at aabb_scale 128), so level 6 has resolution 65536: tcnn's
     # grid_index forms res^2 in uint32, gets 0, and indexes the level as (x + 65536 y) % T -- z drops out. The oracle runs
-    # the same uint32 loop; the HIP table layout serves it through the hashed form (ngp_api.cpp build_xor_layout).
+    # the same uint32 loop; the HIP table layout serves it through the hashed form (ngp_model.cpp build_xor_layout).
     gpu_ctx.set_model(scene_128)
     m = oracle.make_model(scene_128)
     off, res, scl = oracle.grid_layout(m)
