@@ -8,6 +8,7 @@
 #pragma once
 
 #include "ngp_kernels.h"
+#include "cell_cache.h"
 
 namespace ngp {
 
@@ -779,6 +780,7 @@ NGP_DEV void store_features(const FeatureAcc& lo, const FeatureAcc& hi, half8& o
 struct EncodeInFlight {
 	uint2 v[16];
 	float wx[2], wy[2], wz[2];
+	uint32_t cell; // encode_issue_cached only: the tag of the coarse cell this lane gathered and cell_cache_fill is to keep, or CELL_TAG_NONE
 };
 NGP_DEV void encode_issue(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z, EncodeInFlight& e) {
 	const LevelInfo& L0 = lv[h];
@@ -829,6 +831,82 @@ NGP_DEV half8 encode_finish(const EncodeInFlight& e) {
 	store_features(acc[0], acc[1], out);
 	return out;
 }
+// The cell cache of the fused render kernels that have the room for it (trait cell_cache, nerf_kernels.hip). A ray's consecutive samples
+// stay in one cell of levels 0 / 1 / 2 / 3 for 37 / 18 / 9 / 4.6 samples and the rays of a wave are a few pixels apart, so nearly every
+// coarse lane-load re-reads 64 bytes that this wave read a round ago -- an L1 hit that still costs a full lane-load on the texture-address
+// path, the unit that binds the kernel. Each wave therefore keeps, per coarse level, CELL_CACHE_SETS cells (8 corner entries in tcnn
+// corner order + a tag, cell_cache.h) in LDS, direct-mapped by low coordinate bits; a lane whose cell is there reads it with four
+// ds_read_b128 instead of eight gathers. The entries are the table's own, consumed in the same order: results are bit for bit the same.
+// Only the wave itself touches its cache and LDS serves a wave's requests in order, so a lookup (tag read + line reads) and a fill
+// (tag write, tag read-back, line writes) never interleave; the model does not change during a launch, so nothing invalidates a line.
+constexpr int CELL_CACHE_SETS = 8;
+struct CellCache { // one wave's
+	uint4 line[CELL_CACHE_LEVELS][CELL_CACHE_SETS][4];
+	uint32_t tag[CELL_CACHE_LEVELS][CELL_CACHE_SETS];
+};
+NGP_DEV void cell_cache_clear(CellCache* caches, int n_waves, int thread, int n_threads) {
+	for (int i = thread; i < n_waves * CELL_CACHE_LEVELS * CELL_CACHE_SETS; i += n_threads)
+		caches[i / (CELL_CACHE_LEVELS * CELL_CACHE_SETS)].tag[i / CELL_CACHE_SETS % CELL_CACHE_LEVELS][i % CELL_CACHE_SETS] = CELL_TAG_NONE;
+}
+// encode_issue with the lane's coarse level (h) looked up in the wave's cache first. The fine level's gathers go out first, as ever.
+NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z, EncodeInFlight& e, CellCache& cc) {
+	const LevelInfo& L0 = lv[h];
+	const LevelInfo& L1 = lv[h + 4];
+	const CellPos p0 = level_cell(L0, x, y, z), p1 = level_cell(L1, x, y, z);
+	CornerSet c0, c1;
+	e.cell = CELL_TAG_NONE;
+	if (__all((int)level_in_xor_range(L0, p0) & (int)level_in_xor_range(L1, p1))) {
+		level_corners_xor(L1, p1, c1);
+#pragma unroll
+		for (int c = 0; c < 8; ++c) e.v[8 + c] = gather8(xgrid, c1.index[c]);
+		// The tag accesses are wave-scope relaxed atomics: plain ds_read / ds_write that the compiler neither merges nor forwards.
+		// EVERY lane reads its set's line (in the wave's instruction stream that costs what reading it in the hitting lanes costs), and
+		// the lanes that missed then gather over it: both land in e.v[0..7], and an LDS read issued BEHIND a gather into the same
+		// registers -- where the compiler puts a branch of hits -- makes it wait for every gather in flight first.
+		const bool cacheable = cell_cacheable(p0.gx, p0.gy, p0.gz);
+		const uint32_t tag = cell_tag(p0.gx, p0.gy, p0.gz), set = cell_set(tag, CELL_CACHE_SETS);
+		const bool hit = __hip_atomic_load(&cc.tag[h][set], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == tag && cacheable;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const uint4 d = cc.line[h][set][q];
+			e.v[2 * q] = make_uint2(d.x, d.y);
+			e.v[2 * q + 1] = make_uint2(d.z, d.w);
+		}
+		if (!hit) {
+			level_corners_xor(L0, p0, c0);
+#pragma unroll
+			for (int c = 0; c < 8; ++c) e.v[c] = gather8(xgrid, c0.index[c]);
+			if (cacheable) e.cell = tag;
+		}
+	} else { // (positions outside the xor layout's range: the whole wave reads the tcnn-order table and leaves the cache alone)
+		level_corners(L0, p0, c0);
+		level_corners(L1, p1, c1);
+#pragma unroll
+		for (int c = 0; c < 8; ++c) e.v[c] = gather8(grid, c0.index[c]);
+#pragma unroll
+		for (int c = 0; c < 8; ++c) e.v[8 + c] = gather8(grid, c1.index[c]);
+	}
+	e.wx[0] = p0.wx; e.wy[0] = p0.wy; e.wz[0] = p0.wz;
+	e.wx[1] = p1.wx; e.wy[1] = p1.wy; e.wz[1] = p1.wz;
+}
+// After the gathers have landed: the lanes that missed keep their cell. Lanes of the wave that missed on DIFFERENT cells of one set all
+// write their tag; the one that is read back names the lanes whose 64 bytes go in (all of them hold the same cell, so the same bytes).
+// A missing lane consumes its own registers, never the line; a second pass in flight that missed on the same cell gathered it once more.
+NGP_DEV void cell_cache_fill(CellCache& cc, int h, const EncodeInFlight& e) {
+	if (e.cell != CELL_TAG_NONE) {
+		const uint32_t set = cell_set(e.cell, CELL_CACHE_SETS);
+		// Which lanes win rests on the read-back being a real LDS read BEHIND the write of every lane (ds_write_b32, then ds_read_b32 of the
+		// same address in the ISA): a tag forwarded from the lane's own store would let every lane win and tear the line. The compiler
+		// barrier between the two forbids that forwarding; tests/test_cell_cache_gpu.py (bytes against the build without the cache) is the check.
+		__hip_atomic_store(&cc.tag[h][set], e.cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+		asm volatile("" ::: "memory");
+		if (__hip_atomic_load(&cc.tag[h][set], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == e.cell) {
+#pragma unroll
+			for (int q = 0; q < 4; ++q) cc.line[h][set][q] = make_uint4(e.v[2 * q].x, e.v[2 * q].y, e.v[2 * q + 1].x, e.v[2 * q + 1].y);
+		}
+	}
+}
+
 NGP_DEV half8 encode_level_pair(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z) {
 	EncodeInFlight e;
 	encode_issue(grid, xgrid, lv, h, x, y, z, e);

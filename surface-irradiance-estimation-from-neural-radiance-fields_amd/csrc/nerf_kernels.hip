@@ -33,14 +33,23 @@ constexpr int BLOCK = 256;
 // outside: the render box may reach beyond the occupancy grid (geometry mode, a hand-set render box)
 // rgb_mid: the network heads, as mlp_pass takes them (nerf_device.h; -2: linear.json, whose density head has no hidden layer either)
 // plain: static pinhole camera, no depth of field, no environment map (FrameParams::plain, decided by the host)
+// cell_cache: the wave keeps the coarse hash-grid cells it read last in LDS (nerf_device.h encode_issue_cached): 2176 B per wave, for the
+// kernels that have them to spare with three workgroups per CU (the unit kernels: 40 396 -> 49 100 B of the 53 132 B that are known to run
+// three; the <= 5-cascade kernels sit at that limit, the general one runs two workgroups of 69 KB). -DNGP_NO_CELL_CACHE (libngp_hip_nocache.so):
+// off everywhere, for the A/B and the equality test
 // normals: ERenderMode::Normals -- every sample's colour is the unit vector opposite to the density's input gradient (one backward
 // pass through the density head and the encoding per sample, density_gradient_pass); an instantiation of its own, so that no other
 // kernel carries its registers
+#if defined(NGP_NO_CELL_CACHE) || defined(NGP_EXPERIMENT_CELL_CACHE_STATS)
+constexpr bool CELL_CACHE_BUILT = false;
+#else
+constexpr bool CELL_CACHE_BUILT = true;
+#endif
 struct FusedGeneric {
-	static constexpr bool probe = false, unit = false, outside = true, plain = false, normals = false;
+	static constexpr bool probe = false, unit = false, outside = true, plain = false, normals = false, cell_cache = false;
 	static constexpr int prof = 0, mips = (int)NERF_CASCADES, rgb_mid = 1;
 };
-struct FusedUnit : FusedGeneric { static constexpr bool unit = true; static constexpr int mips = 1; };
+struct FusedUnit : FusedGeneric { static constexpr bool unit = true, cell_cache = CELL_CACHE_BUILT; static constexpr int mips = 1; };
 struct FusedUnitPlain : FusedUnit { static constexpr bool plain = true; };
 struct FusedC5 : FusedGeneric { static constexpr bool outside = false; static constexpr int mips = 4; };
 struct FusedC5Plain : FusedC5 { static constexpr bool plain = true; };
@@ -56,7 +65,7 @@ struct FusedProbe : FusedGeneric { static constexpr bool probe = true; };
 
 template <class V>
 NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const FrameParams& F, const ProbeParams& P) {
-	constexpr bool PROBE = V::probe, UNIT = V::unit, OUTSIDE = V::outside, PLAIN = V::plain, NORMALS = V::normals;
+	constexpr bool PROBE = V::probe, UNIT = V::unit, OUTSIDE = V::outside, PLAIN = V::plain, NORMALS = V::normals, CELL_CACHE = V::cell_cache;
 	constexpr int PROF = V::prof, MIPS = V::mips, RGB_MID = V::rgb_mid;
 	const uint32_t max_cascade = UNIT ? 0u : M.max_cascade;
 	const float cone_angle = UNIT ? 0.0f : M.cone_angle;
@@ -70,6 +79,12 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	__shared__ float4 s_samp[BLOCK / 64 * SLOTS]; // samples that wait for the network, in emission order: warped position, warped dt
 	__shared__ uint2 s_res[BLOCK / 64 * SLOTS];   // .x = the lane that owns the sample; after the pass: the network's 4 fp16 outputs (rgb, density)
 	__shared__ float4 s_nrm[NORMALS ? BLOCK / 64 * SLOTS : 1]; // Normals: d logit / d warped position and the logit
+	__shared__ CellCache s_cells[CELL_CACHE ? BLOCK / 64 : 1]; // per wave: the coarse hash-grid cells it read last
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // counting experiment only (profiles/cell_cache_hit_rates.txt): the TAGS of such a cache with 4, 8 and 16 sets per level; results unchanged
+	__shared__ uint32_t s_cst[BLOCK / 64][CELL_CACHE_LEVELS][4 + 8 + 16];
+	for (int i = threadIdx.x; i < BLOCK / 64 * CELL_CACHE_LEVELS * 28; i += BLOCK) (&s_cst[0][0][0])[i] = CELL_TAG_NONE;
+	unsigned long long cst_n = 0, cst_hit[3] = {0, 0, 0};
+#endif
 	// Ray sharing inside a workgroup (knob 7): a wave that has run out of work asks through s_xstate, a busy wave hands it every second
 	// one of its live rays (16 at most at a time) through s_xray (16 words per ray; the SH coefficients go straight into the receiver's s_sh rows), so the last
 	// tiles of a frame -- or a small frame's heavy tiles -- are finished by four waves instead of one.
@@ -89,6 +104,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	if (threadIdx.x < N_LEVELS) s_lv[threadIdx.x] = M.levels[threadIdx.x];
 	for (uint32_t i = threadIdx.x; i < (max_cascade + 1 < (uint32_t)MIPS ? max_cascade + 1 : (uint32_t)MIPS) * COARSE_WORDS_PER_MIP; i += BLOCK) s_coarse[i] = M.coarse[i];
 	if (threadIdx.x < (UNIT ? 1 : (int)NERF_CASCADES) * 16) s_coarse16[threadIdx.x] = M.coarse[NERF_CASCADES * COARSE_WORDS_PER_MIP + threadIdx.x];
+	if (CELL_CACHE) cell_cache_clear(s_cells, BLOCK / 64, threadIdx.x, BLOCK);
 	__syncthreads();
 
 	const int lane = threadIdx.x & 63;
@@ -151,7 +167,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	// (where it ran, when it started on the chip's 100 MHz clock). Layout: tools/wave_trace.py.
 	int tr_slot = -1; // -1: no rays dealt yet, -2: not a traced wave
 	uint32_t tr_it = 0, tr_info0 = 0, tr_info1 = 0, tr_march = 0;
-	uint32_t tr_net[5] = {0, 0, 0, 0, 0}; // [address arithmetic + gather issue, gather wait, corner sums, MFMA chains, hand-back] of the round's passes
+	uint32_t tr_net[7] = {0, 0, 0, 0, 0, 0, 0}; // [address arithmetic + gather issue (with the cell cache: + tag lookup), gather wait, corner sums, MFMA chains, hand-back, wait for the cell cache's lines, its fill] of the round's passes
 	unsigned long long tr_t[5] = {0, 0, 0, 0, 0};
 	auto trace_emit = [&](int upto) { // sections after `upto` did not run this round: their stamps repeat the last one taken
 		if (!PROF || tr_slot < 0) return;
@@ -162,12 +178,12 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			r[5] = tr_info0;
 			r[6] = tr_info1;
 			r[7] = tr_march;
-			for (int k = 0; k < 5; ++k) r[8 + k] = upto >= 3 ? tr_net[k] : 0u; // PROF 2: inside the network section
+			for (int k = 0; k < 7; ++k) r[8 + k] = upto >= 3 ? tr_net[k] : 0u; // PROF 2: inside the network section
 		}
 		++tr_it;
 	};
 	for (;;) {
-		if (PROF) { t0 = stamp(); tr_t[0] = t0; tr_info0 = tr_info1 = tr_march = 0; for (int k = 0; k < 5; ++k) tr_net[k] = 0; }
+		if (PROF) { t0 = stamp(); tr_t[0] = t0; tr_info0 = tr_info1 = tr_march = 0; for (int k = 0; k < 7; ++k) tr_net[k] = 0; }
 		// ---- refill free slots from the tile queue: K1 and the start-of-ray jitter of K2. The skip to the first
 		// occupied voxel that K2 also does (advance_pos_nerf, :356) is the same loop as K4's and runs below with every
 		// other marching lane -- a ray with nothing in front of it must not stall the 63 other slots of its wave.
@@ -548,9 +564,37 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				if (lane < 16) s_nrm[wave_base + 16 * p + lane] = make_float4(dg.g[0] * (1.0f / 128.0f), dg.g[1] * (1.0f / 128.0f), dg.g[2] * (1.0f / 128.0f), (float)dg.sigma);
 			}
 		}
+		// the main passes: the coarse level through the wave's cell cache where the kernel has one
+		auto issue = [&](float sx, float sy, float sz, EncodeInFlight& e) {
+			if constexpr (CELL_CACHE) encode_issue_cached(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e, s_cells[my_wave]);
+			else encode_issue(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e);
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // look the cell up in the three tag arrays; e.cell: the tag, bit 24 + k = missed with 4 << k sets
+			const CellPos p = level_cell(s_lv[hq], sx, sy, sz);
+			e.cell = CELL_TAG_NONE;
+			if (level_in_xor_range(s_lv[hq], p) && cell_cacheable(p.gx, p.gy, p.gz)) {
+				const uint32_t tag = cell_tag(p.gx, p.gy, p.gz);
+				e.cell = tag;
+				++cst_n;
+				for (int k = 0; k < 3; ++k) {
+					const bool hit = s_cst[my_wave][hq][(4 << k) - 4 + cell_set(tag, 4u << k)] == tag;
+					cst_hit[k] += hit ? 1u : 0u;
+					e.cell |= hit ? 0u : 1u << (24 + k);
+				}
+			}
+#endif
+		};
+		auto keep = [&](const EncodeInFlight& e) { // after the gather wait
+			if constexpr (CELL_CACHE) cell_cache_fill(s_cells[my_wave], hq, e);
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS
+			if (e.cell != CELL_TAG_NONE)
+				for (int k = 0; k < 3; ++k)
+					if (e.cell >> (24 + k) & 1u) s_cst[my_wave][hq][(4 << k) - 4 + cell_set(e.cell & 0xFFFFFFu, 4u << k)] = e.cell & 0xFFFFFFu;
+#endif
+		};
 		unsigned long long u0 = 0, u1 = 0;
 		auto lap = [&](int k, bool drain_gathers) { // PROF 2 only: the stamps (and the explicit wait) serialise what the shipped kernel overlaps
 			if (drain_gathers) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			else if (k == 5) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the cached cells' lines have arrived
 			u1 = stamp();
 			tr_net[k] += (uint32_t)(u1 - u0);
 			u0 = u1;
@@ -562,12 +606,15 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			sample_of(p, ax, ay, az, sha);
 			sample_of(p + 1, bx, by, bz, shb);
 			EncodeInFlight ea, eb;
-			encode_issue(t_grid, t_xgrid, s_lv, hq, ax, ay, az, ea);
-			encode_issue(t_grid, t_xgrid, s_lv, hq, bx, by, bz, eb);
-			if (PROF >= 2) { lap(0, false); lap(1, true); }
+			issue(ax, ay, az, ea);
+			issue(bx, by, bz, eb);
+			if (PROF >= 2) { lap(0, false); if (CELL_CACHE) lap(5, false); lap(1, true); }
 			half8 enca = encode_finish(ea);
 			half8 encb = encode_finish(eb);
 			if (PROF >= 2) lap(2, false);
+			keep(ea); // (behind the corner sums: a fill in front of them makes the first fma wait for the gathers of both passes)
+			keep(eb);
+			if (PROF >= 2 && CELL_CACHE) lap(6, false);
 			MlpOut moa = mlp_pass<RGB_MID>(s_w, lane, enca, sha);
 			MlpOut mob = mlp_pass<RGB_MID>(s_w, lane, encb, shb);
 			if (PROF >= 2) lap(3, false);
@@ -580,10 +627,12 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			Sh4 sha;
 			sample_of(p, ax, ay, az, sha);
 			EncodeInFlight e1;
-			encode_issue(t_grid, t_xgrid, s_lv, hq, ax, ay, az, e1);
-			if (PROF >= 2) { lap(0, false); lap(1, true); }
+			issue(ax, ay, az, e1);
+			if (PROF >= 2) { lap(0, false); if (CELL_CACHE) lap(5, false); lap(1, true); }
 			half8 enc = encode_finish(e1);
 			if (PROF >= 2) lap(2, false);
+			keep(e1);
+			if (PROF >= 2 && CELL_CACHE) lap(6, false);
 			MlpOut mo = mlp_pass<RGB_MID>(s_w, lane, enc, sha);
 			if (PROF >= 2) lap(3, false);
 			deliver(p, mo);
@@ -682,6 +731,18 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		atomicAdd(&F.prof[16 + bucket], 1ull);
 	}
 
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // F.prof[64 + 4 level ..]: lookups, hits with 4 / 8 / 16 sets (lane group h = level h: reduce over its 16 lanes first)
+	if (F.prof) {
+		for (int off = 8; off > 0; off >>= 1) {
+			cst_n += __shfl_xor(cst_n, off, 64);
+			for (int k = 0; k < 3; ++k) cst_hit[k] += __shfl_xor(cst_hit[k], off, 64);
+		}
+		if (c == 0) {
+			atomicAdd(&F.prof[64 + 4 * (lane >> 4)], cst_n);
+			for (int k = 0; k < 3; ++k) atomicAdd(&F.prof[64 + 4 * (lane >> 4) + 1 + k], cst_hit[k]);
+		}
+	}
+#endif
 	finish_launch(F, lane, n_alive_init, n_hit, n_samples);
 }
 
@@ -1160,7 +1221,11 @@ static RenderKernel select_render_kernel(const ModelParams& M, const CameraParam
 	const bool unit = M.max_cascade == 0 && M.cone_angle <= 1e-5f;
 	const bool c5 = !unit && M.max_cascade < 5 && !F.outside_possible;
 	const bool plain = C.lens_mode == 0 && C.aperture_size == 0.0f && !C.moving && !F.envmap;
-	if (F.prof) return unit && plain ? (F.prof_level >= 2 ? RK_UNIT_PLAIN_PROF2 : RK_UNIT_PLAIN_PROF) : RK_PROF;
+	bool stamped = F.prof != nullptr;
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // (the counting experiment hands its counters to the shipped kernels through prof)
+	stamped = stamped && F.prof_level > 0;
+#endif
+	if (stamped) return unit && plain ? (F.prof_level >= 2 ? RK_UNIT_PLAIN_PROF2 : RK_UNIT_PLAIN_PROF) : RK_PROF;
 	if (unit) return plain ? RK_UNIT_PLAIN : RK_UNIT;
 	if (c5) return plain ? RK_C5_PLAIN : RK_C5;
 	return RK_GENERIC;

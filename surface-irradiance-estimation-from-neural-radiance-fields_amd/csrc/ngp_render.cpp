@@ -109,6 +109,15 @@ void make_frame_params(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opt
 			}
 		}
 	}
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // counting experiment (tools/cell_cache_stats.py): the shipped kernels add their lookups and hits to prof[64 ..], over all frames
+	if (!F.prof) {
+		if (!ctx->d_prof) {
+			ctx->d_prof.reset(128);
+			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_prof.get(), 0, 1024, stream));
+		}
+		F.prof = ctx->d_prof.get();
+	}
+#endif
 	const bool geometry = opts.testbed_mode == NGP_MODE_GEOMETRY;
 	const bool have_meshes = geometry && !ctx->meshes.empty();
 	if (have_meshes && cam.has_matrix1 && memcmp(cam.matrix, cam.matrix1, sizeof(cam.matrix)) != 0) throw std::runtime_error("a moving camera (matrix1 / rolling shutter) renders NeRF mode");
@@ -438,6 +447,14 @@ int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {
 				out->kernel_device_ms = std::max(out->kernel_device_ms, s.kernel_device_ms);
 			}
 		}
+#ifdef NGP_EXPERIMENT_CELL_CACHE_STATS
+		if (ctx->d_prof) {
+			unsigned long long p[128];
+			NGP_HIP_CHECK(hipMemcpy(p, ctx->d_prof.get(), sizeof(p), hipMemcpyDeviceToHost));
+			for (int l = 0; l < 4; ++l)
+				fprintf(stderr, "[ngp cell cache] level %d lookups %llu hits with 4 / 8 / 16 sets %llu %llu %llu\n", l, p[64 + 4 * l], p[65 + 4 * l], p[66 + 4 * l], p[67 + 4 * l]);
+		}
+#endif
 		if (ctx->d_prof && getenv("NGP_PROFILE_SECTIONS")) {
 			unsigned long long p[128];
 			NGP_HIP_CHECK(hipMemcpy(p, ctx->d_prof.get(), sizeof(p), hipMemcpyDeviceToHost));

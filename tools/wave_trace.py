@@ -2,7 +2,7 @@
 
 usage: python tools/wave_trace.py W H [shard_count] [level]
   level 1: section stamps (refill + spawn, march, network, composite); level 2: also inside the network section
-  (gather issue / gather wait / corner sums / MFMA chains / hand-back -- that build serialises what the shipped kernel overlaps).
+  (gather issue / gather wait / corner sums / MFMA chains / hand-back / the cell cache's line wait and fill -- that build serialises what the shipped kernel overlaps).
 The environment variables the library reads (NGP_PROFILE_SECTIONS, NGP_PROFILE_TRACE) are set here before it is loaded.
 Every stride-th wave that is dealt rays records one 64-byte record per loop round (csrc/ngp_kernels.h FrameParams::trace)."""
 import importlib, os, sys
@@ -77,7 +77,7 @@ for (i, *_rest) in rows:
         if t3 > t2:
             kind = "network"
             n_run_hist[n_run] += 1
-            inner.append(r[j, 8:13])
+            inner.append(r[j, 8:15])
         elif n_ready > 0:
             kind = "stall (waits for marching lanes / chain growth)"
         else:
@@ -95,7 +95,8 @@ nz = np.nonzero(n_run_hist)[0]
 print("# samples per network round (n_run: count): " + " ".join(f"{k}:{n_run_hist[k]}" for k in nz))
 if level >= 2 and inner:
     m = np.array(inner, np.float64).mean(axis=0)
-    print(f"# inside a network round (mean cycles; stamps serialise): address arithmetic + gather issue {m[0]:.0f} | gather wait {m[1]:.0f} | corner sums {m[2]:.0f} | MFMA chains {m[3]:.0f} | hand-back {m[4]:.0f}")
+    print(f"# inside a network round (mean cycles; stamps serialise): address arithmetic + gather issue {m[0]:.0f} | gather wait {m[1]:.0f} | corner sums {m[2]:.0f} | MFMA chains {m[3]:.0f} | hand-back {m[4]:.0f}"
+          f" | cell cache: wait for its lines {m[5]:.0f}, fill {m[6]:.0f} (0 in a kernel without it; the tag lookup is part of the first figure)")
 # ---- the longest wave, round by round (first 24 rounds and the last 8)
 longest = max(rows, key=lambda r: r[3])[0]
 n_it = min(int(hd[longest, 4]), rec.shape[1])
