@@ -22,6 +22,15 @@ struct f3 {
 
 #define NGP_DEV __device__ __forceinline__
 
+// -DNGP_CENSUS (tools/isa_census.py, never a shipped build): comment lines in the ISA at which the instruction census splits a kernel
+// into sections. They emit no instruction and pin nothing but their own order, so the scheduler still moves instructions across them:
+// a section's count is what the compiler PLACED there.
+#ifdef NGP_CENSUS
+#define NGP_SECTION(name) asm volatile("; SECTION " name)
+#else
+#define NGP_SECTION(name)
+#endif
+
 NGP_DEV f3 mk3(float x, float y, float z) { return f3{x, y, z}; }
 NGP_DEV f3 add3(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
 NGP_DEV f3 sub3(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -659,6 +668,16 @@ NGP_DEV CellPos level_cell(const LevelInfo& L, float x, float y, float z) {
 	c.wx = fx - flx; c.wy = fy - fly; c.wz = fz - flz;
 	return c;
 }
+// level_cell for a position inside the unit cube, where fma(scale, x, 0.5) >= 0.5: truncation (v_cvt_u32_f32) is the floor, and
+// f - floor(f) is exact in fp32 (f < 2^24, the difference needs no more bits than f has), so v_fract_f32 returns the bits of the
+// subtraction: 2 instructions per coordinate instead of 4. tests/aux/floor_fract_check.c compares both for every float in [0, 4096].
+NGP_DEV CellPos level_cell_in_cube(const LevelInfo& L, float x, float y, float z) {
+	const float fx = __builtin_fmaf(L.scale, x, 0.5f), fy = __builtin_fmaf(L.scale, y, 0.5f), fz = __builtin_fmaf(L.scale, z, 0.5f);
+	CellPos c;
+	c.gx = (uint32_t)fx; c.gy = (uint32_t)fy; c.gz = (uint32_t)fz;
+	c.wx = __builtin_amdgcn_fractf(fx); c.wy = __builtin_amdgcn_fractf(fy); c.wz = __builtin_amdgcn_fractf(fz);
+	return c;
+}
 NGP_DEV void corner_weights(const CellPos& p, float* weight) {
 	float wx0 = 1.0f - p.wx, wy0 = 1.0f - p.wy, wz0 = 1.0f - p.wz;
 #pragma unroll
@@ -672,6 +691,15 @@ NGP_DEV bool level_in_xor_range(const LevelInfo& L, const CellPos& p) {
 	m = m > p.gz ? m : p.gz;
 	return m <= L.coord_max && !L.xor_disabled;
 }
+// The same question for a whole model, asked once per launch: does every cell that a position in [0, 1]^3 can fall into lie in the xor
+// layout's range on every level? The largest coordinate is that of x = 1, floor(fma(scale, 1, 0.5)) (fma is monotonic in x); hashed
+// levels have coord_max = 0xFFFFFFFF. False only for the dense levels whose uint32 strides wrapped (ngp_model.cpp build_xor_layout).
+NGP_DEV bool unit_cube_in_xor_range(const LevelInfo* lv) {
+	bool ok = true;
+	for (int l = 0; l < N_LEVELS; ++l) ok = ok && !lv[l].xor_disabled && (uint32_t)__builtin_fmaf(lv[l].scale, 1.0f, 0.5f) <= lv[l].coord_max;
+	return ok;
+}
+NGP_DEV bool in_unit_cube(float x, float y, float z) { return fminf(fminf(x, y), z) >= 0.0f && fmaxf(fmaxf(x, y), z) <= 1.0f; }
 
 // tcnn grid_index, byte offsets into ModelParams::grid -- any position, any level shape
 NGP_DEV void level_corners(const LevelInfo& L, const CellPos& p, CornerSet& cs) {
@@ -732,6 +760,12 @@ NGP_DEV uint2 gather8(GridRsrc r, uint32_t offset) {
 //     (tools/micro/mix_probe.hip) -- so the product is formed as an fp32 value of its own (v_fma_mix_f32) and the
 //     features are accumulated as packed pairs (v_cvt_pk_f16_f32 + v_pk_add_f16): 8 instructions per corner.
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+// fp32 -> fp16 of a value that is first rounded to fp32 (no fusing of the producing multiply into v_fma_mix*_f16,
+// which would round the exact product once; see accumulate_corner)
+NGP_DEV half_t to_half_rn(float v) {
+	asm("" : "+v"(v));
+	return (half_t)v;
+}
 struct FeatureAcc {
 	half2_t f01, f23;
 };
@@ -765,6 +799,19 @@ NGP_DEV void accumulate_corner(uint2 v, float w, FeatureAcc& r) {
 	r.f01 = r.f01 + a;
 	r.f23 = r.f23 + b;
 #endif
+}
+// Two corners at once: their fp32 weights are rounded to fp16 by ONE v_cvt_pk_f16_f32 (the caller's) and each fma picks its half of the
+// pair through op_sel / op_sel_hi on that operand -- the same round-to-nearest-even of the same fp32 value and the same four fp16 fmas
+// as two calls of accumulate_corner, with half the conversions.
+NGP_DEV void accumulate_corner_pair(uint2 v0, uint2 v1, half2_t w01, FeatureAcc& r) {
+	const uint32_t wv = __builtin_bit_cast(uint32_t, w01);
+	uint32_t a01 = __builtin_bit_cast(uint32_t, r.f01), a23 = __builtin_bit_cast(uint32_t, r.f23);
+	asm("v_pk_fma_f16 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(a01) : "v"(wv), "v"(v0.x));
+	asm("v_pk_fma_f16 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(a23) : "v"(wv), "v"(v0.y));
+	asm("v_pk_fma_f16 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(a01) : "v"(wv), "v"(v1.x));
+	asm("v_pk_fma_f16 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(a23) : "v"(wv), "v"(v1.y));
+	r.f01 = __builtin_bit_cast(half2_t, a01);
+	r.f23 = __builtin_bit_cast(half2_t, a23);
 }
 NGP_DEV void store_features(const FeatureAcc& lo, const FeatureAcc& hi, half8& out) {
 	out[0] = lo.f01[0]; out[1] = lo.f01[1]; out[2] = lo.f23[0]; out[3] = lo.f23[1];
@@ -816,6 +863,7 @@ NGP_DEV void encode_issue(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, in
 	e.wx[1] = p1.wx; e.wy[1] = p1.wy; e.wz[1] = p1.wz;
 }
 NGP_DEV half8 encode_finish(const EncodeInFlight& e) {
+	NGP_SECTION("encode_finish");
 	FeatureAcc acc[2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
 #pragma unroll
 	for (int l = 0; l < 2; ++l) {
@@ -824,11 +872,20 @@ NGP_DEV half8 encode_finish(const EncodeInFlight& e) {
 		p.wx = e.wx[l]; p.wy = e.wy[l]; p.wz = e.wz[l];
 		float w[8];
 		corner_weights(p, w);
+#if defined(NGP_TCNN_LEGACY_ENCODE) || defined(NGP_NETSEC_V1)
 #pragma unroll
 		for (int c = 0; c < 8; ++c) accumulate_corner(e.v[8 * l + c], w[c], acc[l]);
+#else
+#pragma unroll
+		for (int c = 0; c < 8; c += 2) {
+			const half2_t w01 = {to_half_rn(w[c]), to_half_rn(w[c + 1])};
+			accumulate_corner_pair(e.v[8 * l + c], e.v[8 * l + c + 1], w01, acc[l]);
+		}
+#endif
 	}
 	half8 out;
 	store_features(acc[0], acc[1], out);
+	NGP_SECTION("network");
 	return out;
 }
 // The cell cache of the fused render kernels that have the room for it (trait cell_cache, nerf_kernels.hip). A ray's consecutive samples
@@ -849,13 +906,29 @@ NGP_DEV void cell_cache_clear(CellCache* caches, int n_waves, int thread, int n_
 		caches[i / (CELL_CACHE_LEVELS * CELL_CACHE_SETS)].tag[i / CELL_CACHE_SETS % CELL_CACHE_LEVELS][i % CELL_CACHE_SETS] = CELL_TAG_NONE;
 }
 // encode_issue with the lane's coarse level (h) looked up in the wave's cache first. The fine level's gathers go out first, as ever.
-NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z, EncodeInFlight& e, CellCache& cc) {
+// in_cube (wave-uniform): the caller vouches that every sample of the pass that belongs to a ray lies in [0, 1]^3 and that the model's
+// levels are all in the xor layout's range there (unit_cube_in_xor_range) -- decided once per round from the positions, not per pass
+// and level from the cells. A lane of a tail slot may hold anything: its gathers are bounds-checked buffer loads, and a cell it
+// leaves in the cache carries the tag of the coordinates its entries were read for, like any other.
+// -DNGP_NETSEC_V1 (libngp_hip_netsec_v1.so): the range test per pass and level and level_cell's floor, as before; in_cube is ignored.
+NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z, EncodeInFlight& e, CellCache& cc, bool in_cube) {
+	NGP_SECTION("issue.cells");
 	const LevelInfo& L0 = lv[h];
 	const LevelInfo& L1 = lv[h + 4];
-	const CellPos p0 = level_cell(L0, x, y, z), p1 = level_cell(L1, x, y, z);
+#ifdef NGP_NETSEC_V1
+	CellPos p0 = level_cell(L0, x, y, z), p1 = level_cell(L1, x, y, z);
+	in_cube = __all((int)level_in_xor_range(L0, p0) & (int)level_in_xor_range(L1, p1));
+#else
+	CellPos p0, p1;
+#endif
 	CornerSet c0, c1;
 	e.cell = CELL_TAG_NONE;
-	if (__all((int)level_in_xor_range(L0, p0) & (int)level_in_xor_range(L1, p1))) {
+	if (in_cube) {
+#ifndef NGP_NETSEC_V1
+		p0 = level_cell_in_cube(L0, x, y, z);
+		p1 = level_cell_in_cube(L1, x, y, z);
+#endif
+		NGP_SECTION("issue.fine");
 		level_corners_xor(L1, p1, c1);
 #pragma unroll
 		for (int c = 0; c < 8; ++c) e.v[8 + c] = gather8(xgrid, c1.index[c]);
@@ -863,6 +936,7 @@ NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo*
 		// EVERY lane reads its set's line (in the wave's instruction stream that costs what reading it in the hitting lanes costs), and
 		// the lanes that missed then gather over it: both land in e.v[0..7], and an LDS read issued BEHIND a gather into the same
 		// registers -- where the compiler puts a branch of hits -- makes it wait for every gather in flight first.
+		NGP_SECTION("issue.tag_lines");
 		const bool cacheable = cell_cacheable(p0.gx, p0.gy, p0.gz);
 		const uint32_t tag = cell_tag(p0.gx, p0.gy, p0.gz), set = cell_set(tag, CELL_CACHE_SETS);
 		const bool hit = __hip_atomic_load(&cc.tag[h][set], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == tag && cacheable;
@@ -873,12 +947,19 @@ NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo*
 			e.v[2 * q + 1] = make_uint2(d.z, d.w);
 		}
 		if (!hit) {
+			NGP_SECTION("issue.miss");
 			level_corners_xor(L0, p0, c0);
 #pragma unroll
 			for (int c = 0; c < 8; ++c) e.v[c] = gather8(xgrid, c0.index[c]);
 			if (cacheable) e.cell = tag;
 		}
+		NGP_SECTION("issue.end");
 	} else { // (positions outside the xor layout's range: the whole wave reads the tcnn-order table and leaves the cache alone)
+		NGP_SECTION("issue.tcnn_order");
+#ifndef NGP_NETSEC_V1
+		p0 = level_cell(L0, x, y, z);
+		p1 = level_cell(L1, x, y, z);
+#endif
 		level_corners(L0, p0, c0);
 		level_corners(L1, p1, c1);
 #pragma unroll
@@ -888,11 +969,13 @@ NGP_DEV void encode_issue_cached(GridRsrc grid, GridRsrc xgrid, const LevelInfo*
 	}
 	e.wx[0] = p0.wx; e.wy[0] = p0.wy; e.wz[0] = p0.wz;
 	e.wx[1] = p1.wx; e.wy[1] = p1.wy; e.wz[1] = p1.wz;
+	NGP_SECTION("network");
 }
 // After the gathers have landed: the lanes that missed keep their cell. Lanes of the wave that missed on DIFFERENT cells of one set all
 // write their tag; the one that is read back names the lanes whose 64 bytes go in (all of them hold the same cell, so the same bytes).
 // A missing lane consumes its own registers, never the line; a second pass in flight that missed on the same cell gathered it once more.
 NGP_DEV void cell_cache_fill(CellCache& cc, int h, const EncodeInFlight& e) {
+	NGP_SECTION("cell_cache_fill");
 	if (e.cell != CELL_TAG_NONE) {
 		const uint32_t set = cell_set(e.cell, CELL_CACHE_SETS);
 		// Which lanes win rests on the read-back being a real LDS read BEHIND the write of every lane (ds_write_b32, then ds_read_b32 of the
@@ -905,6 +988,7 @@ NGP_DEV void cell_cache_fill(CellCache& cc, int h, const EncodeInFlight& e) {
 			for (int q = 0; q < 4; ++q) cc.line[h][set][q] = make_uint4(e.v[2 * q].x, e.v[2 * q].y, e.v[2 * q + 1].x, e.v[2 * q + 1].y);
 		}
 	}
+	NGP_SECTION("network");
 }
 
 NGP_DEV half8 encode_level_pair(GridRsrc grid, GridRsrc xgrid, const LevelInfo* lv, int h, float x, float y, float z) {
@@ -973,12 +1057,6 @@ struct MlpOut {
 };
 
 // All 16 SH coefficients of one direction as fp16 (what the owning lane stores once per ray).
-// fp32 -> fp16 of a value that is first rounded to fp32 (no fusing of the producing multiply into v_fma_mix*_f16,
-// which would round the exact product once; see accumulate_corner)
-NGP_DEV half_t to_half_rn(float v) {
-	asm("" : "+v"(v));
-	return (half_t)v;
-}
 NGP_DEV void sh4_all(float dx01, float dy01, float dz01, half_t* out16) {
 	float x = dx01 * 2.0f - 1.0f, y = dy01 * 2.0f - 1.0f, z = dz01 * 2.0f - 1.0f;
 	float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
@@ -1032,6 +1110,7 @@ NGP_DEV half_t density_pass(const uint4* s_w, int lane, half8 enc) {
 // fragment); RGB_MID -2 (linear.json): so is the density head. One MFMA each.
 template <int RGB_MID = 1>
 NGP_DEV MlpOut mlp_pass(const uint4* s_w, int lane, half8 enc, Sh4 shq) {
+	NGP_SECTION("mlp_pass");
 	const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
 	floatx4 d0, d1, d2, d3, dens;
 	half8 b0, b1;
@@ -1091,7 +1170,85 @@ NGP_DEV MlpOut mlp_pass(const uint4* s_w, int lane, half8 enc, Sh4 shq) {
 	out.rgb[0] = (half_t)rgb[0];
 	out.rgb[1] = (half_t)rgb[1];
 	out.rgb[2] = (half_t)rgb[2];
+	NGP_SECTION("network");
 	return out;
+}
+
+// Two passes at once, as the fused kernels run them whenever 17+ samples wait: both chains walk the layers together and every weight
+// fragment is read from LDS ONCE and feeds one MFMA of each chain (mlp_pass twice reads all of them twice: the compiler does not share
+// LDS reads across the two calls). Each chain performs mlp_pass's MFMAs on its own operands in mlp_pass's order, so both results are
+// mlp_pass's bit for bit; the chains stay independent, so the MFMA pipe still has two in flight.
+template <int RGB_MID = 1>
+NGP_DEV void mlp_pass2(const uint4* s_w, int lane, half8 enca, Sh4 sha, half8 encb, Sh4 shb, MlpOut& outa, MlpOut& outb) {
+	NGP_SECTION("mlp_pass");
+	const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
+	floatx4 da[4], db[4], densa, densb;
+	half8 ha[2], hb[2], w;
+	// a 32 -> 64 layer (four fragments) of both chains, ReLU and fp16 rounding behind it
+	auto layer_in = [&](int f, half8 xa, half8 xb) {
+#pragma unroll
+		for (int t = 0; t < 4; ++t) {
+			w = ld_frag(s_w, f + t, lane);
+			da[t] = mfma16(w, xa, zero);
+			db[t] = mfma16(w, xb, zero);
+		}
+		ha[0] = relu_pack(da[0], da[1]); ha[1] = relu_pack(da[2], da[3]);
+		hb[0] = relu_pack(db[0], db[1]); hb[1] = relu_pack(db[2], db[3]);
+	};
+	// a 64 -> 16 output layer (two fragments)
+	auto layer_out = [&](int f, floatx4& ya, floatx4& yb) {
+		w = ld_frag(s_w, f + 0, lane);
+		ya = mfma16(w, ha[0], zero);
+		yb = mfma16(w, hb[0], zero);
+		w = ld_frag(s_w, f + 1, lane);
+		ya = mfma16(w, ha[1], ya);
+		yb = mfma16(w, hb[1], yb);
+	};
+	if (RGB_MID == -2) {
+		w = ld_frag(s_w, FRAG_D0, lane);
+		densa = mfma16(w, enca, zero);
+		densb = mfma16(w, encb, zero);
+	} else {
+		layer_in(FRAG_D0, enca, encb);
+		layer_out(FRAG_D1, densa, densb);
+	}
+	half8 rina, rinb;
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		rina[j] = (half_t)densa[j];
+		rina[4 + j] = sha.v[j];
+		rinb[j] = (half_t)densb[j];
+		rinb[4 + j] = shb.v[j];
+	}
+	outa.sigma = rina[0];
+	outb.sigma = rinb[0];
+	floatx4 rgba, rgbb;
+	if (RGB_MID < 0) {
+		w = ld_frag(s_w, FRAG_R0, lane);
+		rgba = mfma16(w, rina, zero);
+		rgbb = mfma16(w, rinb, zero);
+	} else {
+		layer_in(FRAG_R0, rina, rinb);
+#pragma unroll
+		for (int k = 0; k < RGB_MID; ++k) {
+			const int f = FRAG_R1 + 8 * k;
+#pragma unroll
+			for (int t = 0; t < 4; ++t) {
+				w = ld_frag(s_w, f + 2 * t, lane);
+				da[t] = mfma16(w, ha[0], zero);
+				db[t] = mfma16(w, hb[0], zero);
+				w = ld_frag(s_w, f + 2 * t + 1, lane);
+				da[t] = mfma16(w, ha[1], da[t]);
+				db[t] = mfma16(w, hb[1], db[t]);
+			}
+			ha[0] = relu_pack(da[0], da[1]); ha[1] = relu_pack(da[2], da[3]);
+			hb[0] = relu_pack(db[0], db[1]); hb[1] = relu_pack(db[2], db[3]);
+		}
+		layer_out(FRAG_R1 + 8 * (RGB_MID < 0 ? 0 : RGB_MID), rgba, rgbb);
+	}
+	outa.rgb[0] = (half_t)rgba[0]; outa.rgb[1] = (half_t)rgba[1]; outa.rgb[2] = (half_t)rgba[2];
+	outb.rgb[0] = (half_t)rgbb[0]; outb.rgb[1] = (half_t)rgbb[1]; outb.rgb[2] = (half_t)rgbb[2];
+	NGP_SECTION("network");
 }
 
 // ---------------------------------------------------------------------------------------------------------

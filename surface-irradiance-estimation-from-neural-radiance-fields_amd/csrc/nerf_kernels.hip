@@ -111,6 +111,8 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	const int c = lane & 15;
 	if (lane == 0 && (threadIdx.x >> 6) == 0) atomicMax(&F.results[4], ~realtime()); // start stamp (one per workgroup): max of the complements = the earliest
 	const GridRsrc t_grid = make_grid_rsrc(M.grid, M.grid_bytes), t_xgrid = make_grid_rsrc(M.xgrid, M.xgrid_bytes);
+	const bool cube_in_xor_range = CELL_CACHE && unit_cube_in_xor_range(M.levels); // (wave-uniform, from the kernel arguments)
+	(void)cube_in_xor_range;
 	const float* cam_last = (!PLAIN && C.moving) ? C.m1 : C.m; // depth is measured along camera_matrix1 (src/testbed_nerf.cu:2412)
 	const f3 cam_fwd = mk3(cam_last[6], cam_last[7], cam_last[8]);
 	// direct output: the background's trip through the tonemap is the same for every pixel
@@ -359,6 +361,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		const int max_it = F.tune[1] > k_max ? F.tune[1] : k_max;
 		bool blocked = false; // found a sample but the list is full: the lane stands still until the next round
 		for (int k = 0; k < max_it; ++k) {
+			NGP_SECTION("march");
 			const bool marching = ray.alive && !left_box && !blocked && (int)n_pend < k_max;
 			if (!__any(marching) || n_slots >= (uint32_t)SLOTS) break;
 			if (PROF) { const uint32_t nm = (uint32_t)__popcll(__ballot(marching)); ++p_rounds; p_lane_steps += (unsigned long long)nm; tr_march += 1u + (nm << 8); }
@@ -460,6 +463,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				n_slots = n_slots > (uint32_t)SLOTS ? (uint32_t)SLOTS : n_slots;
 			}
 		}
+		NGP_SECTION("other");
 		const bool can_march = __any(ray.alive && !left_box && !blocked && (int)n_pend < k_max);
 		if (PROF) {
 			t1 = stamp(); pt[1] += t1 - t0; t0 = t1; ++p_iters; tr_t[2] = t1;
@@ -530,21 +534,31 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 
 		// ---- K5: network, 16 samples per pass straight from the list; two passes are run together whenever 17+ samples wait, so that
 		// 32 gathers per lane and two independent MFMA chains are in flight (the loop is latency-, not issue-bound)
+		NGP_SECTION("network");
 		const int n_pass = (int)((n_slots + 15u) >> 4);
 		const int hq = lane >> 4;
 		auto sample_of = [&](int p, float& sx, float& sy, float& sz, Sh4& shq) {
+			NGP_SECTION("sample_of");
 			const float4 a = s_samp[wave_base + 16 * p + c];
 			const uint32_t owner = s_res[wave_base + 16 * p + c].x;
 			sx = a.x; sy = a.y; sz = a.z;
 			union { uint2 u; half_t h[4]; } cv; // the 4 SH coefficients this lane group feeds to the rgb head
+#ifdef NGP_NETSEC_V1
 			cv.u = s_sh[(wave_base + (int)owner) * 4 + hq];
+#else
+			// (a tail slot -- beyond n_slots in the last pass -- holds what an earlier pass delivered there, not a lane: stay inside the wave's rows)
+			cv.u = s_sh[(wave_base + (int)(owner & 63u)) * 4 + hq];
+#endif
 #pragma unroll
 			for (int j = 0; j < 4; ++j) shq.v[j] = cv.h[j];
+			NGP_SECTION("network");
 		};
 		auto deliver = [&](int p, const MlpOut& mo) { // results live in lanes 0..15 (h == 0): slot 16p + c
+			NGP_SECTION("deliver");
 			union { half_t h[4]; uint2 u; } o;
 			o.h[0] = mo.rgb[0]; o.h[1] = mo.rgb[1]; o.h[2] = mo.rgb[2]; o.h[3] = mo.sigma;
 			if (lane < 16) s_res[wave_base + 16 * p + lane] = o.u;
+			NGP_SECTION("network");
 		};
 		int p = 0;
 		if (NORMALS) {
@@ -565,8 +579,19 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			}
 		}
 		// the main passes: the coarse level through the wave's cell cache where the kernel has one
+		// Whether the round's samples take the xor layout is decided here, once, from their positions (every lane looks at one slot of the
+		// list; render samples lie in the unit cube unless the render box was set beyond it) instead of per pass and level from their cells.
+		bool round_in_cube = true;
+#ifndef NGP_NETSEC_V1
+		if constexpr (CELL_CACHE) {
+			NGP_SECTION("round_range");
+			const float4 a = s_samp[wave_base + lane];
+			round_in_cube = cube_in_xor_range && !__any((uint32_t)lane < n_slots && !in_unit_cube(a.x, a.y, a.z));
+			NGP_SECTION("network");
+		}
+#endif
 		auto issue = [&](float sx, float sy, float sz, EncodeInFlight& e) {
-			if constexpr (CELL_CACHE) encode_issue_cached(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e, s_cells[my_wave]);
+			if constexpr (CELL_CACHE) encode_issue_cached(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e, s_cells[my_wave], round_in_cube);
 			else encode_issue(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e);
 #ifdef NGP_EXPERIMENT_CELL_CACHE_STATS // look the cell up in the three tag arrays; e.cell: the tag, bit 24 + k = missed with 4 << k sets
 			const CellPos p = level_cell(s_lv[hq], sx, sy, sz);
@@ -615,8 +640,13 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			keep(ea); // (behind the corner sums: a fill in front of them makes the first fma wait for the gathers of both passes)
 			keep(eb);
 			if (PROF >= 2 && CELL_CACHE) lap(6, false);
+#ifdef NGP_NETSEC_V1
 			MlpOut moa = mlp_pass<RGB_MID>(s_w, lane, enca, sha);
 			MlpOut mob = mlp_pass<RGB_MID>(s_w, lane, encb, shb);
+#else
+			MlpOut moa, mob;
+			mlp_pass2<RGB_MID>(s_w, lane, enca, sha, encb, shb, moa, mob); // (every weight fragment is read once for the two passes)
+#endif
 			if (PROF >= 2) lap(3, false);
 			deliver(p, moa);
 			deliver(p + 1, mob);
@@ -642,6 +672,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		if (PROF) { t1 = stamp(); pt[2] += t1 - t0; t0 = t1; p_passes += (unsigned long long)n_pass; tr_t[3] = t1; tr_info0 |= (n_slots << 8) | ((uint32_t)n_pass << 16); }
 		// ---- K6: composite_kernel_nerf (:569-726): every lane takes its own samples in emission order and stops where its ray ends
 		for (uint32_t k = 0;; ++k) {
+			NGP_SECTION("composite");
 			const bool have = k < n_pend && ray.alive;
 			if (!__any(have)) break;
 			if (have) {
@@ -695,6 +726,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			}
 			n_samples += (uint32_t)__popcll(__ballot(have));
 		}
+		NGP_SECTION("other");
 		if (left_box && ray.alive) { // the ray had left the render box behind its last sample
 			ray.alive = false;
 			finished = true;

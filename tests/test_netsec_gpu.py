@@ -1,0 +1,105 @@
+"""The network section of a render pass (csrc/nerf_device.h) was trimmed of work its result does not need: two corner weights per
+fp16 conversion, level_cell without floor where positions lie in the unit cube, the xor-range test once per round instead of per pass
+and level, every MLP weight fragment read from LDS once per pair of passes. libngp_hip_netsec_v1.so (-DNGP_NETSEC_V1) keeps the earlier
+forms of those functions; both libraries consume the same table entries with the same arithmetic, so frames and encodings are compared
+as BYTES. Each library works in a process of its own."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import pkg
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+SCRIPT = """
+import hashlib, importlib, json, os, sys
+import numpy as np
+sys.path.insert(0, {root!r})
+import torch
+PKG = "surface-irradiance-estimation-from-neural-radiance-fields_amd"
+native, synthetic, scene = (importlib.import_module(PKG + "." + m) for m in ("native", "synthetic", "scene"))
+DEFAULT_SCHEDULE = (64, 4, 32, 1, 1, 4, 1, 1)
+EXACT_MARCH = (64, 4, 32, 1, 1, 4, 0, 1)
+torch.zeros(1, device="cuda")
+ctx = native.Context(0)
+model = synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19)  # the benchmark's model
+ctx.set_model(model)
+out = {{}}
+sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+def frame(name, w, h, az=45.0, el=30.0, radius=4.03, aperture_size=0.0, **opts):
+    cam = native.make_camera(scene.orbit_camera(az, el, radius), w, h, scene.focal_from_fov_x(w, 0.6911), aperture_size=aperture_size, focus_z=1.3)
+    rgba, depth = ctx.render(cam, native.make_opts(**opts), want_depth=True)
+    st = ctx.render_stats()
+    out[name] = dict(rgba=sha(rgba), depth=sha(depth), n_samples=int(st["n_samples"]), n_rays_hit=int(st["n_rays_hit"]), nonzero=int(np.count_nonzero(rgba[..., :3])))
+
+for sched_name, sched in (("default", DEFAULT_SCHEDULE), ("exact_march", EXACT_MARCH)):
+    ctx.set_schedule(*sched)
+    frame(sched_name + "/plain", 320, 180)                                        # render_nerf_fused_unit_plain
+    frame(sched_name + "/plain_inside", 256, 144, az=20.0, el=10.0, radius=0.5)   # a camera inside the object: every pass full
+    frame(sched_name + "/depth_of_field", 320, 180, az=200.0, aperture_size=0.05) # not a plain camera: render_nerf_fused_unit
+    frame(sched_name + "/share8", 320, 180, shard_index=3, shard_count=8)         # few rays per wave: single passes, tail slots
+ctx.set_schedule(*DEFAULT_SCHEDULE)
+frame("default/1080p", 1920, 1080, az=135.0)
+frame("default/1080p_depth_of_field", 1920, 1080, az=135.0, aperture_size=0.02)
+
+# ngp_grid_encode (the stage kernel: any position): inside the unit cube, on its faces, edges and corners, and outside it
+rng = np.random.default_rng(5)
+inside = rng.uniform(0.0, 1.0, (4096, 3)).astype(np.float32)
+faces = rng.uniform(0.0, 1.0, (4096, 3)).astype(np.float32)
+pick = rng.integers(0, 3, 4096)
+faces[np.arange(4096), pick] = rng.integers(0, 2, 4096).astype(np.float32)        # one coordinate exactly 0 or 1
+faces[:512, (pick[:512] + 1) % 3] = rng.integers(0, 2, 512).astype(np.float32)    # an edge
+corners = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)], np.float32)
+outside = rng.uniform(-0.75, 1.75, (4096, 3)).astype(np.float32)
+outside = outside[((outside < 0.0) | (outside > 1.0)).any(axis=1)]
+just_out = np.array([[-1e-7, 0.5, 0.5], [0.5, np.nextafter(np.float32(1.0), np.float32(2.0)), 0.5], [0.3, 0.3, -0.0], [1.0, 1.0, np.nextafter(np.float32(1.0), np.float32(2.0))]], np.float32)
+mixed = np.concatenate([inside[:40], outside[:24], inside[40:100]])                # a wave with lanes on both sides
+for name, pos in (("inside", inside), ("faces", faces), ("corners", corners), ("outside", outside), ("just_outside", just_out), ("mixed", mixed)):
+    enc = ctx.grid_encode(pos)
+    out["encode/" + name] = dict(bytes=sha(enc), n=int(pos.shape[0]), nonzero=int(np.count_nonzero(enc)))
+    d01 = np.full_like(pos, 0.5)
+    out["network/" + name] = dict(bytes=sha(ctx.network(pos, d01)), n=int(pos.shape[0]))
+
+# a render box beyond the unit cube: rays march through space outside the grid before they reach it
+wide = dict(model)
+wide["render_aabb"] = ((-0.25, -0.25, -0.25), (1.25, 1.25, 1.25))
+ctx.set_model(wide)
+frame("wide_box/plain", 320, 180)
+frame("wide_box/depth_of_field", 320, 180, az=200.0, aperture_size=0.05)
+ctx.close()
+print("RESULT " + json.dumps(out))
+"""
+
+
+def _run(lib):
+    r = subprocess.run([sys.executable, "-c", SCRIPT.format(root=ROOT)], env=dict(os.environ, NGP_HIP_LIBRARY=lib), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+    assert line, r.stdout[-1000:]
+    return json.loads(line[-1][len("RESULT "):])
+
+
+@pytest.mark.gpu
+def test_trimmed_network_section_gives_the_same_bytes(native):
+    """Both unit kernels (plain; non-plain through a depth-of-field camera) under the default and the EXACT_MARCH schedule, at reduced
+    size, as an interleaved share, inside the object, at 1920x1080 and with a render box beyond the unit cube; ngp_grid_encode and
+    ngp_network_inference on positions inside, on the faces / edges / corners of, just outside and far outside the unit cube and in waves
+    that mix both: every digest, sample count and hit count of libngp_hip.so equals that of libngp_hip_netsec_v1.so."""
+    build = pkg("build")
+    lib_new, lib_v1 = build.build(), build.build(netsec_v1=True)
+    digest = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()
+    assert digest(lib_new) != digest(lib_v1), "the two libraries are the same file: nothing is compared"
+    new, v1 = _run(lib_new), _run(lib_v1)
+    assert set(new) == set(v1) and len(new) == 8 + 2 + 12 + 2
+    for name in sorted(new):
+        print(name, new[name], v1[name])
+        if "/" in name and not name.startswith(("encode/", "network/")):
+            assert new[name]["n_rays_hit"] > 0 and new[name]["n_samples"] > 0 and new[name]["nonzero"] > 0, name  # (a frame of something)
+        if name.startswith("encode/"):
+            assert new[name]["nonzero"] > 0, name
+        assert new[name] == v1[name], name
