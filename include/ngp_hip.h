@@ -239,6 +239,13 @@ NGP_API int ngp_get_device_render_stats(ngp_ctx* ctx, int device_index, ngp_rend
 /* the same for the last n calls (oldest first; the context keeps 256), read once after a batch of asynchronous
  * ngp_render_device calls so that measuring does not serialise them */
 NGP_API int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out);
+/* Which render kernel the last ngp_render / ngp_render_device of this context launched (for a multi-device context: the primary's share):
+ * "render_nerf_fused" (any box, any camera), "render_nerf_fused_unit" / "_unit_plain" (aabb_scale 1; plain = pinhole, no aperture, no
+ * environment map), "_c5" / "_c5_plain" (aabb_scale up to 16, render box inside the grid), "_mid0" / "_mid2" / "_lin_rgb" / "_lin" (an rgb
+ * head with 1 / 3 hidden layers; an rgb head, or both heads, without one), "_normals", the stamped diagnostic twins "_prof" / "_unit_plain_prof" /
+ * "_unit_plain_prof2", or "wide" (Frequency / Identity encodings). "" before the first frame and after a frame of meshes alone. The string
+ * is static. Recorded on the host where the launch is chosen; tests use it to assert that a frame exercised the kernel they mean. */
+NGP_API const char* ngp_last_render_kernel(ngp_ctx* ctx);
 
 /* Scheduling of the persistent render kernel: knobs[0..n) = refill_min [16,64], skip_steps [1,64], go_min [1,64], max_stall [0,64],
  * samples a ray may emit per round while most of a wave's ray slots are live [1,8], at most once fewer are [1,8] (the reference's n_steps

@@ -1268,11 +1268,19 @@ static const struct { void (*kernel)(ModelParams, CameraParams, FrameParams); bo
 	{render_nerf_fused_c5_plain, true}, {render_nerf_fused_prof, true}, {render_nerf_fused_unit_plain_prof, true},
 	{render_nerf_fused_unit_plain_prof2, true}, {render_nerf_fused_mid0, false}, {render_nerf_fused_mid2, false},
 	{render_nerf_fused_lin_rgb, false}, {render_nerf_fused_lin, false}, {render_nerf_fused_normals, false}};
+// their names as ngp_last_render_kernel reports them, in the order of RenderKernel ("wide": wide_kernels.hip)
+static const char* const RENDER_KERNEL_NAMES[RK_COUNT + 1] = {
+	"render_nerf_fused", "render_nerf_fused_unit", "render_nerf_fused_unit_plain", "render_nerf_fused_c5", "render_nerf_fused_c5_plain", "render_nerf_fused_prof",
+	"render_nerf_fused_unit_plain_prof", "render_nerf_fused_unit_plain_prof2", "render_nerf_fused_mid0", "render_nerf_fused_mid2", "render_nerf_fused_lin_rgb",
+	"render_nerf_fused_lin", "render_nerf_fused_normals", "wide"};
 void launch_render_nerf_wide(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream);
 void launch_trace_probe_wide(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
-void launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream) {
+const char* launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream) {
 	const RenderKernel k = select_render_kernel(M, C, F);
-	if (k == RK_WIDE) return launch_render_nerf_wide(M, C, F, n_cus, stream);
+	if (k == RK_WIDE) {
+		launch_render_nerf_wide(M, C, F, n_cus, stream);
+		return RENDER_KERNEL_NAMES[k];
+	}
 	static const struct PerCu { int v[RK_COUNT]; } resident = []() {
 		PerCu r;
 		for (int i = 0; i < RK_COUNT; ++i) r.v[i] = resident_blocks_per_cu(RENDER_KERNELS[i].kernel);
@@ -1292,6 +1300,7 @@ void launch_render_nerf(const ModelParams& M, const CameraParams& C, const Frame
 	const int n_blocks = grid_blocks(F, n_cus * per_cu);
 	const FrameParams G = with_grid(F, n_blocks);
 	hipLaunchKernelGGL(RENDER_KERNELS[k].kernel, dim3(n_blocks), dim3(BLOCK), 0, stream, M, C, G);
+	return RENDER_KERNEL_NAMES[k];
 }
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream) {
 	if (M.wide.width) return launch_trace_probe_wide(M, F, P, n_cus, stream);

@@ -13,11 +13,22 @@ extern "C" {
 
 const char* ngp_version(void) { return "ngp_hip 0.1 (gfx950)"; }
 
+// NGP_TUNE goes through the same gate as ngp_set_schedule, on every kind of context: a refused list fails the creation, with the gate's message
+static bool schedule_from_env_or_report(ngp_ctx* ctx) {
+	try {
+		schedule_from_env(ctx);
+	} catch (const std::exception& e) {
+		fprintf(stderr, "ngp_create: NGP_TUNE: %s\n", e.what());
+		return false;
+	}
+	return true;
+}
+
 ngp_ctx* ngp_create(int device) {
 	if (device == -1) { // host-only context: file formats and validation, no rendering (there is no CPU renderer)
-		ngp_ctx* ctx = new ngp_ctx();
+		std::unique_ptr<ngp_ctx> ctx(new ngp_ctx());
 		ctx->device = -1;
-		return ctx;
+		return schedule_from_env_or_report(ctx.get()) ? ctx.release() : nullptr;
 	}
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return nullptr;
@@ -31,13 +42,7 @@ ngp_ctx* ngp_create(int device) {
 	} catch (const std::exception&) {
 		return nullptr;
 	}
-	try {
-		schedule_from_env(ctx.get());
-	} catch (const std::exception& e) {
-		fprintf(stderr, "ngp_create: %s\n", e.what());
-		return nullptr;
-	}
-	return ctx.release();
+	return schedule_from_env_or_report(ctx.get()) ? ctx.release() : nullptr;
 }
 
 // peers first; then every owner of the context releases its resources on the owning device, after the last frame

@@ -118,7 +118,7 @@ struct DeviceGuard {
 };
 
 // kernel launchers, nerf_kernels.hip
-void launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream);
+const char* launch_render_nerf(const ModelParams& M, const CameraParams& C, const FrameParams& F, int n_cus, hipStream_t stream); // returns the name of the kernel it chose (ngp_last_render_kernel)
 void launch_grid_encode(const ModelParams& M, uint32_t n, const float* pos01, uint16_t* out, hipStream_t stream);
 void launch_build_normals_fragments(uint4* wfrags, hipStream_t stream); // after every change of the forward fragments
 void launch_density_gradient(const ModelParams& M, uint32_t n, const float* pos01, float* out, hipStream_t stream);
@@ -367,6 +367,7 @@ struct ngp_ctx {
 	ngp::DevArray<uint32_t> d_trace; // wave timelines of the diagnostic build (NGP_PROFILE_TRACE)
 	static constexpr uint32_t TRACE_WAVES = 64, TRACE_ITERS = 1024;
 	int32_t tune[8] = {64, 4, 32, 1, 1, 4, 1, 1}; // FrameParams::tune; changed only through validate_schedule (ngp_render.cpp)
+	const char* last_render_kernel = ""; // what launch_render_nerf chose for the last frame ("": no frame yet, or one of meshes alone)
 
 	// ---- several devices behind this context (ngp_multi.cpp): replicas on the auxiliary devices, tile gather at the primary
 	std::vector<ngp_ctx*> peers;  // owned; empty for a single-device context

@@ -249,11 +249,12 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 
 	order_after_model(ctx, stream); // a training step / grid refresh / peer copy that updated what this frame reads (a device-side wait)
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot], stream));
+	ctx->last_render_kernel = "";
 	if (F.direct) {
 		F.frame_buffer = d_rgba_out;
 		CameraParams C = make_camera_params(cam, cam.spp_index);
 		NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
-		launch_render_nerf(M, C, F, ctx->n_cus, stream);
+		ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream);
 		NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
 	}
 	if (!F.direct && ctx->n_calls > 0 && (ctx->streams_mixed || (ctx->last_stream && ctx->last_stream != stream))) {
@@ -283,7 +284,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
-		if (ctx->model_loaded) launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
+		if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
 		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
 		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame.get(), ctx->d_accum.get(), (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
@@ -496,6 +497,8 @@ int ngp_set_schedule(ngp_ctx* ctx, const int32_t* knobs, int n) {
 		for (int i = 0; i < n; ++i) ctx->tune[i] = knobs[i];
 	});
 }
+
+const char* ngp_last_render_kernel(ngp_ctx* ctx) { return ctx ? ctx->last_render_kernel : ""; }
 
 int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out) {
 	return guarded(ctx, [&] {

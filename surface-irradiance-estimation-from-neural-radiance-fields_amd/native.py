@@ -175,6 +175,8 @@ def load_library():
     L.ngp_get_render_stats.argtypes = [vp, C.POINTER(RenderStats)]
     L.ngp_get_render_history.argtypes = [vp, ip, C.POINTER(RenderStats)]
     L.ngp_set_schedule.argtypes = [vp, vp, ip]
+    if hasattr(L, "ngp_last_render_kernel"):  # (an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
+        L.ngp_last_render_kernel.argtypes = [vp]; L.ngp_last_render_kernel.restype = C.c_char_p
     if hasattr(L, "ngp_get_profile_trace"):  # (diagnostic entry; an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
         L.ngp_get_profile_trace.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.ngp_grid_encode.argtypes = [vp, C.c_uint32, vp, vp]
@@ -317,7 +319,7 @@ class Context:
         else:
             self.h = self.L.ngp_create(device)
         if not self.h:
-            raise RuntimeError("ngp_create failed: no HIP device available (libngp_hip has no CPU fallback)")
+            raise RuntimeError("ngp_create failed: no HIP device available (libngp_hip has no CPU fallback), or NGP_TUNE was refused (the library names the knob on stderr)")
 
     def n_devices(self):
         return self.L.ngp_n_devices(self.h)
@@ -497,6 +499,10 @@ class Context:
         st = RenderStats()
         self._check(self.L.ngp_get_render_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in RenderStats._fields_}
+
+    def last_render_kernel(self):
+        """Name of the kernel the last frame ran ("render_nerf_fused_unit_plain", ..., "wide"; ngp_last_render_kernel)"""
+        return self.L.ngp_last_render_kernel(self.h).decode()
 
     def render_history(self, n):
         arr = (RenderStats * n)()

@@ -40,7 +40,7 @@ def frame(name, w, h, az=45.0, el=30.0, radius=4.03, spp_index=0, snap=True, ape
         rgba, depth = ctx.render(cam, o, want_depth=True)
     st = ctx.render_stats()
     out[name] = dict(rgba=hashlib.sha256(np.ascontiguousarray(rgba).tobytes()).hexdigest(), depth=hashlib.sha256(np.ascontiguousarray(depth).tobytes()).hexdigest(),
-                     n_samples=int(st["n_samples"]), n_rays_hit=int(st["n_rays_hit"]), nonzero=int(np.count_nonzero(rgba[..., :3])))
+                     n_samples=int(st["n_samples"]), n_rays_hit=int(st["n_rays_hit"]), nonzero=int(np.count_nonzero(rgba[..., :3])), kernel=ctx.last_render_kernel())
 
 for sched_name, sched in (("default", DEFAULT_SCHEDULE), ("exact_march", EXACT_MARCH)):
     ctx.set_schedule(*sched)
@@ -81,6 +81,8 @@ def test_frames_with_and_without_cell_cache_are_equal_as_bytes(native):
     for name in sorted(cached):
         print(name, cached[name], plain[name])
         assert cached[name]["n_rays_hit"] > 0 and cached[name]["n_samples"] > 0 and cached[name]["nonzero"] > 0, name  # (a frame of something)
+        # the two kernels that have the cache, and no other: render_nerf_fused (no cache) would make both libraries the same code
+        assert cached[name]["kernel"] == ("render_nerf_fused_unit" if name.endswith("depth_of_field") else "render_nerf_fused_unit_plain"), name
         assert cached[name] == plain[name], name
 
 

@@ -35,7 +35,7 @@ def frame(name, w, h, az=45.0, el=30.0, radius=4.03, aperture_size=0.0, **opts):
     cam = native.make_camera(scene.orbit_camera(az, el, radius), w, h, scene.focal_from_fov_x(w, 0.6911), aperture_size=aperture_size, focus_z=1.3)
     rgba, depth = ctx.render(cam, native.make_opts(**opts), want_depth=True)
     st = ctx.render_stats()
-    out[name] = dict(rgba=sha(rgba), depth=sha(depth), n_samples=int(st["n_samples"]), n_rays_hit=int(st["n_rays_hit"]), nonzero=int(np.count_nonzero(rgba[..., :3])))
+    out[name] = dict(rgba=sha(rgba), depth=sha(depth), n_samples=int(st["n_samples"]), n_rays_hit=int(st["n_rays_hit"]), nonzero=int(np.count_nonzero(rgba[..., :3])), kernel=ctx.last_render_kernel())
 
 for sched_name, sched in (("default", DEFAULT_SCHEDULE), ("exact_march", EXACT_MARCH)):
     ctx.set_schedule(*sched)
@@ -100,6 +100,7 @@ def test_trimmed_network_section_gives_the_same_bytes(native):
         print(name, new[name], v1[name])
         if "/" in name and not name.startswith(("encode/", "network/")):
             assert new[name]["n_rays_hit"] > 0 and new[name]["n_samples"] > 0 and new[name]["nonzero"] > 0, name  # (a frame of something)
+            assert new[name]["kernel"] == ("render_nerf_fused_unit" if name.endswith("depth_of_field") else "render_nerf_fused_unit_plain"), name  # (the kernels whose network section was trimmed)
         if name.startswith("encode/"):
             assert new[name]["nonzero"] > 0, name
         assert new[name] == v1[name], name

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import model_fixtures
 from conftest import pkg, psnr
 
 pytestmark = pytest.mark.gpu
@@ -138,9 +139,7 @@ def test_rgb_heads_with_one_and_three_hidden_layers(n_hidden, gpu_ctx, oracle, n
     """configs/nerf/base_1layer.json / base_3layer.json: rgb_network.n_hidden_layers 1 and 3 (2 in base.json)."""
     from conftest import _with_bitfield
 
-    cfg = scene_mod.base_network_config()
-    cfg["rgb_network"] = dict(cfg["rgb_network"], n_hidden_layers=n_hidden)
-    sc = _with_bitfield(oracle, pkg("synthetic").make_scene(aabb_scale=1, seed=31 + n_hidden, log2_hashmap_size=15, cfg=cfg))
+    sc = _with_bitfield(oracle, model_fixtures.rgb_head_scene(n_hidden))
     gpu_ctx.set_model(sc)
     assert gpu_ctx.get_model().n_hidden_rgb == n_hidden
     m = oracle.make_model(sc)
@@ -170,8 +169,7 @@ def test_heads_without_a_hidden_layer(hidden_density, gpu_ctx, oracle, native, s
     padded to 8 rows rather than 16): network outputs, the rendered image, the Normals gradient, the snapshot round trip."""
     from conftest import _with_bitfield
 
-    cfg = scene_mod.linear_network_config(hidden_density)
-    sc = _with_bitfield(oracle, pkg("synthetic").make_scene(aabb_scale=1, seed=51 + hidden_density, log2_hashmap_size=15, cfg=cfg))
+    sc = _with_bitfield(oracle, model_fixtures.linear_head_scene(hidden_density))
     assert scene_mod.n_params(sc)[:2] == ((512, 256) if hidden_density == 0 else (3072, 256))
     gpu_ctx.set_model(sc)
     d = gpu_ctx.get_model()
