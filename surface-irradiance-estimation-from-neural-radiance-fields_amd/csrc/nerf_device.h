@@ -9,6 +9,7 @@
 
 #include "ngp_kernels.h"
 #include "cell_cache.h"
+#include "occ_index.h"
 
 namespace ngp {
 
@@ -151,6 +152,19 @@ NGP_DEV float unwarp_dt(float dt) { // nerf_device.cuh:311-314
 	return dt * (max_stepsize - stepsize()) + stepsize();
 }
 
+// Gathers are buffer loads (a 128-bit resource descriptor in SGPRs + a 32-bit per-lane byte offset) rather than flat
+// loads from a 64-bit address: no 64-bit add per gather, and an out-of-range offset reads zeros instead of faulting.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __amdgpu_buffer_rsrc_t GridRsrc;
+NGP_DEV GridRsrc make_grid_rsrc(const void* table, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(table), (short)0, (int)bytes, 0x00020000); }
+NGP_DEV uint2 gather8(GridRsrc r, uint32_t offset) {
+	const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)offset, 0, 0);
+	return make_uint2(v.x, v.y);
+}
+// the block-linear copy of the bitfield's 8-byte block words behind the summaries in ModelParams::coarse (occ_index.h; not with -DNGP_ROUND_V1)
+static_assert(OCC_GRIDSIZE == NERF_GRIDSIZE && OCC_SUMMARY4_WORDS_PER_MIP == COARSE_WORDS_PER_MIP && COARSE_SUMMARY_WORDS % 2 == 0, "occ_index.h and ngp_kernels.h describe the same tables");
+NGP_DEV const uint2* occ_words(const uint32_t* __restrict__ coarse) { return (const uint2*)(coarse + COARSE_SUMMARY_WORDS); }
+
 // ---------------------------------------------------------------------------------------------------------
 // Occupancy grid: nerf_device.cuh:316-367,430-447; Morton code as tcnn's morton3D.
 NGP_DEV uint32_t expand_bits(uint32_t v) {
@@ -182,7 +196,7 @@ NGP_DEV bool density_grid_occupied_at(f3 pos, const uint8_t* __restrict__ bitfie
 }
 
 // The same lookup with a 4x4x4-block summary of the bitfield held in LDS (s_coarse: [mip][1024] words). In Morton
-// order a 4x4x4 block is 64 consecutive cells = 8 consecutive bytes, so block = idx >> 6. An empty block answers
+// order a 4x4x4 block is 64 consecutive cells = 8 consecutive bytes of the bitfield. An empty block answers
 // "not occupied" without touching global memory; the decision (and therefore every t the march visits) is unchanged.
 NGP_DEV bool density_grid_occupied_at_lds(f3 pos, const uint8_t* __restrict__ bitfield, const uint32_t* s_coarse, uint32_t mip) {
 	float mip_scale = __builtin_ldexpf(1.0f, -(int)mip);
@@ -192,15 +206,15 @@ NGP_DEV bool density_grid_occupied_at_lds(f3 pos, const uint8_t* __restrict__ bi
 	int iz = (int)(pos.z * (float)NERF_GRIDSIZE);
 	if (ix < 0 || ix >= (int)NERF_GRIDSIZE || iy < 0 || iy >= (int)NERF_GRIDSIZE || iz < 0 || iz >= (int)NERF_GRIDSIZE) return false;
 	uint32_t idx = morton3D((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
-	uint32_t block = idx >> 6;
-	if (!((s_coarse[mip * COARSE_WORDS_PER_MIP + (block >> 5)] >> (block & 31u)) & 1u)) return false;
+	uint32_t block = occ_block4((uint32_t)ix, (uint32_t)iy, (uint32_t)iz); // (the summary's own order, occ_index.h)
+	if (!((s_coarse[occ_summary4_word(mip, block)] >> (block & 31u)) & 1u)) return false;
 	return (bitfield[idx / 8 + (NERF_GRID_N_CELLS / 8) * mip] & (1u << (idx % 8))) != 0;
 }
 
 // Occupancy lookup for the march: 0 = the cell is occupied; otherwise log2 of the side (in cells of this mip) of the
 // largest aligned empty block around pos that the LDS summaries can vouch for: 1 cell (-> 1), 4x4x4 (-> 4) or
 // 16x16x16 (-> 16). Out-of-range positions count as a single empty cell, like density_grid_occupied_at.
-// s_coarse: [mip][1024] words (4^3 blocks = morton >> 6), s_coarse16: [mip][16] words (16^3 blocks = morton >> 12).
+// s_coarse: [mip][1024] words (4^3 blocks), s_coarse16: [mip][16] words (16^3 blocks), both indexed as occ_index.h says.
 // The 64 occupancy bits of a 4x4x4 block are one aligned 8-byte word of the Morton-ordered bitfield; a marching lane
 // keeps the last block it read (a ray spends ~18 consecutive samples in one block), so most lookups touch no memory.
 struct OccBlockCache {
@@ -217,10 +231,10 @@ NGP_DEV uint32_t empty_block_size_at(f3 pos, const uint8_t* __restrict__ bitfiel
 	int iz = (int)(pos.z * (float)NERF_GRIDSIZE);
 	if (ix < 0 || ix >= (int)NERF_GRIDSIZE || iy < 0 || iy >= (int)NERF_GRIDSIZE || iz < 0 || iz >= (int)NERF_GRIDSIZE) return 1u;
 	uint32_t idx = morton3D((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
-	uint32_t b16 = idx >> 12;
-	if (!((s_coarse16[mip * 16u + (b16 >> 5)] >> (b16 & 31u)) & 1u)) return 16u;
-	uint32_t b4 = idx >> 6;
-	if (!((s_coarse[mip * COARSE_WORDS_PER_MIP + (b4 >> 5)] >> (b4 & 31u)) & 1u)) return 4u;
+	uint32_t b16 = occ_block16((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
+	if (!((s_coarse16[occ_summary16_word(mip, b16)] >> (b16 & 31u)) & 1u)) return 16u;
+	uint32_t b4 = idx >> 6, s4 = occ_block4((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
+	if (!((s_coarse[occ_summary4_word(mip, s4)] >> (s4 & 31u)) & 1u)) return 4u;
 	const uint32_t key = (mip << 26) | b4;
 	if (cache.key != key) {
 		cache.bits = *(const uint2*)(bitfield + (size_t)b4 * 8 + (size_t)(NERF_GRID_N_CELLS / 8) * mip);
@@ -240,6 +254,10 @@ struct OccBlock {
 };
 // lds_mips: the summaries of that many cascades are in LDS (s_coarse), those of the outer ones are read from g_coarse (global, a 4 KB
 // table per cascade that the vector L1 keeps): the five-cascade kernel fits a third workgroup per CU that way.
+// Without -DNGP_ROUND_V1 the summaries and a copy of the bitfield's block words (behind the summaries in g_coarse, which must be given) are indexed by the
+// low 15 bits of that key (occ_index.h), so a lane that leaves its block forms no Morton code and no 64-bit address either; `bitfield` is unused.
+// (A plain load from the kernel argument plus a 32-bit index -- global_load with an SGPR base: the render kernels are at their SGPR limit, and a
+// buffer descriptor for this table was either kept in VGPRs and read through a waterfall loop or spilled to VGPR lanes around every use.)
 NGP_DEV uint32_t occupancy_state_at(f3 pos, const uint8_t* __restrict__ bitfield, const uint32_t* s_coarse, const uint32_t* s_coarse16, uint32_t mip, OccBlock& cache,
                                     uint32_t lds_mips = NERF_CASCADES, const uint32_t* __restrict__ g_coarse = nullptr) {
 	float mip_scale = __builtin_ldexpf(1.0f, -(int)mip);
@@ -251,15 +269,23 @@ NGP_DEV uint32_t occupancy_state_at(f3 pos, const uint8_t* __restrict__ bitfield
 	const uint32_t x = (uint32_t)ix, y = (uint32_t)iy, z = (uint32_t)iz;
 	const uint32_t key = (x >> 2) | ((y >> 2) << 5) | ((z >> 2) << 10) | (mip << 15);
 	if (cache.key != key) {
+#ifdef NGP_ROUND_V1
 		const uint32_t b4 = morton3D(x >> 2, y >> 2, z >> 2), b16 = b4 >> 6; // == morton3D(x, y, z) >> 6, >> 12
-		if (!((s_coarse16[mip * 16u + (b16 >> 5)] >> (b16 & 31u)) & 1u)) return 16u; // (32^3 / 64^3 blocks, tried: hardly ever empty where a 16^3 one is)
-		const uint32_t cw = mip < lds_mips ? s_coarse[mip * COARSE_WORDS_PER_MIP + (b4 >> 5)] : g_coarse[mip * COARSE_WORDS_PER_MIP + (b4 >> 5)];
+#else
+		const uint32_t b4 = key & (OCC_BLOCKS_PER_MIP - 1u), b16 = occ_block16(x, y, z); // == occ_block4(x, y, z)
+#endif
+		if (!((s_coarse16[occ_summary16_word(mip, b16)] >> (b16 & 31u)) & 1u)) return 16u; // (32^3 / 64^3 blocks, tried: hardly ever empty where a 16^3 one is)
+		const uint32_t cw = mip < lds_mips ? s_coarse[occ_summary4_word(mip, b4)] : g_coarse[occ_summary4_word(mip, b4)];
 		if (!((cw >> (b4 & 31u)) & 1u)) return 4u;
+#ifdef NGP_ROUND_V1
 		cache.bits = *(const uint2*)(bitfield + (size_t)b4 * 8 + (size_t)(NERF_GRID_N_CELLS / 8) * mip);
+#else
+		cache.bits = occ_words(g_coarse)[occ_block_word(mip, b4)]; // (mip < 8: inside the table)
+#endif
 		cache.key = key;
 	}
 	// the Morton code of the coordinates' low two bits: bit (idx & 63) of the block word
-	const uint32_t bit = (x & 1u) | ((y & 1u) << 1) | ((z & 1u) << 2) | ((x & 2u) << 2) | ((y & 2u) << 3) | ((z & 2u) << 4);
+	const uint32_t bit = occ_bit_in_block(x, y, z);
 	const uint32_t word = (bit & 32u) ? cache.bits.y : cache.bits.x;
 	return ((word >> (bit & 31u)) & 1u) ? 0u : 1u;
 }
@@ -274,9 +300,9 @@ NGP_DEV uint32_t empty_block_summary_at(f3 pos, const uint32_t* s_coarse, const 
 	pos = adds3(scale3(adds3(pos, -0.5f), mip_scale), 0.5f);
 	const int ix = (int)(pos.x * (float)(NERF_GRIDSIZE / 4)), iy = (int)(pos.y * (float)(NERF_GRIDSIZE / 4)), iz = (int)(pos.z * (float)(NERF_GRIDSIZE / 4));
 	if (((uint32_t)ix | (uint32_t)iy | (uint32_t)iz) >= NERF_GRIDSIZE / 4 || pos.x < 0.0f || pos.y < 0.0f || pos.z < 0.0f) return 0u;
-	const uint32_t b4 = morton3D((uint32_t)ix, (uint32_t)iy, (uint32_t)iz), b16 = b4 >> 6;
-	if (!((s_coarse16[mip * 16u + (b16 >> 5)] >> (b16 & 31u)) & 1u)) return 16u;
-	const uint32_t cw = mip < lds_mips ? s_coarse[mip * COARSE_WORDS_PER_MIP + (b4 >> 5)] : g_coarse[mip * COARSE_WORDS_PER_MIP + (b4 >> 5)];
+	const uint32_t b4 = occ_block4_of_block((uint32_t)ix, (uint32_t)iy, (uint32_t)iz), b16 = occ_block16_of_block((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
+	if (!((s_coarse16[occ_summary16_word(mip, b16)] >> (b16 & 31u)) & 1u)) return 16u;
+	const uint32_t cw = mip < lds_mips ? s_coarse[occ_summary4_word(mip, b4)] : g_coarse[occ_summary4_word(mip, b4)];
 	return ((cw >> (b4 & 31u)) & 1u) ? 0u : 4u;
 }
 
@@ -737,15 +763,7 @@ NGP_DEV void level_corners_xor(const LevelInfo& L, const CellPos& p, CornerSet& 
 	}
 }
 
-// Gathers are buffer loads (a 128-bit resource descriptor in SGPRs + a 32-bit per-lane byte offset) rather than flat
-// loads from a 64-bit address: no 64-bit add per gather, and an out-of-range offset reads zeros instead of faulting.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t GridRsrc;
-NGP_DEV GridRsrc make_grid_rsrc(const void* table, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(table), (short)0, (int)bytes, 0x00020000); }
-NGP_DEV uint2 gather8(GridRsrc r, uint32_t offset) {
-	const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)offset, 0, 0);
-	return make_uint2(v.x, v.y);
-}
+// (the gathers' buffer loads: GridRsrc, make_grid_rsrc and gather8 are defined above the occupancy lookups, which use them too)
 
 // The corner sum of tcnn's kernel_grid. tiny-cuda-nn is an un-pinned, un-vendored submodule of the reference
 // (.gitmodules:13-15) and has published two sequences:

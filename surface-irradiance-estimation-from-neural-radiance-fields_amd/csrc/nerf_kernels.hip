@@ -148,6 +148,10 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	occ_cache.key = 0xffffffffu;
 	occ_cache.bits = make_uint2(0u, 0u);
 	bool finished = false; // the ray has ended and waits to be shaded (once per round, with every other finished ray)
+	// wave-uniform: the finished rays that ended by transmittance. Their colour is normalised by their alpha (composite_kernel_nerf, :716-719)
+	// when they are shaded, with every other finished ray, instead of in the composite, where the four divisions ran for one or two lanes in
+	// most rounds of a busy wave; nothing reads acc in between (only live rays are handed to a sibling wave). -DNGP_ROUND_V1: in the composite.
+	unsigned long long norm_mask = 0ull;
 	bool idle = false;     // wave-uniform: this wave has told the workgroup that it is out of work (s_active)
 	const uint32_t my_wave = threadIdx.x >> 6;
 
@@ -189,6 +193,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		// ---- refill free slots from the tile queue: K1 and the start-of-ray jitter of K2. The skip to the first
 		// occupied voxel that K2 also does (advance_pos_nerf, :356) is the same loop as K4's and runs below with every
 		// other marching lane -- a ray with nothing in front of it must not stall the 63 other slots of its wave.
+		NGP_SECTION("retire");
 		unsigned long long dead_mask = __ballot(!ray.alive);
 		int n_dead = __popcll(dead_mask);
 		// ---- retire: K7 for the rays that ended since the last refill, all at once (sRGB->linear is three powf and a
@@ -196,12 +201,17 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		if ((exhausted || n_dead >= F.tune[0]) && __any(finished)) {
 			bool hit = false;
 			if (finished) {
+#ifndef NGP_ROUND_V1
+				if ((norm_mask >> lane) & 1ull) { acc.r /= acc.a; acc.g /= acc.a; acc.b /= acc.a; acc.a /= acc.a; }
+#endif
 				hit = shade_ray<PROBE, PLAIN, NORMALS>(F, P, bg_linear, ray.out, acc, step - 1u, ray.d); // step counts from 1 like the reference's march loop
 				finished = false;
 			}
+			norm_mask = 0ull; // (every finished ray has been shaded)
 			n_hit += (uint32_t)__popcll(__ballot(hit));
 			if (PROF) tr_info1 |= 4u << 24;
 		}
+		NGP_SECTION("refill");
 		if (!exhausted && n_dead >= (F.tune[0] > 16 ? F.tune[0] : 16)) {
 			// the queue deals 4x4-pixel strips (quarters of the 8x8 tiles): one atomic hands this wave n_dead / 16 of them
 			const uint32_t want = (uint32_t)n_dead >> 4, n_strips = F.n_local_tiles * 4u;
@@ -312,6 +322,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			}
 		}
 
+		NGP_SECTION("share");
 		if (!PROBE && F.tune[7] && n_slots == 0u) {
 			// ---- a sibling without work is asking: hand it every second live ray (none of them has a sample in the list at this point)
 			const uint32_t st = __hip_atomic_load(&s_xstate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -346,6 +357,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				}
 			}
 		}
+		NGP_SECTION("other");
 		if (PROF) { t1 = stamp(); pt[0] += t1 - t0; t0 = t1; tr_t[1] = t1; }
 		// ---- K4 / K2: if_unoccupied_advance_to_next_occupied_voxel (nerf_device.cuh:461-494). A lane that reaches an occupied voxel
 		// EMITS a sample -- warped position and step into the next free slot of the wave's sample list in LDS, in emission order -- and
@@ -374,6 +386,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			if (PROBE && ray.t >= t_max) out = true; // a ray-list ray's t_max: what it gathered is shaded, as at the box exit
 			const bool inside = marching && !out;
 			uint32_t mip = 0, empty = 1u;
+			NGP_SECTION("march.lookup");
 			if (inside) {
 				if (!UNIT) {
 					mip = mip_from_pos(pos, NERF_CASCADES - 1);
@@ -381,6 +394,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				}
 				empty = occupancy_state_at(pos, M.bitfield, s_coarse, s_coarse16, mip, occ_cache, MIPS, M.coarse);
 			}
+			NGP_SECTION("march.emit");
 			const bool emit = inside && empty == 0u;
 			const bool skip = inside && empty != 0u;
 			float e_dt = 0.f;
@@ -392,6 +406,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				else e_w = div3(e_w, adiag);
 			}
 			bool ends = marching && out;
+			NGP_SECTION("march.skip");
 			if (skip) {
 				// climb to the largest empty cascade cell around pos (nerf_device.cuh:488-490); each level doubles
 				// the cell, so the block summary of the final level is looked up again
@@ -430,6 +445,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				}
 				++skip_i;
 			}
+			NGP_SECTION("march");
 			if (ends) {
 				if (n_pend == 0) {
 					ray.alive = false;
@@ -439,6 +455,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				}
 			}
 			// ---- K3: the wave64 counterpart of compact_kernel_nerf -- emitting lanes take consecutive slots (ballot + prefix count)
+			NGP_SECTION("march.compact");
 			const unsigned long long emit_mask = __ballot(emit);
 			if (emit_mask) {
 				const uint32_t slot = n_slots + lanes_below(emit_mask);
@@ -675,6 +692,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 			NGP_SECTION("composite");
 			const bool have = k < n_pend && ray.alive;
 			if (!__any(have)) break;
+			bool ended_opaque = false;
 			if (have) {
 				const uint32_t slot = ((k < 4u ? sl_lo >> (8u * k) : sl_hi >> (8u * (k - 4u))) & 0xffu);
 				const float4 a = s_samp[wave_base + slot];
@@ -717,13 +735,20 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				}
 				++step;
 				if (acc.a > (1.0f - F.min_transmittance)) {
+					NGP_SECTION("composite.end");
+#ifdef NGP_ROUND_V1
 					acc.r /= acc.a; acc.g /= acc.a; acc.b /= acc.a; acc.a /= acc.a;
+#else
+					ended_opaque = true;
+#endif
 					ray.alive = false;
 					finished = true;
+					NGP_SECTION("composite");
 				} else if (step >= MARCH_ITER) {
 					ray.alive = false; // never compacted into the hit buffer by the reference loop (:2056)
 				}
 			}
+			norm_mask |= __ballot(ended_opaque);
 			n_samples += (uint32_t)__popcll(__ballot(have));
 		}
 		NGP_SECTION("other");
@@ -1132,6 +1157,7 @@ __global__ void grid_to_bitfield_kernel(uint32_t n_elements, uint32_t n_nonzero_
 	bitfield[i] = bits;
 }
 
+#ifdef NGP_ROUND_V1
 // empty-space summary: one bit per 4x4x4 block (8 consecutive Morton-ordered bytes) of every mip
 __global__ void coarse_occupancy_kernel(const uint8_t* __restrict__ bitfield, uint32_t* __restrict__ coarse) {
 	uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; // output word: 32 blocks = 256 bytes of bitfield
@@ -1155,6 +1181,42 @@ __global__ void coarse16_occupancy_kernel(uint32_t* __restrict__ coarse) {
 	}
 	coarse[NERF_CASCADES * COARSE_WORDS_PER_MIP + w] = bits;
 }
+#else
+// empty-space summaries and the block-linear copy of the bitfield's block words (occ_index.h), rebuilt whenever the bitfield changes.
+// One bit per 4x4x4 block (8 consecutive Morton-ordered bytes of the bitfield) of every mip, in the order of the blocks' coordinates.
+__global__ void coarse_occupancy_kernel(const uint8_t* __restrict__ bitfield, uint32_t* __restrict__ coarse) {
+	uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; // output word: the 32 blocks (bx = 0 .. 31, by, bz) of cascade mip
+	if (w >= NERF_CASCADES * COARSE_WORDS_PER_MIP) return;
+	const uint32_t mip = w / COARSE_WORDS_PER_MIP, by = w & 31u, bz = (w >> 5) & 31u;
+	const uint2* src = (const uint2*)(bitfield + (size_t)(NERF_GRID_N_CELLS / 8) * mip);
+	uint2* words = (uint2*)(coarse + COARSE_SUMMARY_WORDS);
+	uint32_t bits = 0;
+	for (uint32_t bx = 0; bx < 32u; ++bx) {
+		const uint2 v = src[morton3D(bx, by, bz)];
+		const uint32_t block = occ_block4_of_block(bx, by, bz); // == (w % COARSE_WORDS_PER_MIP) * 32 + bx
+		words[occ_block_word(mip, block)] = v;
+		bits |= ((v.x | v.y) != 0u ? 1u : 0u) << (block & 31u);
+	}
+	coarse[w] = bits;
+}
+// second level: one bit per 16x16x16 block = 4 x 4 x 4 blocks of the first level = a nibble of 16 of its words
+__global__ void coarse16_occupancy_kernel(uint32_t* __restrict__ coarse) {
+	uint32_t w = threadIdx.x; // NERF_CASCADES * 16 output words
+	if (w >= NERF_CASCADES * 16) return;
+	const uint32_t mip = w / 16u;
+	uint32_t bits = 0;
+	for (uint32_t b = 0; b < 32u; ++b) {
+		const uint32_t b16 = (w & 15u) * 32u + b, x16 = b16 & 7u, y16 = (b16 >> 3) & 7u, z16 = b16 >> 6;
+		uint32_t any = 0;
+		for (uint32_t k = 0; k < 16u; ++k) {
+			const uint32_t block = occ_block4_of_block(x16 * 4u, y16 * 4u + (k & 3u), z16 * 4u + (k >> 2)); // bx = 4 x16 .. 4 x16 + 3: bits (block & 31) .. + 3 of one word
+			any |= (coarse[occ_summary4_word(mip, block)] >> (block & 31u)) & 0xfu;
+		}
+		bits |= (any != 0u ? 1u : 0u) << b;
+	}
+	coarse[NERF_CASCADES * COARSE_WORDS_PER_MIP + w] = bits;
+}
+#endif
 
 __global__ void bitfield_max_pool_kernel(uint32_t n_elements, const uint8_t* __restrict__ prev_level, uint8_t* __restrict__ next_level) {
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -93,7 +93,8 @@ struct ModelParams {
 	const char* xgrid;       // the same entries in the xor layout: one index formula for dense and hashed levels
 	const uint4* wfrags;     // [N_FRAGS][64] x 8 fp16, MFMA A fragments in lane order
 	const uint8_t* bitfield; // 8 x 128^3 bits
-	const uint32_t* coarse;  // 8 x 32^3 bits: bit (morton >> 6) of mip m is set iff any cell of that 4x4x4 block is occupied
+	const uint32_t* coarse;  // derived from the bitfield (occ_index.h): 8 x 32^3 bits, one per 4x4x4 block of cells that holds an occupied cell; 8 x 8^3 bits,
+	                         // one per 16^3 block; then (COARSE_SUMMARY_WORDS on, not with -DNGP_ROUND_V1) the bitfield's 8-byte block words in block-linear order
 	LevelInfo levels[N_LEVELS];
 	float aabb_min[3], aabb_diag[3];
 	float raabb_min[3], raabb_max[3];
@@ -110,6 +111,12 @@ struct ModelParams {
 	WideModel wide;                   // wide.width != 0: grid / xgrid / wfrags / levels are unused, wide_kernels.hip renders
 };
 constexpr uint32_t COARSE_WORDS_PER_MIP = 32 * 32 * 32 / 32;
+constexpr uint32_t COARSE_SUMMARY_WORDS = NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16; // both summaries (an even count: what follows is 8-byte aligned)
+#ifdef NGP_ROUND_V1
+constexpr uint32_t COARSE_TOTAL_WORDS = COARSE_SUMMARY_WORDS;
+#else
+constexpr uint32_t COARSE_TOTAL_WORDS = COARSE_SUMMARY_WORDS + NERF_CASCADES * (NERF_GRID_N_CELLS / 64) * 2; // + 2 MB of block words
+#endif
 
 struct CameraParams {
 	float m[12]; // column-major 4x3

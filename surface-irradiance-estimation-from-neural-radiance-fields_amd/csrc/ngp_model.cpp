@@ -329,7 +329,7 @@ void upload_occupancy(ngp_ctx* ctx, const ngp_model_desc& d, uint32_t max_cascad
 	}
 	launch_density_grid_to_bitfield(ctx->d_density_f16.get(), (uint32_t)d.n_density_grid, max_cascade, ctx->d_density_f32.get(), ctx->d_partial.get(), ctx->d_bitfield.get(),
 	                                &ctx->bitfield_mean, ctx->stream);
-	ctx->d_coarse.reset((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16);
+	ctx->d_coarse.reset((size_t)COARSE_TOTAL_WORDS); // both summaries and the block words (occ_index.h)
 	launch_coarse_occupancy(ctx->d_bitfield.get(), ctx->d_coarse.get(), ctx->stream);
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 	NGP_HIP_CHECK(hipGetLastError());

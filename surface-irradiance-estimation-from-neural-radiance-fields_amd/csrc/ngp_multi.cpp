@@ -56,7 +56,7 @@ void sync_peer_model(ngp_ctx* primary, ngp_ctx* peer) {
 	if (grid) {
 		const size_t n_cells = (size_t)NERF_GRID_N_CELLS * (primary->max_cascade + 1);
 		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_bitfield.get(), peer->device, primary->d_bitfield.get(), primary->device, (size_t)NERF_GRID_N_CELLS / 8 * NERF_CASCADES, s));
-		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_coarse.get(), peer->device, primary->d_coarse.get(), primary->device, ((size_t)NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16) * sizeof(uint32_t), s));
+		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_coarse.get(), peer->device, primary->d_coarse.get(), primary->device, (size_t)COARSE_TOTAL_WORDS * sizeof(uint32_t), s));
 		NGP_HIP_CHECK(hipMemcpyPeerAsync(peer->d_density_f32.get(), peer->device, primary->d_density_f32.get(), primary->device, n_cells * sizeof(float), s));
 		peer->bitfield_mean = primary->bitfield_mean;
 		peer->grid_rng_state = primary->grid_rng_state;

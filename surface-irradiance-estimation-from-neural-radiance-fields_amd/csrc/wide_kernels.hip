@@ -65,8 +65,8 @@ NGP_DEV uint32_t empty_block_size_global(f3 pos, const uint8_t* __restrict__ bit
 	int iz = (int)(pos.z * (float)NERF_GRIDSIZE);
 	if (ix < 0 || ix >= (int)NERF_GRIDSIZE || iy < 0 || iy >= (int)NERF_GRIDSIZE || iz < 0 || iz >= (int)NERF_GRIDSIZE) return 1u;
 	const uint32_t idx = morton3D((uint32_t)ix, (uint32_t)iy, (uint32_t)iz);
-	const uint32_t b16 = idx >> 12;
-	if (!((s_coarse16[mip * 16u + (b16 >> 5)] >> (b16 & 31u)) & 1u)) return 16u;
+	const uint32_t b16 = occ_block16((uint32_t)ix, (uint32_t)iy, (uint32_t)iz); // (the summary's own order, occ_index.h; the bitfield word below: Morton order)
+	if (!((s_coarse16[occ_summary16_word(mip, b16)] >> (b16 & 31u)) & 1u)) return 16u;
 	const uint32_t b4 = idx >> 6, key = (mip << 26) | b4;
 	if (cache.key != key) {
 		cache.bits = *(const uint2*)(bitfield + (size_t)b4 * 8 + (size_t)(NERF_GRID_N_CELLS / 8) * mip);
