@@ -311,7 +311,13 @@ NGP_API int ngp_get_mesh_info(const ngp_ctx* ctx, int mesh, uint32_t* n_tris, ui
 /* the built BVH: nodes (n_nodes x 32 B: bb.min, bb.max, left_idx, right_idx) and reordered triangles (n_tris x 36 B) */
 NGP_API int ngp_get_mesh_bvh(const ngp_ctx* ctx, int mesh, void* nodes_out, void* triangles_out);
 NGP_API int ngp_set_geometry_opts(ngp_ctx* ctx, const ngp_geometry_opts* opts);
-/* M2 mesh_raytrace_kernel (src/geometry_bvh.cu:646-676): host positions / directions n x 3, updated in place */
+/* M2 mesh_raytrace_kernel (src/geometry_bvh.cu:646-676): host positions / directions n x 3, updated in place.
+ *   Of the loaded meshes only one is traced: the one whose box the ray's line enters at the smallest slab distance below 100.
+ *   The distance's sign is not looked at: a box behind the origin counts, with its negative entry, and beats every box ahead of it (so a
+ *   ray that starts on a mesh only sees that mesh). Within that mesh the closest triangle at a distance t in [0, 100) is the hit:
+ *   position o + t d, direction replaced by the triangle's winding normal (b - a) x (c - a), normalised. Without a hit the ray comes back
+ *   as o + 100 d with its direction unchanged. A ray whose line enters no box within 100 comes back untouched; the mesh
+ *   pass of ngp_render shades such a pixel at the camera's position: alpha 1, depth 0, normal = the ray's direction. */
 NGP_API int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* directions);
 
 

@@ -46,7 +46,7 @@ NGP_DEV void cas(DistIdx& a, DistIdx& b) { // compare_and_swap with "<": sorts d
 
 // GeometryBvh4::ray_intersect_triangle (geometry_bvh.cu:61-109) == TriangleBvh4::ray_intersect (triangle_bvh.cu:150-193)
 NGP_DEV void bvh4_ray_intersect(const TriangleBvhNode* __restrict__ nodes, const Triangle* __restrict__ tris, f3 ro, f3 rd, int& out_idx, float& out_t) {
-	int stack[32];
+	int stack[BVH4_STACK_SIZE]; // deep enough for every BVH the builder lets through (ngp_kernels.h)
 	int sp = 0;
 	stack[sp++] = 0;
 	float mint = MAX_DIST;
@@ -74,7 +74,7 @@ NGP_DEV void bvh4_ray_intersect(const TriangleBvhNode* __restrict__ nodes, const
 			cas(ch[0], ch[2]); cas(ch[1], ch[3]); cas(ch[0], ch[1]); cas(ch[2], ch[3]); cas(ch[1], ch[2]);
 #pragma unroll
 			for (uint32_t i = 0; i < 4; ++i) {
-				if (ch[i].dist < mint && sp < 32) stack[sp++] = (int)ch[i].idx;
+				if (ch[i].dist < mint && sp < BVH4_STACK_SIZE) stack[sp++] = (int)ch[i].idx;
 			}
 		}
 	}
@@ -83,6 +83,12 @@ NGP_DEV void bvh4_ray_intersect(const TriangleBvhNode* __restrict__ nodes, const
 }
 
 // mesh_raytrace_kernel body (geometry_bvh.cu:646-676) + GeometryBvh4::ray_intersect leaf scan (:166-200)
+// Kept as the reference has them (contract: ngp_trace_mesh_rays in include/ngp_hip.h):
+//  - only the mesh whose box has the smallest slab entry below MAX_DIST is traced. The entry's sign is not looked at, so a box
+//    behind the origin (a negative entry) beats every box ahead: a shadow ray, which starts on its own mesh, only ever sees that mesh;
+//  - a ray whose line enters no box within MAX_DIST is left untouched. render_mesh_fused then finds its position, the camera's,
+//    inside the scene box and shades the pixel with alpha 1, depth 0 and N = the ray's direction (NdotV = -1: the ambient term alone);
+//  - a traced ray that hits nothing ends at pos + MAX_DIST * dir, its direction unchanged.
 NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
 	float mint = MAX_DIST;
 	int mesh_idx = -1;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bvh4_build.h"
+
 namespace ngp {
 
 constexpr uint32_t NERF_GRIDSIZE = 128;
@@ -196,14 +198,7 @@ struct ProbeParams {
 constexpr int32_t PROBE_RAY_LIST = 4;
 
 // ---- geometry mode (meshes)
-struct Triangle { // triangle.cuh:163 -- 36 B
-	float a[3], b[3], c[3];
-};
-struct TriangleBvhNode { // triangle_bvh.cuh:28-32 -- 32 B
-	float bmin[3], bmax[3];
-	int left_idx; // negative: leaf, triangles [-left_idx-1, -right_idx-1)
-	int right_idx;
-};
+// Triangle, TriangleBvhNode, BVH4_STACK_SIZE, BVH4_MAX_DEPTH: bvh4_build.h (plain C++, shared with the host-only builder check)
 struct MeshRef {
 	const TriangleBvhNode* nodes;
 	const Triangle* tris;
