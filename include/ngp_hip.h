@@ -407,6 +407,70 @@ NGP_API int ngp_irradiance_rays(ngp_ctx* ctx, uint32_t n, const float* positions
 NGP_API int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc,
                                   float* out /* n x 4 */);
 
+/* --- SH9 irradiance volumes: the incident radiance around a point, traced once over the whole sphere with the meshes occluding and kept
+ * as nine spherical-harmonic coefficients per channel; E(n) for ANY normal is read back from them, and a lattice of such probes gives
+ * E(p, n) inside a box for 8 probe reads where ngp_irradiance_traced traces K rays. This project's own contract (no counterpart in the
+ * reference). Models, render box and device as for ngp_trace_nerf_rays: base.json's heads and the Frequency architecture, the inflated
+ * mesh-scene box while meshes are loaded, the context's primary device only.
+ *
+ * Directions: K = n_u n_v world-space directions, the same for every probe, ray k = u + n_u v: a = (u + .5) / n_u, b = (v + .5) / n_v,
+ *   z = 1 - 2 a, phi = 2 pi b, w_k = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), normalised. The strata have equal area: a ray stands
+ *   for 4 pi / K. Origin = the probe position itself (no offset, no normal); t_min = 0; t_max = the closest triangle hit over all loaded
+ *   meshes with occlude_by_meshes (ngp_irradiance_rays' rule), +inf otherwise.
+ * Basis: the nine real SH of degree <= 2 in the order, signs and constants of the network's SH direction encoding: Y_0 = 0.28209479;
+ *   Y_1..3 = -0.48860251 y, 0.48860251 z, -0.48860251 x; Y_4..8 = 1.09254843 xy, -1.09254843 yz, 0.94617470 z^2 - 0.31539157,
+ *   -1.09254843 xz, 0.54627422 (x^2 - y^2).
+ * Probe record: 28 floats. c[3 m + ch] = (4 pi / K) sum_k L_ch(w_k) Y_m(w_k), m = 0..8, ch = r, g, b, with L the linear premultiplied rgb
+ *   of ngp_trace_nerf_rays (a blocked ray contributes what lies in front of its hit; a mesh adds no radiance of its own). Float 27 = w, the
+ *   fraction of the K rays that no mesh blocks. The sum runs in a fixed order (one wave per probe, lane-strided, then a butterfly; no
+ *   atomics): a record is bit-identical from run to run and for any split of the probes over calls or chunks.
+ * Evaluation: E(n) = sum_m A_m c_m Y_m(n^), n^ = n / |n|, A = pi (m = 0), 2 pi / 3 (m = 1..3), pi / 4 (m = 4..8): the clamped-cosine
+ *   convolution. There is NO clamp: nine coefficients cannot hold a sharp radiance, and E can ring slightly negative on the far side of a
+ *   bright lobe.
+ * Quadrature bias: the midpoint rule in z is not exact for band-limited radiance; its bias falls as 1 / n_u^2. Largest relative error of
+ *   E for a random radiance of degree <= 2 (float64): 5.1 % at 8 x 8, 1.29 % at 16 x 16, 0.081 % at 64 x 64, 0.020 % at 128 x 128. A
+ *   constant radiance L gives c_0 exactly and a small c_6 = -0.0155 L / 0.2821 at 16 x 16.
+ * Limits: n_u, n_v >= 1; K <= 2^21 (a probe never spans a tracer chunk); probes * K <= 2^28 ("too large").
+ * Refusals, each with a message: a host-only context ("no HIP device"), no model, an unsupported head, a non-finite position, a zero or
+ *   non-finite normal, a bad descriptor. */
+typedef struct ngp_irradiance_sh_desc {
+	uint32_t n_u, n_v;        /* K = n_u * n_v directions per probe */
+	float min_transmittance;  /* as in ngp_trace_nerf_rays */
+	int32_t occlude_by_meshes;
+} ngp_irradiance_sh_desc;
+/* a stage entry for tests: the sphere rays of n probes. origins_out / directions_out n K x 3, t_max_out n K; needs no model */
+NGP_API int ngp_irradiance_sphere_rays(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_sh_desc* desc, float* origins_out,
+                                       float* directions_out, float* t_max_out);
+/* the records of n probes at the caller's positions. rays_rgba_out (the test stage): every ray's radiance as traced */
+NGP_API int ngp_irradiance_sh_traced(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_sh_desc* desc, float* sh_out /* n x 28 */,
+                                     float* rays_rgba_out /* nullable, n K x 4 */);
+/* E(n) of n records at n normals (normalised here): plain host code in double precision, no context or device. Returns 0, -1 for a zero
+ * or non-finite normal (nothing is written from that record on), -2 for a null argument */
+NGP_API int ngp_irradiance_sh_eval(uint32_t n, const float* sh /* n x 28 */, const float* normals /* n x 3 */, float* rgb_out /* n x 3 */);
+
+/* The volume: res[0] x res[1] x res[2] probes over the box [aabb_min, aabb_max]; probe (i, j, k) sits at
+ *   aabb_min + (i / (res[0] - 1), j / (res[1] - 1), k / (res[2] - 1)) (aabb_max - aabb_min), formed in double precision from the descriptor's
+ *   floats and rounded to float; an axis of resolution 1 puts its probes at that axis's box centre (fraction 0.5) and takes no part in
+ *   interpolation. Linear index g = i + res[0] (j + res[1] k). res >= 1 per axis; the box and its extent max - min finite (in float), min < max on every axis whose res > 1.
+ * Lookup at (p, n), per axis: s = clamp((p - min) / (max - min), 0, 1) (r - 1), i0 = min(floor(s), r - 2) (0 when r = 1), f = s - i0;
+ *   trilinear weights over the up to 8 corner probes. A probe with w = 0 is dead (every ray blocked: where a probe inside a closed mesh
+ *   ends up) and is skipped; W = the sum of the live corners' weights; c~ = sum live weight c / W, or 0 when W = 0;
+ *   out = (E_rgb(c~, n), W).
+ * Lifetime: the volume is data. It lives on the primary device until it is replaced or cleared; it is NEVER recomputed behind the
+ *   caller's back when the model or the meshes change, and it is not stored in snapshots (ngp_get / ngp_set carry it to and from files).
+ * Further refusals: a lookup or a get without a volume ("no irradiance volume"), non-finite values given to ngp_set_irradiance_volume. */
+typedef struct ngp_irradiance_volume_desc {
+	uint32_t res[3];
+	float aabb_min[3], aabb_max[3];
+	ngp_irradiance_sh_desc sh;
+} ngp_irradiance_volume_desc;
+NGP_API int ngp_compute_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc); /* traced; kept on the primary device */
+NGP_API int ngp_get_irradiance_volume(ngp_ctx* ctx, ngp_irradiance_volume_desc* desc_out, float* sh_out /* nullable, probes x 28 */);
+/* a caller's own records, e.g. reloaded from a file; desc->sh is kept as given and not looked at */
+NGP_API int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh /* probes x 28 */);
+NGP_API int ngp_clear_irradiance_volume(ngp_ctx* ctx);
+NGP_API int ngp_irradiance_volume_at(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const float* normals /* n x 3 */, float* out /* n x 4 */);
+
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),
  * Testbed::train_nerf / train_nerf_step (src/testbed_nerf.cu:2949-3431), training_prep_nerf (:3432-3446). The default

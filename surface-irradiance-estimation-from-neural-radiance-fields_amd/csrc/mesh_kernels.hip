@@ -5,6 +5,7 @@
 // Primary hit, sun shadow ray and BRDF stay in registers; the only traffic is BVH nodes / triangles (cache resident)
 // and one frame/depth write per pixel. Software BVH4 traversal replaces OptiX (north_star: no OptiX).
 #include "render_common.h"
+#include "sh9.h"
 
 namespace ngp {
 
@@ -443,6 +444,157 @@ void launch_irradiance_reduce(uint32_t K, uint64_t r0, uint32_t n, const float4*
 	if (!n) return;
 	const uint64_t n_pts = (r0 + n - 1) / K - r0 / K + 1; // points the chunk touches
 	hipLaunchKernelGGL(irradiance_reduce_kernel, dim3((unsigned)((n_pts + 3) / 4)), dim3(256), 0, stream, K, (unsigned long long)r0, n, rgba, t, part, out);
+}
+
+
+// ---- SH9 irradiance volumes (ngp_irradiance_sphere_rays, ngp_irradiance_sh_traced, ngp_irradiance_volume_at; contract in
+// include/ngp_hip.h, basis in sh9.h). One sphere of rays per probe through the ray-list tracer, projected onto nine coefficients per
+// channel; a lookup blends the up to 8 probes around a point and evaluates the clamped-cosine convolution at the normal.
+
+// direction k = u + n_u v of the sphere, the same for every probe: the centre of an equal-area stratum, z = 1 - 2 a, phi = 2 pi b with
+// (a, b) = ((u + .5) / n_u, (v + .5) / n_v). sqrt(1 - z^2) is formed as 2 sqrt(a (1 - a)), which loses nothing near the poles, and the
+// azimuth's sine and cosine from 2 b in half turns (no rounded 2 pi b). The generator and the reduction both call this.
+NGP_DEV f3 sphere_dir(uint32_t k, uint32_t n_u, uint32_t n_v) {
+	const uint32_t u = k % n_u, v = k / n_u;
+	const float a = ((float)u + 0.5f) / (float)n_u, b = ((float)v + 0.5f) / (float)n_v;
+	const float s = 2.0f * sqrtf(a * (1.0f - a));
+	float sn, cs;
+	sincospif(2.0f * b, &sn, &cs);
+	return normalize3(mk3(s * cs, s * sn, 1.0f - 2.0f * a));
+}
+
+// the n rays of a chunk of whole probes: ray i is direction i % K of the chunk's probe i / K; origin = the probe's position, t = (0, the
+// closest triangle hit over all meshes as in irradiance_rays_kernel, +inf without one). positions holds the chunk's probes.
+__global__ void irradiance_sphere_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
+                                              float* __restrict__ o_out, float* __restrict__ d_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
+	const f3 dir = sphere_dir(k, n_u, n_v);
+	const f3 org = ld3(positions + 3 * (size_t)pl);
+	float t_max = __builtin_huge_valf();
+	if (occlude) {
+		for (uint32_t m = 0; m < S.n_meshes; ++m) {
+			int idx;
+			float t;
+			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
+			if (idx > -1 && t < t_max) t_max = t;
+		}
+	}
+	o_out[3 * (size_t)i] = org.x; o_out[3 * (size_t)i + 1] = org.y; o_out[3 * (size_t)i + 2] = org.z;
+	d_out[3 * (size_t)i] = dir.x; d_out[3 * (size_t)i + 1] = dir.y; d_out[3 * (size_t)i + 2] = dir.z;
+	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// one wave per probe, four per workgroup: c[3 m + ch] = (4 pi / K) sum_k L_ch(w_k) Y_m(w_k) over the probe's K rays (rgba, t: the chunk's
+// rays, probe p's at p K on), lane-strided with w_k recomputed from k (no direction array is read: 24 B a ray), then a butterfly in a fixed
+// order; no atomics, so a probe's record does not depend on the run or on which other probes the launch carries. Lane 0 writes the
+// record: 27 coefficients and w = unblocked / K, as 7 float4 at out[7 p].
+__global__ void irradiance_sh_reduce_kernel(uint32_t n_u, uint32_t n_v, uint32_t n_probes, const float4* __restrict__ rgba, const float2* __restrict__ t,
+                                            float4* __restrict__ out) {
+	const uint32_t p = (blockIdx.x * blockDim.x + threadIdx.x) / 64u;
+	if (p >= n_probes) return; // (wave-uniform)
+	const uint32_t lane = threadIdx.x & 63u, K = n_u * n_v;
+	const size_t base = (size_t)p * K;
+	float acc[27];
+#pragma unroll
+	for (int j = 0; j < 27; ++j) acc[j] = 0.f;
+	uint32_t c = 0;
+	for (uint32_t k = lane; k < K; k += 64u) {
+		const float4 L = rgba[base + k];
+		const f3 w = sphere_dir(k, n_u, n_v);
+		float Y[9];
+		sh9_basis(w.x, w.y, w.z, Y);
+#pragma unroll
+		for (int m = 0; m < 9; ++m) {
+			acc[3 * m] += L.x * Y[m];
+			acc[3 * m + 1] += L.y * Y[m];
+			acc[3 * m + 2] += L.z * Y[m];
+		}
+		c += t[base + k].y == __builtin_huge_valf() ? 1u : 0u;
+	}
+#pragma unroll
+	for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+		for (int j = 0; j < 27; ++j) acc[j] += __shfl_xor(acc[j], s);
+		c += __shfl_xor(c, s);
+	}
+	if (lane != 0) return;
+	const float scale = 4.0f * 3.14159265358979323846f / (float)K;
+#pragma unroll
+	for (int j = 0; j < 27; ++j) acc[j] *= scale;
+	float4* o = out + 7 * (size_t)p;
+#pragma unroll
+	for (int q = 0; q < 6; ++q) o[q] = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+	o[6] = make_float4(acc[24], acc[25], acc[26], (float)((double)c / (double)K));
+}
+
+// cell and weight of a coordinate on an axis of r probes spanning [lo, hi]: s = clamp((x - lo) / (hi - lo), 0, 1) (r - 1),
+// i0 = min(floor(s), r - 2), f = s - i0; an axis of one probe takes no part (i0 = 0, f = 0)
+NGP_DEV void volume_axis(float x, float lo, float hi, uint32_t r, uint32_t& i0, float& f) {
+	i0 = 0u;
+	f = 0.0f;
+	if (r < 2u) return;
+	const float xc = fminf(fmaxf(x, lo), hi); // (inside the box first: x - lo cannot overflow where hi - lo, which the host checks, does not)
+	const float s = saturate((xc - lo) / (hi - lo)) * (float)(r - 1u);
+	const float fl = fminf(__builtin_floorf(s), (float)(r - 2u));
+	i0 = (uint32_t)fl;
+	f = s - fl;
+}
+
+// one thread per point: the trilinear blend of the live probes (w != 0) among the up to 8 around it, renormalised by their weight W, and
+// E(n^) of the blended coefficients; out = (E rgb, W), zeros where every corner is dead. A probe is 7 float4 (112 B, 16-B aligned).
+__global__ void irradiance_volume_lookup_kernel(const IrradianceVolume V, uint32_t n, const float* __restrict__ positions, const float* __restrict__ normals,
+                                                float4* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const f3 p = ld3(positions + 3 * (size_t)i);
+	const f3 nh = normalize3(ld3(normals + 3 * (size_t)i));
+	uint32_t i0[3];
+	float f[3];
+	volume_axis(p.x, V.lo[0], V.hi[0], V.res[0], i0[0], f[0]);
+	volume_axis(p.y, V.lo[1], V.hi[1], V.res[1], i0[1], f[1]);
+	volume_axis(p.z, V.lo[2], V.hi[2], V.res[2], i0[2], f[2]);
+	float c[28];
+#pragma unroll
+	for (int j = 0; j < 28; ++j) c[j] = 0.f;
+	float W = 0.f;
+#pragma unroll
+	for (uint32_t corner = 0; corner < 8u; ++corner) {
+		const uint32_t dx = corner & 1u, dy = (corner >> 1) & 1u, dz = corner >> 2;
+		const float wgt = (dx ? f[0] : 1.0f - f[0]) * (dy ? f[1] : 1.0f - f[1]) * (dz ? f[2] : 1.0f - f[2]);
+		if (wgt == 0.0f) continue; // (also every second probe of an axis of one: its index would lie outside the lattice)
+		const size_t g = (i0[0] + dx) + (size_t)V.res[0] * ((i0[1] + dy) + (size_t)V.res[1] * (i0[2] + dz));
+		const float4* rec = V.sh + 7 * g;
+		const float4 last = rec[6];
+		if (last.w == 0.0f) continue; // a dead probe: every ray blocked
+#pragma unroll
+		for (int q = 0; q < 6; ++q) {
+			const float4 x = rec[q];
+			c[4 * q] += wgt * x.x; c[4 * q + 1] += wgt * x.y; c[4 * q + 2] += wgt * x.z; c[4 * q + 3] += wgt * x.w;
+		}
+		c[24] += wgt * last.x; c[25] += wgt * last.y; c[26] += wgt * last.z;
+		W += wgt;
+	}
+	float E[3] = {0.f, 0.f, 0.f};
+	if (W > 0.0f) {
+		const float inv = 1.0f / W;
+#pragma unroll
+		for (int j = 0; j < 27; ++j) c[j] *= inv;
+		sh9_irradiance(c, nh.x, nh.y, nh.z, E);
+	}
+	out[i] = make_float4(E[0], E[1], E[2], W);
+}
+
+void launch_irradiance_sphere_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, float* o, float* d, float2* t,
+                                   hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_sphere_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, o, d, t);
+}
+void launch_irradiance_sh_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, const float4* rgba, const float2* t, float4* out, hipStream_t stream) {
+	if (n_probes) hipLaunchKernelGGL(irradiance_sh_reduce_kernel, dim3((n_probes + 3) / 4), dim3(256), 0, stream, n_u, n_v, n_probes, rgba, t, out);
+}
+void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_volume_lookup_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, V, n, positions, normals, out);
 }
 
 } // namespace ngp

@@ -152,6 +152,10 @@ void launch_ray_list_prep(const ModelParams& M, uint32_t n, const float* o, floa
 void launch_irradiance_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, float offset, uint64_t r0, uint32_t n, const float* positions,
                             const float* normals, float* o, float* d, float2* t, hipStream_t stream);
 void launch_irradiance_reduce(uint32_t K, uint64_t r0, uint32_t n, const float4* rgba, const float2* t, float4* part, float4* out, hipStream_t stream);
+void launch_irradiance_sphere_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, float* o, float* d, float2* t,
+                                   hipStream_t stream);
+void launch_irradiance_sh_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, const float4* rgba, const float2* t, float4* out, hipStream_t stream);
+void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
 // scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.
@@ -325,6 +329,10 @@ struct ngp_ctx {
 	ngp::DevArray<float4> d_irradiance;
 	uint32_t env_n_theta = 0, env_n_phi = 0;
 	ngp::ProbeParams env_probe{}; // what was traced: mode, shell position(s), grid
+
+	// ---- the SH9 irradiance volume (ngp_compute_irradiance_volume / ngp_set_irradiance_volume): data, never recomputed behind the caller
+	ngp::DevArray<float4> d_sh_volume; // 7 float4 a probe, probe-major
+	ngp_irradiance_volume_desc sh_volume_desc{};
 
 	// ---- environment map behind the NeRF (m_envmap.inference_view(), testbed.h:1297-1316)
 	ngp::DevArray<float4> d_bg_envmap;

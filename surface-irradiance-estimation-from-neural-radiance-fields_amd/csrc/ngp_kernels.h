@@ -221,5 +221,10 @@ struct IrradianceMap { // E(n) tabulated at the probe texture's texel directions
 	uint32_t grid_x, grid_y;  // ShadeGridEnvMap: the probes around the direction of (surface point - center) are blended
 	float center[3];
 };
+struct IrradianceVolume { // a lattice of SH9 probes (sh9.h): probe g = i + res[0] * (j + res[1] * k) is the 7 float4 from sh[7 g] on
+	const float4* sh;
+	uint32_t res[3];
+	float lo[3], hi[3];
+};
 
 } // namespace ngp

@@ -3,6 +3,7 @@
 // .obj reader that replaces the vendored tinyobjloader wrapper (src/tinyobj_loader_wrapper.cu).
 #include "ngp_host.h"
 #include "bvh4_build.h"
+#include "sh9.h"
 
 #include <algorithm>
 #include <cmath>
@@ -538,6 +539,96 @@ void generate_irradiance_rays(ngp_ctx* ctx, const ngp_irradiance_trace_desc* d, 
 	ngp::launch_irradiance_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, d->offset, r0, m, pts.get(), pts.get() + pts.size() / 2, o, dir, t,
 	                            ctx->stream);
 }
+
+// ---- SH9 irradiance volumes (contract: include/ngp_hip.h)
+constexpr uint32_t SH_FLOAT4 = 7; // a record: 28 floats
+
+// the descriptor's checks shared by the SH entries, for n probes; returns K
+uint32_t check_sh_desc(uint64_t n, const ngp_irradiance_sh_desc* d) {
+	if (!d) throw std::runtime_error("null argument");
+	if (d->n_u == 0 || d->n_v == 0) throw std::runtime_error("invalid irradiance descriptor: n_u and n_v must be at least 1");
+	const uint64_t K = (uint64_t)d->n_u * d->n_v;
+	if (K > RAY_CHUNK) throw std::runtime_error("irradiance request too large: n_u * n_v > 2^21 rays per probe");
+	if (n > MAX_TRACED_RAYS || K * n > MAX_TRACED_RAYS) throw std::runtime_error("irradiance request too large: probes * n_u * n_v > 2^28 rays");
+	return (uint32_t)K;
+}
+void check_positions(uint32_t n, const float* positions) {
+	if (n && !positions) throw std::runtime_error("null argument");
+	for (uint32_t i = 0; i < n; ++i)
+		if (!finite3(positions + 3 * (size_t)i)) throw std::runtime_error("position " + std::to_string(i) + " is not finite");
+}
+
+// resolution and box of a volume; returns the number of probes (at most 2^28)
+uint64_t check_volume_lattice(const ngp_irradiance_volume_desc* d) {
+	if (!d) throw std::runtime_error("null argument");
+	uint64_t probes = 1;
+	for (int a = 0; a < 3; ++a) {
+		if (d->res[a] == 0) throw std::runtime_error("invalid irradiance volume descriptor: the resolution must be at least 1 on every axis");
+		if (!std::isfinite(d->aabb_min[a]) || !std::isfinite(d->aabb_max[a])) throw std::runtime_error("invalid irradiance volume descriptor: the box is not finite");
+		if (!std::isfinite(d->aabb_max[a] - d->aabb_min[a])) throw std::runtime_error("invalid irradiance volume descriptor: the box's extent is not finite");
+		if (d->res[a] > 1 && !(d->aabb_min[a] < d->aabb_max[a])) throw std::runtime_error("invalid irradiance volume descriptor: the box needs min < max on every axis with more than one probe");
+		probes *= d->res[a]; // (each factor below 2^32 and the product checked after every step: no overflow)
+		if (probes > MAX_TRACED_RAYS) throw std::runtime_error("irradiance volume too large: more than 2^28 probes");
+	}
+	return probes;
+}
+
+// probe g = i + rx (j + ry k) at min + fraction (max - min), in double from the descriptor's floats, rounded to float
+std::vector<float> volume_positions(const ngp_irradiance_volume_desc* d, uint64_t probes) {
+	std::vector<float> p(3 * (size_t)probes);
+	size_t g = 0;
+	for (uint32_t k = 0; k < d->res[2]; ++k)
+		for (uint32_t j = 0; j < d->res[1]; ++j)
+			for (uint32_t i = 0; i < d->res[0]; ++i, ++g) {
+				const uint32_t ijk[3] = {i, j, k};
+				for (int a = 0; a < 3; ++a) {
+					const double lo = d->aabb_min[a], hi = d->aabb_max[a];
+					const double frac = d->res[a] > 1 ? (double)ijk[a] / (double)(d->res[a] - 1) : 0.5;
+					p[3 * g + a] = (float)(lo + frac * (hi - lo));
+				}
+			}
+	return p;
+}
+
+// the records of n probes at host positions: sphere rays -> the ray-list tracer -> the projection, in chunks of whole probes. Each chunk's
+// records go to h_sh (host, n x 28) and / or d_sh (device, 7 n float4), its rays' radiance to h_rays (host, n K x 4); all nullable.
+void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, float* h_sh, float4* d_sh, float* h_rays) {
+	const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+	const uint32_t cap_pts = (uint32_t)std::min<uint64_t>(n, cap);
+	DevArray<float> pts(3 * (size_t)cap_pts), o(3 * (size_t)cap), dir(3 * (size_t)cap);
+	DevArray<float2> t(cap);
+	DevArray<float4> rgba(cap), rec(SH_FLOAT4 * (size_t)cap_pts);
+	RayListTrace tr(ctx, (uint64_t)n * K, d->min_transmittance);
+	for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) { // (K <= RAY_CHUNK: whole probes)
+		const uint64_t p0 = r0 / K;
+		const uint32_t np = m / K;
+		upload(ctx, pts.get(), positions + 3 * p0, (size_t)np * 3 * sizeof(float));
+		ngp::launch_irradiance_sphere_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts.get(), o.get(), dir.get(), t.get(), ctx->stream);
+		ngp::launch_ray_list_prep(tr.model(), m, o.get(), dir.get(), t.get(), false, ctx->stream);
+		ngp::ProbeParams P{};
+		P.ray_o = o.get();
+		P.ray_d = dir.get();
+		P.ray_t = t.get();
+		P.ray_rgba = rgba.get();
+		tr.trace(P, m);
+		ngp::launch_irradiance_sh_reduce(d->n_u, d->n_v, np, rgba.get(), t.get(), rec.get(), ctx->stream);
+		if (d_sh) NGP_HIP_CHECK(hipMemcpyAsync(d_sh + SH_FLOAT4 * p0, rec.get(), (size_t)np * SH_FLOAT4 * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+		if (h_rays) download(ctx, h_rays + 4 * r0, rgba.get(), (size_t)m * sizeof(float4));
+		if (h_sh) download(ctx, h_sh + 4 * SH_FLOAT4 * p0, rec.get(), (size_t)np * SH_FLOAT4 * sizeof(float4));
+	});
+	tr.finish(); // (synchronises the stream: the chunk buffers may go)
+}
+
+ngp::IrradianceVolume sh_volume_of(const ngp_ctx* ctx) {
+	ngp::IrradianceVolume V{};
+	V.sh = ctx->d_sh_volume.get();
+	for (int a = 0; a < 3; ++a) {
+		V.res[a] = ctx->sh_volume_desc.res[a];
+		V.lo[a] = ctx->sh_volume_desc.aabb_min[a];
+		V.hi[a] = ctx->sh_volume_desc.aabb_max[a];
+	}
+	return V;
+}
 } // namespace
 
 extern "C" {
@@ -632,6 +723,120 @@ int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positions, cons
 		});
 		tr.finish();
 	});
+}
+
+int ngp_irradiance_sphere_rays(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* desc, float* origins_out, float* directions_out,
+                               float* t_max_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		const uint32_t K = check_sh_desc(n, desc);
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!origins_out || !directions_out || !t_max_out) throw std::runtime_error("null argument");
+		const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+		DevArray<float> pts(3 * (size_t)std::min<uint64_t>(n, cap)), o(3 * (size_t)cap), dir(3 * (size_t)cap);
+		DevArray<float2> t(cap);
+		std::vector<float2> t_host(cap);
+		for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) {
+			upload(ctx, pts.get(), positions + 3 * (r0 / K), (size_t)(m / K) * 3 * sizeof(float));
+			ngp::launch_irradiance_sphere_rays(ctx->mesh_scene, desc->occlude_by_meshes != 0, desc->n_u, desc->n_v, m, pts.get(), o.get(), dir.get(), t.get(), ctx->stream);
+			download(ctx, origins_out + 3 * r0, o.get(), (size_t)m * 3 * sizeof(float));
+			download(ctx, directions_out + 3 * r0, dir.get(), (size_t)m * 3 * sizeof(float));
+			download(ctx, t_host.data(), t.get(), (size_t)m * sizeof(float2));
+			for (uint32_t i = 0; i < m; ++i) t_max_out[r0 + i] = t_host[i].y;
+		});
+		NGP_HIP_CHECK(hipGetLastError());
+	});
+}
+
+int ngp_irradiance_sh_traced(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* desc, float* sh_out, float* rays_rgba_out) {
+	return guarded(ctx, [&] {
+		require_probe_model(ctx, "SH irradiance probes");
+		const uint32_t K = check_sh_desc(n, desc);
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!sh_out) throw std::runtime_error("null argument");
+		trace_sh_probes(ctx, n, positions, desc, K, sh_out, nullptr, rays_rgba_out);
+	});
+}
+
+int ngp_compute_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc) {
+	return guarded(ctx, [&] {
+		require_probe_model(ctx, "SH irradiance probes");
+		const uint64_t probes = check_volume_lattice(desc);
+		const uint32_t K = check_sh_desc(probes, &desc->sh);
+		const std::vector<float> positions = volume_positions(desc, probes);
+		DevArray<float4> sh(SH_FLOAT4 * (size_t)probes);
+		trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, sh.get(), nullptr);
+		ctx->d_sh_volume = std::move(sh); // (the previous volume stays in place when the trace throws)
+		ctx->sh_volume_desc = *desc;
+	});
+}
+
+int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		const uint64_t probes = check_volume_lattice(desc);
+		if (!sh) throw std::runtime_error("null argument");
+		for (size_t i = 0; i < 4 * SH_FLOAT4 * (size_t)probes; ++i)
+			if (!std::isfinite(sh[i])) throw std::runtime_error("irradiance volume: value " + std::to_string(i % 28) + " of probe " + std::to_string(i / 28) + " is not finite");
+		DevArray<float4> d;
+		d.upload(reinterpret_cast<const float4*>(sh), SH_FLOAT4 * (size_t)probes);
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old records)
+		ctx->d_sh_volume = std::move(d);
+		ctx->sh_volume_desc = *desc;
+	});
+}
+
+int ngp_get_irradiance_volume(ngp_ctx* ctx, ngp_irradiance_volume_desc* desc_out, float* sh_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+		if (desc_out) *desc_out = ctx->sh_volume_desc;
+		if (sh_out) download(ctx, sh_out, ctx->d_sh_volume.get(), ctx->d_sh_volume.size() * sizeof(float4));
+	});
+}
+
+int ngp_clear_irradiance_volume(ngp_ctx* ctx) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+		ctx->d_sh_volume.reset();
+		ctx->sh_volume_desc = ngp_irradiance_volume_desc{};
+	});
+}
+
+int ngp_irradiance_volume_at(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, float* out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+		if (n == 0) return;
+		if (!positions || !normals || !out) throw std::runtime_error("null argument");
+		check_positions(n, positions);
+		for (uint32_t i = 0; i < n; ++i)
+			if (!finite3(normals + 3 * (size_t)i) || !nonzero3(normals + 3 * (size_t)i)) throw std::runtime_error("normal " + std::to_string(i) + " is zero or not finite");
+		DevArray<float> d_p(3 * (size_t)n), d_n(3 * (size_t)n);
+		DevArray<float4> d_o(n);
+		upload(ctx, d_p.get(), positions, (size_t)n * 3 * sizeof(float));
+		upload(ctx, d_n.get(), normals, (size_t)n * 3 * sizeof(float));
+		ngp::launch_irradiance_volume_lookup(sh_volume_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
+		download(ctx, out, d_o.get(), (size_t)n * sizeof(float4));
+		NGP_HIP_CHECK(hipGetLastError());
+	});
+}
+
+int ngp_irradiance_sh_eval(uint32_t n, const float* sh, const float* normals, float* rgb_out) {
+	if (n == 0) return 0;
+	if (!sh || !normals || !rgb_out) return -2;
+	for (uint32_t i = 0; i < n; ++i) {
+		const float* nr = normals + 3 * (size_t)i;
+		if (!finite3(nr) || !nonzero3(nr)) return -1;
+		const double x = nr[0], y = nr[1], z = nr[2], len = std::sqrt(x * x + y * y + z * z);
+		double E[3];
+		ngp::sh9_irradiance(sh + 28 * (size_t)i, x / len, y / len, z / len, E);
+		for (int c = 0; c < 3; ++c) rgb_out[3 * (size_t)i + c] = (float)E[c];
+	}
+	return 0;
 }
 
 } // extern "C"

@@ -201,6 +201,51 @@ PYBIND11_MODULE(pyngp, m) {
 			return a;
 		}, py::arg("positions"), py::arg("normals"), py::arg("n_u") = 16, py::arg("n_v") = 16, py::arg("offset") = 1e-4f, py::arg("occlude_by_meshes") = true,
 		   "This project's own: the irradiance traced at surface points through the NeRF, (n, 4) = rgb, fraction of rays no mesh blocks")
+		.def("compute_irradiance_sh_at_points", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions, uint32_t n_u, uint32_t n_v,
+		                                           bool occlude_by_meshes) {
+			if (positions.ndim() != 2 || positions.shape(1) != 3) throw std::runtime_error("positions: (n, 3)");
+			const uint32_t n = (uint32_t)positions.shape(0);
+			std::vector<float> sh;
+			{
+				py::gil_scoped_release nogil;
+				sh = t.compute_irradiance_sh_at_points(positions.data(), n, n_u, n_v, occlude_by_meshes);
+			}
+			py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)28});
+			if (n) memcpy(a.mutable_data(), sh.data(), sh.size() * sizeof(float));
+			return a;
+		}, py::arg("positions"), py::arg("n_u") = 32, py::arg("n_v") = 32, py::arg("occlude_by_meshes") = true,
+		   "This project's own: SH9 irradiance probes traced at the points, (n, 28) = 9 coefficients x rgb, fraction of rays no mesh blocks")
+		.def("compute_irradiance_volume", [](Testbed& t, const std::array<uint32_t, 3>& res, py::object aabb, uint32_t n_u, uint32_t n_v, bool occlude_by_meshes) {
+			const std::vector<float> box = aabb6_arg(aabb);
+			std::vector<float> sh;
+			std::array<float, 6> used{};
+			{
+				py::gil_scoped_release nogil;
+				sh = t.compute_irradiance_volume(res, box.empty() ? nullptr : box.data(), n_u, n_v, occlude_by_meshes, used.data());
+			}
+			py::array_t<float> a({(py::ssize_t)res[2], (py::ssize_t)res[1], (py::ssize_t)res[0], (py::ssize_t)28});
+			if (!sh.empty()) memcpy(a.mutable_data(), sh.data(), sh.size() * sizeof(float));
+			py::dict d;
+			d["sh"] = a;
+			d["aabb"] = py::make_tuple(std::array<float, 3>{used[0], used[1], used[2]}, std::array<float, 3>{used[3], used[4], used[5]});
+			return d;
+		}, py::arg("resolution"), py::arg("aabb") = py::none(), py::arg("n_u") = 32, py::arg("n_v") = 32, py::arg("occlude_by_meshes") = true,
+		   "This project's own: a lattice of SH9 irradiance probes, traced and kept for irradiance_volume_lookup: {'sh': (rz, ry, rx, 28), 'aabb': (min, max)} "
+		   "(aabb: None = the render aabb, or (min, max))")
+		.def("irradiance_volume_lookup", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions,
+		                                    py::array_t<float, py::array::c_style | py::array::forcecast> normals) {
+			if (positions.ndim() != 2 || positions.shape(1) != 3 || normals.ndim() != 2 || normals.shape(1) != 3 || positions.shape(0) != normals.shape(0))
+				throw std::runtime_error("positions and normals: (n, 3) each");
+			const uint32_t n = (uint32_t)positions.shape(0);
+			std::vector<float> e;
+			{
+				py::gil_scoped_release nogil;
+				e = t.irradiance_volume_lookup(positions.data(), normals.data(), n);
+			}
+			py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)4});
+			if (n) memcpy(a.mutable_data(), e.data(), e.size() * sizeof(float));
+			return a;
+		}, py::arg("positions"), py::arg("normals"), "E(p, n) read from the irradiance volume: (n, 4) = rgb, weight of the live probes around the point")
 		.def("frame", &Testbed::frame, py::call_guard<py::gil_scoped_release>(), "Process a single frame: one training step when shall_train is set (headless, nothing is drawn).")
 		.def("train", &Testbed::train, py::call_guard<py::gil_scoped_release>(), "Perform a single training step with a specified batch size.")
 		.def("reset", &Testbed::reset_network, py::arg("reset_density_grid") = true, "Reset training.")

@@ -517,6 +517,33 @@ public:
 		check(ngp_irradiance_traced(m_ctx, n, positions, normals, &d, out.data()));
 		return out;
 	}
+	// SH9 irradiance volumes (include/ngp_hip.h): probe records traced at the caller's positions, n x 28
+	std::vector<float> compute_irradiance_sh_at_points(const float* positions, uint32_t n, uint32_t n_u = 32, uint32_t n_v = 32, bool occlude_by_meshes = true) {
+		const ngp_irradiance_sh_desc d{n_u, n_v, nerf.render_min_transmittance, occlude_by_meshes ? 1 : 0};
+		std::vector<float> out((size_t)n * 28);
+		check(ngp_irradiance_sh_traced(m_ctx, n, positions, &d, out.data(), nullptr));
+		return out;
+	}
+	// a lattice of res probes over aabb6 (nullptr: the render aabb), traced and kept in the context; returns the records, probes x 28 in
+	// index order i + rx (j + ry k), and the box in aabb6_out
+	std::vector<float> compute_irradiance_volume(const std::array<uint32_t, 3>& res, const float* aabb6 = nullptr, uint32_t n_u = 32, uint32_t n_v = 32,
+	                                             bool occlude_by_meshes = true, float* aabb6_out = nullptr) {
+		ngp_irradiance_volume_desc d{};
+		const float* box = aabb6 ? aabb6 : m_render_aabb.data();
+		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
+		d.sh = ngp_irradiance_sh_desc{n_u, n_v, nerf.render_min_transmittance, occlude_by_meshes ? 1 : 0};
+		check(ngp_compute_irradiance_volume(m_ctx, &d));
+		std::vector<float> out((size_t)res[0] * res[1] * res[2] * 28);
+		check(ngp_get_irradiance_volume(m_ctx, &d, out.data()));
+		if (aabb6_out) { memcpy(aabb6_out, d.aabb_min, 12); memcpy(aabb6_out + 3, d.aabb_max, 12); }
+		return out;
+	}
+	// E(p, n) read from the volume: n x 4 = rgb irradiance, weight of the live probes around the point
+	std::vector<float> irradiance_volume_lookup(const float* positions, const float* normals, uint32_t n) {
+		std::vector<float> out((size_t)n * 4);
+		check(ngp_irradiance_volume_at(m_ctx, n, positions, normals, out.data()));
+		return out;
+	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path
 	bool m_has_camera_end = false;

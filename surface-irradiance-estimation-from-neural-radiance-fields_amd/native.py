@@ -96,6 +96,14 @@ BVH_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left_idx", 
 TRIANGLE_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3), ("c", "<f4", 3)])
 
 
+class IrradianceShDesc(C.Structure):
+    _fields_ = [("n_u", C.c_uint32), ("n_v", C.c_uint32), ("min_transmittance", C.c_float), ("occlude_by_meshes", C.c_int32)]
+
+
+class IrradianceVolumeDesc(C.Structure):
+    _fields_ = [("res", C.c_uint32 * 3), ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("sh", IrradianceShDesc)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64), ("n_rays_alive_after_init", C.c_uint64), ("n_rays_hit", C.c_uint64), ("n_samples", C.c_uint64),
@@ -208,6 +216,14 @@ def load_library():
     L.ngp_trace_nerf_rays.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_float, vp, vp]
     L.ngp_irradiance_rays.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(IrradianceTraceDesc), vp, vp, vp]
     L.ngp_irradiance_traced.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(IrradianceTraceDesc), vp]
+    L.ngp_irradiance_sphere_rays.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), vp, vp, vp]
+    L.ngp_irradiance_sh_traced.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), vp, vp]
+    L.ngp_irradiance_sh_eval.argtypes = [C.c_uint32, vp, vp, vp]
+    L.ngp_compute_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc)]
+    L.ngp_get_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
+    L.ngp_set_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
+    L.ngp_clear_irradiance_volume.argtypes = [vp]
+    L.ngp_irradiance_volume_at.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -305,6 +321,19 @@ def make_opts(min_transmittance=0.01, background=(0.0, 0.0, 0.0, 1.0), exposure=
     o.depth_scale = depth_scale
     o.color_space = color_space
     return o
+
+
+def irradiance_sh_eval(sh, normals):
+    """E(n) of SH9 probe records (n, 28) at normals (n, 3), normalised by the library: (n, 3). Host code; no context, no device."""
+    sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 28)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if sh.shape[0] != nrm.shape[0]:
+        raise ValueError("records (n, 28) and normals (n, 3)")
+    out = np.zeros((sh.shape[0], 3), np.float32)
+    rc = load_library().ngp_irradiance_sh_eval(sh.shape[0], _p(sh), _p(nrm), _p(out))
+    if rc != 0:
+        raise RuntimeError("ngp_irradiance_sh_eval: " + ("a normal is zero or not finite" if rc == -1 else "null argument"))
+    return out
 
 
 class Context:
@@ -648,6 +677,75 @@ class Context:
         p, n, d = self._irradiance_args(positions, normals, n_u, n_v, offset, occlude_by_meshes, min_transmittance)
         out = np.zeros((p.shape[0], 4), np.float32)
         self._check(self.L.ngp_irradiance_traced(self.h, p.shape[0], _p(p), _p(n), C.byref(d), _p(out)))
+        return out
+
+    # ---------------------------------------------------------------- SH9 irradiance volumes (contract: include/ngp_hip.h)
+    @staticmethod
+    def _sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance):
+        d = IrradianceShDesc()
+        d.n_u, d.n_v, d.min_transmittance, d.occlude_by_meshes = n_u, n_v, min_transmittance, int(bool(occlude_by_meshes))
+        return d
+
+    @staticmethod
+    def _volume_desc(resolution, aabb, sh):
+        d = IrradianceVolumeDesc()
+        for i in range(3):
+            d.res[i], d.aabb_min[i], d.aabb_max[i] = resolution[i], aabb[0][i], aabb[1][i]
+        d.sh = sh
+        return d
+
+    def irradiance_sphere_rays(self, positions, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01):
+        """the sphere rays of the probes at `positions`: (origins (n, K, 3), directions (n, K, 3), t_max (n, K)), K = n_u n_v, k = u + n_u v"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        d = self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance)
+        k = int(n_u) * int(n_v)
+        o = np.zeros((p.shape[0], k, 3), np.float32)
+        dr = np.zeros((p.shape[0], k, 3), np.float32)
+        t = np.zeros((p.shape[0], k), np.float32)
+        self._check(self.L.ngp_irradiance_sphere_rays(self.h, p.shape[0], _p(p), C.byref(d), _p(o), _p(dr), _p(t)))
+        return o, dr, t
+
+    def irradiance_sh_traced(self, positions, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01, return_rays=False):
+        """SH9 probe records traced at `positions`: (n, 28); with return_rays also every ray's rgba as traced, (n, K, 4)"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        d = self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance)
+        sh = np.zeros((p.shape[0], 28), np.float32)
+        rays = np.zeros((p.shape[0], int(n_u) * int(n_v), 4), np.float32) if return_rays else None
+        self._check(self.L.ngp_irradiance_sh_traced(self.h, p.shape[0], _p(p), C.byref(d), _p(sh), _p(rays) if return_rays else None))
+        return (sh, rays) if return_rays else sh
+
+    def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01):
+        """trace a lattice of resolution = (rx, ry, rz) probes over aabb = (min, max); the volume stays on the device (get_irradiance_volume)"""
+        d = self._volume_desc(resolution, aabb, self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance))
+        self._check(self.L.ngp_compute_irradiance_volume(self.h, C.byref(d)))
+
+    def get_irradiance_volume(self):
+        """(desc, records (rz, ry, rx, 28))"""
+        d = IrradianceVolumeDesc()
+        self._check(self.L.ngp_get_irradiance_volume(self.h, C.byref(d), None))
+        sh = np.zeros((d.res[2], d.res[1], d.res[0], 28), np.float32)
+        self._check(self.L.ngp_get_irradiance_volume(self.h, C.byref(d), _p(sh)))
+        return d, sh
+
+    def set_irradiance_volume(self, sh, aabb, n_u=0, n_v=0, occlude_by_meshes=True, min_transmittance=0.01):
+        """a caller's own records (rz, ry, rx, 28) over aabb = (min, max); n_u ... only describe how they were made"""
+        sh = np.ascontiguousarray(sh, np.float32)
+        if sh.ndim != 4 or sh.shape[3] != 28:
+            raise ValueError("records: (rz, ry, rx, 28)")
+        d = self._volume_desc(sh.shape[2::-1], aabb, self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance))
+        self._check(self.L.ngp_set_irradiance_volume(self.h, C.byref(d), _p(sh)))
+
+    def clear_irradiance_volume(self):
+        self._check(self.L.ngp_clear_irradiance_volume(self.h))
+
+    def irradiance_volume_at(self, positions, normals):
+        """E(p, n) read from the volume: (n, 4) = rgb irradiance, weight of the live probes around the point"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != n.shape:
+            raise ValueError("positions and normals: n x 3 each")
+        out = np.zeros((p.shape[0], 4), np.float32)
+        self._check(self.L.ngp_irradiance_volume_at(self.h, p.shape[0], _p(p), _p(n), _p(out)))
         return out
 
     # ---------------------------------------------------------------- stages
