@@ -44,8 +44,17 @@ enum ngp_render_mode {
 	NGP_RENDER_NORMALS = 7,   /* ERenderMode::Normals (composite_kernel_nerf :688-693, shade_kernel_nerf :1379-1381): every sample's colour is the unit
 	                           * vector opposite to the density's gradient w.r.t. the position -- tcnn's input_gradient (src/testbed_nerf.cu:2106-2107):
 	                           * a backward pass through the density MLP and the grid encoding per sample; the pixel is (0.5 n + 0.5) alpha. Grid models. */
-	NGP_RENDER_SHADE_GRID_ENVMAP = 6 /* ERenderMode::ShadeGridEnvMap, the fork's default (testbed.h:880): meshes lit by the GRID of NeRF-derived
+	NGP_RENDER_SHADE_GRID_ENVMAP = 6, /* ERenderMode::ShadeGridEnvMap, the fork's default (testbed.h:880): meshes lit by the GRID of NeRF-derived
 	                           * irradiance probes (ngp_compute_envmap_grid), position-dependent */
+	NGP_RENDER_SHADE_IRRADIANCE_VOLUME = 8 /* this project's own: in Geometry mode every mesh pixel's ambient light is max(E(p, N), 0) / pi per channel, E the
+	                           * SH9 irradiance volume's estimate (ngp_irradiance_volume_at) at the hit point p for the shading normal N = the hit
+	                           * triangle's unit normal as the table modes use it, not face-forwarded. The clamp is there because nine coefficients
+	                           * ring: E can dip below zero on the far side of a bright lobe. Where every probe around p is dead (W = 0) the
+	                           * ambient light is 0. A hit point outside the volume's box is clamped onto it per axis (the lookup's rule). Sun,
+	                           * shadow ray, BRDF, depth, coverage, sharding and packing are those of the other shade modes; ambientcolor and up_dir
+	                           * are not used. Refused with meshes present and no volume ("needs ngp_compute_irradiance_volume or
+	                           * ngp_set_irradiance_volume first"), on a multi-device context too: its auxiliary devices keep replicas of the
+	                           * records, refreshed when the volume is computed, set or cleared. Without meshes, or in NGP_MODE_NERF, it is Shade */
 };
 
 /* ETestbedMode subset (common.h:35-43): Nerf, and the fork's Geometry mode (meshes + NeRF, depth composited) */
@@ -234,6 +243,8 @@ NGP_API int ngp_render_device(ngp_ctx* ctx, const ngp_camera* cam, const ngp_ren
 NGP_API uint32_t ngp_packed_tiles(int32_t width, int32_t height, uint32_t shard_index, uint32_t shard_count);
 /* counters + timings of the last ngp_render / ngp_render_device (synchronises the stream) */
 NGP_API int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out);
+/* duration of the mesh pass (render_mesh_fused) of the last frame's last sample, HIP events on its stream; refused when that frame had none */
+NGP_API int ngp_get_mesh_pass_ms(ngp_ctx* ctx, float* ms_out);
 /* per device of a multi-device context (0 = primary): the last frame's counters and timings of that device's share */
 NGP_API int ngp_get_device_render_stats(ngp_ctx* ctx, int device_index, ngp_render_stats* out);
 /* the same for the last n calls (oldest first; the context keeps 256), read once after a batch of asynchronous
@@ -456,7 +467,8 @@ NGP_API int ngp_irradiance_sh_eval(uint32_t n, const float* sh /* n x 28 */, con
  *   trilinear weights over the up to 8 corner probes. A probe with w = 0 is dead (every ray blocked: where a probe inside a closed mesh
  *   ends up) and is skipped; W = the sum of the live corners' weights; c~ = sum live weight c / W, or 0 when W = 0;
  *   out = (E_rgb(c~, n), W).
- * Lifetime: the volume is data. It lives on the primary device until it is replaced or cleared; it is NEVER recomputed behind the
+ * Lifetime: the volume is data. It lives on the primary device until it is replaced or cleared (get and the lookup read the primary; the
+ *   auxiliary devices of a multi-device context hold replicas for NGP_RENDER_SHADE_IRRADIANCE_VOLUME frames alone); it is NEVER recomputed behind the
  *   caller's back when the model or the meshes change, and it is not stored in snapshots (ngp_get / ngp_set carry it to and from files).
  * Further refusals: a lookup or a get without a volume ("no irradiance volume"), non-finite values given to ngp_set_irradiance_volume. */
 typedef struct ngp_irradiance_volume_desc {

@@ -7,6 +7,8 @@
 #include "render_common.h"
 #include "sh9.h"
 
+#include <type_traits>
+
 namespace ngp {
 
 constexpr float MAX_DIST = 100.0f; // geometry_bvh.cu:23
@@ -233,8 +235,63 @@ NGP_DEV f3 irradiance_lookup(const IrradianceMap& I, f3 pos, f3 N) {
 	           (w00 * e00.z + w10 * e10.z) + (w01 * e01.z + w11 * e11.z));
 }
 
-// render_geometry_mesh (src/testbed_geometry_training.cu:2202-2320), Shade mode, floor disabled, one thread per pixel
-__global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams P, const IrradianceMap I, const CameraParams C, float4* __restrict__ frame_buffer,
+// cell and weight of a coordinate on an axis of r probes spanning [lo, hi]: s = clamp((x - lo) / (hi - lo), 0, 1) (r - 1),
+// i0 = min(floor(s), r - 2), f = s - i0; an axis of one probe takes no part (i0 = 0, f = 0)
+NGP_DEV void volume_axis(float x, float lo, float hi, uint32_t r, uint32_t& i0, float& f) {
+	i0 = 0u;
+	f = 0.0f;
+	if (r < 2u) return;
+	const float xc = fminf(fmaxf(x, lo), hi); // (inside the box first: x - lo cannot overflow where hi - lo, which the host checks, does not)
+	const float s = saturate((xc - lo) / (hi - lo)) * (float)(r - 1u);
+	const float fl = fminf(__builtin_floorf(s), (float)(r - 2u));
+	i0 = (uint32_t)fl;
+	f = s - fl;
+}
+
+// the volume's estimate at (p, n^): the trilinear blend of the live probes (w != 0) among the up to 8 around p, renormalised by their weight
+// W, and E(n^) of the blended coefficients; E = 0 where every corner is dead (W = 0). A probe is 7 float4 (112 B, 16-B aligned). The one
+// definition: the lookup kernel and the mesh pass's ShadeIrradianceVolume ambient both call it.
+NGP_DEV void irradiance_volume_lookup(const IrradianceVolume& V, f3 p, f3 nh, float (&E)[3], float& W) {
+	uint32_t i0[3];
+	float f[3];
+	volume_axis(p.x, V.lo[0], V.hi[0], V.res[0], i0[0], f[0]);
+	volume_axis(p.y, V.lo[1], V.hi[1], V.res[1], i0[1], f[1]);
+	volume_axis(p.z, V.lo[2], V.hi[2], V.res[2], i0[2], f[2]);
+	float c[28];
+#pragma unroll
+	for (int j = 0; j < 28; ++j) c[j] = 0.f;
+	W = 0.f;
+#pragma unroll
+	for (uint32_t corner = 0; corner < 8u; ++corner) {
+		const uint32_t dx = corner & 1u, dy = (corner >> 1) & 1u, dz = corner >> 2;
+		const float wgt = (dx ? f[0] : 1.0f - f[0]) * (dy ? f[1] : 1.0f - f[1]) * (dz ? f[2] : 1.0f - f[2]);
+		if (wgt == 0.0f) continue; // (also every second probe of an axis of one: its index would lie outside the lattice)
+		const size_t g = (i0[0] + dx) + (size_t)V.res[0] * ((i0[1] + dy) + (size_t)V.res[1] * (i0[2] + dz));
+		const float4* rec = V.sh + 7 * g;
+		const float4 last = rec[6];
+		if (last.w == 0.0f) continue; // a dead probe: every ray blocked
+#pragma unroll
+		for (int q = 0; q < 6; ++q) {
+			const float4 x = rec[q];
+			c[4 * q] += wgt * x.x; c[4 * q + 1] += wgt * x.y; c[4 * q + 2] += wgt * x.z; c[4 * q + 3] += wgt * x.w;
+		}
+		c[24] += wgt * last.x; c[25] += wgt * last.y; c[26] += wgt * last.z;
+		W += wgt;
+	}
+	E[0] = E[1] = E[2] = 0.f;
+	if (W > 0.0f) {
+		const float inv = 1.0f / W;
+#pragma unroll
+		for (int j = 0; j < 27; ++j) c[j] *= inv;
+		sh9_irradiance(c, nh.x, nh.y, nh.z, E);
+	}
+}
+
+// render_geometry_mesh (src/testbed_geometry_training.cu:2202-2320), Shade mode, floor disabled, one thread per pixel. The ambient source
+// is fixed at compile time by the type of A: IrradianceMap (the sky term, or the probe table(s) when A.irradiance is set) or
+// IrradianceVolume (ShadeIrradianceVolume: max(E(pos, N), 0) / pi from the SH9 lattice, 0 where every probe around pos is dead).
+template <typename Ambient>
+__global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer,
                                   float* __restrict__ depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed) {
 	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
 	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
@@ -295,10 +352,17 @@ __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams
 	f3 suncol = scale3(scale3(mk3(255.f / 255.0f, 225.f / 255.0f, 195.f / 255.0f), 4.f), shadow);
 	f3 skycol = scale3(scale3(mk3(195.f / 255.0f, 215.f / 255.0f, 255.f / 255.0f), 4.f), skyam);
 	f3 base = ld3(P.basecolor);
-	f3 ambc = mul3(ld3(P.ambientcolor), skycol);
-	if (I.irradiance) { // ShadeEnvMap / ShadeGridEnvMap: ambient light = E(N)/pi from the NeRF-derived irradiance table(s)
-		f3 E = irradiance_lookup(I, pos, N);
-		ambc = mk3(E.x / PI_F, E.y / PI_F, E.z / PI_F);
+	f3 ambc;
+	if constexpr (std::is_same<Ambient, IrradianceVolume>::value) { // the blend's accumulators are live from here on only: both traversals are over
+		float E[3], W;
+		irradiance_volume_lookup(A, pos, N, E, W);
+		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F); // (SH9 rings: E may dip below zero)
+	} else {
+		ambc = mul3(ld3(P.ambientcolor), skycol);
+		if (A.irradiance) { // ShadeEnvMap / ShadeGridEnvMap: ambient light = E(N)/pi from the NeRF-derived irradiance table(s)
+			f3 E = irradiance_lookup(A, pos, N);
+			ambc = mk3(E.x / PI_F, E.y / PI_F, E.z / PI_F);
+		}
 	}
 	f3 color = evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen,
 	                            0.f, P.clearcoat, P.clearcoat_gloss, sun, scale3(normalize3(primary_dir), -1.0f), N);
@@ -316,11 +380,13 @@ __global__ void trace_mesh_rays_kernel(const MeshSceneParams S, uint32_t n, floa
 	directions[3 * (size_t)i] = d.x; directions[3 * (size_t)i + 1] = d.y; directions[3 * (size_t)i + 2] = d.z;
 }
 
-void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const CameraParams& C, float4* frame_buffer, float* depth_buffer,
-                        uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream) {
+// V != nullptr: the ambient light comes from the SH9 volume (ShadeIrradianceVolume) and I is not looked at
+void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const CameraParams& C, float4* frame_buffer,
+                        float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream) {
 	dim3 threads(16, 8, 1);
 	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	hipLaunchKernelGGL(render_mesh_fused, blocks, threads, 0, stream, S, P, I, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
+	if (V) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolume>, blocks, threads, 0, stream, S, P, *V, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
+	else hipLaunchKernelGGL(render_mesh_fused<IrradianceMap>, blocks, threads, 0, stream, S, P, I, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
 }
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)
 __global__ void irradiance_lookup_kernel(const IrradianceMap I, uint32_t n, const float* __restrict__ positions, const float* __restrict__ normals, float4* __restrict__ out) {
@@ -529,60 +595,13 @@ __global__ void irradiance_sh_reduce_kernel(uint32_t n_u, uint32_t n_v, uint32_t
 	o[6] = make_float4(acc[24], acc[25], acc[26], (float)((double)c / (double)K));
 }
 
-// cell and weight of a coordinate on an axis of r probes spanning [lo, hi]: s = clamp((x - lo) / (hi - lo), 0, 1) (r - 1),
-// i0 = min(floor(s), r - 2), f = s - i0; an axis of one probe takes no part (i0 = 0, f = 0)
-NGP_DEV void volume_axis(float x, float lo, float hi, uint32_t r, uint32_t& i0, float& f) {
-	i0 = 0u;
-	f = 0.0f;
-	if (r < 2u) return;
-	const float xc = fminf(fmaxf(x, lo), hi); // (inside the box first: x - lo cannot overflow where hi - lo, which the host checks, does not)
-	const float s = saturate((xc - lo) / (hi - lo)) * (float)(r - 1u);
-	const float fl = fminf(__builtin_floorf(s), (float)(r - 2u));
-	i0 = (uint32_t)fl;
-	f = s - fl;
-}
-
-// one thread per point: the trilinear blend of the live probes (w != 0) among the up to 8 around it, renormalised by their weight W, and
-// E(n^) of the blended coefficients; out = (E rgb, W), zeros where every corner is dead. A probe is 7 float4 (112 B, 16-B aligned).
+// one thread per point: out = (E rgb, W) of irradiance_volume_lookup at the point and its normalised normal
 __global__ void irradiance_volume_lookup_kernel(const IrradianceVolume V, uint32_t n, const float* __restrict__ positions, const float* __restrict__ normals,
                                                 float4* __restrict__ out) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const f3 p = ld3(positions + 3 * (size_t)i);
-	const f3 nh = normalize3(ld3(normals + 3 * (size_t)i));
-	uint32_t i0[3];
-	float f[3];
-	volume_axis(p.x, V.lo[0], V.hi[0], V.res[0], i0[0], f[0]);
-	volume_axis(p.y, V.lo[1], V.hi[1], V.res[1], i0[1], f[1]);
-	volume_axis(p.z, V.lo[2], V.hi[2], V.res[2], i0[2], f[2]);
-	float c[28];
-#pragma unroll
-	for (int j = 0; j < 28; ++j) c[j] = 0.f;
-	float W = 0.f;
-#pragma unroll
-	for (uint32_t corner = 0; corner < 8u; ++corner) {
-		const uint32_t dx = corner & 1u, dy = (corner >> 1) & 1u, dz = corner >> 2;
-		const float wgt = (dx ? f[0] : 1.0f - f[0]) * (dy ? f[1] : 1.0f - f[1]) * (dz ? f[2] : 1.0f - f[2]);
-		if (wgt == 0.0f) continue; // (also every second probe of an axis of one: its index would lie outside the lattice)
-		const size_t g = (i0[0] + dx) + (size_t)V.res[0] * ((i0[1] + dy) + (size_t)V.res[1] * (i0[2] + dz));
-		const float4* rec = V.sh + 7 * g;
-		const float4 last = rec[6];
-		if (last.w == 0.0f) continue; // a dead probe: every ray blocked
-#pragma unroll
-		for (int q = 0; q < 6; ++q) {
-			const float4 x = rec[q];
-			c[4 * q] += wgt * x.x; c[4 * q + 1] += wgt * x.y; c[4 * q + 2] += wgt * x.z; c[4 * q + 3] += wgt * x.w;
-		}
-		c[24] += wgt * last.x; c[25] += wgt * last.y; c[26] += wgt * last.z;
-		W += wgt;
-	}
-	float E[3] = {0.f, 0.f, 0.f};
-	if (W > 0.0f) {
-		const float inv = 1.0f / W;
-#pragma unroll
-		for (int j = 0; j < 27; ++j) c[j] *= inv;
-		sh9_irradiance(c, nh.x, nh.y, nh.z, E);
-	}
+	float E[3], W;
+	irradiance_volume_lookup(V, ld3(positions + 3 * (size_t)i), normalize3(ld3(normals + 3 * (size_t)i)), E, W);
 	out[i] = make_float4(E[0], E[1], E[2], W);
 }
 

@@ -141,8 +141,8 @@ void launch_coarse_occupancy(const uint8_t* bitfield, uint32_t* coarse, hipStrea
 void launch_accumulate_tonemap(uint32_t n_pixels, const float4* frame_buffer, float4* accumulate_buffer, float sample_count, const float* background,
                                float exposure, int to_srgb, int color_space, float4* rgba_out, hipStream_t stream);
 
-void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const CameraParams& C, float4* frame_buffer, float* depth_buffer,
-                        uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream);
+void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const CameraParams& C, float4* frame_buffer,
+                        float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream); // V: the ShadeIrradianceVolume instantiation
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t stream);
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
@@ -331,7 +331,7 @@ struct ngp_ctx {
 	ngp::ProbeParams env_probe{}; // what was traced: mode, shell position(s), grid
 
 	// ---- the SH9 irradiance volume (ngp_compute_irradiance_volume / ngp_set_irradiance_volume): data, never recomputed behind the caller
-	ngp::DevArray<float4> d_sh_volume; // 7 float4 a probe, probe-major
+	ngp::DevArray<float4> d_sh_volume; // 7 float4 a probe, probe-major (a peer holds a replica for ShadeIrradianceVolume frames: sync_peer_geometry)
 	ngp_irradiance_volume_desc sh_volume_desc{};
 
 	// ---- environment map behind the NeRF (m_envmap.inference_view(), testbed.h:1297-1316)
@@ -360,6 +360,8 @@ struct ngp_ctx {
 	}
 	ngp::Event ev_frame0[HISTORY], ev_frame1[HISTORY], ev_kern0[HISTORY], ev_kern1[HISTORY];
 	uint64_t hist_n_rays[HISTORY] = {};
+	ngp::Event ev_mesh0[HISTORY], ev_mesh1[HISTORY]; // around the mesh pass of a frame's last sample (ngp_get_mesh_pass_ms)
+	bool hist_mesh_pass[HISTORY] = {};               // the slot's call was a frame with a mesh pass
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a
@@ -385,6 +387,7 @@ struct ngp_ctx {
 	uint64_t params_generation = 0, synced_params_generation = 0;       // the inference parameters followed a training step
 	uint64_t mesh_generation = 0, synced_mesh_generation = 0;           // the mesh list / BVHs changed (Geometry mode)
 	uint64_t probe_generation = 0, synced_probe_generation = 0;         // the irradiance probe textures were (re)computed
+	uint64_t sh_volume_generation = 0, synced_sh_volume_generation = 0; // the SH9 irradiance volume was computed, set or cleared
 	ngp::DevArray<float4> d_pack_rgba;   // this device's tiles of the current frame, tile-packed
 	ngp::DevArray<float> d_pack_depth;   // (allocated last: its size is that of both)
 	ngp::DevArray<float4> d_gather_rgba; // primary: [device][slots * 64]
@@ -505,7 +508,7 @@ void sync_inference_model(ngp_ctx* ctx); // render what has been trained (no-op 
 void sync_host_params(ngp_ctx* ctx);     // ctx->params <- training parameters, for snapshots
 // ngp_multi.cpp
 void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
-// ngp_mesh.cpp: Geometry mode on an auxiliary device -- the primary's meshes (BVHs as built), shading parameters and irradiance tables
+// ngp_mesh.cpp: Geometry mode on an auxiliary device -- the primary's meshes (BVHs as built), shading parameters, irradiance tables and the SH9 volume
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer);
 inline IrradianceMap irradiance_map_of(const ngp_ctx* ctx) {
 	IrradianceMap I{};
@@ -518,5 +521,15 @@ inline IrradianceMap irradiance_map_of(const ngp_ctx* ctx) {
 	}
 	for (int i = 0; i < 3; ++i) I.center[i] = ctx->env_probe.center[i];
 	return I;
+}
+inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) {
+	IrradianceVolume V{};
+	V.sh = ctx->d_sh_volume.get();
+	for (int a = 0; a < 3; ++a) {
+		V.res[a] = ctx->sh_volume_desc.res[a];
+		V.lo[a] = ctx->sh_volume_desc.aabb_min[a];
+		V.hi[a] = ctx->sh_volume_desc.aabb_max[a];
+	}
+	return V;
 }
 } // namespace ngp

@@ -307,6 +307,7 @@ void compute_probes(ngp_ctx* ctx, ngp::ProbeParams P, float min_transmittance) {
 	launch_irradiance(P, ctx->d_envmap.get(), n_texels, nullptr, ctx->d_irradiance.get(), stream);
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
 	ctx->hist_n_rays[slot] = P.n_rays;
+	ctx->hist_mesh_pass[slot] = false;
 	ctx->last_stream = stream;
 	++ctx->n_calls;
 	NGP_HIP_CHECK(hipStreamSynchronize(stream));
@@ -479,6 +480,7 @@ public:
 		}
 		NGP_HIP_CHECK(hipEventRecord(ctx_->ev_frame1[slot_], stream_));
 		ctx_->hist_n_rays[slot_] = n_rays_;
+		ctx_->hist_mesh_pass[slot_] = false;
 		ctx_->last_stream = stream_;
 		++ctx_->n_calls;
 		NGP_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -619,16 +621,6 @@ void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp
 	tr.finish(); // (synchronises the stream: the chunk buffers may go)
 }
 
-ngp::IrradianceVolume sh_volume_of(const ngp_ctx* ctx) {
-	ngp::IrradianceVolume V{};
-	V.sh = ctx->d_sh_volume.get();
-	for (int a = 0; a < 3; ++a) {
-		V.res[a] = ctx->sh_volume_desc.res[a];
-		V.lo[a] = ctx->sh_volume_desc.aabb_min[a];
-		V.hi[a] = ctx->sh_volume_desc.aabb_max[a];
-	}
-	return V;
-}
 } // namespace
 
 extern "C" {
@@ -770,6 +762,7 @@ int ngp_compute_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc
 		trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, sh.get(), nullptr);
 		ctx->d_sh_volume = std::move(sh); // (the previous volume stays in place when the trace throws)
 		ctx->sh_volume_desc = *desc;
+		++ctx->sh_volume_generation;
 	});
 }
 
@@ -785,6 +778,7 @@ int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* de
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old records)
 		ctx->d_sh_volume = std::move(d);
 		ctx->sh_volume_desc = *desc;
+		++ctx->sh_volume_generation;
 	});
 }
 
@@ -803,6 +797,14 @@ int ngp_clear_irradiance_volume(ngp_ctx* ctx) {
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		ctx->d_sh_volume.reset();
 		ctx->sh_volume_desc = ngp_irradiance_volume_desc{};
+		++ctx->sh_volume_generation;
+		for (ngp_ctx* p : ctx->peers) { // the replicas go too: a multi-device frame refuses like a single-device one
+			ngp::DeviceGuard g(p->device);
+			NGP_HIP_CHECK(hipStreamSynchronize(p->stream));
+			p->d_sh_volume.reset();
+			p->sh_volume_desc = ngp_irradiance_volume_desc{};
+			p->synced_sh_volume_generation = ctx->sh_volume_generation;
+		}
 	});
 }
 
@@ -819,7 +821,7 @@ int ngp_irradiance_volume_at(ngp_ctx* ctx, uint32_t n, const float* positions, c
 		DevArray<float4> d_o(n);
 		upload(ctx, d_p.get(), positions, (size_t)n * 3 * sizeof(float));
 		upload(ctx, d_n.get(), normals, (size_t)n * 3 * sizeof(float));
-		ngp::launch_irradiance_volume_lookup(sh_volume_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
+		ngp::launch_irradiance_volume_lookup(ngp::sh_volume_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
 		download(ctx, out, d_o.get(), (size_t)n * sizeof(float4));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
@@ -843,7 +845,7 @@ int ngp_irradiance_sh_eval(uint32_t n, const float* sh, const float* normals, fl
 
 // Geometry mode on a multi-device context (the reference's render_frame serves every mode on every device, src/testbed.cu:4833-4889,
 // 5575-5616): an auxiliary device gets the primary's meshes exactly as built (same triangle order, same BVH4 nodes -- rebuilt nowhere),
-// the BRDF / sun parameters and, when probes were computed, the tabulated irradiance E(n). Generation counters: only what changed moves.
+// the BRDF / sun parameters and, when they were computed, the tabulated irradiance E(n) and the SH9 irradiance volume. Generation counters: only what changed moves.
 namespace ngp {
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->shade = primary->shade;
@@ -879,6 +881,22 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 		peer->env_n_theta = primary->env_n_theta;
 		peer->env_n_phi = primary->env_n_phi;
 		peer->synced_probe_generation = primary->probe_generation;
+	}
+	if (peer->synced_sh_volume_generation != primary->sh_volume_generation) { // (a cleared volume: the replica is dropped, the peer's frame refuses)
+		const size_t n = primary->d_sh_volume.size();
+		{
+			DeviceGuard g(peer->device);
+			NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // frames on the peer still read the old records
+			peer->d_sh_volume.reset();
+			if (n) peer->d_sh_volume.reset(n);
+		}
+		if (n) {
+			NGP_HIP_CHECK(hipStreamSynchronize(primary->stream)); // the trace / upload that wrote the records ends synchronised; a no-op in practice
+			DeviceGuard g(peer->device);
+			NGP_HIP_CHECK(hipMemcpyPeer(peer->d_sh_volume.get(), peer->device, primary->d_sh_volume.get(), primary->device, n * sizeof(float4)));
+		}
+		peer->sh_volume_desc = primary->sh_volume_desc;
+		peer->synced_sh_volume_generation = primary->sh_volume_generation;
 	}
 }
 } // namespace ngp

@@ -129,7 +129,7 @@ void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_o
 			dev->M.r2l_identity = ctx->M.r2l_identity;
 			dev->M.cone_angle = ctx->M.cone_angle;
 			memcpy(dev->tune, ctx->tune, sizeof(ctx->tune));
-			if (opts.testbed_mode == NGP_MODE_GEOMETRY) sync_peer_geometry(ctx, dev); // meshes + BVHs, BRDF parameters, irradiance tables
+			if (opts.testbed_mode == NGP_MODE_GEOMETRY) sync_peer_geometry(ctx, dev); // meshes + BVHs, BRDF parameters, irradiance tables, the SH9 volume
 		}
 		DeviceGuard g(dev->device);
 		ensure_pack_buffers(dev, packed);

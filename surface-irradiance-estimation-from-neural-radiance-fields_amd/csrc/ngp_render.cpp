@@ -134,7 +134,8 @@ void make_frame_params(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opt
 	// (a rank's share in image layout keeps the general path: the other ranks' pixels must read as an empty frame)
 	F.direct = (spp == 1 && !have_meshes && !geometry && (shard_count == 1 || opts.packed_output)) ? 1 : 0;
 	F.to_srgb = opts.to_srgb;
-	F.render_mode = opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ? NGP_RENDER_SHADE_ENVMAP : opts.render_mode; // (the NeRF pass treats both like Shade)
+	// the NeRF pass knows the grid mode as ShadeEnvMap (shaded like Shade, without its sRGB -> linear step) and ShadeIrradianceVolume, this project's own, as Shade itself
+	F.render_mode = opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ? NGP_RENDER_SHADE_ENVMAP : opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME ? NGP_RENDER_SHADE : opts.render_mode;
 	F.color_space = opts.color_space;
 	if (opts.color_space != 0 && opts.color_space != 1) throw std::runtime_error("color_space: 0 (Linear) or 1 (SRGB)");
 	F.depth_scale = opts.depth_scale != 0.f ? opts.depth_scale : 1.0f / 0.33f;
@@ -157,7 +158,7 @@ void make_frame_params(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opt
 // what can be refused before anything is allocated or enqueued
 void validate_render_request(const ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts) {
 	if (cam.width <= 0 || cam.height <= 0 || cam.width > 65536 || cam.height > 65536) throw std::runtime_error("invalid render resolution"); // (tile counts stay inside 32 bits)
-	if (opts.render_mode < NGP_RENDER_SHADE || opts.render_mode > NGP_RENDER_NORMALS) throw std::runtime_error("render modes implemented: Shade, ShadeEnvMap, ShadeGridEnvMap, AO, Normals, Positions, Depth, Cost");
+	if (opts.render_mode < NGP_RENDER_SHADE || opts.render_mode > NGP_RENDER_SHADE_IRRADIANCE_VOLUME) throw std::runtime_error("render modes implemented: Shade, ShadeEnvMap, ShadeGridEnvMap, ShadeIrradianceVolume, AO, Normals, Positions, Depth, Cost");
 	const bool gbuffer_mode = (opts.render_mode >= NGP_RENDER_AO && opts.render_mode <= NGP_RENDER_COST) || opts.render_mode == NGP_RENDER_NORMALS;
 	if (gbuffer_mode && opts.testbed_mode == NGP_MODE_GEOMETRY) throw std::runtime_error("the G-buffer render modes (AO, Normals, Positions, Depth, Cost) apply to NeRF mode");
 	if (opts.render_mode == NGP_RENDER_NORMALS && ctx->model_loaded && ctx->M.wide.width && (!ctx->M.wide.layers_t[0].n_mtiles || ctx->M.wide.enc_dims > ctx->M.wide.width))
@@ -216,6 +217,8 @@ void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
 			ctx->ev_frame1[i] = new_event();
 			ctx->ev_kern0[i] = new_event();
 			ctx->ev_kern1[i] = new_event();
+			ctx->ev_mesh0[i] = new_event();
+			ctx->ev_mesh1[i] = new_event();
 		}
 	}
 	if (n_pixels <= ctx->d_rgba.size()) return;
@@ -281,7 +284,15 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 				if (!ctx->d_irradiance || ctx->env_probe.mode != 3) throw std::runtime_error("render_mode ShadeGridEnvMap needs ngp_compute_envmap_grid first");
 				I = irradiance_map_of(ctx);
 			}
-			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			IrradianceVolume V{};
+			const bool volume = opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
+			if (volume) {
+				if (!ctx->d_sh_volume) throw std::runtime_error("render_mode ShadeIrradianceVolume needs ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+				V = sh_volume_of(ctx);
+			}
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[slot], stream)); // (ngp_get_mesh_pass_ms)
+			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
 		if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
@@ -293,6 +304,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	NGP_HIP_CHECK(hipGetLastError());
 	ctx->last_stream = stream;
 	ctx->hist_n_rays[slot] = (uint64_t)F.n_local_tiles * 64u * (uint64_t)spp;
+	ctx->hist_mesh_pass[slot] = have_meshes && !F.direct;
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -429,6 +441,17 @@ static void read_history_slot(ngp_ctx* ctx, uint64_t call, ngp_render_stats* out
 	out->n_samples = c[2];
 	NGP_HIP_CHECK(hipEventElapsedTime(&out->kernel_ms, ctx->ev_kern0[slot], ctx->ev_kern1[slot]));
 	NGP_HIP_CHECK(hipEventElapsedTime(&out->frame_ms, ctx->ev_frame0[slot], ctx->ev_frame1[slot]));
+}
+
+int ngp_get_mesh_pass_ms(ngp_ctx* ctx, float* ms_out) {
+	return guarded(ctx, [&] {
+		if (!ms_out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls) throw std::runtime_error("nothing rendered yet");
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		if (!ctx->hist_mesh_pass[slot]) throw std::runtime_error("the last frame had no mesh pass");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms_out, ctx->ev_mesh0[slot], ctx->ev_mesh1[slot]));
+	});
 }
 
 int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {

@@ -52,7 +52,7 @@ PYBIND11_MODULE(pyngp, m) {
 		.value("AO", ERenderMode::AO).value("Shade", ERenderMode::Shade).value("Normals", ERenderMode::Normals)
 		.value("Positions", ERenderMode::Positions).value("Depth", ERenderMode::Depth).value("Distortion", ERenderMode::Distortion)
 		.value("Cost", ERenderMode::Cost).value("Slice", ERenderMode::Slice).value("ShadeNerf", ERenderMode::ShadeNerf)
-		.value("ShadeEnvMap", ERenderMode::ShadeEnvMap).value("ShadeGridEnvMap", ERenderMode::ShadeGridEnvMap)
+		.value("ShadeEnvMap", ERenderMode::ShadeEnvMap).value("ShadeGridEnvMap", ERenderMode::ShadeGridEnvMap).value("ShadeIrradianceVolume", ERenderMode::ShadeIrradianceVolume)
 		.export_values();
 
 	// nested under Testbed like python_api.cu does (py::class_<Testbed::Nerf> nerf(testbed, "Nerf")): the exported enum
@@ -232,6 +232,22 @@ PYBIND11_MODULE(pyngp, m) {
 		}, py::arg("resolution"), py::arg("aabb") = py::none(), py::arg("n_u") = 32, py::arg("n_v") = 32, py::arg("occlude_by_meshes") = true,
 		   "This project's own: a lattice of SH9 irradiance probes, traced and kept for irradiance_volume_lookup: {'sh': (rz, ry, rx, 28), 'aabb': (min, max)} "
 		   "(aabb: None = the render aabb, or (min, max))")
+		.def("get_irradiance_volume", [](Testbed& t) {
+			std::array<uint32_t, 3> res{};
+			std::array<float, 6> box{};
+			std::vector<float> sh;
+			{
+				py::gil_scoped_release nogil;
+				sh = t.get_irradiance_volume(res, box.data());
+			}
+			py::array_t<float> a({(py::ssize_t)res[2], (py::ssize_t)res[1], (py::ssize_t)res[0], (py::ssize_t)28});
+			if (!sh.empty()) memcpy(a.mutable_data(), sh.data(), sh.size() * sizeof(float));
+			py::dict d;
+			d["sh"] = a;
+			d["aabb"] = py::make_tuple(std::array<float, 3>{box[0], box[1], box[2]}, std::array<float, 3>{box[3], box[4], box[5]});
+			return d;
+		}, "The irradiance volume the context holds, as compute_irradiance_volume returns it (a ShadeIrradianceVolume render computes a default one when there is none)")
+		.def_readwrite("irradiance_volume_res", &Testbed::m_irradiance_volume_res, "probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none")
 		.def("irradiance_volume_lookup", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions,
 		                                    py::array_t<float, py::array::c_style | py::array::forcecast> normals) {
 			if (positions.ndim() != 2 || positions.shape(1) != 3 || normals.ndim() != 2 || normals.shape(1) != 3 || positions.shape(0) != normals.shape(0))

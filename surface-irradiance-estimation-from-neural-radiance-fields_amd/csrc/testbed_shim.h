@@ -20,7 +20,7 @@ namespace ngp {
 enum class ETestbedMode : int { Nerf, Sdf, Image, Volume, Geometry, None }; // common.h:35-43
 enum class ELossType : int { L2, L1, Mape, Smape, Huber, LogL1, RelativeL2 }; // common.h:84-92
 enum class EColorSpace : int { Linear, SRGB, VisPosNeg }; // common.h
-enum class ERenderMode : int { AO, Shade, ShadeNerf, ShadeEnvMap, ShadeGridEnvMap, Normals, Positions, Depth, Distortion, Cost, Slice, NumRenderModes, EncodingVis }; // common.h:58-72
+enum class ERenderMode : int { AO, Shade, ShadeNerf, ShadeEnvMap, ShadeGridEnvMap, Normals, Positions, Depth, Distortion, Cost, Slice, NumRenderModes, EncodingVis, ShadeIrradianceVolume }; // common.h:58-72; ShadeIrradianceVolume is this project's own, appended so that the reference's values stay put
 
 class Testbed {
 public:
@@ -422,13 +422,17 @@ public:
 		}
 		const bool gbuffer = m_render_mode == ERenderMode::AO || m_render_mode == ERenderMode::Positions || m_render_mode == ERenderMode::Depth || m_render_mode == ERenderMode::Cost ||
 		                     m_render_mode == ERenderMode::Normals;
-		const bool shade_family = m_render_mode == ERenderMode::Shade || m_render_mode == ERenderMode::ShadeEnvMap || m_render_mode == ERenderMode::ShadeGridEnvMap;
-		if (!shade_family && !gbuffer) throw std::runtime_error("render modes supported: Shade, ShadeEnvMap, ShadeGridEnvMap, AO, Normals, Positions, Depth, Cost");
+		const bool shade_family = m_render_mode == ERenderMode::Shade || m_render_mode == ERenderMode::ShadeEnvMap || m_render_mode == ERenderMode::ShadeGridEnvMap ||
+		                          m_render_mode == ERenderMode::ShadeIrradianceVolume;
+		if (!shade_family && !gbuffer) throw std::runtime_error("render modes supported: Shade, ShadeEnvMap, ShadeGridEnvMap, ShadeIrradianceVolume, AO, Normals, Positions, Depth, Cost");
 		// pre computation of the envmap: src/main.cu:184-188 runs it before the first frame; a Python session has no such hook
 		// (python_api.cu binds neither function), so the first Geometry-mode render in these modes runs it with the defaults
 		if (m_testbed_mode == ETestbedMode::Geometry && ngp_n_meshes(m_ctx) > 0) {
 			if (m_render_mode == ERenderMode::ShadeGridEnvMap && !m_envmap_grid_ready) computeEnvmapGrid();
 			if (m_render_mode == ERenderMode::ShadeEnvMap && !m_envmap_ready) computeEnvmapMultipleMain();
+			// ShadeIrradianceVolume: a context without a volume gets the default one; a volume the caller set or computed is never replaced
+			if (m_render_mode == ERenderMode::ShadeIrradianceVolume && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0)
+				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res});
 		}
 		ngp_camera cam{};
 		memcpy(cam.matrix, m_camera.data(), sizeof(cam.matrix));
@@ -454,7 +458,7 @@ public:
 			memcpy(cam.lens_params, m_render_lens_params.data(), sizeof(cam.lens_params));
 		}
 		ngp_render_opts o{};
-		o.render_mode = m_render_mode == ERenderMode::ShadeEnvMap ? NGP_RENDER_SHADE_ENVMAP : m_render_mode == ERenderMode::ShadeGridEnvMap ? NGP_RENDER_SHADE_GRID_ENVMAP : m_render_mode == ERenderMode::AO ? NGP_RENDER_AO
+		o.render_mode = m_render_mode == ERenderMode::ShadeIrradianceVolume ? NGP_RENDER_SHADE_IRRADIANCE_VOLUME : m_render_mode == ERenderMode::ShadeEnvMap ? NGP_RENDER_SHADE_ENVMAP : m_render_mode == ERenderMode::ShadeGridEnvMap ? NGP_RENDER_SHADE_GRID_ENVMAP : m_render_mode == ERenderMode::AO ? NGP_RENDER_AO
 		              : m_render_mode == ERenderMode::Normals ? NGP_RENDER_NORMALS : m_render_mode == ERenderMode::Positions ? NGP_RENDER_POSITIONS : m_render_mode == ERenderMode::Depth ? NGP_RENDER_DEPTH : m_render_mode == ERenderMode::Cost ? NGP_RENDER_COST : NGP_RENDER_SHADE;
 		o.min_transmittance = nerf.render_min_transmittance;
 		memcpy(o.background, m_background_color.data(), sizeof(o.background));
@@ -538,6 +542,17 @@ public:
 		if (aabb6_out) { memcpy(aabb6_out, d.aabb_min, 12); memcpy(aabb6_out + 3, d.aabb_max, 12); }
 		return out;
 	}
+	// the volume the context holds (computed here, by a ShadeIrradianceVolume render or set through the C ABI): its records, resolution and box
+	std::vector<float> get_irradiance_volume(std::array<uint32_t, 3>& res_out, float* aabb6_out) {
+		ngp_irradiance_volume_desc d{};
+		check(ngp_get_irradiance_volume(m_ctx, &d, nullptr));
+		std::vector<float> out((size_t)d.res[0] * d.res[1] * d.res[2] * 28);
+		check(ngp_get_irradiance_volume(m_ctx, &d, out.data()));
+		for (int a = 0; a < 3; ++a) res_out[a] = d.res[a];
+		memcpy(aabb6_out, d.aabb_min, 12);
+		memcpy(aabb6_out + 3, d.aabb_max, 12);
+		return out;
+	}
 	// E(p, n) read from the volume: n x 4 = rgb irradiance, weight of the live probes around the point
 	std::vector<float> irradiance_volume_lookup(const float* positions, const float* normals, uint32_t n) {
 		std::vector<float> out((size_t)n * 4);
@@ -545,6 +560,7 @@ public:
 		return out;
 	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
+	uint32_t m_irradiance_volume_res = 8; // probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none (32 x 32 rays, meshes occluding)
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path
 	bool m_has_camera_end = false;
 	std::array<float, 4> m_rolling_shutter{0.f, 0.f, 0.f, 1.f}; // what Testbed::render_to_cpu passes (src/python_api.cu:183)

@@ -91,6 +91,7 @@ class IrradianceTraceDesc(C.Structure):
 
 MODE_NERF, MODE_GEOMETRY = 0, 1
 RENDER_SHADE, RENDER_SHADE_ENVMAP, RENDER_AO, RENDER_POSITIONS, RENDER_DEPTH, RENDER_COST, RENDER_SHADE_GRID_ENVMAP, RENDER_NORMALS = 0, 1, 2, 3, 4, 5, 6, 7
+RENDER_SHADE_IRRADIANCE_VOLUME = 8  # meshes lit by the SH9 irradiance volume (compute_irradiance_volume / set_irradiance_volume)
 PROBE_CENTER, PROBE_CENTER_OUTWARD, PROBE_MULTI_CENTER = 0, 1, 2
 BVH_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("left_idx", "<i4"), ("right_idx", "<i4")])
 TRIANGLE_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3), ("c", "<f4", 3)])
@@ -181,6 +182,7 @@ def load_library():
     L.ngp_packed_tiles.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]
     L.ngp_packed_tiles.restype = C.c_uint32
     L.ngp_get_render_stats.argtypes = [vp, C.POINTER(RenderStats)]
+    L.ngp_get_mesh_pass_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_get_render_history.argtypes = [vp, ip, C.POINTER(RenderStats)]
     L.ngp_set_schedule.argtypes = [vp, vp, ip]
     if hasattr(L, "ngp_last_render_kernel"):  # (an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
@@ -523,6 +525,12 @@ class Context:
 
     def render_device(self, cam, opts, d_rgba_ptr, d_depth_ptr=None, stream=None):
         self._check(self.L.ngp_render_device(self.h, C.byref(cam), C.byref(opts), d_rgba_ptr, d_depth_ptr, stream))
+
+    def mesh_pass_ms(self):
+        """device time of the last frame's mesh pass (its last sample), from HIP events on its stream"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_mesh_pass_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def render_stats(self):
         st = RenderStats()

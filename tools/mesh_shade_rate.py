@@ -1,0 +1,104 @@
+"""What the mesh pass costs per shade mode on the MI355X: the device time of render_mesh_fused at 1920 x 1080 on the meshes of the mesh
+tests' render scene (cube, icosphere, upright torus; the icosphere and the torus finer, so that the BVHs have some depth), lit by the sky
+term (Shade), by the grid of lat-long irradiance tables (ShadeGridEnvMap) and by the SH9 irradiance volume (ShadeIrradianceVolume) at 8^3 and
+at 32^3 probes.
+
+    python tools/mesh_shade_rate.py [--width 1920] [--height 1080] [--frames 30] [--warmup 5] [--out profiles/mesh_shade_rate.json]
+
+Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
+The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
+volumes over the scene box with the meshes occluding. Needs a GPU; there is no CPU path."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "surface-irradiance-estimation-from-neural-radiance-fields_amd"
+
+
+def pkg(sub):
+    import importlib
+
+    return importlib.import_module(PKG + "." + sub)
+
+
+def scene():
+    mi = pkg("meshio")
+    cube = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)])
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tris = np.asarray([[cube[a], cube[b], cube[c]] for q in quads for a, b, c in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))], np.float32)
+    return [(tris, (0.0, 0.0, 0.0)), (mi.icosphere(4), (0.3, 1.6, 0.3)), (np.ascontiguousarray(mi.torus(96, 48)[..., [0, 2, 1]]), (1.15, 0.3, 0.0))]
+
+
+def look_at(pos, target, up=(0.0, 0.0, 1.0)):
+    pos, target = np.asarray(pos, np.float64), np.asarray(target, np.float64)
+    fwd = (target - pos) / np.linalg.norm(target - pos)
+    right = np.cross(fwd, np.asarray(up, np.float64))
+    right /= np.linalg.norm(right)
+    return np.stack([right, np.cross(fwd, right), fwd, pos], 1).astype(np.float32)
+
+
+def median_ms(ctx, cam, opts, frames, warmup):
+    ts = []
+    for i in range(warmup + frames):
+        _, depth = ctx.render(cam, opts, want_depth=True)
+        if i >= warmup:
+            ts.append(ctx.mesh_pass_ms())
+    return float(np.median(ts)), float(np.min(ts)), float((depth < 16384.0).mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_shade_rate.json"))
+    args = ap.parse_args()
+    if args.frames < 20:
+        raise SystemExit("--frames: at least 20")
+    pkg("build").build()
+    native, synthetic = pkg("native"), pkg("synthetic")
+    meshes = scene()
+    ctx = native.Context(0)  # the benchmark's model (bench.py): what the tables and the volumes are traced in
+    ctx.set_model(synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19))
+    for tris, center in meshes:
+        ctx.add_mesh(tris, center)
+    info = ctx.mesh_info(-1)
+    lo, hi = info["aabb"]
+    # the same view as the mesh tests' frames, the focal length scaled to the frame
+    cam = native.make_camera(look_at((0.93, 6.3, 0.57), (1.0, 0.5, 0.5)), args.width, args.height, (100.0 * args.width / 64.0,) * 2)
+    geo = dict(testbed_mode=native.MODE_GEOMETRY, background=(0, 0, 0, 0))
+    out = {"how": "device time of the mesh pass (render_mesh_fused) per Geometry-mode frame, HIP events around its launch (ngp_get_mesh_pass_ms), "
+                  "median (and minimum) of --frames frames after --warmup; ratio = median / the Shade median of the same run",
+           "width": args.width, "height": args.height, "frames": args.frames, "triangles": int(info["n_tris"]), "modes": {}}
+    ctx.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
+    rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid")]
+    rows += [("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r) for r in (8, 32)]
+    for name, mode, what in rows:
+        if what == "grid":  # the reference's default grid: 8 x 8 probes of 64 x 32 texels
+            ctx.compute_envmap_grid(8, 8, 64, 32)
+        elif what is not None:  # over the scene box, meshes occluding: the probes inside the closed meshes are dead
+            ctx.compute_irradiance_volume((what,) * 3, (lo, hi), 16, 16)
+        med, mn, cover = median_ms(ctx, cam, native.make_opts(render_mode=mode, **geo), args.frames, args.warmup)
+        out["modes"][name] = {"median_ms": round(med, 4), "min_ms": round(mn, 4), "pixels_with_depth": round(cover, 3)}
+        if isinstance(what, int):
+            out["modes"][name]["dead_probes"] = round(float((ctx.get_irradiance_volume()[1][..., 27] == 0).mean()), 4)
+        print(f"{name:28s} median {med:.4f} ms  min {mn:.4f} ms", flush=True)
+    base = out["modes"]["Shade"]["median_ms"]
+    for m in out["modes"].values():
+        m["ratio_to_shade"] = round(m["median_ms"] / base, 3)
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
