@@ -52,7 +52,8 @@ enum ngp_render_mode {
 	                           * ring: E can dip below zero on the far side of a bright lobe. Where every probe around p is dead (W = 0) the
 	                           * ambient light is 0. A hit point outside the volume's box is clamped onto it per axis (the lookup's rule). Sun,
 	                           * shadow ray, BRDF, depth, coverage, sharding and packing are those of the other shade modes; ambientcolor and up_dir
-	                           * are not used. Refused with meshes present and no volume ("needs ngp_compute_irradiance_volume or
+	                           * are not used. While the context holds probe visibility (ngp_compute_irradiance_volume_visibility) E is the
+	                           * visible lookup's (ngp_irradiance_volume_at_visible). Refused with meshes present and no volume ("needs ngp_compute_irradiance_volume or
 	                           * ngp_set_irradiance_volume first"), on a multi-device context too: its auxiliary devices keep replicas of the
 	                           * records, refreshed when the volume is computed, set or cleared. Without meshes, or in NGP_MODE_NERF, it is Shade */
 };
@@ -482,6 +483,64 @@ NGP_API int ngp_get_irradiance_volume(ngp_ctx* ctx, ngp_irradiance_volume_desc* 
 NGP_API int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh /* probes x 28 */);
 NGP_API int ngp_clear_irradiance_volume(ngp_ctx* ctx);
 NGP_API int ngp_irradiance_volume_at(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const float* normals /* n x 3 */, float* out /* n x 4 */);
+
+/* --- probe visibility: the plain lookup blends a probe on the far side of an inserted mesh with full weight, so light and darkness leak
+ * through walls. Each probe of the volume gets a small map of the mean and mean squared distance to the nearest mesh surface per
+ * direction, and the lookup multiplies a probe's trilinear weight by the Chebyshev bound of the chance that the point is visible from
+ * it (Majercik et al., "Dynamic Diffuse Global Illumination with Ray-Traced Irradiance Fields", JCGT 2019). This project's own contract.
+ * Only BVH rays are traced: no model is needed and the NeRF's density occludes nothing.
+ *
+ * Distance map of a probe: 8 x 8 octahedral texels, texel q = i + 8 j, stored as 64 float2 (m1, m2) = 512 B a probe, probe-major in the
+ *   volume's index order g, 16-B aligned.
+ * Texel direction w_q: (a, b) = (2 (i + .5) / 8 - 1, 2 (j + .5) / 8 - 1), z = 1 - |a| - |b|, (x, y) = (a, b); if z < 0:
+ *   (x, y) = ((1 - |b|) sgn a, (1 - |a|) sgn b) with sgn 0 = +1; (x, y, z) normalised.
+ * Rays: the K = n_u n_v sphere directions w_k of the SH9 section, origin = the probe, t_min = 0. d_k = min(t_max_k, D), t_max_k the closest
+ *   triangle hit over all loaded meshes (+inf without one: d_k = D). D = max_distance; a descriptor value <= 0 selects 1.5 x the diagonal
+ *   of one lattice cell (an axis of resolution 1 counts with extent 0; every axis of resolution 1: 1.5 x the box diagonal), formed in
+ *   double and rounded to float. ngp_get_irradiance_volume_visibility writes the D in use back.
+ * Moments: x_qk = max(0, w_q . w_k); rho_qk = x_qk^(2^e), formed by e squarings in float32, e = sharpness_log2 in 0..6;
+ *   S_q = sum_k rho_qk, m1_q = sum_k rho_qk d_k / S_q, m2_q = sum_k rho_qk d_k^2 / S_q; a texel with S_q = 0 (possible at very small K;
+ *   every rho underflowing float32 counts) stores (D, D^2). The sums run over k ascending, one texel a lane, no atomics: a map is
+ *   bit-identical from run to run and for any split of the probes over calls or chunks.
+ * Visible lookup at (p, n): axis cells and trilinear weights wgt_c exactly those of ngp_irradiance_volume_at (from the clamped position);
+ *   dead probes (w = 0) are skipped as there. For each remaining corner with wgt_c != 0: v = (p + normal_bias n^) - x_g with the UNCLAMPED p
+ *   and x_g the probe position as the lattice formula gives it in float; r = |v|; r = 0: vis = 1. Otherwise the corner probe's map is read at
+ *   v / r: the octahedral encode is the inverse of the decode above (divide by |x| + |y| + |z|, fold when z < 0), s = 4 (a + 1) - .5,
+ *   t = 4 (b + 1) - .5, bilinear over the texels (floor s + {0, 1}, floor t + {0, 1}); an index outside 0..7 wraps across the octahedron's
+ *   edge: i < 0 -> (-1 - i, 7 - j), i > 7 -> (15 - i, 7 - j), then the same rule for j with the roles swapped (no border texels).
+ *   vis = 1 if r <= m1; else var = max(m2 - m1^2, 1e-4 D^2) and vis = (var / (var + (r - m1)^2))^3: continuous in r, m1 and m2.
+ *   W' = sum wgt_c vis_c, c~ = sum wgt_c vis_c c / W', out = (E_rgb(c~, n), W'), zeros when W' = 0. With no meshes loaded and
+ *   normal_bias = 0 every vis is exactly 1 for points inside the box, and the result is ngp_irradiance_volume_at's, bit for bit.
+ * Out of scope: the backface (wrap-shading) weight and the weight crush of the DDGI paper; maps larger than 8 x 8; NeRF density as an
+ *   occluder. Known limit: a point within about a texel's angular width of a wall, seen from the probe behind it, is only partly
+ *   suppressed.
+ * Lifetime: visibility is data like the volume. It lives on the primary device (auxiliary devices hold replicas for frames), is NEVER
+ *   recomputed behind the caller's back and is not stored in snapshots. Computing, setting or clearing the VOLUME drops it: the lattice may
+ *   have changed. While the context holds it, NGP_RENDER_SHADE_IRRADIANCE_VOLUME frames use the visible lookup (ambient light
+ *   max(E, 0) / pi, 0 where W' = 0); no other mode looks at it.
+ * Limits: n_u, n_v >= 1; K <= 2^21; probes * K <= 2^28.
+ * Refusals, each with a message: a host-only context; no volume, for compute, set, get and the visible lookup ("no irradiance volume");
+ *   no visibility, for get and the visible lookup ("no irradiance visibility: call ngp_compute_irradiance_volume_visibility or
+ *   ngp_set_irradiance_volume_visibility first"); sharpness_log2 > 6; a non-finite max_distance; a non-finite or negative normal_bias;
+ *   non-finite positions; a zero or non-finite normal; set with a non-finite value, m1 < 0 or m2 < 0. */
+typedef struct ngp_irradiance_visibility_desc {
+	uint32_t n_u, n_v;       /* K = n_u * n_v sphere directions per probe */
+	uint32_t sharpness_log2; /* e: rho = max(0, cos)^(2^e), 0..6 */
+	float max_distance;      /* D; <= 0 selects 1.5 x the lattice cell's diagonal (ngp_irradiance_distance_maps: must be > 0) */
+	float normal_bias;       /* finite and >= 0, ngp units */
+} ngp_irradiance_visibility_desc;
+/* a stage entry for tests: the maps of n probes at the caller's positions. Needs a device, but no model and no volume; max_distance must
+ * be > 0; normal_bias is not looked at */
+NGP_API int ngp_irradiance_distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_visibility_desc* desc,
+                                         float* maps_out /* n x 64 x 2 */);
+/* the maps of the lattice of the volume the context holds; kept on the primary device */
+NGP_API int ngp_compute_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_visibility_desc* desc);
+NGP_API int ngp_get_irradiance_volume_visibility(ngp_ctx* ctx, ngp_irradiance_visibility_desc* desc_out, float* maps_out /* nullable, probes x 64 x 2 */);
+/* a caller's own maps, e.g. reloaded from a file, for the probes of the held volume; desc->max_distance (> 0), sharpness_log2 and
+ * normal_bias are kept, n_u and n_v are kept as given and not looked at */
+NGP_API int ngp_set_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_visibility_desc* desc, const float* maps /* probes x 64 x 2 */);
+NGP_API int ngp_clear_irradiance_volume_visibility(ngp_ctx* ctx);
+NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const float* normals /* n x 3 */, float* out /* n x 4 */);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

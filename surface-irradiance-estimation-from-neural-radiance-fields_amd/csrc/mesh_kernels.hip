@@ -287,9 +287,110 @@ NGP_DEV void irradiance_volume_lookup(const IrradianceVolume& V, f3 p, f3 nh, fl
 	}
 }
 
+// ---- visibility-weighted lookup (contract: include/ngp_hip.h, "probe visibility"). A probe's distance map is 8 x 8 octahedral texels of
+// (m1, m2), texel q = i + 8 j.
+// the direction of texel q: (a, b) = the texel centre in [-1, 1]^2, z = 1 - |a| - |b|, the lower half folded over the diagonals
+NGP_DEV f3 distance_texel_dir(uint32_t q) {
+	const float a = 2.0f * ((float)(q & 7u) + 0.5f) / 8.0f - 1.0f, b = 2.0f * ((float)(q >> 3) + 0.5f) / 8.0f - 1.0f;
+	const float z = 1.0f - fabsf(a) - fabsf(b);
+	float x = a, y = b;
+	if (z < 0.0f) {
+		x = (1.0f - fabsf(b)) * (a < 0.0f ? -1.0f : 1.0f);
+		y = (1.0f - fabsf(a)) * (b < 0.0f ? -1.0f : 1.0f);
+	}
+	return normalize3(mk3(x, y, z));
+}
+// texel (i, j) of a map, i and j in -1..8: an index outside 0..7 continues across the octahedron's edge
+NGP_DEV float2 distance_map_texel(const float2* __restrict__ map, int i, int j) {
+	if (i < 0) { i = -1 - i; j = 7 - j; }
+	else if (i > 7) { i = 15 - i; j = 7 - j; }
+	if (j < 0) { j = -1 - j; i = 7 - i; }
+	else if (j > 7) { j = 15 - j; i = 7 - i; }
+	return map[i + 8 * j];
+}
+// bilinear read of a map at the unit direction d: the inverse of distance_texel_dir, then the four texels around (s, t)
+NGP_DEV float2 distance_map_read(const float2* __restrict__ map, f3 d) {
+	const float inv = 1.0f / (fabsf(d.x) + fabsf(d.y) + fabsf(d.z));
+	float a = d.x * inv, b = d.y * inv;
+	if (d.z < 0.0f) {
+		const float fa = (1.0f - fabsf(b)) * (a < 0.0f ? -1.0f : 1.0f), fb = (1.0f - fabsf(a)) * (b < 0.0f ? -1.0f : 1.0f);
+		a = fa;
+		b = fb;
+	}
+	const float s = 4.0f * (a + 1.0f) - 0.5f, t = 4.0f * (b + 1.0f) - 0.5f;
+	const float fs = __builtin_floorf(s), ft = __builtin_floorf(t);
+	const int i0 = min(max((int)fs, -1), 7), j0 = min(max((int)ft, -1), 7); // (|a|, |b| <= 1 up to rounding: the clamp keeps every read inside the map)
+	const float ws = s - fs, wt = t - ft;
+	const float2 t00 = distance_map_texel(map, i0, j0), t10 = distance_map_texel(map, i0 + 1, j0);
+	const float2 t01 = distance_map_texel(map, i0, j0 + 1), t11 = distance_map_texel(map, i0 + 1, j0 + 1);
+	const float w00 = (1.0f - ws) * (1.0f - wt), w10 = ws * (1.0f - wt), w01 = (1.0f - ws) * wt, w11 = ws * wt;
+	return make_float2((w00 * t00.x + w10 * t10.x) + (w01 * t01.x + w11 * t11.x), (w00 * t00.y + w10 * t10.y) + (w01 * t01.y + w11 * t11.y));
+}
+// position of probe i on an axis of r probes over [lo, hi], as the host places it: in double, rounded to float
+NGP_DEV float volume_probe_coord(float lo, float hi, uint32_t r, uint32_t i) {
+	const double frac = r > 1u ? (double)i / (double)(r - 1u) : 0.5;
+	return (float)((double)lo + frac * ((double)hi - (double)lo));
+}
+
+// irradiance_volume_lookup with every live corner's weight multiplied by the Chebyshev visibility of the point from that probe: cells, weights
+// and the order of operations are the plain lookup's, so vis = 1 at every corner gives its bits. The one definition: the visible lookup
+// kernel and the mesh pass's third instantiation both call it.
+NGP_DEV void irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, f3 p, f3 nh, float (&E)[3], float& W) {
+	const IrradianceVolume& V = A.V;
+	uint32_t i0[3];
+	float f[3];
+	volume_axis(p.x, V.lo[0], V.hi[0], V.res[0], i0[0], f[0]);
+	volume_axis(p.y, V.lo[1], V.hi[1], V.res[1], i0[1], f[1]);
+	volume_axis(p.z, V.lo[2], V.hi[2], V.res[2], i0[2], f[2]);
+	const f3 pb = add3(p, scale3(nh, A.normal_bias));
+	const float var_floor = 1e-4f * A.D * A.D;
+	float c[28];
+#pragma unroll
+	for (int j = 0; j < 28; ++j) c[j] = 0.f;
+	W = 0.f;
+#pragma unroll
+	for (uint32_t corner = 0; corner < 8u; ++corner) {
+		const uint32_t dx = corner & 1u, dy = (corner >> 1) & 1u, dz = corner >> 2;
+		const float wgt = (dx ? f[0] : 1.0f - f[0]) * (dy ? f[1] : 1.0f - f[1]) * (dz ? f[2] : 1.0f - f[2]);
+		if (wgt == 0.0f) continue;
+		const size_t g = (i0[0] + dx) + (size_t)V.res[0] * ((i0[1] + dy) + (size_t)V.res[1] * (i0[2] + dz));
+		const float4* rec = V.sh + 7 * g;
+		const float4 last = rec[6];
+		if (last.w == 0.0f) continue; // a dead probe
+		const f3 v = sub3(pb, mk3(volume_probe_coord(V.lo[0], V.hi[0], V.res[0], i0[0] + dx), volume_probe_coord(V.lo[1], V.hi[1], V.res[1], i0[1] + dy),
+		                          volume_probe_coord(V.lo[2], V.hi[2], V.res[2], i0[2] + dz)));
+		const float r = __builtin_sqrtf(dot3(v, v));
+		float vis = 1.0f;
+		if (r > 0.0f) {
+			const float2 m = distance_map_read(A.maps + DISTANCE_MAP_TEXELS * g, mk3(v.x / r, v.y / r, v.z / r));
+			if (!(r <= m.x)) {
+				const float var = fmaxf(m.y - m.x * m.x, var_floor), d = r - m.x;
+				const float ch = var / (var + d * d);
+				vis = ch * ch * ch;
+			}
+		}
+		const float wv = wgt * vis;
+#pragma unroll
+		for (int q = 0; q < 6; ++q) {
+			const float4 x = rec[q];
+			c[4 * q] += wv * x.x; c[4 * q + 1] += wv * x.y; c[4 * q + 2] += wv * x.z; c[4 * q + 3] += wv * x.w;
+		}
+		c[24] += wv * last.x; c[25] += wv * last.y; c[26] += wv * last.z;
+		W += wv;
+	}
+	E[0] = E[1] = E[2] = 0.f;
+	if (W > 0.0f) {
+		const float inv = 1.0f / W;
+#pragma unroll
+		for (int j = 0; j < 27; ++j) c[j] *= inv;
+		sh9_irradiance(c, nh.x, nh.y, nh.z, E);
+	}
+}
+
 // render_geometry_mesh (src/testbed_geometry_training.cu:2202-2320), Shade mode, floor disabled, one thread per pixel. The ambient source
-// is fixed at compile time by the type of A: IrradianceMap (the sky term, or the probe table(s) when A.irradiance is set) or
-// IrradianceVolume (ShadeIrradianceVolume: max(E(pos, N), 0) / pi from the SH9 lattice, 0 where every probe around pos is dead).
+// is fixed at compile time by the type of A: IrradianceMap (the sky term, or the probe table(s) when A.irradiance is set),
+// IrradianceVolume (ShadeIrradianceVolume: max(E(pos, N), 0) / pi from the SH9 lattice, 0 where every probe around pos is dead) or
+// IrradianceVolumeVisible (the same mode while the context holds the probes' distance maps: the visibility-weighted estimate).
 template <typename Ambient>
 __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer,
                                   float* __restrict__ depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed) {
@@ -357,6 +458,10 @@ __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams
 		float E[3], W;
 		irradiance_volume_lookup(A, pos, N, E, W);
 		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F); // (SH9 rings: E may dip below zero)
+	} else if constexpr (std::is_same<Ambient, IrradianceVolumeVisible>::value) {
+		float E[3], W;
+		irradiance_volume_lookup_visible(A, pos, N, E, W);
+		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
 	} else {
 		ambc = mul3(ld3(P.ambientcolor), skycol);
 		if (A.irradiance) { // ShadeEnvMap / ShadeGridEnvMap: ambient light = E(N)/pi from the NeRF-derived irradiance table(s)
@@ -380,12 +485,14 @@ __global__ void trace_mesh_rays_kernel(const MeshSceneParams S, uint32_t n, floa
 	directions[3 * (size_t)i] = d.x; directions[3 * (size_t)i + 1] = d.y; directions[3 * (size_t)i + 2] = d.z;
 }
 
-// V != nullptr: the ambient light comes from the SH9 volume (ShadeIrradianceVolume) and I is not looked at
-void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const CameraParams& C, float4* frame_buffer,
-                        float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream) {
+// V != nullptr: the ambient light comes from the SH9 volume (ShadeIrradianceVolume) and I is not looked at; VV != nullptr: from the volume
+// weighted by its probes' visibility, and neither V nor I is looked at
+void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
+                        const CameraParams& C, float4* frame_buffer, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream) {
 	dim3 threads(16, 8, 1);
 	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	if (V) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolume>, blocks, threads, 0, stream, S, P, *V, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
+	if (VV) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolumeVisible>, blocks, threads, 0, stream, S, P, *VV, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
+	else if (V) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolume>, blocks, threads, 0, stream, S, P, *V, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
 	else hipLaunchKernelGGL(render_mesh_fused<IrradianceMap>, blocks, threads, 0, stream, S, P, I, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
 }
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)
@@ -605,6 +712,63 @@ __global__ void irradiance_volume_lookup_kernel(const IrradianceVolume V, uint32
 	out[i] = make_float4(E[0], E[1], E[2], W);
 }
 
+// one wave per probe, four per workgroup: lane q owns texel q of the probe's distance map and sums rho = max(0, w_q . w_k)^(2^e), rho d and
+// rho d^2 over the probe's K rays in k order, d = min(t_max, D) (t: the chunk's rays as irradiance_sphere_rays_kernel wrote them, probe p's
+// at p K on). The rays are staged 64 at a time: lane j forms (w_k, d_k) of ray 64 c + j once and puts it into the wave's 1 KB of LDS, then
+// every lane walks the staged rays (all lanes read one address: a broadcast). No atomics and no butterfly: a map does not depend on the
+// run or on which other probes the launch carries. Every wave of a workgroup runs the same number of barriers (K is the launch's); a wave
+// past the last probe works on the last probe again and stores nothing.
+__global__ void __launch_bounds__(256) irradiance_distance_reduce_kernel(uint32_t n_u, uint32_t n_v, uint32_t n_probes, uint32_t sharpness_log2, float D,
+                                                                         const float2* __restrict__ t, float2* __restrict__ out) {
+	__shared__ float4 staged[4][64];
+	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, K = n_u * n_v;
+	const uint32_t p_own = blockIdx.x * 4u + wave;
+	const bool live = p_own < n_probes;
+	const uint32_t p = live ? p_own : n_probes - 1u;
+	const size_t base = (size_t)p * K;
+	const f3 wq = distance_texel_dir(lane);
+	float S = 0.f, s1 = 0.f, s2 = 0.f;
+	for (uint32_t k0 = 0; k0 < K; k0 += 64u) {
+		const uint32_t k = k0 + lane;
+		float4 ray = make_float4(0.f, 0.f, 0.f, 0.f);
+		if (k < K) { // (a tail chunk: no read past the probe's rays)
+			const f3 w = sphere_dir(k, n_u, n_v);
+			ray = make_float4(w.x, w.y, w.z, fminf(t[base + k].y, D));
+		}
+		staged[wave][lane] = ray;
+		__syncthreads();
+		const uint32_t m = K - k0 < 64u ? K - k0 : 64u; // (and no weight for a missing ray)
+		for (uint32_t j = 0; j < m; ++j) {
+			const float4 r = staged[wave][j];
+			float rho = fmaxf(0.0f, (wq.x * r.x + wq.y * r.y) + wq.z * r.z);
+			for (uint32_t i = 0; i < sharpness_log2; ++i) rho *= rho;
+			const float rd = rho * r.w;
+			S += rho;
+			s1 += rd;
+			s2 += rd * r.w;
+		}
+		__syncthreads(); // the next chunk overwrites the stage
+	}
+	if (!live) return; // (behind the last barrier)
+	out[(size_t)p * DISTANCE_MAP_TEXELS + lane] = S > 0.0f ? make_float2(s1 / S, s2 / S) : make_float2(D, D * D);
+}
+
+// one thread per point: out = (E rgb, W') of irradiance_volume_lookup_visible at the point and its normalised normal
+__global__ void irradiance_volume_lookup_visible_kernel(const IrradianceVolumeVisible A, uint32_t n, const float* __restrict__ positions, const float* __restrict__ normals,
+                                                        float4* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	float E[3], W;
+	irradiance_volume_lookup_visible(A, ld3(positions + 3 * (size_t)i), normalize3(ld3(normals + 3 * (size_t)i)), E, W);
+	out[i] = make_float4(E[0], E[1], E[2], W);
+}
+
+void launch_irradiance_distance_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, uint32_t sharpness_log2, float D, const float2* t, float2* out, hipStream_t stream) {
+	if (n_probes) hipLaunchKernelGGL(irradiance_distance_reduce_kernel, dim3((n_probes + 3) / 4), dim3(256), 0, stream, n_u, n_v, n_probes, sharpness_log2, D, t, out);
+}
+void launch_irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_volume_lookup_visible_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, A, n, positions, normals, out);
+}
 void launch_irradiance_sphere_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, float* o, float* d, float2* t,
                                    hipStream_t stream) {
 	if (n) hipLaunchKernelGGL(irradiance_sphere_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, o, d, t);

@@ -141,8 +141,9 @@ void launch_coarse_occupancy(const uint8_t* bitfield, uint32_t* coarse, hipStrea
 void launch_accumulate_tonemap(uint32_t n_pixels, const float4* frame_buffer, float4* accumulate_buffer, float sample_count, const float* background,
                                float exposure, int to_srgb, int color_space, float4* rgba_out, hipStream_t stream);
 
-void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const CameraParams& C, float4* frame_buffer,
-                        float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream); // V: the ShadeIrradianceVolume instantiation
+void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
+                        const CameraParams& C, float4* frame_buffer, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
+                        hipStream_t stream); // V: the ShadeIrradianceVolume instantiation; VV: the one that weights the probes by visibility
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t stream);
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
@@ -156,6 +157,8 @@ void launch_irradiance_sphere_rays(const MeshSceneParams& S, bool occlude, uint3
                                    hipStream_t stream);
 void launch_irradiance_sh_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, const float4* rgba, const float2* t, float4* out, hipStream_t stream);
 void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
+void launch_irradiance_distance_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, uint32_t sharpness_log2, float D, const float2* t, float2* out, hipStream_t stream);
+void launch_irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
 // scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.
@@ -333,6 +336,9 @@ struct ngp_ctx {
 	// ---- the SH9 irradiance volume (ngp_compute_irradiance_volume / ngp_set_irradiance_volume): data, never recomputed behind the caller
 	ngp::DevArray<float4> d_sh_volume; // 7 float4 a probe, probe-major (a peer holds a replica for ShadeIrradianceVolume frames: sync_peer_geometry)
 	ngp_irradiance_volume_desc sh_volume_desc{};
+	// ---- its probes' distance maps (ngp_compute_irradiance_volume_visibility / ngp_set_irradiance_volume_visibility): data like the volume, dropped with it
+	ngp::DevArray<float2> d_sh_visibility; // 64 float2 a probe, probe-major; empty: no visibility (a peer holds a replica like the volume's)
+	ngp_irradiance_visibility_desc sh_visibility_desc{}; // max_distance holds D
 
 	// ---- environment map behind the NeRF (m_envmap.inference_view(), testbed.h:1297-1316)
 	ngp::DevArray<float4> d_bg_envmap;
@@ -387,7 +393,7 @@ struct ngp_ctx {
 	uint64_t params_generation = 0, synced_params_generation = 0;       // the inference parameters followed a training step
 	uint64_t mesh_generation = 0, synced_mesh_generation = 0;           // the mesh list / BVHs changed (Geometry mode)
 	uint64_t probe_generation = 0, synced_probe_generation = 0;         // the irradiance probe textures were (re)computed
-	uint64_t sh_volume_generation = 0, synced_sh_volume_generation = 0; // the SH9 irradiance volume was computed, set or cleared
+	uint64_t sh_volume_generation = 0, synced_sh_volume_generation = 0; // the SH9 irradiance volume or its visibility was computed, set or cleared
 	ngp::DevArray<float4> d_pack_rgba;   // this device's tiles of the current frame, tile-packed
 	ngp::DevArray<float> d_pack_depth;   // (allocated last: its size is that of both)
 	ngp::DevArray<float4> d_gather_rgba; // primary: [device][slots * 64]
@@ -531,5 +537,13 @@ inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) {
 		V.hi[a] = ctx->sh_volume_desc.aabb_max[a];
 	}
 	return V;
+}
+inline IrradianceVolumeVisible sh_volume_visible_of(const ngp_ctx* ctx) {
+	IrradianceVolumeVisible A{};
+	A.V = sh_volume_of(ctx);
+	A.maps = ctx->d_sh_visibility.get();
+	A.D = ctx->sh_visibility_desc.max_distance;
+	A.normal_bias = ctx->sh_visibility_desc.normal_bias;
+	return A;
 }
 } // namespace ngp

@@ -226,5 +226,12 @@ struct IrradianceVolume { // a lattice of SH9 probes (sh9.h): probe g = i + res[
 	uint32_t res[3];
 	float lo[3], hi[3];
 };
+constexpr uint32_t DISTANCE_MAP_SIDE = 8, DISTANCE_MAP_TEXELS = 64; // a probe's octahedral map of (mean, mean squared) occluder distance
+struct IrradianceVolumeVisible { // the volume and its probes' distance maps: probe g's 64 float2 start at maps[64 g]
+	IrradianceVolume V;
+	const float2* maps;
+	float D;           // the distance the maps were capped at
+	float normal_bias; // the point a probe is looked at from: p + normal_bias n^
+};
 
 } // namespace ngp

@@ -621,6 +621,66 @@ void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp
 	tr.finish(); // (synchronises the stream: the chunk buffers may go)
 }
 
+// ---- probe visibility (contract: include/ngp_hip.h)
+void drop_visibility(ngp_ctx* ctx) {
+	ctx->d_sh_visibility.reset();
+	ctx->sh_visibility_desc = ngp_irradiance_visibility_desc{};
+}
+void require_volume(const ngp_ctx* ctx) {
+	if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+}
+void require_visibility(const ngp_ctx* ctx) {
+	if (!ctx->d_sh_visibility)
+		throw std::runtime_error("no irradiance visibility: call ngp_compute_irradiance_volume_visibility or ngp_set_irradiance_volume_visibility first");
+}
+// the descriptor's checks shared by the visibility entries, for n probes (rays: the entry traces); returns K, 0 without rays
+uint32_t check_visibility_desc(uint64_t n, const ngp_irradiance_visibility_desc* d, bool rays) {
+	if (!d) throw std::runtime_error("null argument");
+	if (d->sharpness_log2 > 6) throw std::runtime_error("invalid irradiance visibility descriptor: sharpness_log2 must be at most 6");
+	if (!std::isfinite(d->max_distance)) throw std::runtime_error("invalid irradiance visibility descriptor: max_distance is not finite");
+	if (!std::isfinite(d->normal_bias) || d->normal_bias < 0.0f) throw std::runtime_error("invalid irradiance visibility descriptor: normal_bias must be finite and >= 0");
+	if (!rays) return 0;
+	ngp_irradiance_sh_desc sh{};
+	sh.n_u = d->n_u;
+	sh.n_v = d->n_v;
+	return check_sh_desc(n, &sh);
+}
+// D of a volume whose descriptor asks for the default: 1.5 x the diagonal of one lattice cell, an axis of one probe counting with extent
+// 0; 1.5 x the box diagonal when every axis has one probe
+float default_max_distance(const ngp_irradiance_volume_desc& v) {
+	double cell = 0.0, box = 0.0;
+	for (int a = 0; a < 3; ++a) {
+		const double ext = (double)v.aabb_max[a] - (double)v.aabb_min[a];
+		box += ext * ext;
+		if (v.res[a] > 1) cell += (ext / (double)(v.res[a] - 1)) * (ext / (double)(v.res[a] - 1));
+	}
+	return (float)(1.5 * std::sqrt(v.res[0] > 1 || v.res[1] > 1 || v.res[2] > 1 ? cell : box));
+}
+// the maps of n probes at host positions: sphere rays against the meshes -> the moments, in chunks of whole probes (no tracer: the maps
+// need the BVHs alone). Each chunk's maps go to h_maps (host, n x 128 floats) and / or d_maps (device, 64 n float2); both nullable.
+void distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_visibility_desc* d, uint32_t K, float D, float* h_maps, float2* d_maps) {
+	const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+	const uint32_t cap_pts = (uint32_t)std::min<uint64_t>(n, cap);
+	DevArray<float> pts(3 * (size_t)cap_pts), o(3 * (size_t)cap), dir(3 * (size_t)cap);
+	DevArray<float2> t(cap), maps(ngp::DISTANCE_MAP_TEXELS * (size_t)cap_pts);
+	for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) { // (K <= RAY_CHUNK: whole probes)
+		const uint64_t p0 = r0 / K;
+		const uint32_t np = m / K;
+		upload(ctx, pts.get(), positions + 3 * p0, (size_t)np * 3 * sizeof(float));
+		ngp::launch_irradiance_sphere_rays(ctx->mesh_scene, true, d->n_u, d->n_v, m, pts.get(), o.get(), dir.get(), t.get(), ctx->stream);
+		ngp::launch_irradiance_distance_reduce(d->n_u, d->n_v, np, d->sharpness_log2, D, t.get(), maps.get(), ctx->stream);
+		const size_t bytes = (size_t)np * ngp::DISTANCE_MAP_TEXELS * sizeof(float2);
+		if (d_maps) NGP_HIP_CHECK(hipMemcpyAsync(d_maps + ngp::DISTANCE_MAP_TEXELS * p0, maps.get(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
+		if (h_maps) download(ctx, h_maps + 2 * ngp::DISTANCE_MAP_TEXELS * p0, maps.get(), bytes);
+	});
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (the chunk buffers may go)
+	NGP_HIP_CHECK(hipGetLastError());
+}
+void check_normals(uint32_t n, const float* normals) {
+	for (uint32_t i = 0; i < n; ++i)
+		if (!finite3(normals + 3 * (size_t)i) || !nonzero3(normals + 3 * (size_t)i)) throw std::runtime_error("normal " + std::to_string(i) + " is zero or not finite");
+}
+
 } // namespace
 
 extern "C" {
@@ -762,6 +822,7 @@ int ngp_compute_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc
 		trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, sh.get(), nullptr);
 		ctx->d_sh_volume = std::move(sh); // (the previous volume stays in place when the trace throws)
 		ctx->sh_volume_desc = *desc;
+		drop_visibility(ctx); // (the lattice may have changed)
 		++ctx->sh_volume_generation;
 	});
 }
@@ -778,6 +839,7 @@ int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* de
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old records)
 		ctx->d_sh_volume = std::move(d);
 		ctx->sh_volume_desc = *desc;
+		drop_visibility(ctx);
 		++ctx->sh_volume_generation;
 	});
 }
@@ -797,12 +859,14 @@ int ngp_clear_irradiance_volume(ngp_ctx* ctx) {
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
 		ctx->d_sh_volume.reset();
 		ctx->sh_volume_desc = ngp_irradiance_volume_desc{};
+		drop_visibility(ctx);
 		++ctx->sh_volume_generation;
 		for (ngp_ctx* p : ctx->peers) { // the replicas go too: a multi-device frame refuses like a single-device one
 			ngp::DeviceGuard g(p->device);
 			NGP_HIP_CHECK(hipStreamSynchronize(p->stream));
 			p->d_sh_volume.reset();
 			p->sh_volume_desc = ngp_irradiance_volume_desc{};
+			drop_visibility(p);
 			p->synced_sh_volume_generation = ctx->sh_volume_generation;
 		}
 	});
@@ -822,6 +886,95 @@ int ngp_irradiance_volume_at(ngp_ctx* ctx, uint32_t n, const float* positions, c
 		upload(ctx, d_p.get(), positions, (size_t)n * 3 * sizeof(float));
 		upload(ctx, d_n.get(), normals, (size_t)n * 3 * sizeof(float));
 		ngp::launch_irradiance_volume_lookup(ngp::sh_volume_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
+		download(ctx, out, d_o.get(), (size_t)n * sizeof(float4));
+		NGP_HIP_CHECK(hipGetLastError());
+	});
+}
+
+int ngp_irradiance_distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_visibility_desc* desc, float* maps_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		const uint32_t K = check_visibility_desc(n, desc, true);
+		if (!(desc->max_distance > 0.0f)) throw std::runtime_error("invalid irradiance visibility descriptor: max_distance must be > 0 here");
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!maps_out) throw std::runtime_error("null argument");
+		distance_maps(ctx, n, positions, desc, K, desc->max_distance, maps_out, nullptr);
+	});
+}
+
+int ngp_compute_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_visibility_desc* desc) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_volume(ctx);
+		const uint64_t probes = ctx->d_sh_volume.size() / SH_FLOAT4;
+		const uint32_t K = check_visibility_desc(probes, desc, true);
+		const float D = desc->max_distance > 0.0f ? desc->max_distance : default_max_distance(ctx->sh_volume_desc);
+		if (!(D > 0.0f) || !std::isfinite(D)) throw std::runtime_error("invalid irradiance visibility descriptor: the default max_distance of this volume is not a positive finite number");
+		const std::vector<float> positions = volume_positions(&ctx->sh_volume_desc, probes);
+		DevArray<float2> maps(ngp::DISTANCE_MAP_TEXELS * (size_t)probes);
+		distance_maps(ctx, (uint32_t)probes, positions.data(), desc, K, D, nullptr, maps.get());
+		ctx->d_sh_visibility = std::move(maps); // (the previous maps stay in place when a launch throws)
+		ctx->sh_visibility_desc = *desc;
+		ctx->sh_visibility_desc.max_distance = D;
+		++ctx->sh_volume_generation;
+	});
+}
+
+int ngp_get_irradiance_volume_visibility(ngp_ctx* ctx, ngp_irradiance_visibility_desc* desc_out, float* maps_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_volume(ctx);
+		require_visibility(ctx);
+		if (desc_out) *desc_out = ctx->sh_visibility_desc;
+		if (maps_out) download(ctx, maps_out, ctx->d_sh_visibility.get(), ctx->d_sh_visibility.size() * sizeof(float2));
+	});
+}
+
+int ngp_set_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_visibility_desc* desc, const float* maps) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_volume(ctx);
+		check_visibility_desc(0, desc, false);
+		if (!(desc->max_distance > 0.0f)) throw std::runtime_error("invalid irradiance visibility descriptor: max_distance must be > 0 for maps that are set");
+		if (!maps) throw std::runtime_error("null argument");
+		const size_t probes = ctx->d_sh_volume.size() / SH_FLOAT4, texels = ngp::DISTANCE_MAP_TEXELS * probes;
+		for (size_t i = 0; i < 2 * texels; ++i)
+			if (!std::isfinite(maps[i]) || maps[i] < 0.0f)
+				throw std::runtime_error("irradiance visibility: m" + std::to_string(i % 2 + 1) + " of texel " + std::to_string(i / 2 % 64) + " of probe " + std::to_string(i / 128) +
+				                         (std::isfinite(maps[i]) ? " is negative" : " is not finite"));
+		DevArray<float2> d;
+		d.upload(reinterpret_cast<const float2*>(maps), texels);
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old maps)
+		ctx->d_sh_visibility = std::move(d);
+		ctx->sh_visibility_desc = *desc;
+		++ctx->sh_volume_generation;
+	});
+}
+
+int ngp_clear_irradiance_volume_visibility(ngp_ctx* ctx) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+		drop_visibility(ctx);
+		++ctx->sh_volume_generation;
+	});
+}
+
+int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, float* out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_volume(ctx);
+		require_visibility(ctx);
+		if (n == 0) return;
+		if (!positions || !normals || !out) throw std::runtime_error("null argument");
+		check_positions(n, positions);
+		check_normals(n, normals);
+		DevArray<float> d_p(3 * (size_t)n), d_n(3 * (size_t)n);
+		DevArray<float4> d_o(n);
+		upload(ctx, d_p.get(), positions, (size_t)n * 3 * sizeof(float));
+		upload(ctx, d_n.get(), normals, (size_t)n * 3 * sizeof(float));
+		ngp::launch_irradiance_volume_lookup_visible(ngp::sh_volume_visible_of(ctx), n, d_p.get(), d_n.get(), d_o.get(), ctx->stream);
 		download(ctx, out, d_o.get(), (size_t)n * sizeof(float4));
 		NGP_HIP_CHECK(hipGetLastError());
 	});
@@ -895,6 +1048,16 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 			DeviceGuard g(peer->device);
 			NGP_HIP_CHECK(hipMemcpyPeer(peer->d_sh_volume.get(), peer->device, primary->d_sh_volume.get(), primary->device, n * sizeof(float4)));
 		}
+		const size_t nv = primary->d_sh_visibility.size(); // the distance maps follow the records (a volume without visibility: the replica's are dropped)
+		{
+			DeviceGuard g(peer->device);
+			peer->d_sh_visibility.reset();
+			if (nv) {
+				peer->d_sh_visibility.reset(nv);
+				NGP_HIP_CHECK(hipMemcpyPeer(peer->d_sh_visibility.get(), peer->device, primary->d_sh_visibility.get(), primary->device, nv * sizeof(float2)));
+			}
+		}
+		peer->sh_visibility_desc = primary->sh_visibility_desc;
 		peer->sh_volume_desc = primary->sh_volume_desc;
 		peer->synced_sh_volume_generation = primary->sh_volume_generation;
 	}

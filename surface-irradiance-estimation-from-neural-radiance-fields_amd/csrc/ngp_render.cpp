@@ -290,8 +290,10 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 				if (!ctx->d_sh_volume) throw std::runtime_error("render_mode ShadeIrradianceVolume needs ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
 				V = sh_volume_of(ctx);
 			}
+			const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
+			const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[slot], stream)); // (ngp_get_mesh_pass_ms)
-			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));

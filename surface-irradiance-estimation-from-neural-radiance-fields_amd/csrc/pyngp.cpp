@@ -249,19 +249,35 @@ PYBIND11_MODULE(pyngp, m) {
 		}, "The irradiance volume the context holds, as compute_irradiance_volume returns it (a ShadeIrradianceVolume render computes a default one when there is none)")
 		.def_readwrite("irradiance_volume_res", &Testbed::m_irradiance_volume_res, "probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none")
 		.def("irradiance_volume_lookup", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions,
-		                                    py::array_t<float, py::array::c_style | py::array::forcecast> normals) {
+		                                    py::array_t<float, py::array::c_style | py::array::forcecast> normals, bool visible) {
 			if (positions.ndim() != 2 || positions.shape(1) != 3 || normals.ndim() != 2 || normals.shape(1) != 3 || positions.shape(0) != normals.shape(0))
 				throw std::runtime_error("positions and normals: (n, 3) each");
 			const uint32_t n = (uint32_t)positions.shape(0);
 			std::vector<float> e;
 			{
 				py::gil_scoped_release nogil;
-				e = t.irradiance_volume_lookup(positions.data(), normals.data(), n);
+				e = t.irradiance_volume_lookup(positions.data(), normals.data(), n, visible);
 			}
 			py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)4});
 			if (n) memcpy(a.mutable_data(), e.data(), e.size() * sizeof(float));
 			return a;
-		}, py::arg("positions"), py::arg("normals"), "E(p, n) read from the irradiance volume: (n, 4) = rgb, weight of the live probes around the point")
+		}, py::arg("positions"), py::arg("normals"), py::arg("visible") = false,
+		   "E(p, n) read from the irradiance volume: (n, 4) = rgb, weight of the live probes around the point (visible: weighted by the probes' visibility)")
+		.def("compute_irradiance_volume_visibility", [](Testbed& t, uint32_t n_u, uint32_t n_v, uint32_t sharpness_log2, float max_distance, float normal_bias) {
+			std::array<uint32_t, 3> res{};
+			std::vector<float> maps;
+			{
+				py::gil_scoped_release nogil;
+				maps = t.compute_irradiance_volume_visibility(n_u, n_v, sharpness_log2, max_distance, normal_bias, &res);
+			}
+			py::array_t<float> a({(py::ssize_t)res[2], (py::ssize_t)res[1], (py::ssize_t)res[0], (py::ssize_t)64, (py::ssize_t)2});
+			if (!maps.empty()) memcpy(a.mutable_data(), maps.data(), maps.size() * sizeof(float));
+			return a;
+		}, py::arg("n_u") = 16, py::arg("n_v") = 16, py::arg("sharpness_log2") = 5, py::arg("max_distance") = 0.f, py::arg("normal_bias") = 0.f,
+		   "This project's own: distance maps for the probes of the held irradiance volume, (rz, ry, rx, 64, 2) = mean and mean squared distance to the nearest mesh per "
+		   "octahedral texel; while they are held, ShadeIrradianceVolume frames weight every probe by its visibility")
+		.def_readwrite("irradiance_volume_visibility", &Testbed::m_irradiance_volume_visibility,
+		               "the default volume a ShadeIrradianceVolume render computes also gets visibility (compute_irradiance_volume_visibility with its defaults)")
 		.def("frame", &Testbed::frame, py::call_guard<py::gil_scoped_release>(), "Process a single frame: one training step when shall_train is set (headless, nothing is drawn).")
 		.def("train", &Testbed::train, py::call_guard<py::gil_scoped_release>(), "Perform a single training step with a specified batch size.")
 		.def("reset", &Testbed::reset_network, py::arg("reset_density_grid") = true, "Reset training.")

@@ -431,8 +431,10 @@ public:
 			if (m_render_mode == ERenderMode::ShadeGridEnvMap && !m_envmap_grid_ready) computeEnvmapGrid();
 			if (m_render_mode == ERenderMode::ShadeEnvMap && !m_envmap_ready) computeEnvmapMultipleMain();
 			// ShadeIrradianceVolume: a context without a volume gets the default one; a volume the caller set or computed is never replaced
-			if (m_render_mode == ERenderMode::ShadeIrradianceVolume && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0)
+			if (m_render_mode == ERenderMode::ShadeIrradianceVolume && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0) {
 				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res});
+				if (m_irradiance_volume_visibility) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
+			}
 		}
 		ngp_camera cam{};
 		memcpy(cam.matrix, m_camera.data(), sizeof(cam.matrix));
@@ -553,13 +555,28 @@ public:
 		memcpy(aabb6_out + 3, d.aabb_max, 12);
 		return out;
 	}
-	// E(p, n) read from the volume: n x 4 = rgb irradiance, weight of the live probes around the point
-	std::vector<float> irradiance_volume_lookup(const float* positions, const float* normals, uint32_t n) {
+	// E(p, n) read from the volume: n x 4 = rgb irradiance, weight of the live probes around the point; visible: the probes weighted by
+	// their visibility from the point (compute_irradiance_volume_visibility)
+	std::vector<float> irradiance_volume_lookup(const float* positions, const float* normals, uint32_t n, bool visible = false) {
 		std::vector<float> out((size_t)n * 4);
-		check(ngp_irradiance_volume_at(m_ctx, n, positions, normals, out.data()));
+		check(visible ? ngp_irradiance_volume_at_visible(m_ctx, n, positions, normals, out.data()) : ngp_irradiance_volume_at(m_ctx, n, positions, normals, out.data()));
+		return out;
+	}
+	// distance maps for the probes of the held volume, kept in the context: ShadeIrradianceVolume frames and visible lookups use them.
+	// Returns the maps, probes x 64 x 2 in index order, and the lattice's resolution in res_out
+	std::vector<float> compute_irradiance_volume_visibility(uint32_t n_u = 16, uint32_t n_v = 16, uint32_t sharpness_log2 = 5, float max_distance = 0.f, float normal_bias = 0.f,
+	                                                        std::array<uint32_t, 3>* res_out = nullptr) {
+		ngp_irradiance_visibility_desc d{n_u, n_v, sharpness_log2, max_distance, normal_bias};
+		check(ngp_compute_irradiance_volume_visibility(m_ctx, &d));
+		ngp_irradiance_volume_desc v{};
+		check(ngp_get_irradiance_volume(m_ctx, &v, nullptr));
+		std::vector<float> out((size_t)v.res[0] * v.res[1] * v.res[2] * 128);
+		check(ngp_get_irradiance_volume_visibility(m_ctx, &d, out.data()));
+		if (res_out) *res_out = {v.res[0], v.res[1], v.res[2]};
 		return out;
 	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
+	bool m_irradiance_volume_visibility = false; // the default volume of a ShadeIrradianceVolume render also gets distance maps (16 x 16 rays, sharpness 2^5, D and bias default)
 	uint32_t m_irradiance_volume_res = 8; // probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none (32 x 32 rays, meshes occluding)
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path
 	bool m_has_camera_end = false;

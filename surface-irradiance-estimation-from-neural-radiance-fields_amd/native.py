@@ -105,6 +105,10 @@ class IrradianceVolumeDesc(C.Structure):
     _fields_ = [("res", C.c_uint32 * 3), ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("sh", IrradianceShDesc)]
 
 
+class IrradianceVisibilityDesc(C.Structure):
+    _fields_ = [("n_u", C.c_uint32), ("n_v", C.c_uint32), ("sharpness_log2", C.c_uint32), ("max_distance", C.c_float), ("normal_bias", C.c_float)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64), ("n_rays_alive_after_init", C.c_uint64), ("n_rays_hit", C.c_uint64), ("n_samples", C.c_uint64),
@@ -226,6 +230,12 @@ def load_library():
     L.ngp_set_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
     L.ngp_clear_irradiance_volume.argtypes = [vp]
     L.ngp_irradiance_volume_at.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    L.ngp_irradiance_distance_maps.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceVisibilityDesc), vp]
+    L.ngp_compute_irradiance_volume_visibility.argtypes = [vp, C.POINTER(IrradianceVisibilityDesc)]
+    L.ngp_get_irradiance_volume_visibility.argtypes = [vp, C.POINTER(IrradianceVisibilityDesc), vp]
+    L.ngp_set_irradiance_volume_visibility.argtypes = [vp, C.POINTER(IrradianceVisibilityDesc), vp]
+    L.ngp_clear_irradiance_volume_visibility.argtypes = [vp]
+    L.ngp_irradiance_volume_at_visible.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -746,15 +756,62 @@ class Context:
     def clear_irradiance_volume(self):
         self._check(self.L.ngp_clear_irradiance_volume(self.h))
 
-    def irradiance_volume_at(self, positions, normals):
-        """E(p, n) read from the volume: (n, 4) = rgb irradiance, weight of the live probes around the point"""
+    def irradiance_volume_at(self, positions, normals, visible=False):
+        """E(p, n) read from the volume: (n, 4) = rgb irradiance, weight of the live probes around the point; visible: every probe weighted
+        by its visibility from the point (needs compute_irradiance_volume_visibility or set_irradiance_volume_visibility)"""
         p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
         n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         if p.shape != n.shape:
             raise ValueError("positions and normals: n x 3 each")
         out = np.zeros((p.shape[0], 4), np.float32)
-        self._check(self.L.ngp_irradiance_volume_at(self.h, p.shape[0], _p(p), _p(n), _p(out)))
+        f = self.L.ngp_irradiance_volume_at_visible if visible else self.L.ngp_irradiance_volume_at
+        self._check(f(self.h, p.shape[0], _p(p), _p(n), _p(out)))
         return out
+
+    # ---------------------------------------------------------------- probe visibility (contract: include/ngp_hip.h)
+    @staticmethod
+    def _visibility_desc(n_u, n_v, sharpness_log2, max_distance, normal_bias):
+        d = IrradianceVisibilityDesc()
+        d.n_u, d.n_v, d.sharpness_log2, d.max_distance, d.normal_bias = n_u, n_v, sharpness_log2, max_distance, normal_bias
+        return d
+
+    def irradiance_distance_maps(self, positions, n_u=16, n_v=16, sharpness_log2=5, max_distance=1.0):
+        """the distance maps of probes at `positions`: (n, 64, 2) = mean and mean squared distance to the nearest mesh per octahedral texel"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        d = self._visibility_desc(n_u, n_v, sharpness_log2, max_distance, 0.0)
+        maps = np.zeros((p.shape[0], 64, 2), np.float32)
+        self._check(self.L.ngp_irradiance_distance_maps(self.h, p.shape[0], _p(p), C.byref(d), _p(maps)))
+        return maps
+
+    def compute_irradiance_volume_visibility(self, n_u=16, n_v=16, sharpness_log2=5, max_distance=0.0, normal_bias=0.0):
+        """distance maps for the probes of the held volume; they stay on the device (get_irradiance_volume_visibility). max_distance <= 0:
+        1.5 x the diagonal of a lattice cell"""
+        d = self._visibility_desc(n_u, n_v, sharpness_log2, max_distance, normal_bias)
+        self._check(self.L.ngp_compute_irradiance_volume_visibility(self.h, C.byref(d)))
+
+    def get_irradiance_volume_visibility(self):
+        """(desc, maps (rz, ry, rx, 64, 2)); desc.max_distance is the D in use"""
+        v = IrradianceVolumeDesc()
+        self._check(self.L.ngp_get_irradiance_volume(self.h, C.byref(v), None))
+        d = IrradianceVisibilityDesc()
+        maps = np.zeros((v.res[2], v.res[1], v.res[0], 64, 2), np.float32)
+        self._check(self.L.ngp_get_irradiance_volume_visibility(self.h, C.byref(d), _p(maps)))
+        return d, maps
+
+    def set_irradiance_volume_visibility(self, maps, max_distance, sharpness_log2=5, normal_bias=0.0, n_u=0, n_v=0):
+        """a caller's own maps (rz, ry, rx, 64, 2) for the held volume's probes; n_u, n_v only describe how they were made"""
+        maps = np.ascontiguousarray(maps, np.float32)
+        if maps.ndim != 5 or maps.shape[3:] != (64, 2):
+            raise ValueError("maps: (rz, ry, rx, 64, 2)")
+        v = IrradianceVolumeDesc()
+        self._check(self.L.ngp_get_irradiance_volume(self.h, C.byref(v), None))
+        if maps.shape[:3] != (v.res[2], v.res[1], v.res[0]):
+            raise ValueError("maps: the held volume has (rz, ry, rx) = (%d, %d, %d)" % (v.res[2], v.res[1], v.res[0]))
+        d = self._visibility_desc(n_u, n_v, sharpness_log2, max_distance, normal_bias)
+        self._check(self.L.ngp_set_irradiance_volume_visibility(self.h, C.byref(d), _p(maps)))
+
+    def clear_irradiance_volume_visibility(self):
+        self._check(self.L.ngp_clear_irradiance_volume_visibility(self.h))
 
     # ---------------------------------------------------------------- stages
     def grid_encode(self, pos01):

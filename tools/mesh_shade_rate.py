@@ -1,9 +1,11 @@
 """What the mesh pass costs per shade mode on the MI355X: the device time of render_mesh_fused at 1920 x 1080 on the meshes of the mesh
 tests' render scene (cube, icosphere, upright torus; the icosphere and the torus finer, so that the BVHs have some depth), lit by the sky
 term (Shade), by the grid of lat-long irradiance tables (ShadeGridEnvMap) and by the SH9 irradiance volume (ShadeIrradianceVolume) at 8^3 and
-at 32^3 probes.
+at 32^3 probes. With --visibility: Shade, the plain volume and the volume with its probes weighted by visibility (distance maps of 16 x 16 rays,
+sharpness 2^5, default D) at 8^3 and 32^3 probes in one run, and the wall time of computing the maps of 16^3 probes x 16 x 16 rays.
 
     python tools/mesh_shade_rate.py [--width 1920] [--height 1080] [--frames 30] [--warmup 5] [--out profiles/mesh_shade_rate.json]
+    python tools/mesh_shade_rate.py --visibility [--out profiles/mesh_shade_visibility_rate.json]
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -48,7 +50,7 @@ def median_ms(ctx, cam, opts, frames, warmup):
         _, depth = ctx.render(cam, opts, want_depth=True)
         if i >= warmup:
             ts.append(ctx.mesh_pass_ms())
-    return float(np.median(ts)), float(np.min(ts)), float((depth < 16384.0).mean())
+    return float(np.median(ts)), float(np.min(ts)), float((depth < 16384.0).mean()), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
 
 
 def main():
@@ -57,8 +59,11 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_shade_rate.json"))
+    ap.add_argument("--visibility", action="store_true", help="the visibility-weighted volume against Shade and the plain volume, and the maps' compute time")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -79,19 +84,42 @@ def main():
     ctx.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
     rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid")]
     rows += [("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r) for r in (8, 32)]
+    if args.visibility:  # one run: Shade, then per resolution the plain volume and the same volume with visibility
+        rows = [rows[0]] + [row for r in (8, 32) for row in (("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r),
+                                                             ("ShadeIrradianceVolumeVisible_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, -r))]
     for name, mode, what in rows:
         if what == "grid":  # the reference's default grid: 8 x 8 probes of 64 x 32 texels
             ctx.compute_envmap_grid(8, 8, 64, 32)
-        elif what is not None:  # over the scene box, meshes occluding: the probes inside the closed meshes are dead
+        elif what is not None and what > 0:  # over the scene box, meshes occluding: the probes inside the closed meshes are dead
             ctx.compute_irradiance_volume((what,) * 3, (lo, hi), 16, 16)
-        med, mn, cover = median_ms(ctx, cam, native.make_opts(render_mode=mode, **geo), args.frames, args.warmup)
-        out["modes"][name] = {"median_ms": round(med, 4), "min_ms": round(mn, 4), "pixels_with_depth": round(cover, 3)}
-        if isinstance(what, int):
+        elif what is not None:  # the volume of the row before, with distance maps
+            ctx.compute_irradiance_volume_visibility(16, 16, 5)
+        med, mn, cover, p10, p90 = median_ms(ctx, cam, native.make_opts(render_mode=mode, **geo), args.frames, args.warmup)
+        out["modes"][name] = {"median_ms": round(med, 4), "min_ms": round(mn, 4), "p10_ms": round(p10, 4), "p90_ms": round(p90, 4), "pixels_with_depth": round(cover, 3)}
+        if isinstance(what, int) and what > 0:
             out["modes"][name]["dead_probes"] = round(float((ctx.get_irradiance_volume()[1][..., 27] == 0).mean()), 4)
         print(f"{name:28s} median {med:.4f} ms  min {mn:.4f} ms", flush=True)
     base = out["modes"]["Shade"]["median_ms"]
     for m in out["modes"].values():
         m["ratio_to_shade"] = round(m["median_ms"] / base, 3)
+    if args.visibility:
+        import time
+
+        for r in (8, 32):
+            out["modes"]["ShadeIrradianceVolumeVisible_%d" % r]["ratio_to_plain_volume"] = round(
+                out["modes"]["ShadeIrradianceVolumeVisible_%d" % r]["median_ms"] / out["modes"]["ShadeIrradianceVolume_%d" % r]["median_ms"], 3)
+        # the maps' compute: 16^3 probes x 16 x 16 rays against the BVHs, wall time of the whole call (it ends synchronised). The device time
+        # is not measured: the call has no timing entry.
+        ctx.compute_irradiance_volume((16,) * 3, (lo, hi), 8, 8)
+        ts = []
+        for i in range(2 + 7):
+            t0 = time.perf_counter()
+            ctx.compute_irradiance_volume_visibility(16, 16, 5)
+            if i >= 2:
+                ts.append(1e3 * (time.perf_counter() - t0))
+        out["visibility_compute_16x16x16_probes_16x16_rays"] = {"wall_median_ms": round(float(np.median(ts)), 3), "wall_min_ms": round(min(ts), 3), "wall_max_ms": round(max(ts), 3),
+                                                                 "runs": len(ts), "warmup": 2, "device_ms": None}
+        print("visibility compute, 16^3 probes x 256 rays: wall median %.3f ms (min %.3f, max %.3f)" % (np.median(ts), min(ts), max(ts)), flush=True)
     print(json.dumps(out))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
