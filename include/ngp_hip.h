@@ -413,7 +413,7 @@ NGP_API int ngp_irradiance_rays(ngp_ctx* ctx, uint32_t n, const float* positions
 /* ngp_irradiance_traced: the estimate. The generator's rays go through ngp_trace_nerf_rays' tracer (t_min = 0, t_max as generated) and a
  *   reduction writes per point out n x 4: rgb = (pi / K) sum_k rgb_k, the cosine-weighted estimator (a constant radiance L gives pi L),
  *   and w = the fraction of the point's K rays that no mesh blocks (1 without occlusion). A blocked ray still contributes the NeRF
- *   radiance in front of its hit; a mesh adds no radiance of its own (no interreflection). The sum runs in a fixed order (one wave per
+ *   radiance in front of its hit; a mesh adds no radiance of its own here (interreflection: the SH9 volume's bounces, below). The sum runs in a fixed order (one wave per
  *   point, lane-strided, then a butterfly; no atomics), so the result is bit-identical from run to run and does not depend on how many
  *   points one call carries. Limits and refusals as for ngp_irradiance_rays; no model is refused too. */
 NGP_API int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_irradiance_trace_desc* desc,
@@ -433,7 +433,7 @@ NGP_API int ngp_irradiance_traced(ngp_ctx* ctx, uint32_t n, const float* positio
  *   Y_1..3 = -0.48860251 y, 0.48860251 z, -0.48860251 x; Y_4..8 = 1.09254843 xy, -1.09254843 yz, 0.94617470 z^2 - 0.31539157,
  *   -1.09254843 xz, 0.54627422 (x^2 - y^2).
  * Probe record: 28 floats. c[3 m + ch] = (4 pi / K) sum_k L_ch(w_k) Y_m(w_k), m = 0..8, ch = r, g, b, with L the linear premultiplied rgb
- *   of ngp_trace_nerf_rays (a blocked ray contributes what lies in front of its hit; a mesh adds no radiance of its own). Float 27 = w, the
+ *   of ngp_trace_nerf_rays (a blocked ray contributes what lies in front of its hit; a mesh adds no radiance of its own: that is the bounces' part, below). Float 27 = w, the
  *   fraction of the K rays that no mesh blocks. The sum runs in a fixed order (one wave per probe, lane-strided, then a butterfly; no
  *   atomics): a record is bit-identical from run to run and for any split of the probes over calls or chunks.
  * Evaluation: E(n) = sum_m A_m c_m Y_m(n^), n^ = n / |n|, A = pi (m = 0), 2 pi / 3 (m = 1..3), pi / 4 (m = 4..8): the clamped-cosine
@@ -541,6 +541,50 @@ NGP_API int ngp_get_irradiance_volume_visibility(ngp_ctx* ctx, ngp_irradiance_vi
 NGP_API int ngp_set_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_visibility_desc* desc, const float* maps /* probes x 64 x 2 */);
 NGP_API int ngp_clear_irradiance_volume_visibility(ngp_ctx* ctx);
 NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const float* normals /* n x 3 */, float* out /* n x 4 */);
+
+/* --- bounces: diffuse interreflection between the inserted meshes and the volume. A probe ray that a mesh blocks carries, in the records
+ * above, the NeRF in front of the hit and nothing from the hit itself: meshes only darken. A bounce pass adds the light the hit surface
+ * throws back, read from the volume of the pass before. This project's own contract.
+ *
+ * Let V_0 be the records ngp_compute_irradiance_volume produces. For bounce b = 1..N and every probe g:
+ * Rays: the volume's own K = n_u n_v sphere directions w_k, origin o = the probe.
+ * Closest hit: t_k = the closest triangle hit over all loaded meshes (the SH9 section's rule), m its mesh and i its triangle. Without a
+ *   hit, or with occlude_by_meshes == 0, the ray carries no bounce.
+ * Hit point and normal: h = o + t_k w_k in float32, the product rounded before the sum (no fused multiply-add);
+ *   N = normalize(cross(b - a, c - a)) of the hit triangle, the normal ngp_trace_mesh_rays leaves; N_ff = N if N . w_k < 0, else -N.
+ * Source: (E, W) = the lookup of V_{b-1} at (h, N_ff): ngp_irradiance_volume_at's, or, when the call is given a visibility descriptor,
+ *   ngp_irradiance_volume_at_visible's with that lookup's own normal_bias and no other offset.
+ * Radiance leaving the hit: M_ch = albedo_ch max(E_ch, 0) / pi; 0 where W = 0. The mesh is opaque and diffuse.
+ * Bounce radiance of the ray: B_k = (1 - alpha_k) M, alpha_k the alpha of the ray's NeRF trace (the rgba.w V_0 was projected from): the
+ *   NeRF in front of the hit attenuates the bounce.
+ * Records: R_b = the SH9 section's projection of B (the same order, the 4 pi / K scale, coefficients 0..26); V_b[j] = V_0[j] + R_b[j] in
+ *   float32 for j < 27; float 27 (w, the unblocked fraction) stays V_0's, so the dead-probe rule is unchanged.
+ * Order: every probe of V_b reads V_{b-1} alone: the records are double-buffered, never updated in place.
+ * Determinism: no atomics; bit-identical from run to run and for any chunking. With N = 0, every albedo channel 0, no meshes loaded or
+ *   occlude_by_meshes == 0 no pass runs and the records are V_0's as bytes.
+ * Limits: N <= 16; every albedo channel finite and in [0, 1]; each refused with a message that names the field.
+ * Out of scope: sun light on the meshes as a bounce source; glossy transport; a NeRF surface lit by the meshes; probes inside closed
+ *   meshes (they stay dead: a room built of meshes alone gets nothing); bounces for the lat-long probe tables.
+ * Refusals: those of the volume and visibility sections; ngp_irradiance_sh_bounce without a volume ("no irradiance volume") and with
+ *   use_visible without visibility ("no irradiance visibility"); a non-finite alpha. */
+typedef struct ngp_irradiance_bounce_desc {
+	uint32_t n_bounces; /* N, at most 16 */
+	float albedo[3];    /* of every mesh, each channel in [0, 1] */
+} ngp_irradiance_bounce_desc;
+/* V_N, kept like ngp_compute_irradiance_volume's result: on the primary device, the held visibility dropped. With `visibility` non-NULL
+ * the distance maps of the new lattice are computed BEFORE the bounces, used by them, and left in the context as
+ * ngp_compute_irradiance_volume_visibility would leave them. The per-ray alpha of the whole volume (one float a ray, at most 2^28 rays =
+ * 1 GB) lives for the duration of the call: the NeRF is traced ONCE however large N is. */
+NGP_API int ngp_compute_irradiance_volume_bounced(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                                  const ngp_irradiance_visibility_desc* visibility /* nullable */);
+/* a stage entry for tests: ONE bounce pass at the caller's probes from the volume (and, with use_visible, the visibility) the context
+ * HOLDS. Needs the meshes and a volume, no model. alpha: n K caller-given values (NULL: 0); desc->min_transmittance is not looked at.
+ * rays_out (nullable) n K x 4 = (B_rgb, t of the hit or +inf); sh_out n x 28 = R, float 27 = the unblocked fraction */
+NGP_API int ngp_irradiance_sh_bounce(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_sh_desc* desc, const float albedo[3],
+                                     const float* alpha /* nullable, n K */, int use_visible, float* sh_out /* n x 28 */, float* rays_out /* nullable, n K x 4 */);
+/* device time (HIP events) of the last bounce pass of either entry, ms: its chunks' uploads, rays, projections and sums. Nothing in the
+ * contract depends on it; tools/irradiance_bounce_rate.py reads it. */
+NGP_API int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -780,4 +780,84 @@ void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, cons
 	if (n) hipLaunchKernelGGL(irradiance_volume_lookup_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, V, n, positions, normals, out);
 }
 
+
+// ---- diffuse interreflection (ngp_compute_irradiance_volume_bounced, ngp_irradiance_sh_bounce; contract in include/ngp_hip.h, "bounces").
+// One pass feeds a volume back into itself at the mesh hits of its probes' sphere rays: the rays of irradiance_sphere_rays_kernel, the
+// closest hit with its mesh and triangle kept, the volume's estimate at the hit, and irradiance_sh_reduce_kernel unchanged behind it.
+
+// the n rays of a chunk of whole probes, one thread a ray: rgba_out = (B rgb, t of the hit or +inf), t_out = (0, the same t) as the
+// projection counts it. B = (1 - alpha) albedo max(E, 0) / pi with (E, W) the lookup A at the hit point o + t w and the hit triangle's
+// winding normal turned against the ray; 0 without a hit and where W = 0. alpha: the chunk's rays' NeRF alpha (nullptr: 0). The lookup's
+// accumulators are live behind the traversals only, as in render_mesh_fused.
+template <typename Lookup>
+__global__ void irradiance_bounce_rays_kernel(const MeshSceneParams S, const Lookup A, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
+                                              float albedo_r, float albedo_g, float albedo_b, const float* __restrict__ alpha, float4* __restrict__ rgba_out,
+                                              float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
+	const f3 dir = sphere_dir(k, n_u, n_v);
+	const f3 org = ld3(positions + 3 * (size_t)pl);
+	float t_max = __builtin_huge_valf();
+	int mesh = -1, tri_idx = -1;
+	if (occlude) {
+		for (uint32_t m = 0; m < S.n_meshes; ++m) {
+			int idx;
+			float t;
+			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
+			if (idx > -1 && t < t_max) {
+				t_max = t;
+				mesh = (int)m;
+				tri_idx = idx;
+			}
+		}
+	}
+	f3 B = mk3(0.f, 0.f, 0.f);
+	if (mesh > -1) {
+		const Triangle& tri = S.meshes[mesh].tris[tri_idx];
+		const f3 a = ld3(tri.a);
+		const f3 N = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
+		const f3 nff = dot3(N, dir) < 0.0f ? N : scale3(N, -1.0f);
+		const f3 h = add3(org, scale3(dir, t_max));
+		float E[3], W;
+		if constexpr (std::is_same<Lookup, IrradianceVolumeVisible>::value) irradiance_volume_lookup_visible(A, h, nff, E, W);
+		else irradiance_volume_lookup(A, h, nff, E, W);
+		if (W > 0.0f) {
+			const float through = 1.0f - (alpha ? alpha[i] : 0.0f);
+			B = mk3(through * (albedo_r * fmaxf(E[0], 0.0f) / PI_F), through * (albedo_g * fmaxf(E[1], 0.0f) / PI_F), through * (albedo_b * fmaxf(E[2], 0.0f) / PI_F));
+		}
+	}
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// out = v0 + r on the 27 coefficients of every record, one thread per float4 (7 a probe); the seventh keeps v0's w
+__global__ void irradiance_volume_add_kernel(uint32_t n_float4, const float4* __restrict__ v0, const float4* __restrict__ r, float4* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_float4) return;
+	const float4 a = v0[i], b = r[i];
+	out[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, i % 7u == 6u ? a.w : a.w + b.w);
+}
+
+// alpha[i] = rgba[i].w: the tracer's alpha of a chunk's rays, kept for the bounce passes
+__global__ void ray_alpha_kernel(uint32_t n, const float4* __restrict__ rgba, float* __restrict__ alpha) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) alpha[i] = rgba[i].w;
+}
+
+// VV != nullptr: the lookup weighted by the probes' visibility, and V is not looked at
+void launch_irradiance_bounce_rays(const MeshSceneParams& S, const IrradianceVolume& V, const IrradianceVolumeVisible* VV, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n,
+                                   const float* positions, const float* albedo, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
+	if (!n) return;
+	const dim3 blocks((n + 127) / 128), threads(128);
+	if (VV) hipLaunchKernelGGL(irradiance_bounce_rays_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, S, *VV, occlude ? 1 : 0, n_u, n_v, n, positions, albedo[0], albedo[1], albedo[2], alpha, rgba, t);
+	else hipLaunchKernelGGL(irradiance_bounce_rays_kernel<IrradianceVolume>, blocks, threads, 0, stream, S, V, occlude ? 1 : 0, n_u, n_v, n, positions, albedo[0], albedo[1], albedo[2], alpha, rgba, t);
+}
+void launch_irradiance_volume_add(uint32_t n_float4, const float4* v0, const float4* r, float4* out, hipStream_t stream) {
+	if (n_float4) hipLaunchKernelGGL(irradiance_volume_add_kernel, dim3((n_float4 + 255) / 256), dim3(256), 0, stream, n_float4, v0, r, out);
+}
+void launch_ray_alpha(uint32_t n, const float4* rgba, float* alpha, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(ray_alpha_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rgba, alpha);
+}
+
 } // namespace ngp

@@ -159,6 +159,10 @@ void launch_irradiance_sh_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, 
 void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 void launch_irradiance_distance_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, uint32_t sharpness_log2, float D, const float2* t, float2* out, hipStream_t stream);
 void launch_irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
+void launch_irradiance_bounce_rays(const MeshSceneParams& S, const IrradianceVolume& V, const IrradianceVolumeVisible* VV, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n,
+                                   const float* positions, const float* albedo, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // VV: the visible lookup
+void launch_irradiance_volume_add(uint32_t n_float4, const float4* v0, const float4* r, float4* out, hipStream_t stream);
+void launch_ray_alpha(uint32_t n, const float4* rgba, float* alpha, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
 // scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.
@@ -407,6 +411,7 @@ struct ngp_ctx {
 	std::vector<float> mc_V, mc_N, mc_C;
 	std::vector<uint32_t> mc_F;
 	bool mc_valid = false, mc_attrs = false;
+	float sh_bounce_ms = 0.f; // device time of the last bounce pass over the SH9 volume's probes (ngp_get_irradiance_bounce_ms)
 	float mc_ms[3] = {0.f, 0.f, 0.f}; // device time of the last ngp_compute_marching_cubes_mesh: lattice, marching cubes, normals + colours
 
 	// ---- training (ngp_train.cpp)

@@ -593,8 +593,10 @@ std::vector<float> volume_positions(const ngp_irradiance_volume_desc* d, uint64_
 }
 
 // the records of n probes at host positions: sphere rays -> the ray-list tracer -> the projection, in chunks of whole probes. Each chunk's
-// records go to h_sh (host, n x 28) and / or d_sh (device, 7 n float4), its rays' radiance to h_rays (host, n K x 4); all nullable.
-void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, float* h_sh, float4* d_sh, float* h_rays) {
+// records go to h_sh (host, n x 28) and / or d_sh (device, 7 n float4), its rays' radiance to h_rays (host, n K x 4) and their alpha to
+// d_alpha (device, n K floats: what the bounce passes attenuate by); all nullable.
+void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, float* h_sh, float4* d_sh, float* h_rays,
+                     float* d_alpha = nullptr) {
 	const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
 	const uint32_t cap_pts = (uint32_t)std::min<uint64_t>(n, cap);
 	DevArray<float> pts(3 * (size_t)cap_pts), o(3 * (size_t)cap), dir(3 * (size_t)cap);
@@ -615,6 +617,7 @@ void trace_sh_probes(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp
 		tr.trace(P, m);
 		ngp::launch_irradiance_sh_reduce(d->n_u, d->n_v, np, rgba.get(), t.get(), rec.get(), ctx->stream);
 		if (d_sh) NGP_HIP_CHECK(hipMemcpyAsync(d_sh + SH_FLOAT4 * p0, rec.get(), (size_t)np * SH_FLOAT4 * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+		if (d_alpha) ngp::launch_ray_alpha(m, rgba.get(), d_alpha + r0, ctx->stream);
 		if (h_rays) download(ctx, h_rays + 4 * r0, rgba.get(), (size_t)m * sizeof(float4));
 		if (h_sh) download(ctx, h_sh + 4 * SH_FLOAT4 * p0, rec.get(), (size_t)np * SH_FLOAT4 * sizeof(float4));
 	});
@@ -656,6 +659,12 @@ float default_max_distance(const ngp_irradiance_volume_desc& v) {
 	}
 	return (float)(1.5 * std::sqrt(v.res[0] > 1 || v.res[1] > 1 || v.res[2] > 1 ? cell : box));
 }
+// D of a visibility descriptor for the lattice v: its own max_distance, or the default; refused when that is no positive finite number
+float visibility_distance(const ngp_irradiance_visibility_desc* d, const ngp_irradiance_volume_desc& v) {
+	const float D = d->max_distance > 0.0f ? d->max_distance : default_max_distance(v);
+	if (!(D > 0.0f) || !std::isfinite(D)) throw std::runtime_error("invalid irradiance visibility descriptor: the default max_distance of this volume is not a positive finite number");
+	return D;
+}
 // the maps of n probes at host positions: sphere rays against the meshes -> the moments, in chunks of whole probes (no tracer: the maps
 // need the BVHs alone). Each chunk's maps go to h_maps (host, n x 128 floats) and / or d_maps (device, 64 n float2); both nullable.
 void distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_visibility_desc* d, uint32_t K, float D, float* h_maps, float2* d_maps) {
@@ -679,6 +688,44 @@ void distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_i
 void check_normals(uint32_t n, const float* normals) {
 	for (uint32_t i = 0; i < n; ++i)
 		if (!finite3(normals + 3 * (size_t)i) || !nonzero3(normals + 3 * (size_t)i)) throw std::runtime_error("normal " + std::to_string(i) + " is zero or not finite");
+}
+
+// ---- diffuse interreflection (contract: include/ngp_hip.h)
+constexpr uint32_t MAX_BOUNCES = 16;
+void check_albedo(const float* albedo) {
+	if (!albedo) throw std::runtime_error("null argument");
+	for (int c = 0; c < 3; ++c)
+		if (!std::isfinite(albedo[c]) || albedo[c] < 0.0f || albedo[c] > 1.0f)
+			throw std::runtime_error("invalid irradiance bounce descriptor: albedo must be finite and in [0, 1] on every channel");
+}
+// one bounce pass at n probes (host positions) from the source volume V (VV non-null: through its visible lookup): sphere rays against the
+// meshes, the lookup at the hits, the projection, in chunks of whole probes (no tracer: a pass needs the BVHs and the records alone).
+// d_alpha: the rays' NeRF alpha, n K floats on the device (nullable: 0). Each chunk's records R go to h_sh (host, n x 28), its rays to h_rays
+// (host, n K x 4) and d_v0 + R to d_next (device, 7 n float4 each); all nullable.
+void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const float* albedo, const ngp::IrradianceVolume& V,
+                 const ngp::IrradianceVolumeVisible* VV, const float* d_alpha, float* h_sh, float* h_rays, const float4* d_v0, float4* d_next) {
+	const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK);
+	const uint32_t cap_pts = (uint32_t)std::min<uint64_t>(n, cap);
+	DevArray<float> pts(3 * (size_t)cap_pts);
+	DevArray<float2> t(cap);
+	DevArray<float4> rgba(cap), rec(SH_FLOAT4 * (size_t)cap_pts);
+	const ngp::Event ev0 = ngp::new_event(), ev1 = ngp::new_event();
+	NGP_HIP_CHECK(hipEventRecord(ev0, ctx->stream));
+	for_each_irradiance_chunk(n, K, [&](uint64_t r0, uint32_t m) { // (K <= RAY_CHUNK: whole probes)
+		const uint64_t p0 = r0 / K;
+		const uint32_t np = m / K;
+		upload(ctx, pts.get(), positions + 3 * p0, (size_t)np * 3 * sizeof(float));
+		ngp::launch_irradiance_bounce_rays(ctx->mesh_scene, V, VV, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts.get(), albedo, d_alpha ? d_alpha + r0 : nullptr, rgba.get(),
+		                                   t.get(), ctx->stream);
+		ngp::launch_irradiance_sh_reduce(d->n_u, d->n_v, np, rgba.get(), t.get(), rec.get(), ctx->stream);
+		if (d_next) ngp::launch_irradiance_volume_add(SH_FLOAT4 * np, d_v0 + SH_FLOAT4 * p0, rec.get(), d_next + SH_FLOAT4 * p0, ctx->stream);
+		if (h_rays) download(ctx, h_rays + 4 * r0, rgba.get(), (size_t)m * sizeof(float4));
+		if (h_sh) download(ctx, h_sh + 4 * SH_FLOAT4 * p0, rec.get(), (size_t)np * SH_FLOAT4 * sizeof(float4));
+	});
+	NGP_HIP_CHECK(hipEventRecord(ev1, ctx->stream));
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (the chunk buffers may go)
+	NGP_HIP_CHECK(hipGetLastError());
+	NGP_HIP_CHECK(hipEventElapsedTime(&ctx->sh_bounce_ms, ev0, ev1));
 }
 
 } // namespace
@@ -827,6 +874,84 @@ int ngp_compute_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc
 	});
 }
 
+int ngp_compute_irradiance_volume_bounced(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                          const ngp_irradiance_visibility_desc* visibility) {
+	return guarded(ctx, [&] {
+		if (!bounce) throw std::runtime_error("null argument");
+		if (bounce->n_bounces > MAX_BOUNCES) throw std::runtime_error("invalid irradiance bounce descriptor: n_bounces must be at most 16");
+		check_albedo(bounce->albedo);
+		require_probe_model(ctx, "SH irradiance probes");
+		const uint64_t probes = check_volume_lattice(desc);
+		const uint32_t K = check_sh_desc(probes, &desc->sh);
+		const uint32_t K_vis = visibility ? check_visibility_desc(probes, visibility, true) : 0;
+		const float D = visibility ? visibility_distance(visibility, *desc) : 0.0f;
+		const std::vector<float> positions = volume_positions(desc, probes);
+		// without a source (no pass asked for, a black albedo, nothing to hit) the records are V_0's own: no pass runs
+		const float* al = bounce->albedo;
+		const uint32_t n_bounces = (al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) && !ctx->meshes.empty() && desc->sh.occlude_by_meshes != 0 ? bounce->n_bounces : 0;
+		DevArray<float4> v0(SH_FLOAT4 * (size_t)probes), even(n_bounces > 1 ? v0.size() : 0), odd(n_bounces > 0 ? v0.size() : 0);
+		DevArray<float> alpha(n_bounces ? (size_t)probes * K : 0); // the whole volume's rays: the NeRF is traced once
+		trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, v0.get(), nullptr, n_bounces ? alpha.get() : nullptr);
+		DevArray<float2> maps(visibility ? ngp::DISTANCE_MAP_TEXELS * (size_t)probes : 0);
+		if (visibility) distance_maps(ctx, (uint32_t)probes, positions.data(), visibility, K_vis, D, nullptr, maps.get());
+		ngp::IrradianceVolumeVisible A{};
+		for (int a = 0; a < 3; ++a) {
+			A.V.res[a] = desc->res[a];
+			A.V.lo[a] = desc->aabb_min[a];
+			A.V.hi[a] = desc->aabb_max[a];
+		}
+		A.maps = maps.get();
+		A.D = D;
+		A.normal_bias = visibility ? visibility->normal_bias : 0.0f;
+		const float4* prev = v0.get();
+		for (uint32_t b = 1; b <= n_bounces; ++b) { // V_b = V_0 + R(V_{b-1}): every probe of a pass reads the pass before it alone
+			float4* next = b % 2u ? odd.get() : even.get();
+			A.V.sh = prev;
+			bounce_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, al, A.V, visibility ? &A : nullptr, alpha.get(), nullptr, nullptr, v0.get(), next);
+			prev = next;
+		}
+		ctx->d_sh_volume = std::move(n_bounces == 0 ? v0 : n_bounces % 2u ? odd : even); // (the previous volume stays in place when a launch throws)
+		ctx->sh_volume_desc = *desc;
+		drop_visibility(ctx);
+		if (visibility) {
+			ctx->d_sh_visibility = std::move(maps);
+			ctx->sh_visibility_desc = *visibility;
+			ctx->sh_visibility_desc.max_distance = D;
+		}
+		++ctx->sh_volume_generation;
+	});
+}
+
+int ngp_irradiance_sh_bounce(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* desc, const float* albedo, const float* alpha, int use_visible,
+                             float* sh_out, float* rays_out) {
+	return guarded(ctx, [&] {
+		check_albedo(albedo);
+		require_device(ctx);
+		require_volume(ctx);
+		if (use_visible) require_visibility(ctx);
+		const uint32_t K = check_sh_desc(n, desc);
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!sh_out) throw std::runtime_error("null argument");
+		const size_t rays = (size_t)n * K;
+		if (alpha)
+			for (size_t i = 0; i < rays; ++i)
+				if (!std::isfinite(alpha[i])) throw std::runtime_error("alpha " + std::to_string(i) + " is not finite");
+		DevArray<float> d_alpha(alpha ? rays : 0);
+		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
+		const ngp::IrradianceVolumeVisible A = use_visible ? ngp::sh_volume_visible_of(ctx) : ngp::IrradianceVolumeVisible{};
+		bounce_pass(ctx, n, positions, desc, K, albedo, ngp::sh_volume_of(ctx), use_visible ? &A : nullptr, alpha ? d_alpha.get() : nullptr, sh_out, rays_out, nullptr, nullptr);
+	});
+}
+
+int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = ctx->sh_bounce_ms;
+	});
+}
+
 int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh) {
 	return guarded(ctx, [&] {
 		require_device(ctx);
@@ -909,8 +1034,7 @@ int ngp_compute_irradiance_volume_visibility(ngp_ctx* ctx, const ngp_irradiance_
 		require_volume(ctx);
 		const uint64_t probes = ctx->d_sh_volume.size() / SH_FLOAT4;
 		const uint32_t K = check_visibility_desc(probes, desc, true);
-		const float D = desc->max_distance > 0.0f ? desc->max_distance : default_max_distance(ctx->sh_volume_desc);
-		if (!(D > 0.0f) || !std::isfinite(D)) throw std::runtime_error("invalid irradiance visibility descriptor: the default max_distance of this volume is not a positive finite number");
+		const float D = visibility_distance(desc, ctx->sh_volume_desc);
 		const std::vector<float> positions = volume_positions(&ctx->sh_volume_desc, probes);
 		DevArray<float2> maps(ngp::DISTANCE_MAP_TEXELS * (size_t)probes);
 		distance_maps(ctx, (uint32_t)probes, positions.data(), desc, K, D, nullptr, maps.get());

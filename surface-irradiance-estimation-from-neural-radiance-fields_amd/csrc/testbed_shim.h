@@ -432,8 +432,11 @@ public:
 			if (m_render_mode == ERenderMode::ShadeEnvMap && !m_envmap_ready) computeEnvmapMultipleMain();
 			// ShadeIrradianceVolume: a context without a volume gets the default one; a volume the caller set or computed is never replaced
 			if (m_render_mode == ERenderMode::ShadeIrradianceVolume && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0) {
-				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res});
-				if (m_irradiance_volume_visibility) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
+				// (bounces: the visibility is computed inside that call, ahead of the passes that look the volume up through it)
+				const bool vis_in_bounces = m_irradiance_volume_visibility && m_irradiance_volume_bounces > 0;
+				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res}, nullptr, 32, 32, true, nullptr, m_irradiance_volume_bounces, nullptr,
+				                          vis_in_bounces);
+				if (m_irradiance_volume_visibility && !vis_in_bounces) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
 			}
 		}
 		ngp_camera cam{};
@@ -531,14 +534,25 @@ public:
 		return out;
 	}
 	// a lattice of res probes over aabb6 (nullptr: the render aabb), traced and kept in the context; returns the records, probes x 28 in
-	// index order i + rx (j + ry k), and the box in aabb6_out
+	// index order i + rx (j + ry k), and the box in aabb6_out. bounces > 0: that many passes of diffuse interreflection off the meshes, of
+	// colour albedo3 (nullptr: the base colour squared per channel, clamped to [0, 1]: what the mesh pass hands the BRDF); with_visibility
+	// (bounces > 0 alone): the distance maps (their defaults) are computed ahead of the passes, used by them and kept
 	std::vector<float> compute_irradiance_volume(const std::array<uint32_t, 3>& res, const float* aabb6 = nullptr, uint32_t n_u = 32, uint32_t n_v = 32,
-	                                             bool occlude_by_meshes = true, float* aabb6_out = nullptr) {
+	                                             bool occlude_by_meshes = true, float* aabb6_out = nullptr, uint32_t bounces = 0, const float* albedo3 = nullptr,
+	                                             bool with_visibility = false) {
 		ngp_irradiance_volume_desc d{};
 		const float* box = aabb6 ? aabb6 : m_render_aabb.data();
 		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
 		d.sh = ngp_irradiance_sh_desc{n_u, n_v, nerf.render_min_transmittance, occlude_by_meshes ? 1 : 0};
-		check(ngp_compute_irradiance_volume(m_ctx, &d));
+		if (bounces > 0) {
+			ngp_irradiance_bounce_desc b{};
+			b.n_bounces = bounces;
+			for (int c = 0; c < 3; ++c) b.albedo[c] = albedo3 ? albedo3[c] : std::min(std::max(brdf.basecolor[c] * brdf.basecolor[c], 0.0f), 1.0f);
+			const ngp_irradiance_visibility_desc v{16, 16, 5, 0.f, 0.f};
+			check(ngp_compute_irradiance_volume_bounced(m_ctx, &d, &b, with_visibility ? &v : nullptr));
+		} else {
+			check(ngp_compute_irradiance_volume(m_ctx, &d));
+		}
 		std::vector<float> out((size_t)res[0] * res[1] * res[2] * 28);
 		check(ngp_get_irradiance_volume(m_ctx, &d, out.data()));
 		if (aabb6_out) { memcpy(aabb6_out, d.aabb_min, 12); memcpy(aabb6_out + 3, d.aabb_max, 12); }
@@ -577,6 +591,7 @@ public:
 	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	bool m_irradiance_volume_visibility = false; // the default volume of a ShadeIrradianceVolume render also gets distance maps (16 x 16 rays, sharpness 2^5, D and bias default)
+	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)
 	uint32_t m_irradiance_volume_res = 8; // probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none (32 x 32 rays, meshes occluding)
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path
 	bool m_has_camera_end = false;

@@ -109,6 +109,10 @@ class IrradianceVisibilityDesc(C.Structure):
     _fields_ = [("n_u", C.c_uint32), ("n_v", C.c_uint32), ("sharpness_log2", C.c_uint32), ("max_distance", C.c_float), ("normal_bias", C.c_float)]
 
 
+class IrradianceBounceDesc(C.Structure):
+    _fields_ = [("n_bounces", C.c_uint32), ("albedo", C.c_float * 3)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64), ("n_rays_alive_after_init", C.c_uint64), ("n_rays_hit", C.c_uint64), ("n_samples", C.c_uint64),
@@ -236,6 +240,9 @@ def load_library():
     L.ngp_set_irradiance_volume_visibility.argtypes = [vp, C.POINTER(IrradianceVisibilityDesc), vp]
     L.ngp_clear_irradiance_volume_visibility.argtypes = [vp]
     L.ngp_irradiance_volume_at_visible.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    L.ngp_compute_irradiance_volume_bounced.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), C.POINTER(IrradianceBounceDesc), C.POINTER(IrradianceVisibilityDesc)]
+    L.ngp_irradiance_sh_bounce.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), vp, vp, C.c_int, vp, vp]
+    L.ngp_get_irradiance_bounce_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -732,10 +739,50 @@ class Context:
         self._check(self.L.ngp_irradiance_sh_traced(self.h, p.shape[0], _p(p), C.byref(d), _p(sh), _p(rays) if return_rays else None))
         return (sh, rays) if return_rays else sh
 
-    def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01):
-        """trace a lattice of resolution = (rx, ry, rz) probes over aabb = (min, max); the volume stays on the device (get_irradiance_volume)"""
+    def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01, bounces=0, albedo=None, visibility=None):
+        """trace a lattice of resolution = (rx, ry, rz) probes over aabb = (min, max); the volume stays on the device (get_irradiance_volume).
+        bounces > 0: that many passes of diffuse interreflection off the meshes, of colour albedo (three channels in [0, 1], or one number for
+        all three; None: the default base colour 0.8 squared, in float32); visibility: None, or the keywords of compute_irradiance_volume_visibility
+        as a dict: the distance maps are computed first, the bounces look the volume up through them, and they stay in the context"""
         d = self._volume_desc(resolution, aabb, self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance))
-        self._check(self.L.ngp_compute_irradiance_volume(self.h, C.byref(d)))
+        if not bounces:
+            if albedo is not None or visibility is not None:
+                raise ValueError("albedo and visibility belong to bounces > 0")
+            self._check(self.L.ngp_compute_irradiance_volume(self.h, C.byref(d)))
+            return
+        b = self._bounce_desc(bounces, np.float32(0.8) * np.float32(0.8) if albedo is None else albedo)
+        v = None if visibility is None else self._visibility_desc(**dict(dict(n_u=16, n_v=16, sharpness_log2=5, max_distance=0.0, normal_bias=0.0), **visibility))
+        self._check(self.L.ngp_compute_irradiance_volume_bounced(self.h, C.byref(d), C.byref(b), C.byref(v) if v is not None else None))
+
+    @staticmethod
+    def _bounce_desc(bounces, albedo):
+        b = IrradianceBounceDesc()
+        b.n_bounces = bounces
+        b.albedo[:] = [float(x) for x in np.broadcast_to(np.asarray(albedo, np.float32), (3,))]
+        return b
+
+    def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
+        """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass
+        adds, float 27 the unblocked fraction; with return_rays also every ray's (B rgb, t of the hit or inf), (n, K, 4). alpha: None or the
+        rays' NeRF alpha (n, K)"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        k = int(n_u) * int(n_v)
+        d = self._sh_desc(n_u, n_v, occlude_by_meshes, 0.01)
+        al = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, np.float32), (3,)))
+        a = None if alpha is None else np.ascontiguousarray(alpha, np.float32)
+        if a is not None and a.size != p.shape[0] * k:
+            raise ValueError("alpha: n x K values")
+        sh = np.zeros((p.shape[0], 28), np.float32)
+        rays = np.zeros((p.shape[0], k, 4), np.float32) if return_rays else None
+        self._check(self.L.ngp_irradiance_sh_bounce(self.h, p.shape[0], _p(p), C.byref(d), _p(al), _p(a) if a is not None else None, int(bool(visible)), _p(sh),
+                                                    _p(rays) if return_rays else None))
+        return (sh, rays) if return_rays else sh
+
+    def irradiance_bounce_ms(self):
+        """device time of the last bounce pass (compute_irradiance_volume with bounces, irradiance_sh_bounce), ms"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_irradiance_bounce_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def get_irradiance_volume(self):
         """(desc, records (rz, ry, rx, 28))"""

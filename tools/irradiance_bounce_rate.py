@@ -1,0 +1,86 @@
+"""What bounces cost on the MI355X: the wall time of a 16^3 volume at 32 x 32 rays a probe on the benchmark's model among the meshes of
+tools/mesh_shade_rate.py's scene with N = 0, 1, 2 and 4 bounce passes, and the device time of one pass.
+
+    python tools/irradiance_bounce_rate.py [--res 16] [--k 32] [--repeat 3] [--out profiles/irradiance_bounce_rate.json]
+
+The volume spans the box of the meshes (it overlaps the NeRF's unit cube), the meshes occlude, albedo 0.64. Wall times are
+medians over --repeat calls after a warm-up and include the host's share; the pass time is HIP events around the last pass's chunks in
+the context's stream (ngp_get_irradiance_bounce_ms), the median over the same calls, with the plain and with the visible lookup (distance
+maps of 16 x 16 rays, computed inside the call and inside its wall time). Nothing is asserted on these numbers. Needs a GPU; there is
+no CPU path."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+PKG = "surface-irradiance-estimation-from-neural-radiance-fields_amd"
+BOUNCES = (0, 1, 2, 4)
+
+
+def pkg(sub):
+    import importlib
+
+    return importlib.import_module(PKG + "." + sub)
+
+
+def timed(ctx, f, repeat):
+    """median wall time of `repeat` calls of f after one warm-up call, and the median of the last pass's device time behind each"""
+    f()
+    ts, dev = [], []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        f()
+        ts.append(time.perf_counter() - t0)
+        dev.append(ctx.irradiance_bounce_ms())
+    return float(np.median(ts)), float(np.median(dev))
+
+
+def main():
+    from mesh_shade_rate import scene
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=16)
+    ap.add_argument("--k", type=int, default=32)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "irradiance_bounce_rate.json"))
+    args = ap.parse_args()
+    pkg("build").build()
+    native, synthetic = pkg("native"), pkg("synthetic")
+    ctx = native.Context(0)
+    ctx.set_model(synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19))
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for i, (tris, center) in enumerate(scene()):
+        ctx.add_mesh(tris, center)
+        bmin, bmax = ctx.mesh_info(i)["aabb"]
+        lo, hi = np.minimum(lo, bmin), np.maximum(hi, bmax)
+    box = (lo.astype(np.float32), hi.astype(np.float32))
+    res, k = (args.res,) * 3, args.k
+    rays = args.res ** 3 * k * k
+    out = {"how": "median wall time of --repeat calls after a warm-up; pass = HIP events around the last bounce pass's chunks, the median over the same calls; one MI355X, one run",
+           "resolution": list(res), "rays_per_probe": k * k, "rays": rays, "albedo": 0.64, "plain": {}, "visible": {}}
+    for name, vis in (("plain", None), ("visible", {})):
+        for n in BOUNCES:
+            if n == 0 and vis is not None:
+                continue
+            kw = dict(bounces=n, albedo=0.64, visibility=vis) if n else {}
+            t, dev = timed(ctx, lambda: ctx.compute_irradiance_volume(res, box, k, k, **kw), args.repeat)
+            out[name][str(n)] = {"wall_ms": round(1e3 * t, 2), "pass_device_ms": round(dev, 3) if n else None, "pass_ms_per_million_rays": round(dev / (rays * 1e-6), 3) if n else None}
+            print(f"{name:7s} N = {n}: {1e3 * t:8.2f} ms wall" + (f", one pass {dev:.3f} ms on the device ({dev / (rays * 1e-6):.3f} ms per million rays)" if n else ""), flush=True)
+    d, sh = ctx.get_irradiance_volume()
+    out["blocked_share"] = round(float(1.0 - sh[..., 27].mean()), 4)
+    ctx.close()
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
