@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libngp_hip.so")
-SOURCES = ["nerf_kernels.hip", "wide_kernels.hip", "mesh_kernels.hip", "train_kernels.hip", "mc_kernels.hip", "ngp_api.cpp", "ngp_model.cpp", "ngp_snapshot.cpp", "ngp_dataset.cpp", "ngp_render.cpp", "ngp_mesh.cpp", "ngp_train.cpp", "ngp_multi.cpp", "ngp_mc.cpp"]
+SOURCES = ["nerf_kernels.hip", "wide_kernels.hip", "mesh_kernels.hip", "train_kernels.hip", "mc_kernels.hip", "ngp_api.cpp", "ngp_model.cpp", "ngp_snapshot.cpp", "ngp_dataset.cpp", "ngp_render.cpp", "ngp_mesh.cpp", "ngp_irradiance.cpp", "ngp_train.cpp", "ngp_multi.cpp", "ngp_mc.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 
 
@@ -50,7 +50,10 @@ def build(force=False, verbose=False, legacy=False, nocache=False, cellstats=Fal
     lib = LIB_LEGACY if legacy else LIB_NOCACHE if nocache else LIB_CELLSTATS if cellstats else LIB_NETSEC_V1 if netsec_v1 else LIB_ROUND_V1 if round_v1 else LIB
     if not force and not needs_build(lib):
         return lib
-    srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES]
+    missing = [s for s in srcs if not os.path.exists(s)]
+    if missing:
+        raise RuntimeError("missing source(s): " + ", ".join(missing))
     # link to a private name and rename: another process (a rank of the same job, a test worker) may be dlopen-ing the
     # library at this moment and must see either the old file or the complete new one
     tmp = "%s.%d.tmp" % (lib, os.getpid())

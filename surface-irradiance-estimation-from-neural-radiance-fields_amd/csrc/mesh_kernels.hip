@@ -115,6 +115,24 @@ NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
 	}
 }
 
+// the closest triangle hit of a ray over ALL meshes (trace_mesh's rule is another: one mesh, chosen by box entry): its t, +inf without a
+// hit. mesh / tri (nullable) receive the hit's mesh and triangle; they are left alone without a hit. What the irradiance ray generators see.
+// S by value: through a reference the compiler no longer sees that the mesh table is global memory and reads the BVHs with flat loads.
+NGP_DEV float closest_hit(const MeshSceneParams S, f3 org, f3 dir, int* mesh = nullptr, int* tri = nullptr) {
+	float t_max = __builtin_huge_valf();
+	for (uint32_t m = 0; m < S.n_meshes; ++m) {
+		int idx;
+		float t;
+		bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
+		if (idx > -1 && t < t_max) {
+			t_max = t;
+			if (mesh) *mesh = (int)m;
+			if (tri) *tri = idx;
+		}
+	}
+	return t_max;
+}
+
 // ---- BRDF: testbed_geometry_training.cu:46-144 (double-typed literals are kept, they promote like the reference)
 NGP_DEV float square(float x) { return x * x; }
 NGP_DEV float mixf(float a, float b, float t) { return a + (b - a) * t; }
@@ -554,15 +572,7 @@ __global__ void irradiance_rays_kernel(const MeshSceneParams S, int occlude, uin
 	local_frame(nrm, frame);
 	const f3 dir = normalize3(m3_mulv(frame, mk3(sa * cosf(phi), sa * sinf(phi), sqrtf(1.0f - a))));
 	const f3 org = add3(ld3(positions + 3 * pl), scale3(nrm, offset));
-	float t_max = __builtin_huge_valf();
-	if (occlude) {
-		for (uint32_t m = 0; m < S.n_meshes; ++m) {
-			int idx;
-			float t;
-			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
-			if (idx > -1 && t < t_max) t_max = t;
-		}
-	}
+	const float t_max = occlude ? closest_hit(S, org, dir) : __builtin_huge_valf();
 	o_out[3 * (size_t)i] = org.x; o_out[3 * (size_t)i + 1] = org.y; o_out[3 * (size_t)i + 2] = org.z;
 	d_out[3 * (size_t)i] = dir.x; d_out[3 * (size_t)i + 1] = dir.y; d_out[3 * (size_t)i + 2] = dir.z;
 	t_out[i] = make_float2(0.0f, t_max);
@@ -645,15 +655,7 @@ __global__ void irradiance_sphere_rays_kernel(const MeshSceneParams S, int occlu
 	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
 	const f3 dir = sphere_dir(k, n_u, n_v);
 	const f3 org = ld3(positions + 3 * (size_t)pl);
-	float t_max = __builtin_huge_valf();
-	if (occlude) {
-		for (uint32_t m = 0; m < S.n_meshes; ++m) {
-			int idx;
-			float t;
-			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
-			if (idx > -1 && t < t_max) t_max = t;
-		}
-	}
+	const float t_max = occlude ? closest_hit(S, org, dir) : __builtin_huge_valf();
 	o_out[3 * (size_t)i] = org.x; o_out[3 * (size_t)i + 1] = org.y; o_out[3 * (size_t)i + 2] = org.z;
 	d_out[3 * (size_t)i] = dir.x; d_out[3 * (size_t)i + 1] = dir.y; d_out[3 * (size_t)i + 2] = dir.z;
 	t_out[i] = make_float2(0.0f, t_max);
@@ -798,20 +800,8 @@ __global__ void irradiance_bounce_rays_kernel(const MeshSceneParams S, const Loo
 	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
 	const f3 dir = sphere_dir(k, n_u, n_v);
 	const f3 org = ld3(positions + 3 * (size_t)pl);
-	float t_max = __builtin_huge_valf();
 	int mesh = -1, tri_idx = -1;
-	if (occlude) {
-		for (uint32_t m = 0; m < S.n_meshes; ++m) {
-			int idx;
-			float t;
-			bvh4_ray_intersect(S.meshes[m].nodes, S.meshes[m].tris, org, dir, idx, t);
-			if (idx > -1 && t < t_max) {
-				t_max = t;
-				mesh = (int)m;
-				tri_idx = idx;
-			}
-		}
-	}
+	const float t_max = occlude ? closest_hit(S, org, dir, &mesh, &tri_idx) : __builtin_huge_valf();
 	f3 B = mk3(0.f, 0.f, 0.f);
 	if (mesh > -1) {
 		const Triangle& tri = S.meshes[mesh].tris[tri_idx];

@@ -1,5 +1,5 @@
 // C ABI of libngp_hip (include/ngp_hip.h): contexts, errors and the point queries. The rest of the ABI sits with its subject:
-// ngp_model.cpp, ngp_snapshot.cpp, ngp_dataset.cpp, ngp_render.cpp, ngp_mesh.cpp, ngp_train.cpp, ngp_multi.cpp, ngp_mc.cpp.
+// ngp_model.cpp, ngp_snapshot.cpp, ngp_dataset.cpp, ngp_render.cpp, ngp_mesh.cpp, ngp_irradiance.cpp, ngp_train.cpp, ngp_multi.cpp, ngp_mc.cpp.
 // Host logic only; every device computation lives in the .hip files. There is no CPU fallback: each entry point
 // that computes needs a HIP device and fails with an error otherwise.
 #include "ngp_host.h"

@@ -521,6 +521,7 @@ void sync_host_params(ngp_ctx* ctx);     // ctx->params <- training parameters, 
 void render_frames_multi(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
 // ngp_mesh.cpp: Geometry mode on an auxiliary device -- the primary's meshes (BVHs as built), shading parameters, irradiance tables and the SH9 volume
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer);
+// what ngp_irradiance.cpp computes, as the kernels take it (the render and the peer sync read these too)
 inline IrradianceMap irradiance_map_of(const ngp_ctx* ctx) {
 	IrradianceMap I{};
 	I.irradiance = ctx->d_irradiance.get();
@@ -533,16 +534,23 @@ inline IrradianceMap irradiance_map_of(const ngp_ctx* ctx) {
 	for (int i = 0; i < 3; ++i) I.center[i] = ctx->env_probe.center[i];
 	return I;
 }
-inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) {
+// texels of the context's probe texture(s): a grid holds grid_x * grid_y textures back to back
+inline size_t env_texels(const ngp_ctx* ctx) {
+	const ProbeParams& P = ctx->env_probe;
+	return (size_t)P.n_theta * P.n_phi * (P.mode == 3 ? P.grid_x * P.grid_y : 1u);
+}
+// the lattice of d over the records sh (device, 7 float4 a probe)
+inline IrradianceVolume irradiance_volume_from(const ngp_irradiance_volume_desc& d, const float4* sh) {
 	IrradianceVolume V{};
-	V.sh = ctx->d_sh_volume.get();
+	V.sh = sh;
 	for (int a = 0; a < 3; ++a) {
-		V.res[a] = ctx->sh_volume_desc.res[a];
-		V.lo[a] = ctx->sh_volume_desc.aabb_min[a];
-		V.hi[a] = ctx->sh_volume_desc.aabb_max[a];
+		V.res[a] = d.res[a];
+		V.lo[a] = d.aabb_min[a];
+		V.hi[a] = d.aabb_max[a];
 	}
 	return V;
 }
+inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) { return irradiance_volume_from(ctx->sh_volume_desc, ctx->d_sh_volume.get()); }
 inline IrradianceVolumeVisible sh_volume_visible_of(const ngp_ctx* ctx) {
 	IrradianceVolumeVisible A{};
 	A.V = sh_volume_of(ctx);

@@ -15,7 +15,7 @@ import mesh_reference as mref
 import mesh_visibility_cases as vc
 import mesh_volume_cases as mv
 from irradiance_volume_cases import GEN_POINTS, UNSAFE_CAP, gen_meshes
-from test_irradiance_visibility_gpu import NO_VISIBILITY, NO_VOLUME, SLAB_CAMERA, _load, _opts, _set_volume, _testbed, _wall_and_floor, _write_slab_scene
+from test_irradiance_visibility_gpu import NO_VISIBILITY, NO_VOLUME, SLAB_CAMERA, _load, _many_probes, _opts, _set_volume, _small_scene, _testbed, _wall_and_floor, _write_slab_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -106,6 +106,29 @@ def test_a_pass_is_deterministic_and_independent_of_the_split(ctx):
                     ctx.irradiance_sh_bounce(GEN_POINTS, br.STAGE_ALBEDO, nu, nv, alpha=np.zeros_like(alpha), visible=visible).tobytes()
                 off, off_rays = ctx.irradiance_sh_bounce(GEN_POINTS, br.STAGE_ALBEDO, nu, nv, alpha=alpha, visible=visible, occlude_by_meshes=False, return_rays=True)
                 assert np.all(off[:, :27] == 0) and np.all(off[:, 27] == 1) and np.all(off_rays[..., :3] == 0) and np.all(np.isinf(off_rays[..., 3]))
+    finally:
+        ctx.clear_irradiance_volume()
+        ctx.clear_meshes()
+
+
+@pytest.mark.parametrize("visible", [False, True])
+def test_a_pass_over_two_host_chunks(visible, ctx):
+    """600 probes x 64 x 64 rays (a host chunk of 512 whole probes and a tail of 88, see _many_probes), each ray with an alpha of its own:
+    every probe's record and every ray from the one call is the bytes of the same probe asked for in calls of 100 probes (one chunk each). A
+    probe's result does not depend on which probes share its launch, so the small calls are the reference. The stage volume was made for
+    other meshes; here it is only a source of numbers (the last asserts see to it that light does come back in both chunks)."""
+    _load(ctx, _small_scene())
+    _hold_stage_volume(ctx, visible)
+    try:
+        probes, alpha = _many_probes(), br.stage_alpha(600, 64 * 64)
+        sh, rays = ctx.irradiance_sh_bounce(probes, br.STAGE_ALBEDO, 64, 64, alpha=alpha, visible=visible, return_rays=True)
+        assert sh.shape == (600, 28) and rays.shape == (600, 4096, 4) and np.isfinite(sh).all() and not np.isnan(rays).any()
+        for i in range(0, 600, 100):
+            s = slice(i, i + 100)
+            part_sh, part_rays = ctx.irradiance_sh_bounce(probes[s], br.STAGE_ALBEDO, 64, 64, alpha=alpha[s], visible=visible, return_rays=True)
+            assert np.array_equal(sh[s], part_sh) and np.array_equal(rays[s], part_rays), i
+        for chunk in (slice(0, 512), slice(512, 600)):  # (light comes back in both chunks, and some rays of both see the sky)
+            assert np.abs(sh[chunk, :27]).max() > 1e-2 and np.isinf(rays[chunk, :, 3]).any() and np.isfinite(rays[chunk, :, 3]).any()
     finally:
         ctx.clear_irradiance_volume()
         ctx.clear_meshes()

@@ -128,6 +128,32 @@ def test_maps_are_deterministic_and_independent_of_the_split(ctx):
         ctx.clear_meshes()
 
 
+def _small_scene():
+    """32 triangles: an icosahedron in [0, 1]^3 and a cube beside it"""
+    return [(pkg("meshio").icosphere(0), (0.0, 0.0, 0.0)), (mc.cube(), (1.2, 0.3, 0.1))]
+
+
+def _many_probes(n=600, seed=41):
+    """probes around and inside _small_scene's meshes. 600 of them with 64 x 64 rays each are 2.46 M rays: more than the 2^21 rays the host
+    sends in one launch, so a call runs a chunk of 512 whole probes and a tail of 88"""
+    return np.random.default_rng(seed).uniform(-0.4, 2.0, (n, 3)).astype(np.float32)
+
+
+def test_maps_over_two_host_chunks(ctx):
+    """every one of the 600 probes' maps from one call (two host chunks) is the bytes of the same probe asked for in calls of 100 probes (one
+    chunk each): a probe's map does not depend on which probes share its launch, so the small calls are the reference"""
+    _load(ctx, _small_scene())
+    try:
+        probes = _many_probes()
+        whole = ctx.irradiance_distance_maps(probes, 64, 64, 5, 1.5)
+        parts = np.concatenate([ctx.irradiance_distance_maps(probes[i:i + 100], 64, 64, 5, 1.5) for i in range(0, 600, 100)])
+        assert whole.shape == (600, 64, 2) and np.isfinite(whole).all()
+        assert np.array_equal(whole, parts)
+        assert np.unique(whole[:512, :, 0]).size > 50 and np.unique(whole[512:, :, 0]).size > 50  # (neither chunk's maps are flat)
+    finally:
+        ctx.clear_meshes()
+
+
 def test_no_meshes_is_the_plain_lookup(ctx):
     ctx.clear_meshes()
     sh, res, lo, hi = mv.varying_volume()
