@@ -563,7 +563,7 @@ NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const flo
  * Determinism: no atomics; bit-identical from run to run and for any chunking. With N = 0, every albedo channel 0, no meshes loaded or
  *   occlude_by_meshes == 0 no pass runs and the records are V_0's as bytes.
  * Limits: N <= 16; every albedo channel finite and in [0, 1]; each refused with a message that names the field.
- * Out of scope: sun light on the meshes as a bounce source; glossy transport; a NeRF surface lit by the meshes; probes inside closed
+ * Out of scope: glossy transport; a NeRF surface lit by the meshes; probes inside closed
  *   meshes (they stay dead: a room built of meshes alone gets nothing); bounces for the lat-long probe tables.
  * Refusals: those of the volume and visibility sections; ngp_irradiance_sh_bounce without a volume ("no irradiance volume") and with
  *   use_visible without visibility ("no irradiance visibility"); a non-finite alpha. */
@@ -585,6 +585,48 @@ NGP_API int ngp_irradiance_sh_bounce(ngp_ctx* ctx, uint32_t n, const float* posi
 /* device time (HIP events) of the last bounce pass of either entry, ms: its chunks' uploads, rays, projections and sums. Nothing in the
  * contract depends on it; tools/irradiance_bounce_rate.py reads it. */
 NGP_API int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms);
+
+/* --- sun: the sun's light on the inserted meshes as a bounce source. In an NGP_RENDER_SHADE frame the sun is the strongest light on a
+ * mesh (suncol = 4 (255, 225, 195) / 255), and the records above hold none of it: a sunlit floor does not brighten what stands on it. The
+ * sun pass adds the sun's FIRST bounce off the meshes to V_0, and the bounce passes carry it on. This project's own contract.
+ *
+ * V_0, the rays w_k, the closest hit (t_k, m, i), h = o + t_k w_k and N_ff are the bounce section's. s^ = direction / |direction|, the
+ *   quotient formed in double precision from the descriptor's floats and rounded to float.
+ * Per ray: c_k = N_ff . s^. The ray carries no sun light without a hit, with occlude_by_meshes == 0, or where c_k <= 0. Otherwise a shadow
+ *   ray starts at q = h + shadow_bias N_ff (float32, every product rounded before its sum) and runs along s^; it is blocked when any
+ *   triangle of ANY loaded mesh is hit at 0 <= t < 100 (the traversal's range, MAX_DIST); vis_k = 0 when blocked, else 1.
+ *   B^sun_k,ch = (1 - alpha_k) ((albedo_ch radiance_ch) c_k / pi) vis_k in float32, alpha_k the alpha of the ray's NeRF trace, albedo
+ *   ngp_irradiance_bounce_desc::albedo. The term does not depend on the volume: a hit among dead probes is lit like any other.
+ * Records: R_sun = the SH9 section's projection of B^sun (the same kernel, order and 4 pi / K scale); S[j] = V_0[j] + R_sun[j] in float32
+ *   for j < 27; float 27 stays V_0's, so dead probes stay dead. S takes V_0's place in the bounce recurrence: V_b = S + R(V_{b-1}) with
+ *   V_0 := S. With N = 0 the held volume is S, the sun's first bounce alone; with N passes sun light has bounced N + 1 times and NeRF
+ *   light N times.
+ * Determinism: no atomics; bit-identical from run to run and for any chunking. With sun == NULL, every radiance channel 0, every albedo
+ *   channel 0, no meshes loaded or occlude_by_meshes == 0 no sun pass runs and the records are ngp_compute_irradiance_volume_bounced's as
+ *   bytes.
+ * Stated limits: the NeRF's density does not block the sun (the frames' own shadow ray does not test it either); the sun as seen
+ *   directly from a probe is not in the records (the BRDF's direct term has it); one directional light; the frames' shadow ray follows
+ *   the reference's one-mesh rule (ngp_trace_mesh_rays), this one sees all meshes.
+ * Refusals, each naming its field: a zero or non-finite direction; a negative or non-finite radiance; a negative or non-finite
+ *   shadow_bias; a NULL bounce descriptor when the sun is given; albedo x radiance overflowing float; everything the volume, visibility
+ *   and bounce sections refuse. */
+typedef struct ngp_irradiance_sun_desc {
+	float direction[3]; /* towards the sun; normalised here; finite and not zero */
+	float radiance[3];  /* what a surface facing the sun receives (the frames' suncol); finite, >= 0 */
+	float shadow_bias;  /* finite, >= 0; the frames use 1e-3 */
+} ngp_irradiance_sun_desc;
+/* ngp_compute_irradiance_volume_bounced with the sun pass between the trace (and the distance maps) and the bounce passes. The per-ray
+ * alpha is kept whenever a sun pass or a bounce pass runs. The volume, the maps and one step of the generation counter are committed
+ * together; a failed call leaves the held volume alone. */
+NGP_API int ngp_compute_irradiance_volume_sunlit(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                                 const ngp_irradiance_visibility_desc* visibility /* nullable */, const ngp_irradiance_sun_desc* sun /* nullable */);
+/* a stage entry for tests: ONE sun pass at the caller's probes. Needs a device and the meshes, no model and no volume. alpha: n K
+ * caller-given values (NULL: 0); desc->min_transmittance is not looked at. rays_out (nullable) n K x 4 = (B^sun_rgb, t of the primary hit
+ * or +inf); sh_out n x 28 = R_sun, float 27 = the unblocked fraction */
+NGP_API int ngp_irradiance_sh_sun(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_sh_desc* desc, const ngp_irradiance_sun_desc* sun,
+                                  const float albedo[3], const float* alpha /* nullable, n K */, float* sh_out /* n x 28 */, float* rays_out /* nullable, n K x 4 */);
+/* device time (HIP events) of the last sun pass of either entry, ms, as ngp_get_irradiance_bounce_ms reports a bounce pass's */
+NGP_API int ngp_get_irradiance_sun_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

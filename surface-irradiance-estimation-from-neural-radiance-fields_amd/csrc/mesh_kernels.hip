@@ -850,4 +850,92 @@ void launch_ray_alpha(uint32_t n, const float4* rgba, float* alpha, hipStream_t 
 	if (n) hipLaunchKernelGGL(ray_alpha_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rgba, alpha);
 }
 
+
+// ---- sun light on the meshes as a bounce source (ngp_compute_irradiance_volume_sunlit, ngp_irradiance_sh_sun; contract in
+// include/ngp_hip.h, "sun"). One pass puts the sun's first bounce off the meshes into the records: the rays of
+// irradiance_sphere_rays_kernel, the closest hit with its mesh and triangle kept, a shadow query from the hit towards the sun, and
+// irradiance_sh_reduce_kernel unchanged behind it.
+
+#ifdef NGP_EXPERIMENT_SUN_ANY_HIT // tools/irradiance_bounce_rate.py --sun alone: the shadow query as an any-hit traversal. Measured against the closest hit it buys 4-6 % of a sun pass, inside the spread of repeats, so it does not ship.
+// is any triangle of one mesh hit at 0 <= t < MAX_DIST? The traversal of bvh4_ray_intersect without what only the closest hit needs: the
+// children are not sorted, the range never shrinks (every child whose box entry lies below MAX_DIST is pushed), and the first triangle
+// inside the range ends the walk.
+NGP_DEV bool bvh4_ray_occluded(const TriangleBvhNode* __restrict__ nodes, const Triangle* __restrict__ tris, f3 ro, f3 rd) {
+	int stack[BVH4_STACK_SIZE];
+	int sp = 0;
+	stack[sp++] = 0;
+	while (sp > 0) {
+		int idx = stack[--sp];
+		const int left = nodes[idx].left_idx, right = nodes[idx].right_idx;
+		if (left < 0) {
+			int end = -right - 1;
+			for (int i = -left - 1; i < end; ++i) {
+				if (tri_ray_intersect(tris[i], ro, rd) < MAX_DIST) return true;
+			}
+		} else {
+#pragma unroll
+			for (uint32_t i = 0; i < 4; ++i) {
+				const TriangleBvhNode& c = nodes[left + (int)i];
+				if (aabb_ray_entry(c.bmin, c.bmax, ro, rd) < MAX_DIST && sp < BVH4_STACK_SIZE) stack[sp++] = left + (int)i;
+			}
+		}
+	}
+	return false;
+}
+#endif
+
+// is the ray blocked by a triangle of any mesh within MAX_DIST? The closest hit decides: it finds every hit inside the traversal's range.
+// S by value, as in closest_hit.
+NGP_DEV bool any_hit(const MeshSceneParams S, f3 org, f3 dir) {
+#ifdef NGP_EXPERIMENT_SUN_ANY_HIT
+	for (uint32_t m = 0; m < S.n_meshes; ++m)
+		if (bvh4_ray_occluded(S.meshes[m].nodes, S.meshes[m].tris, org, dir)) return true;
+	return false;
+#else
+	return closest_hit(S, org, dir) < MAX_DIST;
+#endif
+}
+
+// the n rays of a chunk of whole probes, one thread a ray: rgba_out = (B rgb, t of the hit or +inf), t_out = (0, the same t) as the
+// projection counts it. B_ch = (1 - alpha) albedo_ch radiance_ch c vis / pi with c = N_ff . sun (N_ff the hit triangle's winding normal
+// turned against the ray, sun a unit vector), vis = 0 where a triangle of any mesh lies within MAX_DIST of q = h + bias N_ff along sun;
+// 0 without a hit and where c <= 0. alpha: the chunk's rays' NeRF alpha (nullptr: 0). No volume is read.
+__global__ void irradiance_sun_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions, float sun_x,
+                                           float sun_y, float sun_z, float bias, float source_r, float source_g, float source_b, const float* __restrict__ alpha,
+                                           float4* __restrict__ rgba_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
+	const f3 dir = sphere_dir(k, n_u, n_v);
+	const f3 org = ld3(positions + 3 * (size_t)pl);
+	int mesh = -1, tri_idx = -1;
+	const float t_max = occlude ? closest_hit(S, org, dir, &mesh, &tri_idx) : __builtin_huge_valf();
+	f3 B = mk3(0.f, 0.f, 0.f);
+	if (mesh > -1) {
+		const Triangle& tri = S.meshes[mesh].tris[tri_idx];
+		const f3 a = ld3(tri.a);
+		const f3 N = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
+		const f3 nff = dot3(N, dir) < 0.0f ? N : scale3(N, -1.0f);
+		const f3 sun = mk3(sun_x, sun_y, sun_z);
+		const float c = dot3(nff, sun);
+		if (c > 0.0f) {
+			const f3 h = add3(org, scale3(dir, t_max));
+			const f3 q = add3(h, scale3(nff, bias));
+			if (!any_hit(S, q, sun)) {
+				const float through = 1.0f - (alpha ? alpha[i] : 0.0f);
+				B = mk3(through * (source_r * c / PI_F), through * (source_g * c / PI_F), through * (source_b * c / PI_F));
+			}
+		}
+	}
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// sun: the unit direction towards the sun; source: albedo x radiance per channel, as the host forms it in float
+void launch_irradiance_sun_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
+                                const float* source, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_sun_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias,
+	                          source[0], source[1], source[2], alpha, rgba, t);
+}
+
 } // namespace ngp

@@ -1,5 +1,5 @@
 // Irradiance, host side of the C ABI (contract: include/ngp_hip.h): envmap probes and their E(n) tables, caller rays and traced E(p, n)
-// through the ray-list tracer, SH9 irradiance volumes, probe visibility and the diffuse bounce passes. What the generations share is
+// through the ray-list tracer, SH9 irradiance volumes, probe visibility, the sun pass and the diffuse bounce passes. What the generations share is
 // written once, up here: one tracer call, one whole-probe chunk loop, one ray download, a point lookup in each of its two forms, one check of each kind.
 #include "ngp_host.h"
 #include "sh9.h"
@@ -229,6 +229,28 @@ void check_albedo(const float* albedo) {
 			throw std::runtime_error("invalid irradiance bounce descriptor: albedo must be finite and in [0, 1] on every channel");
 }
 
+// a sun descriptor as the passes use it: the unit direction (formed in double, rounded to float) and albedo x radiance per channel
+struct SunLight {
+	float dir[3], source[3], bias;
+	bool lit; // some channel of the source is not 0
+};
+SunLight check_sun(const ngp_irradiance_sun_desc* s, const float* albedo) {
+	if (!finite3(s->direction) || !nonzero3(s->direction)) throw std::runtime_error("invalid irradiance sun descriptor: direction must be finite and not zero");
+	for (int c = 0; c < 3; ++c)
+		if (!std::isfinite(s->radiance[c]) || s->radiance[c] < 0.0f) throw std::runtime_error("invalid irradiance sun descriptor: radiance must be finite and >= 0 on every channel");
+	if (!std::isfinite(s->shadow_bias) || s->shadow_bias < 0.0f) throw std::runtime_error("invalid irradiance sun descriptor: shadow_bias must be finite and >= 0");
+	SunLight L{};
+	const double x = s->direction[0], y = s->direction[1], z = s->direction[2], len = std::sqrt(x * x + y * y + z * z);
+	L.dir[0] = (float)(x / len); L.dir[1] = (float)(y / len); L.dir[2] = (float)(z / len);
+	for (int c = 0; c < 3; ++c) {
+		L.source[c] = albedo[c] * s->radiance[c];
+		if (!std::isfinite(L.source[c])) throw std::runtime_error("invalid irradiance sun descriptor: albedo x radiance is not finite");
+		L.lit = L.lit || L.source[c] != 0.0f;
+	}
+	L.bias = s->shadow_bias;
+	return L;
+}
+
 void require_volume(const ngp_ctx* ctx) {
 	if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
 }
@@ -406,21 +428,21 @@ void distance_maps(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_i
 	NGP_HIP_CHECK(hipGetLastError());
 }
 
-// ---- diffuse interreflection (contract: include/ngp_hip.h)
-// one bounce pass at n probes (host positions) from the source volume V (VV non-null: through its visible lookup): sphere rays against the
-// meshes, the lookup at the hits, the projection, in chunks of whole probes (no tracer: a pass needs the BVHs and the records alone).
-// d_alpha: the rays' NeRF alpha, n K floats on the device (nullable: 0). Each chunk's records R go to h_sh (host, n x 28), its rays to h_rays
-// (host, n K x 4) and d_v0 + R to d_next (device, 7 n float4 each); all nullable.
-void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const float* albedo, const IrradianceVolume& V,
-                 const IrradianceVolumeVisible* VV, const float* d_alpha, float* h_sh, float* h_rays, const float4* d_v0, float4* d_next) {
+// ---- light off the meshes: the sun pass and the diffuse bounce passes (contract: include/ngp_hip.h, "bounces" and "sun")
+// one pass at n probes (host positions), in chunks of whole probes: rays(pts, r0, m, rgba, t) launches the generator that leaves a chunk's
+// rays' (B rgb, t) and (0, t), the projection follows (no tracer: a pass needs the BVHs alone, a bounce pass the records too). Each chunk's
+// records R go to h_sh (host, n x 28), its rays to h_rays (host, n K x 4) and d_v0 + R to d_next (device, 7 n float4 each, not d_v0
+// itself); all nullable. ms: the pass's device time.
+template <typename Rays>
+void mesh_light_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, Rays&& rays, float* h_sh, float* h_rays,
+                     const float4* d_v0, float4* d_next, float* ms) {
 	ProbeChunks chunks(n, K);
 	DevArray<float2> t(chunks.cap);
 	DevArray<float4> rgba(chunks.cap), rec(SH_FLOAT4 * (size_t)chunks.cap_pts);
 	const Event ev0 = new_event(), ev1 = new_event();
 	NGP_HIP_CHECK(hipEventRecord(ev0, ctx->stream));
 	chunks.for_each(ctx, positions, [&](uint64_t p0, uint32_t np, uint64_t r0, uint32_t m) {
-		launch_irradiance_bounce_rays(ctx->mesh_scene, V, VV, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, chunks.pts.get(), albedo, d_alpha ? d_alpha + r0 : nullptr,
-		                              rgba.get(), t.get(), ctx->stream);
+		rays(chunks.pts.get(), r0, m, rgba.get(), t.get());
 		launch_irradiance_sh_reduce(d->n_u, d->n_v, np, rgba.get(), t.get(), rec.get(), ctx->stream);
 		if (d_next) launch_irradiance_volume_add(SH_FLOAT4 * np, d_v0 + SH_FLOAT4 * p0, rec.get(), d_next + SH_FLOAT4 * p0, ctx->stream);
 		if (h_rays) download(ctx, h_rays + 4 * r0, rgba.get(), (size_t)m * sizeof(float4));
@@ -429,12 +451,30 @@ void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irr
 	NGP_HIP_CHECK(hipEventRecord(ev1, ctx->stream));
 	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (the chunk buffers may go)
 	NGP_HIP_CHECK(hipGetLastError());
-	NGP_HIP_CHECK(hipEventElapsedTime(&ctx->sh_bounce_ms, ev0, ev1));
+	NGP_HIP_CHECK(hipEventElapsedTime(ms, ev0, ev1));
+}
+// one bounce pass from the source volume V (VV non-null: through its visible lookup): the lookup at the rays' mesh hits. d_alpha: the
+// rays' NeRF alpha, n K floats on the device (nullable: 0).
+void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const float* albedo, const IrradianceVolume& V,
+                 const IrradianceVolumeVisible* VV, const float* d_alpha, float* h_sh, float* h_rays, const float4* d_v0, float4* d_next) {
+	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
+		launch_irradiance_bounce_rays(ctx->mesh_scene, V, VV, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, albedo, d_alpha ? d_alpha + r0 : nullptr, rgba, t, ctx->stream);
+	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_bounce_ms);
+}
+// the sun pass: the shadow query at the rays' mesh hits that face the sun; no volume is read. d_alpha as above.
+void sun_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun, const float* d_alpha, float* h_sh,
+              float* h_rays, const float4* d_v0, float4* d_next) {
+	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
+		launch_irradiance_sun_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_alpha ? d_alpha + r0 : nullptr, rgba, t,
+		                           ctx->stream);
+	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_sun_ms);
 }
 
-// the volume of desc: V_0 traced through the NeRF, then `bounce` (nullable: none) passes V_b = V_0 + R(V_{b-1}) looked up through the
-// distance maps of `visibility` (nullable: none, and none kept). The context's volume is replaced once every launch has succeeded.
-void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_visibility_desc* visibility) {
+// the volume of desc: V_0 traced through the NeRF, then the sun's first bounce off the meshes S = V_0 + R_sun (`sun` nullable: none, S =
+// V_0), then `bounce` (nullable: none) passes V_b = S + R(V_{b-1}) looked up through the distance maps of `visibility` (nullable: none,
+// and none kept). The context's volume is replaced once every launch has succeeded.
+void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_visibility_desc* visibility,
+                    const SunLight* sun = nullptr) {
 	require_probe_model(ctx, "SH irradiance probes");
 	const uint64_t probes = check_volume_lattice(desc);
 	const uint32_t K = check_sh_desc(probes, &desc->sh);
@@ -443,17 +483,21 @@ void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const 
 	const std::vector<float> positions = volume_positions(desc, probes);
 	// without a source (no pass asked for, a black albedo, nothing to hit) the records are V_0's own: no pass runs
 	const float* al = bounce ? bounce->albedo : nullptr;
-	const uint32_t n_bounces = al && (al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) && !ctx->meshes.empty() && desc->sh.occlude_by_meshes != 0 ? bounce->n_bounces : 0;
-	DevArray<float4> v0(SH_FLOAT4 * (size_t)probes), even(n_bounces > 1 ? v0.size() : 0), odd(n_bounces > 0 ? v0.size() : 0);
-	DevArray<float> alpha(n_bounces ? (size_t)probes * K : 0); // the whole volume's rays: the NeRF is traced once
+	const bool hits = !ctx->meshes.empty() && desc->sh.occlude_by_meshes != 0;
+	const uint32_t n_bounces = al && (al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) && hits ? bounce->n_bounces : 0;
+	const bool sunlit = sun && sun->lit && hits; // (a black albedo leaves no channel of the source lit)
+	DevArray<float4> traced(SH_FLOAT4 * (size_t)probes), lit(sunlit ? traced.size() : 0), even(n_bounces > 1 ? traced.size() : 0), odd(n_bounces > 0 ? traced.size() : 0);
+	DevArray<float> alpha(n_bounces || sunlit ? (size_t)probes * K : 0); // the whole volume's rays: the NeRF is traced once
 	// (alpha is empty without a pass: an empty DevArray's get() is nullptr, which is how trace_sh_probes and bounce_pass are told "none")
-	trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, v0.get(), nullptr, alpha.get());
+	trace_sh_probes(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, nullptr, traced.get(), nullptr, alpha.get());
 	DevArray<float2> maps(visibility ? DISTANCE_MAP_TEXELS * (size_t)probes : 0);
 	if (visibility) distance_maps(ctx, (uint32_t)probes, positions.data(), visibility, K_vis, D, nullptr, maps.get());
 	IrradianceVolumeVisible A{};
 	A.maps = maps.get();
 	A.D = D;
 	A.normal_bias = visibility ? visibility->normal_bias : 0.0f;
+	if (sunlit) sun_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, alpha.get(), nullptr, nullptr, traced.get(), lit.get());
+	DevArray<float4>& v0 = sunlit ? lit : traced; // what the passes add to: the sun's light bounces with the NeRF's
 	const float4* prev = v0.get();
 	for (uint32_t b = 1; b <= n_bounces; ++b) { // every probe of a pass reads the pass before it alone
 		float4* next = b % 2u ? odd.get() : even.get();
@@ -677,6 +721,47 @@ int ngp_compute_irradiance_volume_bounced(ngp_ctx* ctx, const ngp_irradiance_vol
 		if (bounce->n_bounces > MAX_BOUNCES) throw std::runtime_error("invalid irradiance bounce descriptor: n_bounces must be at most 16");
 		check_albedo(bounce->albedo);
 		compute_volume(ctx, desc, bounce, visibility);
+	});
+}
+
+int ngp_compute_irradiance_volume_sunlit(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                         const ngp_irradiance_visibility_desc* visibility, const ngp_irradiance_sun_desc* sun) {
+	return guarded(ctx, [&] {
+		if (!bounce) throw std::runtime_error(sun ? "invalid irradiance sun descriptor: the bounce descriptor (its albedo) is needed with a sun" : "null argument");
+		if (bounce->n_bounces > MAX_BOUNCES) throw std::runtime_error("invalid irradiance bounce descriptor: n_bounces must be at most 16");
+		check_albedo(bounce->albedo);
+		SunLight L{};
+		if (sun) L = check_sun(sun, bounce->albedo);
+		compute_volume(ctx, desc, bounce, visibility, sun ? &L : nullptr);
+	});
+}
+
+int ngp_irradiance_sh_sun(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* desc, const ngp_irradiance_sun_desc* sun, const float* albedo,
+                          const float* alpha, float* sh_out, float* rays_out) {
+	return guarded(ctx, [&] {
+		check_albedo(albedo);
+		if (!sun) throw std::runtime_error("null argument");
+		const SunLight L = check_sun(sun, albedo);
+		require_device(ctx);
+		const uint32_t K = check_sh_desc(n, desc);
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!sh_out) throw std::runtime_error("null argument");
+		const size_t rays = (size_t)n * K;
+		if (alpha)
+			for (size_t i = 0; i < rays; ++i)
+				if (!std::isfinite(alpha[i])) throw std::runtime_error("alpha " + std::to_string(i) + " is not finite");
+		DevArray<float> d_alpha(alpha ? rays : 0);
+		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
+		sun_pass(ctx, n, positions, desc, K, L, d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+	});
+}
+
+int ngp_get_irradiance_sun_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = ctx->sh_sun_ms;
 	});
 }
 

@@ -435,7 +435,7 @@ public:
 				// (bounces: the visibility is computed inside that call, ahead of the passes that look the volume up through it)
 				const bool vis_in_bounces = m_irradiance_volume_visibility && m_irradiance_volume_bounces > 0;
 				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res}, nullptr, 32, 32, true, nullptr, m_irradiance_volume_bounces, nullptr,
-				                          vis_in_bounces);
+				                          vis_in_bounces, m_irradiance_volume_sun);
 				if (m_irradiance_volume_visibility && !vis_in_bounces) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
 			}
 		}
@@ -536,20 +536,26 @@ public:
 	// a lattice of res probes over aabb6 (nullptr: the render aabb), traced and kept in the context; returns the records, probes x 28 in
 	// index order i + rx (j + ry k), and the box in aabb6_out. bounces > 0: that many passes of diffuse interreflection off the meshes, of
 	// colour albedo3 (nullptr: the base colour squared per channel, clamped to [0, 1]: what the mesh pass hands the BRDF); with_visibility
-	// (bounces > 0 alone): the distance maps (their defaults) are computed ahead of the passes, used by them and kept
+	// (bounces > 0 alone): the distance maps (their defaults) are computed ahead of the passes, used by them and kept. sun: the frame's sun
+	// (m_sun_dir, m_irradiance_volume_sun_radiance, the frame's shadow bias 1e-3) throws its first bounce off the meshes into the records
+	// ahead of the passes, also with bounces = 0; the albedo is the same
 	std::vector<float> compute_irradiance_volume(const std::array<uint32_t, 3>& res, const float* aabb6 = nullptr, uint32_t n_u = 32, uint32_t n_v = 32,
 	                                             bool occlude_by_meshes = true, float* aabb6_out = nullptr, uint32_t bounces = 0, const float* albedo3 = nullptr,
-	                                             bool with_visibility = false) {
+	                                             bool with_visibility = false, bool sun = false) {
 		ngp_irradiance_volume_desc d{};
 		const float* box = aabb6 ? aabb6 : m_render_aabb.data();
 		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
 		d.sh = ngp_irradiance_sh_desc{n_u, n_v, nerf.render_min_transmittance, occlude_by_meshes ? 1 : 0};
-		if (bounces > 0) {
+		if (bounces > 0 || sun) {
 			ngp_irradiance_bounce_desc b{};
 			b.n_bounces = bounces;
 			for (int c = 0; c < 3; ++c) b.albedo[c] = albedo3 ? albedo3[c] : std::min(std::max(brdf.basecolor[c] * brdf.basecolor[c], 0.0f), 1.0f);
 			const ngp_irradiance_visibility_desc v{16, 16, 5, 0.f, 0.f};
-			check(ngp_compute_irradiance_volume_bounced(m_ctx, &d, &b, with_visibility ? &v : nullptr));
+			ngp_irradiance_sun_desc s{};
+			for (int c = 0; c < 3; ++c) { s.direction[c] = m_sun_dir[c]; s.radiance[c] = m_irradiance_volume_sun_radiance[c]; }
+			s.shadow_bias = 1e-3f;
+			check(sun ? ngp_compute_irradiance_volume_sunlit(m_ctx, &d, &b, with_visibility ? &v : nullptr, &s)
+			          : ngp_compute_irradiance_volume_bounced(m_ctx, &d, &b, with_visibility ? &v : nullptr));
 		} else {
 			check(ngp_compute_irradiance_volume(m_ctx, &d));
 		}
@@ -591,6 +597,8 @@ public:
 	}
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	bool m_irradiance_volume_visibility = false; // the default volume of a ShadeIrradianceVolume render also gets distance maps (16 x 16 rays, sharpness 2^5, D and bias default)
+	bool m_irradiance_volume_sun = false; // that default volume also holds the sun's first bounce off the meshes (the frame's sun: m_sun_dir, the radiance below, bias 1e-3)
+	std::array<float, 3> m_irradiance_volume_sun_radiance{255.f / 255.0f * 4.f, 225.f / 255.0f * 4.f, 195.f / 255.0f * 4.f}; // the frames' suncol (mesh_kernels.hip)
 	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)
 	uint32_t m_irradiance_volume_res = 8; // probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none (32 x 32 rays, meshes occluding)
 	std::array<float, 12> m_camera_end{};                       // camera_matrix1 of the frame being rendered along a path

@@ -113,6 +113,13 @@ class IrradianceBounceDesc(C.Structure):
     _fields_ = [("n_bounces", C.c_uint32), ("albedo", C.c_float * 3)]
 
 
+class IrradianceSunDesc(C.Structure):
+    _fields_ = [("direction", C.c_float * 3), ("radiance", C.c_float * 3), ("shadow_bias", C.c_float)]
+
+
+SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64), ("n_rays_alive_after_init", C.c_uint64), ("n_rays_hit", C.c_uint64), ("n_samples", C.c_uint64),
@@ -243,6 +250,10 @@ def load_library():
     L.ngp_compute_irradiance_volume_bounced.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), C.POINTER(IrradianceBounceDesc), C.POINTER(IrradianceVisibilityDesc)]
     L.ngp_irradiance_sh_bounce.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), vp, vp, C.c_int, vp, vp]
     L.ngp_get_irradiance_bounce_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_compute_irradiance_volume_sunlit.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), C.POINTER(IrradianceBounceDesc), C.POINTER(IrradianceVisibilityDesc),
+                                                       C.POINTER(IrradianceSunDesc)]
+    L.ngp_irradiance_sh_sun.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), C.POINTER(IrradianceSunDesc), vp, vp, vp, vp]
+    L.ngp_get_irradiance_sun_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -739,12 +750,21 @@ class Context:
         self._check(self.L.ngp_irradiance_sh_traced(self.h, p.shape[0], _p(p), C.byref(d), _p(sh), _p(rays) if return_rays else None))
         return (sh, rays) if return_rays else sh
 
-    def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01, bounces=0, albedo=None, visibility=None):
+    def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01, bounces=0, albedo=None, visibility=None,
+                                  sun=None):
         """trace a lattice of resolution = (rx, ry, rz) probes over aabb = (min, max); the volume stays on the device (get_irradiance_volume).
         bounces > 0: that many passes of diffuse interreflection off the meshes, of colour albedo (three channels in [0, 1], or one number for
         all three; None: the default base colour 0.8 squared, in float32); visibility: None, or the keywords of compute_irradiance_volume_visibility
-        as a dict: the distance maps are computed first, the bounces look the volume up through them, and they stay in the context"""
+        as a dict: the distance maps are computed first, the bounces look the volume up through them, and they stay in the context.
+        sun: None, or the sun whose first bounce off the meshes joins the records ahead of the passes (also with bounces = 0): a dict with
+        direction and optionally radiance (default: the frames' sun colour) and shadow_bias (1e-3), or a tuple in that order"""
         d = self._volume_desc(resolution, aabb, self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance))
+        if sun is not None:
+            b = self._bounce_desc(bounces, np.float32(0.8) * np.float32(0.8) if albedo is None else albedo)
+            v = None if visibility is None else self._visibility_desc(**dict(dict(n_u=16, n_v=16, sharpness_log2=5, max_distance=0.0, normal_bias=0.0), **visibility))
+            s = self._sun_desc(sun)
+            self._check(self.L.ngp_compute_irradiance_volume_sunlit(self.h, C.byref(d), C.byref(b), C.byref(v) if v is not None else None, C.byref(s)))
+            return
         if not bounces:
             if albedo is not None or visibility is not None:
                 raise ValueError("albedo and visibility belong to bounces > 0")
@@ -760,6 +780,49 @@ class Context:
         b.n_bounces = bounces
         b.albedo[:] = [float(x) for x in np.broadcast_to(np.asarray(albedo, np.float32), (3,))]
         return b
+
+    @staticmethod
+    def _sun_desc(sun):
+        if isinstance(sun, IrradianceSunDesc):
+            return sun
+        if isinstance(sun, dict):
+            extra = set(sun) - {"direction", "radiance", "shadow_bias"}
+            if extra or "direction" not in sun:
+                raise ValueError("sun: direction, and optionally radiance and shadow_bias")
+            sun = (sun["direction"], sun.get("radiance", SUN_RADIANCE), sun.get("shadow_bias", 1e-3))
+        sun = tuple(sun)
+        if not 1 <= len(sun) <= 3 or np.ndim(sun[0]) != 1:
+            raise ValueError("sun: (direction, radiance, shadow_bias)")
+        sun = sun + (SUN_RADIANCE, 1e-3)[len(sun) - 1:]
+        s = IrradianceSunDesc()
+        s.direction[:] = [float(x) for x in np.asarray(sun[0], np.float32).reshape(3)]
+        s.radiance[:] = [float(x) for x in np.broadcast_to(np.asarray(sun[1], np.float32), (3,))]
+        s.shadow_bias = float(sun[2])
+        return s
+
+    def irradiance_sh_sun(self, positions, sun, albedo, n_u=32, n_v=32, alpha=None, occlude_by_meshes=True, return_rays=False):
+        """one sun pass at the probes at `positions` (no model, no volume): the records R_sun (n, 28) of the sun's first bounce off the meshes,
+        float 27 the unblocked fraction; with return_rays also every ray's (B rgb, t of the primary hit or inf), (n, K, 4). sun: as
+        compute_irradiance_volume takes it; alpha: None or the rays' NeRF alpha (n, K)"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        k = int(n_u) * int(n_v)
+        d = self._sh_desc(n_u, n_v, occlude_by_meshes, 0.01)
+        s = self._sun_desc(sun)
+        al = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, np.float32), (3,)))
+        a = None if alpha is None else np.ascontiguousarray(alpha, np.float32)
+        if a is not None and a.size != p.shape[0] * k:
+            raise ValueError("alpha: n x K values")
+        sh = np.zeros((p.shape[0], 28), np.float32)
+        rays = np.zeros((p.shape[0], k, 4), np.float32) if return_rays else None
+        self._check(self.L.ngp_irradiance_sh_sun(self.h, p.shape[0], _p(p), C.byref(d), C.byref(s), _p(al), _p(a) if a is not None else None, _p(sh),
+                                                 _p(rays) if return_rays else None))
+        return (sh, rays) if return_rays else sh
+
+    def irradiance_sun_ms(self):
+        """device time of the last sun pass (compute_irradiance_volume with a sun, irradiance_sh_sun), ms"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_irradiance_sun_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
         """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass

@@ -2,12 +2,18 @@
 tools/mesh_shade_rate.py's scene with N = 0, 1, 2 and 4 bounce passes, and the device time of one pass.
 
     python tools/irradiance_bounce_rate.py [--res 16] [--k 32] [--repeat 3] [--out profiles/irradiance_bounce_rate.json]
+    python tools/irradiance_bounce_rate.py --sun [--repeat 5] [--out profiles/irradiance_sun_rate.json]
 
 The volume spans the box of the meshes (it overlaps the NeRF's unit cube), the meshes occlude, albedo 0.64. Wall times are
 medians over --repeat calls after a warm-up and include the host's share; the pass time is HIP events around the last pass's chunks in
 the context's stream (ngp_get_irradiance_bounce_ms), the median over the same calls, with the plain and with the visible lookup (distance
 maps of 16 x 16 rays, computed inside the call and inside its wall time). Nothing is asserted on these numbers. Needs a GPU; there is
-no CPU path."""
+no CPU path.
+
+--sun measures the sun pass instead (ngp_get_irradiance_sun_ms), beside the bounce pass and the NeRF trace of the same call: a volume with
+the frames' sun (1, 1, 1) and N = 1, every repeat listed so that the run-to-run spread shows. It then runs the same calls in a child process
+on libngp_hip_sun_any_hit.so (build.py: build(sun_any_hit=True)), whose shadow query is an unsorted traversal that ends at the first hit
+instead of the shipped closest hit: what that early exit would buy. --lib PATH measures one library alone and builds nothing."""
 import argparse
 import json
 import os
@@ -41,17 +47,10 @@ def timed(ctx, f, repeat):
     return float(np.median(ts)), float(np.median(dev))
 
 
-def main():
+def load(native, synthetic):
+    """the benchmark's model among mesh_shade_rate's meshes: (context, the box of the meshes)"""
     from mesh_shade_rate import scene
 
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--res", type=int, default=16)
-    ap.add_argument("--k", type=int, default=32)
-    ap.add_argument("--repeat", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "irradiance_bounce_rate.json"))
-    args = ap.parse_args()
-    pkg("build").build()
-    native, synthetic = pkg("native"), pkg("synthetic")
     ctx = native.Context(0)
     ctx.set_model(synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19))
     lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
@@ -59,7 +58,66 @@ def main():
         ctx.add_mesh(tris, center)
         bmin, bmax = ctx.mesh_info(i)["aabb"]
         lo, hi = np.minimum(lo, bmin), np.maximum(hi, bmax)
-    box = (lo.astype(np.float32), hi.astype(np.float32))
+    return ctx, (lo.astype(np.float32), hi.astype(np.float32))
+
+
+def sun_passes(args):
+    """the device times of --repeat sunlit volumes with one bounce pass on the library native.py loads: every repeat's sun pass, bounce pass
+    and trace, ms"""
+    native, synthetic = pkg("native"), pkg("synthetic")
+    ctx, box = load(native, synthetic)
+    res, k = (args.res,) * 3, args.k
+    sun, bounce, trace = [], [], []
+    for i in range(args.repeat + 1):
+        ctx.compute_irradiance_volume(res, box, k, k, bounces=1, albedo=0.64, sun=((1.0, 1.0, 1.0), native.SUN_RADIANCE, 1e-3))
+        if i:  # (the first call warms up)
+            sun.append(round(ctx.irradiance_sun_ms(), 3))
+            bounce.append(round(ctx.irradiance_bounce_ms(), 3))
+            trace.append(round(ctx.render_stats()["kernel_ms"], 3))
+    _, sh = ctx.get_irradiance_volume()
+    ctx.close()
+    return {"library": os.path.basename(native.load_library()._name), "sun_pass_ms": sun, "bounce_pass_ms": bounce, "trace_ms": trace,
+            "blocked_share": round(float(1.0 - sh[..., 27].mean()), 4)}
+
+
+def main_sun(args):
+    import subprocess
+
+    if args.lib:  # one library, as the parent asks
+        os.environ["NGP_HIP_LIBRARY"] = os.path.abspath(args.lib)
+        print(json.dumps(sun_passes(args)))
+        return
+    out = {"how": "HIP events around the chunks of the last sun pass and bounce pass, and the tracer's kernel time, of a sunlit volume with N = 1; every repeat after a warm-up; "
+                  "closest_hit: the shipped library; any_hit: the same calls on the build whose shadow query ends at the first hit; one MI355X, one run",
+           "resolution": [args.res] * 3, "rays_per_probe": args.k * args.k, "rays": args.res ** 3 * args.k * args.k, "albedo": 0.64, "sun": [1, 1, 1]}
+    for name, lib in (("closest_hit", pkg("build").build()), ("any_hit", pkg("build").build(sun_any_hit=True))):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--sun", "--lib", lib, "--res", str(args.res), "--k", str(args.k), "--repeat", str(args.repeat)],
+                           capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            raise RuntimeError(r.stdout + r.stderr)
+        out[name] = json.loads(r.stdout.strip().splitlines()[-1])
+        print(f"{name:11s}: sun pass {out[name]['sun_pass_ms']} ms, bounce pass {out[name]['bounce_pass_ms']} ms, trace {out[name]['trace_ms']} ms", flush=True)
+    print(json.dumps(out))
+    path = args.out or os.path.join(ROOT, "profiles", "irradiance_sun_rate.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=16)
+    ap.add_argument("--k", type=int, default=32)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sun", action="store_true")
+    ap.add_argument("--lib", default=None)
+    args = ap.parse_args()
+    if args.sun:
+        return main_sun(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "irradiance_bounce_rate.json")
+    pkg("build").build()
+    native, synthetic = pkg("native"), pkg("synthetic")
+    ctx, box = load(native, synthetic)
     res, k = (args.res,) * 3, args.k
     rays = args.res ** 3 * k * k
     out = {"how": "median wall time of --repeat calls after a warm-up; pass = HIP events around the last bounce pass's chunks, the median over the same calls; one MI355X, one run",
