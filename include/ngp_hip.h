@@ -604,8 +604,8 @@ NGP_API int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms);
  * Determinism: no atomics; bit-identical from run to run and for any chunking. With sun == NULL, every radiance channel 0, every albedo
  *   channel 0, no meshes loaded or occlude_by_meshes == 0 no sun pass runs and the records are ngp_compute_irradiance_volume_bounced's as
  *   bytes.
- * Stated limits: the NeRF's density does not block the sun (the frames' own shadow ray does not test it either); the sun as seen
- *   directly from a probe is not in the records (the BRDF's direct term has it); one directional light; the frames' shadow ray follows
+ * Stated limits: the NeRF's density blocks the sun only through the *_shadowed entries below (the frames' own shadow ray does not test
+ *   it); the sun as seen directly from a probe is not in the records (the BRDF's direct term has it); one directional light; the frames' shadow ray follows
  *   the reference's one-mesh rule (ngp_trace_mesh_rays), this one sees all meshes.
  * Refusals, each naming its field: a zero or non-finite direction; a negative or non-finite radiance; a negative or non-finite
  *   shadow_bias; a NULL bounce descriptor when the sun is given; albedo x radiance overflowing float; everything the volume, visibility
@@ -627,6 +627,42 @@ NGP_API int ngp_irradiance_sh_sun(ngp_ctx* ctx, uint32_t n, const float* positio
                                   const float albedo[3], const float* alpha /* nullable, n K */, float* sh_out /* n x 28 */, float* rays_out /* nullable, n K x 4 */);
 /* device time (HIP events) of the last sun pass of either entry, ms, as ngp_get_irradiance_bounce_ms reports a bounce pass's */
 NGP_API int ngp_get_irradiance_sun_ms(ngp_ctx* ctx, float* ms);
+
+/* The NeRF's density in front of the sun. Without it a floor under the NeRF's object is lit as if the object were not there.
+ *
+ * The shadow ray: one exists for every probe ray k the sun pass above lights: a hit, c_k > 0, vis_k = 1. Its origin is q_k = h_k +
+ *   shadow_bias N_ff, the very float32 value the mesh shadow query uses; its direction is s^ as formed above. It is traced through the
+ *   NeRF with the semantics of ngp_trace_nerf_rays (the tracer's normalisation of the direction, the render box in force, which is the
+ *   inflated mesh box while meshes are loaded), with t_range = (t_min, +inf) and min_transmittance from the descriptor below.
+ * The result: alpha_s,k = that ray's alpha; T_s,k = max(1 - alpha_s,k, 0) in float32; B'_k,ch = fl(T_s,k B^sun_k,ch), one float32 product
+ *   per channel on the sun pass's value. Rays without a shadow ray keep B' = B = 0 and report alpha_s = 0. The projection, S = V_0 + R_sun
+ *   and the bounce recurrence are unchanged, with B' in B^sun's place; float 27 of a record is unchanged.
+ * Determinism: no atomics; bit-identical from run to run and for any chunking (the shadow-ray list is not compacted: one entry per probe
+ *   ray, dead where there is no shadow ray).
+ * Stated limits: the NeRF attenuates the sun but is not lit by it; the frames' own direct sun term on a mesh pixel still ignores the NeRF,
+ *   as in the reference, and no frame of another mode changes; a hit that sits inside the NeRF's own density shadows itself unless t_min
+ *   skips it.
+ * Refusals, each naming its field: a NaN min_transmittance; a negative or non-finite t_min; everything the sun section refuses. The bounce
+ *   descriptor is looked at first, then the sun's, then this one, before anything else, on any context. */
+typedef struct ngp_irradiance_sun_nerf_desc {
+	float min_transmittance; /* as in ngp_trace_nerf_rays (<= 0 selects 0.01); NaN refused */
+	float t_min;             /* the NeRF is ignored within t_min of q along the sun direction; finite, >= 0 */
+} ngp_irradiance_sun_nerf_desc;
+/* ngp_compute_irradiance_volume_sunlit with the shadow rays in its sun pass. nerf == NULL is that entry as bytes; sun == NULL (or any of
+ * its no-source cases) runs no pass and the records are ngp_compute_irradiance_volume_bounced's as bytes. The volume, the maps and one step
+ * of the generation counter are committed together, and peers get the volume, as there. ngp_get_render_stats reports the shadow trace
+ * like any tracer call. */
+NGP_API int ngp_compute_irradiance_volume_sunlit_shadowed(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                                          const ngp_irradiance_visibility_desc* visibility /* nullable */, const ngp_irradiance_sun_desc* sun /* nullable */,
+                                                          const ngp_irradiance_sun_nerf_desc* nerf /* nullable */);
+/* a stage entry for tests: ONE shadowed sun pass at the caller's probes. Needs a device and a model (the meshes too, to light anything), no
+ * volume. alpha as in ngp_irradiance_sh_sun. rays_out (nullable) n K x 4 = (B'_rgb, t of the primary hit or +inf); shadow_out (nullable)
+ * n K x 4 = (q_xyz, alpha_s), zeros where there is no shadow ray; sh_out n x 28 = the projection of B', float 27 = the unblocked fraction */
+NGP_API int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const ngp_irradiance_sh_desc* desc, const ngp_irradiance_sun_desc* sun,
+                                           const float albedo[3], const float* alpha /* nullable, n K */, const ngp_irradiance_sun_nerf_desc* nerf,
+                                           float* rays_out /* nullable, n K x 4 */, float* shadow_out /* nullable, n K x 4 */, float* sh_out /* n x 28 */);
+/* device time (HIP events) of the shadow rays' prep and trace in the last sun pass, ms, summed over its chunks; 0 after a pass without them */
+NGP_API int ngp_get_irradiance_sun_shadow_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -896,39 +896,93 @@ NGP_DEV bool any_hit(const MeshSceneParams S, f3 org, f3 dir) {
 #endif
 }
 
-// the n rays of a chunk of whole probes, one thread a ray: rgba_out = (B rgb, t of the hit or +inf), t_out = (0, the same t) as the
-// projection counts it. B_ch = (1 - alpha) albedo_ch radiance_ch c vis / pi with c = N_ff . sun (N_ff the hit triangle's winding normal
-// turned against the ray, sun a unit vector), vis = 0 where a triangle of any mesh lies within MAX_DIST of q = h + bias N_ff along sun;
-// 0 without a hit and where c <= 0. alpha: the chunk's rays' NeRF alpha (nullptr: 0). No volume is read.
-__global__ void irradiance_sun_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions, float sun_x,
-                                           float sun_y, float sun_z, float bias, float source_r, float source_g, float source_b, const float* __restrict__ alpha,
-                                           float4* __restrict__ rgba_out, float2* __restrict__ t_out) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
+// ray i of a chunk of whole probes under the sun: B_ch = (1 - alpha) albedo_ch radiance_ch c vis / pi with c = N_ff . sun (N_ff the hit
+// triangle's winding normal turned against the ray, sun a unit vector), vis = 0 where a triangle of any mesh lies within MAX_DIST of
+// q = h + bias N_ff along sun; 0 without a hit and where c <= 0. Returns t of the primary hit (+inf without one). alpha: the chunk's rays'
+// NeRF alpha (nullptr: 0). No volume is read. lit: the ray has a hit, c > 0 and vis = 1, and q is that ray's lifted hit point (zeros
+// otherwise); a caller that drops both keeps the code it had before they were returned. S by value, as in closest_hit.
+NGP_DEV float sun_ray(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t i, const float* __restrict__ positions, f3 sun, float bias, f3 source,
+                      const float* __restrict__ alpha, f3& B, f3& q_out, bool& lit) {
 	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
 	const f3 dir = sphere_dir(k, n_u, n_v);
 	const f3 org = ld3(positions + 3 * (size_t)pl);
 	int mesh = -1, tri_idx = -1;
 	const float t_max = occlude ? closest_hit(S, org, dir, &mesh, &tri_idx) : __builtin_huge_valf();
-	f3 B = mk3(0.f, 0.f, 0.f);
+	B = mk3(0.f, 0.f, 0.f);
+	q_out = mk3(0.f, 0.f, 0.f);
+	lit = false;
 	if (mesh > -1) {
 		const Triangle& tri = S.meshes[mesh].tris[tri_idx];
 		const f3 a = ld3(tri.a);
 		const f3 N = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
 		const f3 nff = dot3(N, dir) < 0.0f ? N : scale3(N, -1.0f);
-		const f3 sun = mk3(sun_x, sun_y, sun_z);
 		const float c = dot3(nff, sun);
 		if (c > 0.0f) {
 			const f3 h = add3(org, scale3(dir, t_max));
 			const f3 q = add3(h, scale3(nff, bias));
 			if (!any_hit(S, q, sun)) {
 				const float through = 1.0f - (alpha ? alpha[i] : 0.0f);
-				B = mk3(through * (source_r * c / PI_F), through * (source_g * c / PI_F), through * (source_b * c / PI_F));
+				B = mk3(through * (source.x * c / PI_F), through * (source.y * c / PI_F), through * (source.z * c / PI_F));
+				q_out = q;
+				lit = true;
 			}
 		}
 	}
+	return t_max;
+}
+
+// the n rays of a chunk of whole probes, one thread a ray: rgba_out = (B rgb, t of the hit or +inf), t_out = (0, the same t) as the
+// projection counts it; B as sun_ray forms it.
+__global__ void irradiance_sun_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions, float sun_x,
+                                           float sun_y, float sun_z, float bias, float source_r, float source_g, float source_b, const float* __restrict__ alpha,
+                                           float4* __restrict__ rgba_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B, q;
+	bool lit;
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, mk3(source_r, source_g, source_b), alpha, B, q, lit);
 	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
 	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// ---- the NeRF's density in front of the sun (ngp_compute_irradiance_volume_sunlit_shadowed, ngp_irradiance_sh_sun_shadowed; contract in
+// include/ngp_hip.h, "sun"). The generator below also writes the chunk's shadow-ray list for the ray-list tracer, one entry per probe ray
+// in the chunk's own layout (no compaction: any chunking gives the same bytes); the apply kernel scales B by what the tracer let through.
+
+// irradiance_sun_rays_kernel, and entry i of the shadow-ray list: origin q, direction sun, t = (t_min, +inf) for a ray the sun lights;
+// origin 0, t = (0, 0) for every other ray, which ray_list_prep_kernel leaves dead
+__global__ void irradiance_sun_shadow_rays_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions, float sun_x,
+                                                  float sun_y, float sun_z, float bias, float source_r, float source_g, float source_b, const float* __restrict__ alpha,
+                                                  float t_min, float4* __restrict__ rgba_out, float2* __restrict__ t_out, float* __restrict__ o_out, float* __restrict__ d_out,
+                                                  float2* __restrict__ st_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B, q;
+	bool lit;
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, mk3(source_r, source_g, source_b), alpha, B, q, lit);
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+	o_out[3 * (size_t)i] = q.x; o_out[3 * (size_t)i + 1] = q.y; o_out[3 * (size_t)i + 2] = q.z;
+	d_out[3 * (size_t)i] = sun_x; d_out[3 * (size_t)i + 1] = sun_y; d_out[3 * (size_t)i + 2] = sun_z;
+	st_out[i] = lit ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
+}
+
+// B' = max(1 - alpha_s, 0) B on the chunk's rays, one float32 product a channel: alpha_s = the tracer's alpha of the ray's shadow ray
+// (traced: its rgba), 0 for a ray without one (st.y = 0, as the generator left it; the prep step moves st.x alone). rgba: (B rgb, t) in
+// place, t untouched; shadow_out (nullable): (q, alpha_s), zeros without a shadow ray.
+__global__ void irradiance_sun_shadow_apply_kernel(uint32_t n, const float4* __restrict__ traced, const float* __restrict__ o, const float2* __restrict__ st,
+                                                   float4* __restrict__ rgba, float4* __restrict__ shadow_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool has = st[i].y != 0.0f;
+	const float alpha_s = has ? traced[i].w : 0.0f;
+	if (has) {
+		const float through = fmaxf(1.0f - alpha_s, 0.0f);
+		float4 b = rgba[i];
+		b.x = through * b.x; b.y = through * b.y; b.z = through * b.z;
+		rgba[i] = b;
+	}
+	if (shadow_out) shadow_out[i] = has ? make_float4(o[3 * (size_t)i], o[3 * (size_t)i + 1], o[3 * (size_t)i + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // sun: the unit direction towards the sun; source: albedo x radiance per channel, as the host forms it in float
@@ -936,6 +990,15 @@ void launch_irradiance_sun_rays(const MeshSceneParams& S, bool occlude, uint32_t
                                 const float* source, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
 	if (n) hipLaunchKernelGGL(irradiance_sun_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias,
 	                          source[0], source[1], source[2], alpha, rgba, t);
+}
+// the same pass with the shadow-ray list of its chunk: o, d (3 n floats each) and st (n) for launch_ray_list_prep and the ray-list tracer
+void launch_irradiance_sun_shadow_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
+                                       const float* source, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_sun_shadow_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2],
+	                          bias, source[0], source[1], source[2], alpha, t_min, rgba, t, o, d, st);
+}
+void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const float* o, const float2* st, float4* rgba, float4* shadow_out, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_sun_shadow_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, traced, o, st, rgba, shadow_out);
 }
 
 } // namespace ngp

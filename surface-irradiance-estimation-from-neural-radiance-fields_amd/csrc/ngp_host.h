@@ -165,6 +165,9 @@ void launch_irradiance_volume_add(uint32_t n_float4, const float4* v0, const flo
 void launch_ray_alpha(uint32_t n, const float4* rgba, float* alpha, hipStream_t stream);
 void launch_irradiance_sun_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
                                 const float* source, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // sun: unit; source: albedo x radiance
+void launch_irradiance_sun_shadow_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
+                                       const float* source, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st, hipStream_t stream);
+void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const float* o, const float2* st, float4* rgba, float4* shadow_out, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
 // scratch (chunk x 3 floats, chunk x 4 fp16); grid models need none.
@@ -415,6 +418,7 @@ struct ngp_ctx {
 	bool mc_valid = false, mc_attrs = false;
 	float sh_bounce_ms = 0.f; // device time of the last bounce pass over the SH9 volume's probes (ngp_get_irradiance_bounce_ms)
 	float sh_sun_ms = 0.f;    // device time of the last sun pass over them (ngp_get_irradiance_sun_ms)
+	float sh_sun_shadow_ms = 0.f; // of it, the shadow rays through the NeRF: prep and trace (ngp_get_irradiance_sun_shadow_ms); 0 after a pass without them
 	float mc_ms[3] = {0.f, 0.f, 0.f}; // device time of the last ngp_compute_marching_cubes_mesh: lattice, marching cubes, normals + colours
 
 	// ---- training (ngp_train.cpp)

@@ -251,6 +251,23 @@ SunLight check_sun(const ngp_irradiance_sun_desc* s, const float* albedo) {
 	return L;
 }
 
+// the NeRF's density in front of the sun (nullable: the meshes alone shadow it)
+void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d) {
+	if (!d) return;
+	if (std::isnan(d->min_transmittance)) throw std::runtime_error("invalid irradiance sun NeRF descriptor: min_transmittance is NaN");
+	if (!std::isfinite(d->t_min) || d->t_min < 0.0f) throw std::runtime_error("invalid irradiance sun NeRF descriptor: t_min must be finite and >= 0");
+}
+// bounce, then sun, then the NeRF shadow: what the sunlit entries look at before anything else. Returns the sun as the passes use it.
+SunLight check_sunlit(const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_sun_desc* sun, const ngp_irradiance_sun_nerf_desc* nerf) {
+	if (!bounce) throw std::runtime_error(sun ? "invalid irradiance sun descriptor: the bounce descriptor (its albedo) is needed with a sun" : "null argument");
+	if (bounce->n_bounces > MAX_BOUNCES) throw std::runtime_error("invalid irradiance bounce descriptor: n_bounces must be at most 16");
+	check_albedo(bounce->albedo);
+	SunLight L{};
+	if (sun) L = check_sun(sun, bounce->albedo);
+	check_sun_nerf(nerf);
+	return L;
+}
+
 void require_volume(const ngp_ctx* ctx) {
 	if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
 }
@@ -468,13 +485,45 @@ void sun_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradi
 		launch_irradiance_sun_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_alpha ? d_alpha + r0 : nullptr, rgba, t,
 		                           ctx->stream);
 	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_sun_ms);
+	ctx->sh_sun_shadow_ms = 0.f;
+}
+
+// the sun pass with the NeRF's density in front of the sun: per chunk the generator also leaves the shadow-ray list (one entry a probe ray,
+// dead where the sun lights nothing), the ray-list tracer walks it inside ONE tracer call, and the apply kernel scales B ahead of the
+// projection. h_shadow (host, n K x 4, nullable): (q, alpha_s) per ray. Needs a model (require_probe_model is the caller's).
+void sun_pass_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun,
+                       const ngp_irradiance_sun_nerf_desc& nerf, const float* d_alpha, float* h_sh, float* h_rays, float* h_shadow, const float4* d_v0, float4* d_next) {
+	const size_t cap = (size_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK); // (ProbeChunks' cap)
+	DevArray<float> o(3 * cap), dir(3 * cap);
+	DevArray<float2> st(cap);
+	DevArray<float4> traced(cap), shadow(h_shadow ? cap : 0);
+	std::vector<std::pair<Event, Event>> spans; // one chunk's prep and trace each
+	TracerCall tr(ctx, (uint64_t)n * K, nerf.min_transmittance);
+	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
+		launch_irradiance_sun_shadow_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_alpha ? d_alpha + r0 : nullptr,
+		                                  nerf.t_min, rgba, t, o.get(), dir.get(), st.get(), ctx->stream);
+		spans.emplace_back(new_event(), new_event());
+		NGP_HIP_CHECK(hipEventRecord(spans.back().first, ctx->stream));
+		launch_ray_list_prep(tr.model(), m, o.get(), dir.get(), st.get(), true, ctx->stream);
+		tr.trace_rays(m, o.get(), dir.get(), st.get(), traced.get());
+		NGP_HIP_CHECK(hipEventRecord(spans.back().second, ctx->stream));
+		launch_irradiance_sun_shadow_apply(m, traced.get(), o.get(), st.get(), rgba, shadow.get(), ctx->stream);
+		if (h_shadow) download(ctx, h_shadow + 4 * r0, shadow.get(), (size_t)m * sizeof(float4));
+	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_sun_ms);
+	tr.finish(); // (synchronises the stream: the list may go)
+	ctx->sh_sun_shadow_ms = 0.f;
+	for (const auto& s : spans) {
+		float ms = 0.f;
+		NGP_HIP_CHECK(hipEventElapsedTime(&ms, s.first, s.second));
+		ctx->sh_sun_shadow_ms += ms;
+	}
 }
 
 // the volume of desc: V_0 traced through the NeRF, then the sun's first bounce off the meshes S = V_0 + R_sun (`sun` nullable: none, S =
-// V_0), then `bounce` (nullable: none) passes V_b = S + R(V_{b-1}) looked up through the distance maps of `visibility` (nullable: none,
+// V_0; `nerf` nullable: the NeRF's density does not shadow the sun), then `bounce` (nullable: none) passes V_b = S + R(V_{b-1}) looked up through the distance maps of `visibility` (nullable: none,
 // and none kept). The context's volume is replaced once every launch has succeeded.
 void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_visibility_desc* visibility,
-                    const SunLight* sun = nullptr) {
+                    const SunLight* sun = nullptr, const ngp_irradiance_sun_nerf_desc* nerf = nullptr) {
 	require_probe_model(ctx, "SH irradiance probes");
 	const uint64_t probes = check_volume_lattice(desc);
 	const uint32_t K = check_sh_desc(probes, &desc->sh);
@@ -496,7 +545,8 @@ void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const 
 	A.maps = maps.get();
 	A.D = D;
 	A.normal_bias = visibility ? visibility->normal_bias : 0.0f;
-	if (sunlit) sun_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, alpha.get(), nullptr, nullptr, traced.get(), lit.get());
+	if (sunlit && nerf) sun_pass_shadowed(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, *nerf, alpha.get(), nullptr, nullptr, nullptr, traced.get(), lit.get());
+	else if (sunlit) sun_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, alpha.get(), nullptr, nullptr, traced.get(), lit.get());
 	DevArray<float4>& v0 = sunlit ? lit : traced; // what the passes add to: the sun's light bounces with the NeRF's
 	const float4* prev = v0.get();
 	for (uint32_t b = 1; b <= n_bounces; ++b) { // every probe of a pass reads the pass before it alone
@@ -727,12 +777,16 @@ int ngp_compute_irradiance_volume_bounced(ngp_ctx* ctx, const ngp_irradiance_vol
 int ngp_compute_irradiance_volume_sunlit(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
                                          const ngp_irradiance_visibility_desc* visibility, const ngp_irradiance_sun_desc* sun) {
 	return guarded(ctx, [&] {
-		if (!bounce) throw std::runtime_error(sun ? "invalid irradiance sun descriptor: the bounce descriptor (its albedo) is needed with a sun" : "null argument");
-		if (bounce->n_bounces > MAX_BOUNCES) throw std::runtime_error("invalid irradiance bounce descriptor: n_bounces must be at most 16");
-		check_albedo(bounce->albedo);
-		SunLight L{};
-		if (sun) L = check_sun(sun, bounce->albedo);
+		const SunLight L = check_sunlit(bounce, sun, nullptr);
 		compute_volume(ctx, desc, bounce, visibility, sun ? &L : nullptr);
+	});
+}
+
+int ngp_compute_irradiance_volume_sunlit_shadowed(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce,
+                                                  const ngp_irradiance_visibility_desc* visibility, const ngp_irradiance_sun_desc* sun, const ngp_irradiance_sun_nerf_desc* nerf) {
+	return guarded(ctx, [&] {
+		const SunLight L = check_sunlit(bounce, sun, nerf);
+		compute_volume(ctx, desc, bounce, visibility, sun ? &L : nullptr, nerf);
 	});
 }
 
@@ -754,6 +808,37 @@ int ngp_irradiance_sh_sun(ngp_ctx* ctx, uint32_t n, const float* positions, cons
 		DevArray<float> d_alpha(alpha ? rays : 0);
 		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
 		sun_pass(ctx, n, positions, desc, K, L, d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+	});
+}
+
+int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* desc, const ngp_irradiance_sun_desc* sun, const float* albedo,
+                                   const float* alpha, const ngp_irradiance_sun_nerf_desc* nerf, float* rays_out, float* shadow_out, float* sh_out) {
+	return guarded(ctx, [&] {
+		check_albedo(albedo);
+		if (!sun || !nerf) throw std::runtime_error("null argument");
+		const SunLight L = check_sun(sun, albedo);
+		check_sun_nerf(nerf);
+		require_model(ctx, "the sun's shadow rays are traced through the model");
+		require_probe_model(ctx, "the sun's shadow rays");
+		const uint32_t K = check_sh_desc(n, desc);
+		check_positions(n, positions);
+		if (n == 0) return;
+		if (!sh_out) throw std::runtime_error("null argument");
+		const size_t rays = (size_t)n * K;
+		if (alpha)
+			for (size_t i = 0; i < rays; ++i)
+				if (!std::isfinite(alpha[i])) throw std::runtime_error("alpha " + std::to_string(i) + " is not finite");
+		DevArray<float> d_alpha(alpha ? rays : 0);
+		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
+		sun_pass_shadowed(ctx, n, positions, desc, K, L, *nerf, d_alpha.get(), sh_out, rays_out, shadow_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+	});
+}
+
+int ngp_get_irradiance_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = ctx->sh_sun_shadow_ms;
 	});
 }
 

@@ -216,7 +216,7 @@ PYBIND11_MODULE(pyngp, m) {
 		}, py::arg("positions"), py::arg("n_u") = 32, py::arg("n_v") = 32, py::arg("occlude_by_meshes") = true,
 		   "This project's own: SH9 irradiance probes traced at the points, (n, 28) = 9 coefficients x rgb, fraction of rays no mesh blocks")
 		.def("compute_irradiance_volume", [](Testbed& t, const std::array<uint32_t, 3>& res, py::object aabb, uint32_t n_u, uint32_t n_v, bool occlude_by_meshes, uint32_t bounces,
-		                                     py::object albedo, bool sun) {
+		                                     py::object albedo, bool sun, bool sun_nerf_shadow) {
 			const std::vector<float> box = aabb6_arg(aabb);
 			const bool own_albedo = !albedo.is_none();
 			const std::array<float, 3> al = own_albedo ? albedo.cast<std::array<float, 3>>() : std::array<float, 3>{};
@@ -224,7 +224,7 @@ PYBIND11_MODULE(pyngp, m) {
 			std::array<float, 6> used{};
 			{
 				py::gil_scoped_release nogil;
-				sh = t.compute_irradiance_volume(res, box.empty() ? nullptr : box.data(), n_u, n_v, occlude_by_meshes, used.data(), bounces, own_albedo ? al.data() : nullptr, false, sun);
+				sh = t.compute_irradiance_volume(res, box.empty() ? nullptr : box.data(), n_u, n_v, occlude_by_meshes, used.data(), bounces, own_albedo ? al.data() : nullptr, false, sun, sun_nerf_shadow);
 			}
 			py::array_t<float> a({(py::ssize_t)res[2], (py::ssize_t)res[1], (py::ssize_t)res[0], (py::ssize_t)28});
 			if (!sh.empty()) memcpy(a.mutable_data(), sh.data(), sh.size() * sizeof(float));
@@ -233,10 +233,11 @@ PYBIND11_MODULE(pyngp, m) {
 			d["aabb"] = py::make_tuple(std::array<float, 3>{used[0], used[1], used[2]}, std::array<float, 3>{used[3], used[4], used[5]});
 			return d;
 		}, py::arg("resolution"), py::arg("aabb") = py::none(), py::arg("n_u") = 32, py::arg("n_v") = 32, py::arg("occlude_by_meshes") = true, py::arg("bounces") = 0,
-		   py::arg("albedo") = py::none(), py::arg("sun") = false,
+		   py::arg("albedo") = py::none(), py::arg("sun") = false, py::arg("sun_nerf_shadow") = false,
 		   "This project's own: a lattice of SH9 irradiance probes, traced and kept for irradiance_volume_lookup: {'sh': (rz, ry, rx, 28), 'aabb': (min, max)} "
 		   "(aabb: None = the render aabb, or (min, max); bounces: passes of diffuse interreflection off the meshes, of colour albedo = (r, g, b) in [0, 1], None = the base colour squared; "
-		   "sun: the frame's sun, sun_dir with irradiance_volume_sun_radiance, throws its first bounce off the meshes into the records ahead of the passes)")
+		   "sun: the frame's sun, sun_dir with irradiance_volume_sun_radiance, throws its first bounce off the meshes into the records ahead of the passes; "
+		   "sun_nerf_shadow: with sun, the NeRF's density stands in front of it, traced with render_min_transmittance)")
 		.def("get_irradiance_volume", [](Testbed& t) {
 			std::array<uint32_t, 3> res{};
 			std::array<float, 6> box{};
@@ -256,6 +257,8 @@ PYBIND11_MODULE(pyngp, m) {
 		               "passes of diffuse interreflection off the meshes in the volume a ShadeIrradianceVolume render computes when the context holds none (albedo: the base colour squared)")
 		.def_readwrite("irradiance_volume_sun", &Testbed::m_irradiance_volume_sun,
 		               "the volume a ShadeIrradianceVolume render computes when the context holds none also holds the sun's first bounce off the meshes (sun_dir, irradiance_volume_sun_radiance)")
+		.def_readwrite("irradiance_volume_sun_nerf_shadow", &Testbed::m_irradiance_volume_sun_nerf_shadow,
+		               "with irradiance_volume_sun: the NeRF's density shadows that sun in the default volume (render_min_transmittance, t_min 0)")
 		.def_readwrite("irradiance_volume_sun_radiance", &Testbed::m_irradiance_volume_sun_radiance, "what a surface facing the sun receives in a sunlit volume; default: the frames' sun colour")
 		.def_readwrite("irradiance_volume_res", &Testbed::m_irradiance_volume_res, "probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none")
 		.def("irradiance_volume_lookup", [](Testbed& t, py::array_t<float, py::array::c_style | py::array::forcecast> positions,

@@ -435,7 +435,7 @@ public:
 				// (bounces: the visibility is computed inside that call, ahead of the passes that look the volume up through it)
 				const bool vis_in_bounces = m_irradiance_volume_visibility && m_irradiance_volume_bounces > 0;
 				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res}, nullptr, 32, 32, true, nullptr, m_irradiance_volume_bounces, nullptr,
-				                          vis_in_bounces, m_irradiance_volume_sun);
+				                          vis_in_bounces, m_irradiance_volume_sun, m_irradiance_volume_sun && m_irradiance_volume_sun_nerf_shadow);
 				if (m_irradiance_volume_visibility && !vis_in_bounces) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
 			}
 		}
@@ -538,10 +538,11 @@ public:
 	// colour albedo3 (nullptr: the base colour squared per channel, clamped to [0, 1]: what the mesh pass hands the BRDF); with_visibility
 	// (bounces > 0 alone): the distance maps (their defaults) are computed ahead of the passes, used by them and kept. sun: the frame's sun
 	// (m_sun_dir, m_irradiance_volume_sun_radiance, the frame's shadow bias 1e-3) throws its first bounce off the meshes into the records
-	// ahead of the passes, also with bounces = 0; the albedo is the same
+	// ahead of the passes, also with bounces = 0; the albedo is the same. sun_nerf_shadow (with sun alone): the NeRF's density stands in front
+	// of that sun (the frame's render_min_transmittance, t_min 0)
 	std::vector<float> compute_irradiance_volume(const std::array<uint32_t, 3>& res, const float* aabb6 = nullptr, uint32_t n_u = 32, uint32_t n_v = 32,
 	                                             bool occlude_by_meshes = true, float* aabb6_out = nullptr, uint32_t bounces = 0, const float* albedo3 = nullptr,
-	                                             bool with_visibility = false, bool sun = false) {
+	                                             bool with_visibility = false, bool sun = false, bool sun_nerf_shadow = false) {
 		ngp_irradiance_volume_desc d{};
 		const float* box = aabb6 ? aabb6 : m_render_aabb.data();
 		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
@@ -554,9 +555,13 @@ public:
 			ngp_irradiance_sun_desc s{};
 			for (int c = 0; c < 3; ++c) { s.direction[c] = m_sun_dir[c]; s.radiance[c] = m_irradiance_volume_sun_radiance[c]; }
 			s.shadow_bias = 1e-3f;
-			check(sun ? ngp_compute_irradiance_volume_sunlit(m_ctx, &d, &b, with_visibility ? &v : nullptr, &s)
-			          : ngp_compute_irradiance_volume_bounced(m_ctx, &d, &b, with_visibility ? &v : nullptr));
+			const ngp_irradiance_sun_nerf_desc ns{nerf.render_min_transmittance, 0.f};
+			if (sun_nerf_shadow && !sun) throw std::runtime_error("compute_irradiance_volume: sun_nerf_shadow belongs to sun");
+			check(sun && sun_nerf_shadow ? ngp_compute_irradiance_volume_sunlit_shadowed(m_ctx, &d, &b, with_visibility ? &v : nullptr, &s, &ns)
+			      : sun                  ? ngp_compute_irradiance_volume_sunlit(m_ctx, &d, &b, with_visibility ? &v : nullptr, &s)
+			                             : ngp_compute_irradiance_volume_bounced(m_ctx, &d, &b, with_visibility ? &v : nullptr));
 		} else {
+			if (sun_nerf_shadow) throw std::runtime_error("compute_irradiance_volume: sun_nerf_shadow belongs to sun");
 			check(ngp_compute_irradiance_volume(m_ctx, &d));
 		}
 		std::vector<float> out((size_t)res[0] * res[1] * res[2] * 28);
@@ -598,6 +603,7 @@ public:
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	bool m_irradiance_volume_visibility = false; // the default volume of a ShadeIrradianceVolume render also gets distance maps (16 x 16 rays, sharpness 2^5, D and bias default)
 	bool m_irradiance_volume_sun = false; // that default volume also holds the sun's first bounce off the meshes (the frame's sun: m_sun_dir, the radiance below, bias 1e-3)
+	bool m_irradiance_volume_sun_nerf_shadow = false; // ... with the NeRF's density in front of that sun (render_min_transmittance, t_min 0); looked at with m_irradiance_volume_sun alone
 	std::array<float, 3> m_irradiance_volume_sun_radiance{255.f / 255.0f * 4.f, 225.f / 255.0f * 4.f, 195.f / 255.0f * 4.f}; // the frames' suncol (mesh_kernels.hip)
 	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)
 	uint32_t m_irradiance_volume_res = 8; // probes per axis of the volume a ShadeIrradianceVolume render computes when the context holds none (32 x 32 rays, meshes occluding)

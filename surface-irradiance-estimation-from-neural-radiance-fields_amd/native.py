@@ -117,6 +117,10 @@ class IrradianceSunDesc(C.Structure):
     _fields_ = [("direction", C.c_float * 3), ("radiance", C.c_float * 3), ("shadow_bias", C.c_float)]
 
 
+class IrradianceSunNerfDesc(C.Structure):
+    _fields_ = [("min_transmittance", C.c_float), ("t_min", C.c_float)]
+
+
 SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
 
 
@@ -254,6 +258,10 @@ def load_library():
                                                        C.POINTER(IrradianceSunDesc)]
     L.ngp_irradiance_sh_sun.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), C.POINTER(IrradianceSunDesc), vp, vp, vp, vp]
     L.ngp_get_irradiance_sun_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_compute_irradiance_volume_sunlit_shadowed.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), C.POINTER(IrradianceBounceDesc), C.POINTER(IrradianceVisibilityDesc),
+                                                                C.POINTER(IrradianceSunDesc), C.POINTER(IrradianceSunNerfDesc)]
+    L.ngp_irradiance_sh_sun_shadowed.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), C.POINTER(IrradianceSunDesc), vp, vp, C.POINTER(IrradianceSunNerfDesc), vp, vp, vp]
+    L.ngp_get_irradiance_sun_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -751,18 +759,25 @@ class Context:
         return (sh, rays) if return_rays else sh
 
     def compute_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, occlude_by_meshes=True, min_transmittance=0.01, bounces=0, albedo=None, visibility=None,
-                                  sun=None):
+                                  sun=None, sun_nerf_shadow=None):
         """trace a lattice of resolution = (rx, ry, rz) probes over aabb = (min, max); the volume stays on the device (get_irradiance_volume).
         bounces > 0: that many passes of diffuse interreflection off the meshes, of colour albedo (three channels in [0, 1], or one number for
         all three; None: the default base colour 0.8 squared, in float32); visibility: None, or the keywords of compute_irradiance_volume_visibility
         as a dict: the distance maps are computed first, the bounces look the volume up through them, and they stay in the context.
         sun: None, or the sun whose first bounce off the meshes joins the records ahead of the passes (also with bounces = 0): a dict with
-        direction and optionally radiance (default: the frames' sun colour) and shadow_bias (1e-3), or a tuple in that order"""
+        direction and optionally radiance (default: the frames' sun colour) and shadow_bias (1e-3), or a tuple in that order.
+        sun_nerf_shadow: None, or the NeRF's density in front of that sun: True (min_transmittance 0.01, t_min 0), or a dict or a tuple of
+        min_transmittance and t_min (without a sun no pass runs)"""
         d = self._volume_desc(resolution, aabb, self._sh_desc(n_u, n_v, occlude_by_meshes, min_transmittance))
-        if sun is not None:
+        ns = self._sun_nerf_desc(sun_nerf_shadow)
+        if sun is not None or ns is not None:
             b = self._bounce_desc(bounces, np.float32(0.8) * np.float32(0.8) if albedo is None else albedo)
             v = None if visibility is None else self._visibility_desc(**dict(dict(n_u=16, n_v=16, sharpness_log2=5, max_distance=0.0, normal_bias=0.0), **visibility))
-            s = self._sun_desc(sun)
+            s = None if sun is None else self._sun_desc(sun)
+            if ns is not None:
+                self._check(self.L.ngp_compute_irradiance_volume_sunlit_shadowed(self.h, C.byref(d), C.byref(b), C.byref(v) if v is not None else None,
+                                                                                 C.byref(s) if s is not None else None, C.byref(ns)))
+                return
             self._check(self.L.ngp_compute_irradiance_volume_sunlit(self.h, C.byref(d), C.byref(b), C.byref(v) if v is not None else None, C.byref(s)))
             return
         if not bounces:
@@ -800,10 +815,36 @@ class Context:
         s.shadow_bias = float(sun[2])
         return s
 
-    def irradiance_sh_sun(self, positions, sun, albedo, n_u=32, n_v=32, alpha=None, occlude_by_meshes=True, return_rays=False):
+    @staticmethod
+    def _sun_nerf_desc(shadow):
+        """None and False: none; True: the defaults; a dict or a tuple of min_transmittance and t_min"""
+        if shadow is None or shadow is False:
+            return None
+        if isinstance(shadow, IrradianceSunNerfDesc):
+            return shadow
+        if shadow is True:
+            shadow = {}
+        if isinstance(shadow, dict):
+            if set(shadow) - {"min_transmittance", "t_min"}:
+                raise ValueError("sun_nerf_shadow: min_transmittance and t_min")
+            shadow = (shadow.get("min_transmittance", 0.01), shadow.get("t_min", 0.0))
+        shadow = tuple(shadow)
+        if not 1 <= len(shadow) <= 2:
+            raise ValueError("sun_nerf_shadow: (min_transmittance, t_min)")
+        shadow = shadow + (0.0,)[len(shadow) - 1:]
+        ns = IrradianceSunNerfDesc()
+        ns.min_transmittance, ns.t_min = float(shadow[0]), float(shadow[1])
+        return ns
+
+    def irradiance_sh_sun(self, positions, sun, albedo, n_u=32, n_v=32, alpha=None, occlude_by_meshes=True, return_rays=False, nerf_shadow=None, return_shadow=False):
         """one sun pass at the probes at `positions` (no model, no volume): the records R_sun (n, 28) of the sun's first bounce off the meshes,
         float 27 the unblocked fraction; with return_rays also every ray's (B rgb, t of the primary hit or inf), (n, K, 4). sun: as
-        compute_irradiance_volume takes it; alpha: None or the rays' NeRF alpha (n, K)"""
+        compute_irradiance_volume takes it; alpha: None or the rays' NeRF alpha (n, K). nerf_shadow: as compute_irradiance_volume's
+        sun_nerf_shadow; the pass then needs a model, the rays are B', and return_shadow adds every ray's (q xyz, alpha_s), (n, K, 4), zeros
+        where there is no shadow ray. The results come in the order records, rays, shadow."""
+        ns = self._sun_nerf_desc(nerf_shadow)
+        if return_shadow and ns is None:
+            raise ValueError("return_shadow belongs to nerf_shadow")
         p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
         k = int(n_u) * int(n_v)
         d = self._sh_desc(n_u, n_v, occlude_by_meshes, 0.01)
@@ -814,6 +855,12 @@ class Context:
             raise ValueError("alpha: n x K values")
         sh = np.zeros((p.shape[0], 28), np.float32)
         rays = np.zeros((p.shape[0], k, 4), np.float32) if return_rays else None
+        if ns is not None:
+            shadow = np.zeros((p.shape[0], k, 4), np.float32) if return_shadow else None
+            self._check(self.L.ngp_irradiance_sh_sun_shadowed(self.h, p.shape[0], _p(p), C.byref(d), C.byref(s), _p(al), _p(a) if a is not None else None, C.byref(ns),
+                                                              _p(rays) if return_rays else None, _p(shadow) if return_shadow else None, _p(sh)))
+            out = (sh,) + ((rays,) if return_rays else ()) + ((shadow,) if return_shadow else ())
+            return out if len(out) > 1 else sh
         self._check(self.L.ngp_irradiance_sh_sun(self.h, p.shape[0], _p(p), C.byref(d), C.byref(s), _p(al), _p(a) if a is not None else None, _p(sh),
                                                  _p(rays) if return_rays else None))
         return (sh, rays) if return_rays else sh
@@ -822,6 +869,12 @@ class Context:
         """device time of the last sun pass (compute_irradiance_volume with a sun, irradiance_sh_sun), ms"""
         ms = C.c_float(0)
         self._check(self.L.ngp_get_irradiance_sun_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def irradiance_sun_shadow_ms(self):
+        """device time of the shadow rays' prep and trace in the last sun pass, ms; 0 after a pass without a NeRF shadow"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_irradiance_sun_shadow_ms(self.h, C.byref(ms)))
         return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):

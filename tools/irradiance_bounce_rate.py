@@ -3,6 +3,7 @@ tools/mesh_shade_rate.py's scene with N = 0, 1, 2 and 4 bounce passes, and the d
 
     python tools/irradiance_bounce_rate.py [--res 16] [--k 32] [--repeat 3] [--out profiles/irradiance_bounce_rate.json]
     python tools/irradiance_bounce_rate.py --sun [--repeat 5] [--out profiles/irradiance_sun_rate.json]
+    python tools/irradiance_bounce_rate.py --sun --nerf-shadow [--repeat 6] [--out profiles/irradiance_sun_shadow_rate.json]
 
 The volume spans the box of the meshes (it overlaps the NeRF's unit cube), the meshes occlude, albedo 0.64. Wall times are
 medians over --repeat calls after a warm-up and include the host's share; the pass time is HIP events around the last pass's chunks in
@@ -13,7 +14,11 @@ no CPU path.
 --sun measures the sun pass instead (ngp_get_irradiance_sun_ms), beside the bounce pass and the NeRF trace of the same call: a volume with
 the frames' sun (1, 1, 1) and N = 1, every repeat listed so that the run-to-run spread shows. It then runs the same calls in a child process
 on libngp_hip_sun_any_hit.so (build.py: build(sun_any_hit=True)), whose shadow query is an unsorted traversal that ends at the first hit
-instead of the shipped closest hit: what that early exit would buy. --lib PATH measures one library alone and builds nothing."""
+instead of the shipped closest hit: what that early exit would buy. --lib PATH measures one library alone and builds nothing.
+
+--sun --nerf-shadow measures what the NeRF's density in front of the sun costs: the same volume with and without sun_nerf_shadow, every
+repeat listed, the shadow trace's own device time (ngp_get_irradiance_sun_shadow_ms) and its tracer statistics beside the V_0 trace's, and
+the share of the uncompacted shadow-ray list that is live (one stage pass at the volume's probes, outside the timing)."""
 import argparse
 import json
 import os
@@ -80,8 +85,59 @@ def sun_passes(args):
             "blocked_share": round(float(1.0 - sh[..., 27].mean()), 4)}
 
 
+def main_sun_shadow(args):
+    pkg("build").build()
+    native, synthetic = pkg("native"), pkg("synthetic")
+    ctx, box = load(native, synthetic)
+    res, k = (args.res,) * 3, args.k
+    sun = ((1.0, 1.0, 1.0), native.SUN_RADIANCE, 1e-3)
+    out = {"how": "HIP events around the chunks of the last sun pass (sun_pass_ms), around the shadow rays' prep and trace inside it (shadow_trace_ms), and the tracer's kernel time "
+                  "and samples of the last tracer call (plain: the V_0 trace; shadowed: the shadow trace), of a sunlit volume with N = 1; every repeat after a warm-up; "
+                  "plain and shadowed alternate call by call in one session; one MI355X, one run",
+           "resolution": [args.res] * 3, "rays_per_probe": k * k, "rays": args.res ** 3 * k * k, "albedo": 0.64, "sun": [1, 1, 1], "min_transmittance": 0.01, "t_min": 0.0,
+           "plain": {"sun_pass_ms": [], "v0_trace_ms": [], "v0_trace_samples": []}, "shadowed": {"sun_pass_ms": [], "shadow_trace_ms": [], "shadow_trace_kernel_ms": [], "shadow_trace_samples": []}}
+    for i in range(args.repeat + 1):
+        for name, shadow in (("plain", None), ("shadowed", True)):
+            ctx.compute_irradiance_volume(res, box, k, k, bounces=1, albedo=0.64, sun=sun, sun_nerf_shadow=shadow)
+            if not i:  # (the first call of each warms up)
+                continue
+            st, o = ctx.render_stats(), out[name]
+            o["sun_pass_ms"].append(round(ctx.irradiance_sun_ms(), 3))
+            if shadow:
+                o["shadow_trace_ms"].append(round(ctx.irradiance_sun_shadow_ms(), 3))
+                o["shadow_trace_kernel_ms"].append(round(st["kernel_ms"], 3))
+                o["shadow_trace_samples"].append(int(st["n_samples"]))
+            else:
+                o["v0_trace_ms"].append(round(st["kernel_ms"], 3))
+                o["v0_trace_samples"].append(int(st["n_samples"]))
+    # the list's live share: the probes of the volume, as the library places them (double from the box's floats, rounded to float)
+    ax = [(np.float64(box[0][a]) + np.arange(args.res) / max(args.res - 1, 1) * (np.float64(box[1][a]) - np.float64(box[0][a]))).astype(np.float32) for a in range(3)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    probes = np.stack([x, y, z], -1).reshape(-1, 3)
+    live = blocked = n = 0
+    for p0 in range(0, probes.shape[0], 512):
+        _, shadow = ctx.irradiance_sh_sun(probes[p0:p0 + 512], sun, 0.64, k, k, nerf_shadow=True, return_shadow=True)
+        has = np.any(shadow[..., :3] != 0, axis=-1)
+        live, blocked, n = live + int(has.sum()), blocked + int((shadow[..., 3][has] > 0.9).sum()), n + has.size
+    ctx.close()
+    out["live_share"] = round(live / n, 4)
+    out["blocked_share_of_live"] = round(blocked / max(live, 1), 4)
+    med = lambda v: float(np.median(v))
+    print(f"sun pass: plain {out['plain']['sun_pass_ms']} ms, shadowed {out['shadowed']['sun_pass_ms']} ms; shadow trace {out['shadowed']['shadow_trace_ms']} ms; "
+          f"V_0 trace {out['plain']['v0_trace_ms']} ms; live share {out['live_share']}", flush=True)
+    out["medians"] = {"sun_pass_plain_ms": med(out["plain"]["sun_pass_ms"]), "sun_pass_shadowed_ms": med(out["shadowed"]["sun_pass_ms"]),
+                      "shadow_trace_ms": med(out["shadowed"]["shadow_trace_ms"]), "v0_trace_ms": med(out["plain"]["v0_trace_ms"])}
+    print(json.dumps(out))
+    path = args.out or os.path.join(ROOT, "profiles", "irradiance_sun_shadow_rate.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main_sun(args):
     import subprocess
+
+    if args.nerf_shadow:
+        return main_sun_shadow(args)
 
     if args.lib:  # one library, as the parent asks
         os.environ["NGP_HIP_LIBRARY"] = os.path.abspath(args.lib)
@@ -110,6 +166,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sun", action="store_true")
+    ap.add_argument("--nerf-shadow", action="store_true", help="with --sun: what the NeRF's density in front of the sun costs")
     ap.add_argument("--lib", default=None)
     args = ap.parse_args()
     if args.sun:
