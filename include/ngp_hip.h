@@ -640,7 +640,7 @@ NGP_API int ngp_get_irradiance_sun_ms(ngp_ctx* ctx, float* ms);
  * Determinism: no atomics; bit-identical from run to run and for any chunking (the shadow-ray list is not compacted: one entry per probe
  *   ray, dead where there is no shadow ray).
  * Stated limits: the NeRF attenuates the sun but is not lit by it; the frames' own direct sun term on a mesh pixel still ignores the NeRF,
- *   as in the reference, and no frame of another mode changes; a hit that sits inside the NeRF's own density shadows itself unless t_min
+ *   as in the reference, unless ngp_set_sun_nerf_shadow (the next block) is on, and no frame of another mode changes; a hit that sits inside the NeRF's own density shadows itself unless t_min
  *   skips it.
  * Refusals, each naming its field: a NaN min_transmittance; a negative or non-finite t_min; everything the sun section refuses. The bounce
  *   descriptor is looked at first, then the sun's, then this one, before anything else, on any context. */
@@ -663,6 +663,44 @@ NGP_API int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float
                                            float* rays_out /* nullable, n K x 4 */, float* shadow_out /* nullable, n K x 4 */, float* sh_out /* n x 28 */);
 /* device time (HIP events) of the shadow rays' prep and trace in the last sun pass, ms, summed over its chunks; 0 after a pass without them */
 NGP_API int ngp_get_irradiance_sun_shadow_ms(ngp_ctx* ctx, float* ms);
+
+/* sun: the NeRF in front of the frames' sun. With the block above the ambient light under the captured object darkens; this option lets the
+ * same density stand in front of the frames' own direct sun term on mesh pixels. Context state, set like the geometry options; off by
+ * default, and with it off every frame is the one it was, as bytes.
+ *
+ * Which frames: Geometry mode, meshes loaded, a model loaded (such a frame always takes the general, non-direct path). All four mesh shade
+ *   modes (Shade, ShadeEnvMap, ShadeGridEnvMap, ShadeIrradianceVolume with or without visibility).
+ * Which pixels get a shadow ray: for each sample of the frame, a pixel whose primary ray hits a mesh inside the scene box AND whose mesh
+ *   shadow ray (ngp_trace_mesh_rays' one-mesh rule, as in every frame) is unblocked. Pixels without a hit and pixels the meshes already
+ *   shadow get none and report q = 0, alpha_s = 0.
+ * The ray: origin q = pos + 1e-3 normalize(ff), the very float32 value the mesh shadow ray starts from before it is advanced to the scene
+ *   box, ff the shading normal turned against the primary ray; direction s^ = normalize(normalize(sun_dir)) as the mesh pass forms it. It
+ *   is traced with the semantics of ngp_trace_nerf_rays (the tracer normalises the direction; the render box in force, which is the
+ *   inflated mesh box), t_range = (t_min, +inf), min_transmittance from the descriptor (<= 0 selects 0.01). alpha_s = that ray's alpha.
+ * The colour: T_s = max(1 - alpha_s, 0) in float32; the mesh pass's shadow factor becomes fl(shadow T_s); nothing else changes, so T_s = 1
+ *   gives the option-off bits. Depth, coverage, the ambient term, sharding, packing and the NeRF pass that follows are untouched.
+ * Determinism: no atomics decide a value; frames are bit-identical from run to run. Everything runs on the frame's stream and
+ *   ngp_render_device stays asynchronous.
+ * Statistics: ngp_get_render_stats of the frame reports the frame's NeRF pass alone (n_rays, n_rays_hit, n_samples equal the option-off
+ *   frame's); the shadow trace's own time is ngp_get_frame_sun_shadow_ms, inside ngp_get_mesh_pass_ms.
+ * Identities as bytes (the frame is the option-off frame): the option off; NeRF mode; no meshes; no model (meshes only); a t_min beyond the
+ *   box (>= its diagonal); a model whose density is empty along every shadow ray.
+ * Refusals: ngp_set_sun_nerf_shadow refuses what ngp_irradiance_sun_nerf_desc's section refuses (a NaN min_transmittance; a negative or
+ *   non-finite t_min), on any context. A model the ray-list tracer does not serve (an rgb head other than configs/nerf/base.json's) is
+ *   refused when the frame is rendered, with the tracer's message, naming the option. A moving camera with meshes is refused as before.
+ * Several devices: the option travels to the peers with the geometry and each device traces the shadow rays of its own tiles;
+ *   ngp_get_frame_sun_shadow and ngp_get_frame_sun_shadow_ms read the primary's share only.
+ * Stated limits: the NeRF attenuates the sun and is not lit by it; the meshes still throw no shadow onto the NeRF; one directional light; a
+ *   hit that sits inside the NeRF's own density shadows itself unless t_min skips it. */
+/* nerf == NULL: off (the default). Refusals as ngp_irradiance_sun_nerf_desc's: NaN min_transmittance; negative or non-finite t_min. */
+NGP_API int ngp_set_sun_nerf_shadow(ngp_ctx* ctx, const ngp_irradiance_sun_nerf_desc* nerf /* nullable */);
+NGP_API int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int* enabled);
+/* stage entry for tests: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on a multi-device context
+ * the primary's tile-packed share): (q_xyz, alpha_s); zeros where the pixel had no shadow ray. n_pixels must be that frame's extent.
+ * Refuses when the last frame ran no shadow trace. */
+NGP_API int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
+/* device time (HIP events) of the shadow rays' prep and trace in the last frame's last sample; 0 after a frame without them */
+NGP_API int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -513,6 +513,152 @@ void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, cons
 	else if (V) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolume>, blocks, threads, 0, stream, S, P, *V, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
 	else hipLaunchKernelGGL(render_mesh_fused<IrradianceMap>, blocks, threads, 0, stream, S, P, I, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
 }
+// ---- the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow; contract in include/ngp_hip.h, "sun: the NeRF in front of the frames'
+// sun"). render_mesh_fused split around a ray-list trace: M1-M4 leave a G-buffer and one shadow-ray entry per local pixel, in idx order and
+// not compacted; the tracer walks the list; M5 shades from the G-buffer with shadow scaled by what the tracer let through. The statements
+// are render_mesh_fused's, in its order, on the same leaf functions, so a pixel whose T_s is 1 gets the fused kernel's bits.
+// G-buffer of n pixels, three planes of n float4: (pos, shadow), (raw normal, covered), (primary_dir, 0).
+
+__global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, float* __restrict__ depth_buffer, uint32_t shard_index,
+                                    uint32_t shard_count, int packed, float t_min, uint32_t n_pixels, float4* __restrict__ gbuf, float* __restrict__ ray_o,
+                                    float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
+	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
+	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
+	if (tile % shard_count != shard_index) return;
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	if (C.moving || idx >= n_pixels) return;
+	const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
+	const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
+	// M1
+	float u = ((float)x + C.pixel_offset[0]) / (float)C.width;
+	float v = ((float)y + C.pixel_offset[1]) / (float)C.height;
+	f3 dir;
+	lens_direction(C, u, v, dir);
+	dir = m3_mulv(C.m, dir);
+	f3 origin = cam_pos;
+	if (C.aperture_size != 0.0f) {
+		float o3[3] = {origin.x, origin.y, origin.z}, d3[3] = {dir.x, dir.y, dir.z}, cm[6];
+		for (int i = 0; i < 6; ++i) cm[i] = C.m[i];
+		apply_aperture(cm, C.aperture_size, C.focus_z, C.spp, (uint32_t)(int)(u * (float)C.width) * 19349663u + (uint32_t)(int)(v * (float)C.height) * 96925573u, o3, d3);
+		origin = mk3(o3[0], o3[1], o3[2]);
+		dir = mk3(d3[0], d3[1], d3[2]);
+	}
+	origin = add3(origin, scale3(dir, C.near_distance));
+	depth_buffer[idx] = MAX_DEPTH;
+	const f3 sun = normalize3(ld3(P.sun_dir));
+	const f3 sdir = normalize3(sun);
+	// the dead entry irradiance_sun_shadow_rays_kernel writes: origin 0, the sun's direction, t = (0, 0)
+	ray_d[3 * (size_t)idx] = sdir.x; ray_d[3 * (size_t)idx + 1] = sdir.y; ray_d[3 * (size_t)idx + 2] = sdir.z;
+	if (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f) {
+		gbuf[(size_t)n_pixels + idx] = make_float4(0.f, 0.f, 0.f, 0.f); // not covered
+		ray_o[3 * (size_t)idx] = 0.f; ray_o[3 * (size_t)idx + 1] = 0.f; ray_o[3 * (size_t)idx + 2] = 0.f;
+		ray_t[idx] = make_float2(0.f, 0.f);
+		return;
+	}
+	dir = normalize3(dir);
+	float t = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, origin, dir), 0.0f);
+	f3 pos = add3(origin, scale3(dir, t + 1e-6f));
+	const f3 primary_dir = dir;
+	// M2
+	f3 normal = dir;
+	trace_mesh(S, pos, normal);
+	// M3
+	float shadow;
+	f3 q;
+	{
+		float nd = dot3(normal, primary_dir);
+		f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f);
+		f3 view_pos = add3(pos, scale3(normalize3(ff), 1e-3f));
+		q = view_pos; // the NeRF shadow ray starts where the mesh shadow ray does, before that one is advanced to the scene box
+		float st = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, view_pos, sdir) + 1e-6f, 0.0f);
+		view_pos = add3(view_pos, scale3(sdir, st));
+		f3 spos = view_pos;
+		f3 sn = box_contains(S.scene_min, S.scene_max, view_pos) ? sdir : primary_dir;
+		trace_mesh(S, spos, sn);
+		// M4
+		shadow = box_contains(S.scene_min, S.scene_max, spos) ? 0.0f : 1.0f;
+	}
+	const bool covered = box_contains(S.scene_min, S.scene_max, pos);
+	const bool has = covered && shadow == 1.0f;
+	if (!has) q = mk3(0.f, 0.f, 0.f);
+	gbuf[idx] = make_float4(pos.x, pos.y, pos.z, shadow);
+	gbuf[(size_t)n_pixels + idx] = make_float4(normal.x, normal.y, normal.z, covered ? 1.0f : 0.0f);
+	gbuf[2 * (size_t)n_pixels + idx] = make_float4(primary_dir.x, primary_dir.y, primary_dir.z, 0.0f);
+	ray_o[3 * (size_t)idx] = q.x; ray_o[3 * (size_t)idx + 1] = q.y; ray_o[3 * (size_t)idx + 2] = q.z;
+	ray_t[idx] = has ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
+	if (covered) depth_buffer[idx] = dot3(cam_fwd, sub3(pos, cam_pos));
+}
+
+// M5 from the G-buffer. traced: the tracer's rgba of the pixel's list entry; a pixel has a shadow ray where ray_t.y != 0 (the prep step
+// moves ray_t.x alone). record: (q, alpha_s), zeros without a shadow ray (ngp_get_frame_sun_shadow).
+template <typename Ambient>
+__global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer, uint32_t shard_index,
+                                           uint32_t shard_count, int packed, uint32_t n_pixels, const float4* __restrict__ gbuf, const float* __restrict__ ray_o,
+                                           const float2* __restrict__ ray_t, const float4* __restrict__ traced, float4* __restrict__ record) {
+	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
+	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
+	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
+	if (tile % shard_count != shard_index) return;
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	if (C.moving || idx >= n_pixels) return;
+	const float4 g1 = gbuf[(size_t)n_pixels + idx];
+	const bool has = g1.w != 0.0f && ray_t[idx].y != 0.0f;
+	const float alpha_s = has ? traced[idx].w : 0.0f;
+	record[idx] = has ? make_float4(ray_o[3 * (size_t)idx], ray_o[3 * (size_t)idx + 1], ray_o[3 * (size_t)idx + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
+	if (g1.w == 0.0f) return;
+	const float4 g0 = gbuf[idx], g2 = gbuf[2 * (size_t)n_pixels + idx];
+	const f3 pos = mk3(g0.x, g0.y, g0.z), normal = mk3(g1.x, g1.y, g1.z), primary_dir = mk3(g2.x, g2.y, g2.z);
+	float shadow = g0.w;
+	if (has) shadow = shadow * fmaxf(1.0f - alpha_s, 0.0f); // T_s
+	const f3 sun = normalize3(ld3(P.sun_dir));
+	// M5
+	f3 N = normalize3(normal);
+	f3 up = normalize3(ld3(P.up_dir));
+	float skyam = -dot3(N, up) * 0.5f + 0.5f;
+	f3 suncol = scale3(scale3(mk3(255.f / 255.0f, 225.f / 255.0f, 195.f / 255.0f), 4.f), shadow);
+	f3 skycol = scale3(scale3(mk3(195.f / 255.0f, 215.f / 255.0f, 255.f / 255.0f), 4.f), skyam);
+	f3 base = ld3(P.basecolor);
+	f3 ambc;
+	if constexpr (std::is_same<Ambient, IrradianceVolume>::value) {
+		float E[3], W;
+		irradiance_volume_lookup(A, pos, N, E, W);
+		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
+	} else if constexpr (std::is_same<Ambient, IrradianceVolumeVisible>::value) {
+		float E[3], W;
+		irradiance_volume_lookup_visible(A, pos, N, E, W);
+		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
+	} else {
+		ambc = mul3(ld3(P.ambientcolor), skycol);
+		if (A.irradiance) {
+			f3 E = irradiance_lookup(A, pos, N);
+			ambc = mk3(E.x / PI_F, E.y / PI_F, E.z / PI_F);
+		}
+	}
+	f3 color = evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen,
+	                            0.f, P.clearcoat, P.clearcoat_gloss, sun, scale3(normalize3(primary_dir), -1.0f), N);
+	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
+}
+
+// the two halves of launch_render_mesh around the caller's trace of (ray_o, ray_d, ray_t); n_pixels: the extent of every per-pixel buffer
+void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
+                         float t_min, uint32_t n_pixels, float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
+	dim3 threads(16, 8, 1);
+	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
+	hipLaunchKernelGGL(mesh_gbuffer_kernel, blocks, threads, 0, stream, S, P, C, depth_buffer, shard_index, shard_count, packed, t_min, n_pixels, gbuf, ray_o, ray_d, ray_t);
+}
+void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
+                                float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
+                                const float2* ray_t, const float4* traced, float4* record, hipStream_t stream) {
+	dim3 threads(16, 8, 1);
+	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
+	if (VV) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, P, *VV, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
+	else if (V) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolume>, blocks, threads, 0, stream, P, *V, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
+	else hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceMap>, blocks, threads, 0, stream, P, I, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
+}
+
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)
 __global__ void irradiance_lookup_kernel(const IrradianceMap I, uint32_t n, const float* __restrict__ positions, const float* __restrict__ normals, float4* __restrict__ out) {
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

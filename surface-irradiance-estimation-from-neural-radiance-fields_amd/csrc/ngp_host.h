@@ -144,6 +144,11 @@ void launch_accumulate_tonemap(uint32_t n_pixels, const float4* frame_buffer, fl
 void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
                         const CameraParams& C, float4* frame_buffer, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
                         hipStream_t stream); // V: the ShadeIrradianceVolume instantiation; VV: the one that weights the probes by visibility
+void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
+                         float t_min, uint32_t n_pixels, float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
+void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
+                                float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
+                                const float2* ray_t, const float4* traced, float4* record, hipStream_t stream); // M5 of launch_render_mesh behind the trace
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t stream);
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
@@ -377,6 +382,19 @@ struct ngp_ctx {
 	uint64_t hist_n_rays[HISTORY] = {};
 	ngp::Event ev_mesh0[HISTORY], ev_mesh1[HISTORY]; // around the mesh pass of a frame's last sample (ngp_get_mesh_pass_ms)
 	bool hist_mesh_pass[HISTORY] = {};               // the slot's call was a frame with a mesh pass
+	// ---- the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow); a peer's copy follows the primary's with the geometry
+	bool sun_nerf_shadow = false;
+	ngp_irradiance_sun_nerf_desc sun_nerf_shadow_desc{};
+	// its per-pixel scratch, allocated when a frame first uses the option and grown like the frame buffers (d_ss_record, allocated last, holds the size of all)
+	ngp::DevArray<float4> d_ss_gbuf;   // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, 0)
+	ngp::DevArray<float> d_ss_o, d_ss_d; // the shadow-ray list, one entry a local pixel
+	ngp::DevArray<float2> d_ss_t;
+	ngp::DevArray<float4> d_ss_traced; // the tracer's rgba of the list
+	ngp::DevArray<float4> d_ss_record; // (q, alpha_s) of the last sample (ngp_get_frame_sun_shadow)
+	ngp::DevArray<unsigned long long> d_ss_results; // where the shadow trace's counters go: the slot's results stay the NeRF pass's
+	ngp::Event ev_ss0[HISTORY], ev_ss1[HISTORY]; // around prep + trace of a frame's last sample (ngp_get_frame_sun_shadow_ms)
+	bool hist_sun_shadow[HISTORY] = {};                  // the slot's call was a frame that traced shadow rays
+	size_t ss_n_pixels = 0;                                    // pixels of the last such frame
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a
@@ -519,6 +537,12 @@ void schedule_from_env(ngp_ctx* ctx);
 void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels); // (0: the per-call slots and events alone)
 CameraParams make_camera_params(const ngp_camera& cam, uint32_t spp_index);
 void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba, float* d_depth, hipStream_t stream);
+// ngp_irradiance.cpp: the ray-list tracer as a frame uses it (TracerCall, there, adds the slot bookkeeping of a call of its own)
+void require_probe_model(ngp_ctx* ctx, const char* what); // the models the tracer serves; `what` names the caller's work in the refusal
+void tracer_frame_params(const ngp_ctx* ctx, int slot, float min_transmittance, FrameParams& F);
+ProbeParams ray_list_params(uint32_t n, const float* o, const float* dir, const float2* t, float4* rgba, float* depth);
+void launch_probe_trace(const ngp_ctx* ctx, const ModelParams& M, FrameParams& F, const ProbeParams& P, bool add_results, hipStream_t stream); // clears P's outputs, then one persistent launch
+void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d); // (nullable)
 // ngp_train.cpp
 void free_training(ngp_ctx* ctx);
 bool probe_image_size(const std::string& path, int& width, int& height);

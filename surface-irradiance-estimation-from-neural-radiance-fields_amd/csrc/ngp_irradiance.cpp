@@ -11,6 +11,52 @@
 
 using namespace ngp;
 
+namespace ngp {
+// the models the probe tracer serves: base.json's heads and the Frequency architecture (`what` names the caller's work in the refusal)
+void require_probe_model(ngp_ctx* ctx, const char* what) {
+	require_model(ctx);
+	sync_inference_model(ctx);
+	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error(std::string(what) + " are built for the configs/nerf/base.json rgb head (2 hidden layers)");
+	ensure_frame_buffers(ctx, 0);
+}
+// what a tracer launch on history slot `slot` needs of FrameParams: the slot's queue and counters, one shard, the call's transmittance floor
+void tracer_frame_params(const ngp_ctx* ctx, int slot, float min_transmittance, FrameParams& F) {
+	ctx->bind_slot(F, slot);
+	F.shard_index = 0;
+	F.shard_count = 1;
+	F.min_transmittance = min_transmittance > 0.f ? min_transmittance : 0.01f;
+	F.linear_colors = ctx->desc.linear_colors;
+	memcpy(F.tune, ctx->tune, sizeof(F.tune));
+}
+// n caller rays (o, dir, t as launch_ray_list_prep left them) into rgba and depth (nullable)
+ProbeParams ray_list_params(uint32_t n, const float* o, const float* dir, const float2* t, float4* rgba, float* depth) {
+	ProbeParams P{};
+	P.mode = PROBE_RAY_LIST;
+	P.n_rays = n;
+	P.ray_o = o;
+	P.ray_d = dir;
+	P.ray_t = t;
+	P.ray_rgba = rgba;
+	P.ray_depth = depth;
+	return P;
+}
+// one persistent launch over the P.n_rays rays of P (its ray_rgba and ray_depth are cleared here); add_results: the launch's counters
+// are added to F.results instead of replacing them. Nothing here waits: a frame puts it on its own stream.
+void launch_probe_trace(const ngp_ctx* ctx, const ModelParams& M, FrameParams& F, const ProbeParams& P, bool add_results, hipStream_t stream) {
+	NGP_HIP_CHECK(hipMemsetAsync(P.ray_rgba, 0, (size_t)P.n_rays * sizeof(float4), stream));
+	if (P.ray_depth) NGP_HIP_CHECK(hipMemsetAsync(P.ray_depth, 0, (size_t)P.n_rays * sizeof(float), stream));
+	F.n_local_tiles = (P.n_rays + 63) / 64;
+	F.add_results = add_results ? 1 : 0;
+	launch_trace_probe(M, F, P, ctx->n_cus, stream);
+}
+// the NeRF's density in front of the sun (nullable: the meshes alone shadow it)
+void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d) {
+	if (!d) return;
+	if (std::isnan(d->min_transmittance)) throw std::runtime_error("invalid irradiance sun NeRF descriptor: min_transmittance is NaN");
+	if (!std::isfinite(d->t_min) || d->t_min < 0.0f) throw std::runtime_error("invalid irradiance sun NeRF descriptor: t_min must be finite and >= 0");
+}
+} // namespace ngp
+
 namespace {
 // rays per tracer launch: bounds the ray-list workspace (48 B a ray). Every ray is traced on its own, so chunking changes no result.
 constexpr uint32_t RAY_CHUNK = 1u << 21;
@@ -19,13 +65,6 @@ constexpr uint32_t SH_FLOAT4 = 7; // an SH9 record: 28 floats
 constexpr uint32_t MAX_BOUNCES = 16;
 
 // ------------------------------------------------------------------------------------------------ the tracer
-// the models the probe tracer serves: base.json's heads and the Frequency architecture (`what` names the caller's work in the refusal)
-void require_probe_model(ngp_ctx* ctx, const char* what) {
-	require_model(ctx);
-	sync_inference_model(ctx);
-	if (ctx->M.rgb_mid != 1 && !ctx->M.wide.width) throw std::runtime_error(std::string(what) + " are built for the configs/nerf/base.json rgb head (2 hidden layers)");
-	ensure_frame_buffers(ctx, 0);
-}
 // the model as probe rays see it: in Geometry mode load_scene made the inflated mesh box the render box (testbed_geometry_training.cu:3185-3189)
 ModelParams probe_model(const ngp_ctx* ctx) {
 	ModelParams M = ctx->M;
@@ -48,39 +87,20 @@ public:
 		if (ctx->last_stream && ctx->last_stream != stream_) NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 		slot_ = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 		if (ctx->n_calls >= (uint64_t)ngp_ctx::HISTORY) NGP_HIP_CHECK(hipStreamWaitEvent(stream_, ctx->ev_frame1[slot_], 0)); // the slot's previous launch
-		ctx->bind_slot(F_, slot_);
-		F_.shard_index = 0;
-		F_.shard_count = 1;
-		F_.min_transmittance = min_transmittance > 0.f ? min_transmittance : 0.01f;
-		F_.linear_colors = ctx->desc.linear_colors;
-		memcpy(F_.tune, ctx->tune, sizeof(F_.tune));
+		tracer_frame_params(ctx, slot_, min_transmittance, F_);
 		M_ = probe_model(ctx);
 		NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot_], stream_));
 	}
 	const ModelParams& model() const { return M_; }
-	// one persistent launch over the P.n_rays rays of P (its ray_rgba and ray_depth are cleared here)
+	// one persistent launch over the P.n_rays rays of P (launch_probe_trace); the call's launches add up in its slot
 	void trace(const ProbeParams& P) {
-		NGP_HIP_CHECK(hipMemsetAsync(P.ray_rgba, 0, (size_t)P.n_rays * sizeof(float4), stream_));
-		if (P.ray_depth) NGP_HIP_CHECK(hipMemsetAsync(P.ray_depth, 0, (size_t)P.n_rays * sizeof(float), stream_));
 		if (!traced_) NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern0[slot_], stream_));
-		F_.n_local_tiles = (P.n_rays + 63) / 64;
-		F_.add_results = traced_ ? 1 : 0;
-		launch_trace_probe(M_, F_, P, ctx_->n_cus, stream_);
+		launch_probe_trace(ctx_, M_, F_, P, traced_, stream_);
 		NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern1[slot_], stream_));
 		traced_ = true;
 	}
 	// n caller rays (o, dir, t as launch_ray_list_prep left them) into rgba and depth (nullable)
-	void trace_rays(uint32_t n, const float* o, const float* dir, const float2* t, float4* rgba, float* depth = nullptr) {
-		ProbeParams P{};
-		P.mode = PROBE_RAY_LIST;
-		P.n_rays = n;
-		P.ray_o = o;
-		P.ray_d = dir;
-		P.ray_t = t;
-		P.ray_rgba = rgba;
-		P.ray_depth = depth;
-		trace(P);
-	}
+	void trace_rays(uint32_t n, const float* o, const float* dir, const float2* t, float4* rgba, float* depth = nullptr) { trace(ray_list_params(n, o, dir, t, rgba, depth)); }
 	void finish() {
 		if (!traced_) {
 			NGP_HIP_CHECK(hipEventRecord(ctx_->ev_kern0[slot_], stream_));
@@ -251,12 +271,6 @@ SunLight check_sun(const ngp_irradiance_sun_desc* s, const float* albedo) {
 	return L;
 }
 
-// the NeRF's density in front of the sun (nullable: the meshes alone shadow it)
-void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d) {
-	if (!d) return;
-	if (std::isnan(d->min_transmittance)) throw std::runtime_error("invalid irradiance sun NeRF descriptor: min_transmittance is NaN");
-	if (!std::isfinite(d->t_min) || d->t_min < 0.0f) throw std::runtime_error("invalid irradiance sun NeRF descriptor: t_min must be finite and >= 0");
-}
 // bounce, then sun, then the NeRF shadow: what the sunlit entries look at before anything else. Returns the sun as the passes use it.
 SunLight check_sunlit(const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_sun_desc* sun, const ngp_irradiance_sun_nerf_desc* nerf) {
 	if (!bounce) throw std::runtime_error(sun ? "invalid irradiance sun descriptor: the bounce descriptor (its albedo) is needed with a sun" : "null argument");

@@ -75,7 +75,7 @@ void usage() {
 	std::cout << "ngp_hip_main [files...] [--scene PATH] [--snapshot|--load_snapshot PATH] [--width W] [--height H] [--spp N]\n"
 	             "             [--screenshot OUT.png] [--screenshot_transforms T.json --screenshot_dir DIR] [--render_mode Shade|ShadeEnvMap|ShadeGridEnvMap|ShadeIrradianceVolume|AO|Normals|Positions|Depth]\n"
 	             "             [--irradiance_volume_res N] [--irradiance_volume_visibility] [--irradiance_volume_bounces N] [--irradiance_volume_sun]\n"
-	             "             [--irradiance_volume_sun_nerf_shadow]\n"
+	             "             [--irradiance_volume_sun_nerf_shadow] [--sun_nerf_shadow [--sun_nerf_shadow_t_min X]]\n"
 	             "             [--exposure E] [--n_steps N] [--save_snapshot OUT.ingp] [--network CONFIG.json]\n"
 	             "             [--save_mesh OUT.obj|OUT.ply [--marching_cubes_res N] [--marching_cubes_density_thresh T]] [--no-gui] [--no-train] [--version]\n"
 	             "             [--video_camera_path PATH.json --video_output DIR/%04d.png [--video_n_seconds S] [--video_fps F] [--video_spp N]]\n";
@@ -91,8 +91,8 @@ int main(int argc, char** argv) {
 		float mc_thresh = 2.5f;
 		std::string scene, snapshot, screenshot, shot_transforms, shot_dir, render_mode = "Shade", save_snapshot, network, video_path, video_output = "video_%04d.png";
 		int width = 1920, height = 1080, spp = 1, volume_res = 8, volume_bounces = 0, n_steps = -1, video_seconds = 1, video_fps = 60, video_spp = 8;
-		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false;
-		float exposure = 0.f;
+		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false, sun_nerf_shadow = false;
+		float exposure = 0.f, sun_nerf_shadow_t_min = 0.f;
 		for (int i = 1; i < argc; ++i) {
 			std::string a = argv[i];
 			auto val = [&]() -> std::string {
@@ -114,6 +114,8 @@ int main(int argc, char** argv) {
 			else if (a == "--irradiance_volume_visibility") volume_visibility = true; // ... and its probes are weighted by their visibility
 			else if (a == "--irradiance_volume_bounces") volume_bounces = std::atoi(val().c_str()); // ... and it holds that many passes of light thrown back by the meshes
 			else if (a == "--irradiance_volume_sun_nerf_shadow") volume_sun_nerf_shadow = true; // ... with the NeRF's density in front of that sun (with --irradiance_volume_sun)
+			else if (a == "--sun_nerf_shadow") sun_nerf_shadow = true; // Geometry frames: the NeRF's density shadows the frames' own sun on mesh pixels
+			else if (a == "--sun_nerf_shadow_t_min") sun_nerf_shadow_t_min = (float)std::atof(val().c_str()); // ... ignoring the NeRF within this distance of the surface
 			else if (a == "--irradiance_volume_sun") volume_sun = true; // ... and the sun's first bounce off the meshes, the frame's sun
 			else if (a == "--exposure") exposure = (float)std::atof(val().c_str());
 			else if (a == "--n_steps") n_steps = std::atoi(val().c_str()); // scripts/run.py:66
@@ -141,6 +143,8 @@ int main(int argc, char** argv) {
 		testbed.m_irradiance_volume_visibility = volume_visibility;
 		testbed.m_irradiance_volume_sun = volume_sun;
 		testbed.m_irradiance_volume_sun_nerf_shadow = volume_sun_nerf_shadow;
+		testbed.m_sun_nerf_shadow = sun_nerf_shadow;
+		testbed.m_sun_nerf_shadow_t_min = sun_nerf_shadow_t_min;
 		for (auto& f : files) {
 			std::cerr << "Loading file " << f << "\n";
 			testbed.load_file(f);

@@ -229,6 +229,30 @@ void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ctx->d_rgba.reset(n_pixels);
 }
 
+// the per-pixel scratch of a frame with the NeRF in front of its sun (ngp_set_sun_nerf_shadow): allocated by the first frame that uses the
+// option, grown as ensure_frame_buffers grows (releasing device memory waits for the device: nothing goes under a frame in flight)
+void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->d_ss_results) {
+		ctx->d_ss_results.reset(8);
+		NGP_HIP_CHECK(hipMemset(ctx->d_ss_results.get(), 0, 8 * sizeof(unsigned long long)));
+		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
+			ctx->ev_ss0[i] = new_event();
+			ctx->ev_ss1[i] = new_event();
+		}
+	}
+	if (n_pixels <= ctx->d_ss_record.size()) return;
+	ctx->d_ss_gbuf.reset(), ctx->d_ss_o.reset(), ctx->d_ss_d.reset(), ctx->d_ss_t.reset(), ctx->d_ss_traced.reset(), ctx->d_ss_record.reset();
+	ctx->d_ss_gbuf.reset(3 * n_pixels);
+	ctx->d_ss_o.reset(3 * n_pixels);
+	ctx->d_ss_d.reset(3 * n_pixels);
+	ctx->d_ss_t.reset(n_pixels);
+	ctx->d_ss_traced.reset(n_pixels);
+	ctx->d_ss_record.reset(n_pixels);
+	// (list entries no pixel of a frame owns -- another shard's, a partial tile's -- are dead through their t alone; their o and d are never garbage)
+	NGP_HIP_CHECK(hipMemset(ctx->d_ss_o.get(), 0, ctx->d_ss_o.bytes()));
+	NGP_HIP_CHECK(hipMemset(ctx->d_ss_d.get(), 0, ctx->d_ss_d.bytes()));
+}
+
 // Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
 void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba_out, float* d_depth_out, hipStream_t stream) {
 	require_device(ctx, "rendering needs an MI355X");
@@ -238,6 +262,13 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	// frame-buffer extent: the whole image, or only this shard's tiles in tile-packed order
 	const size_t n_pixels = opts.packed_output ? (size_t)tile_share(cam.width, cam.height, opts.shard_index, shard_count_of(opts)) * 64 : (size_t)cam.width * cam.height;
 	ensure_frame_buffers(ctx, n_pixels ? n_pixels : 1);
+	// the NeRF in front of the frames' sun: a Geometry frame with meshes and a model (always the general path). The mesh pass is split
+	// around one ray-list trace per sample, all of it on `stream`; nothing waits.
+	const bool sun_shadow = ctx->sun_nerf_shadow && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded;
+	if (sun_shadow) {
+		require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
+		ensure_sun_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
+	}
 	const int spp = opts.spp > 0 ? opts.spp : 1;
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
@@ -293,7 +324,24 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 			const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
 			const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[slot], stream)); // (ngp_get_mesh_pass_ms)
-			launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			if (sun_shadow) { // G-buffer -> prep -> trace -> deferred shade; the trace borrows the slot's queue ahead of the NeRF launch and reports into a block of its own
+				const uint32_t n = (uint32_t)n_pixels;
+				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_t.get(), 0, n_pixels * sizeof(float2), stream)); // entries no pixel owns stay dead
+				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_record.get(), 0, n_pixels * sizeof(float4), stream));
+				launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, F.depth_buffer, F.shard_index, F.shard_count, F.packed, ctx->sun_nerf_shadow_desc.t_min, n, ctx->d_ss_gbuf.get(),
+				                    ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), stream);
+				if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss0[slot], stream)); // (ngp_get_frame_sun_shadow_ms)
+				launch_ray_list_prep(M, n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), true, stream);
+				FrameParams FT{};
+				tracer_frame_params(ctx, slot, ctx->sun_nerf_shadow_desc.min_transmittance, FT);
+				FT.results = ctx->d_ss_results.get();
+				if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), nullptr), false, stream); // (a shard without tiles traces nothing)
+				if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss1[slot], stream));
+				launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.shard_index, F.shard_count, F.packed, n,
+				                           ctx->d_ss_gbuf.get(), ctx->d_ss_o.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), ctx->d_ss_record.get(), stream);
+			} else {
+				launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
+			}
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
@@ -307,6 +355,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->last_stream = stream;
 	ctx->hist_n_rays[slot] = (uint64_t)F.n_local_tiles * 64u * (uint64_t)spp;
 	ctx->hist_mesh_pass[slot] = have_meshes && !F.direct;
+	ctx->hist_sun_shadow[slot] = sun_shadow;
+	if (sun_shadow) ctx->ss_n_pixels = n_pixels;
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -453,6 +503,46 @@ int ngp_get_mesh_pass_ms(ngp_ctx* ctx, float* ms_out) {
 		if (!ctx->hist_mesh_pass[slot]) throw std::runtime_error("the last frame had no mesh pass");
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 		NGP_HIP_CHECK(hipEventElapsedTime(ms_out, ctx->ev_mesh0[slot], ctx->ev_mesh1[slot]));
+	});
+}
+
+int ngp_set_sun_nerf_shadow(ngp_ctx* ctx, const ngp_irradiance_sun_nerf_desc* nerf) {
+	return guarded(ctx, [&] {
+		check_sun_nerf(nerf);
+		ctx->sun_nerf_shadow = nerf != nullptr;
+		ctx->sun_nerf_shadow_desc = nerf ? *nerf : ngp_irradiance_sun_nerf_desc{};
+	});
+}
+
+int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = ctx->sun_nerf_shadow_desc;
+		*enabled = ctx->sun_nerf_shadow ? 1 : 0;
+	});
+}
+
+int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls || !ctx->hist_sun_shadow[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)");
+		if (n_pixels != ctx->ss_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ss_n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ss_record.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = 0.f;
+		if (!ctx->n_calls) return;
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		if (!ctx->hist_sun_shadow[slot]) return;
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ss0[slot], ctx->ev_ss1[slot]));
 	});
 }
 

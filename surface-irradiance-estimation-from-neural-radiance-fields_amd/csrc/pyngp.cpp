@@ -257,6 +257,10 @@ PYBIND11_MODULE(pyngp, m) {
 		               "passes of diffuse interreflection off the meshes in the volume a ShadeIrradianceVolume render computes when the context holds none (albedo: the base colour squared)")
 		.def_readwrite("irradiance_volume_sun", &Testbed::m_irradiance_volume_sun,
 		               "the volume a ShadeIrradianceVolume render computes when the context holds none also holds the sun's first bounce off the meshes (sun_dir, irradiance_volume_sun_radiance)")
+		.def_readwrite("sun_nerf_shadow", &Testbed::m_sun_nerf_shadow,
+		               "Geometry frames with meshes and a model: the NeRF's density shadows the frames' own sun on mesh pixels (default False)")
+		.def_readwrite("sun_nerf_shadow_min_transmittance", &Testbed::m_sun_nerf_shadow_min_transmittance, "with sun_nerf_shadow: the shadow rays' transmittance floor (0.01)")
+		.def_readwrite("sun_nerf_shadow_t_min", &Testbed::m_sun_nerf_shadow_t_min, "with sun_nerf_shadow: the NeRF is ignored within this distance of the surface (0)")
 		.def_readwrite("irradiance_volume_sun_nerf_shadow", &Testbed::m_irradiance_volume_sun_nerf_shadow,
 		               "with irradiance_volume_sun: the NeRF's density shadows that sun in the default volume (render_min_transmittance, t_min 0)")
 		.def_readwrite("irradiance_volume_sun_radiance", &Testbed::m_irradiance_volume_sun_radiance, "what a surface facing the sun receives in a sunlit volume; default: the frames' sun colour")

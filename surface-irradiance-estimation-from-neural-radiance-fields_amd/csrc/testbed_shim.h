@@ -492,6 +492,10 @@ public:
 		memcpy(g.basecolor, brdf.basecolor.data(), 12);
 		memcpy(g.ambientcolor, brdf.ambientcolor.data(), 12);
 		ngp_set_geometry_opts(m_ctx, &g);
+		{ // the NeRF in front of the frames' sun on mesh pixels (off: NULL)
+			const ngp_irradiance_sun_nerf_desc ns{m_sun_nerf_shadow_min_transmittance, m_sun_nerf_shadow_t_min};
+			check(ngp_set_sun_nerf_shadow(m_ctx, m_sun_nerf_shadow ? &ns : nullptr));
+		}
 		check(ngp_render(m_ctx, &cam, &o, out, depth_out));
 	}
 	// irradiance probe pre-pass: what src/main.cu:185-188 calls before the render loop in ShadeEnvMap mode
@@ -603,6 +607,8 @@ public:
 	bool m_envmap_ready = false, m_envmap_grid_ready = false;
 	bool m_irradiance_volume_visibility = false; // the default volume of a ShadeIrradianceVolume render also gets distance maps (16 x 16 rays, sharpness 2^5, D and bias default)
 	bool m_irradiance_volume_sun = false; // that default volume also holds the sun's first bounce off the meshes (the frame's sun: m_sun_dir, the radiance below, bias 1e-3)
+	bool m_sun_nerf_shadow = false; // Geometry frames with meshes and a model: the NeRF's density stands in front of the frames' own sun on mesh pixels (ngp_set_sun_nerf_shadow)
+	float m_sun_nerf_shadow_min_transmittance = 0.01f, m_sun_nerf_shadow_t_min = 0.f; // ... traced down to this transmittance, ignoring the NeRF within t_min of the surface
 	bool m_irradiance_volume_sun_nerf_shadow = false; // ... with the NeRF's density in front of that sun (render_min_transmittance, t_min 0); looked at with m_irradiance_volume_sun alone
 	std::array<float, 3> m_irradiance_volume_sun_radiance{255.f / 255.0f * 4.f, 225.f / 255.0f * 4.f, 195.f / 255.0f * 4.f}; // the frames' suncol (mesh_kernels.hip)
 	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)

@@ -262,6 +262,10 @@ def load_library():
                                                                 C.POINTER(IrradianceSunDesc), C.POINTER(IrradianceSunNerfDesc)]
     L.ngp_irradiance_sh_sun_shadowed.argtypes = [vp, C.c_uint32, vp, C.POINTER(IrradianceShDesc), C.POINTER(IrradianceSunDesc), vp, vp, C.POINTER(IrradianceSunNerfDesc), vp, vp, vp]
     L.ngp_get_irradiance_sun_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_set_sun_nerf_shadow.argtypes = [vp, C.POINTER(IrradianceSunNerfDesc)]
+    L.ngp_get_sun_nerf_shadow.argtypes = [vp, C.POINTER(IrradianceSunNerfDesc), C.POINTER(C.c_int)]
+    L.ngp_get_frame_sun_shadow.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_sun_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -875,6 +879,31 @@ class Context:
         """device time of the shadow rays' prep and trace in the last sun pass, ms; 0 after a pass without a NeRF shadow"""
         ms = C.c_float(0)
         self._check(self.L.ngp_get_irradiance_sun_shadow_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def set_sun_nerf_shadow(self, shadow=True):
+        """the NeRF's density in front of the frames' sun on mesh pixels (Geometry frames with meshes and a model): None or False switches it
+        off (the default), True takes min_transmittance 0.01 and t_min 0, a dict or a tuple gives min_transmittance and t_min"""
+        ns = self._sun_nerf_desc(shadow)
+        self._check(self.L.ngp_set_sun_nerf_shadow(self.h, C.byref(ns) if ns is not None else None))
+
+    def sun_nerf_shadow(self):
+        """None while the option is off, else dict(min_transmittance=, t_min=) as set"""
+        ns, on = IrradianceSunNerfDesc(), C.c_int(0)
+        self._check(self.L.ngp_get_sun_nerf_shadow(self.h, C.byref(ns), C.byref(on)))
+        return dict(min_transmittance=ns.min_transmittance, t_min=ns.t_min) if on.value else None
+
+    def frame_sun_shadow(self, n_pixels):
+        """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (q xyz, alpha_s) of its shadow ray through the
+        NeRF; zeros where the pixel had none. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros((int(n_pixels), 4), np.float32)
+        self._check(self.L.ngp_get_frame_sun_shadow(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def frame_sun_shadow_ms(self):
+        """device time of the shadow rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_frame_sun_shadow_ms(self.h, C.byref(ms)))
         return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):

@@ -6,6 +6,11 @@ sharpness 2^5, default D) at 8^3 and 32^3 probes in one run, and the wall time o
 
     python tools/mesh_shade_rate.py [--width 1920] [--height 1080] [--frames 30] [--warmup 5] [--out profiles/mesh_shade_rate.json]
     python tools/mesh_shade_rate.py --visibility [--out profiles/mesh_shade_visibility_rate.json]
+    python tools/mesh_shade_rate.py --sun-nerf-shadow [--out profiles/mesh_shade_sun_shadow_rate.json]
+
+With --sun-nerf-shadow: per shade mode, in one run, the mesh pass with the option off (render_mesh_fused) and on (G-buffer kernel, prep and
+ray-list trace of one shadow ray a local pixel, deferred shade kernel; ngp_set_sun_nerf_shadow at its defaults), of the latter the prep and
+trace alone (ngp_get_frame_sun_shadow_ms), the frame's NeRF pass (kernel_ms) beside them, and how many pixels own a shadow ray.
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -53,6 +58,64 @@ def median_ms(ctx, cam, opts, frames, warmup):
     return float(np.median(ts)), float(np.min(ts)), float((depth < 16384.0).mean()), float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
 
 
+def median_on_off(ctx, cam, opts, frames, warmup, n_pixels):
+    """the option off, then on, in one run: medians (and p10 / p90) of the mesh pass, of the shadow rays' prep and trace, and of the NeRF pass"""
+    row = {}
+    for key, shadow in (("off", None), ("on", True)):
+        ctx.set_sun_nerf_shadow(shadow)
+        mesh, trace, nerf = [], [], []
+        for i in range(warmup + frames):
+            ctx.render(cam, opts)
+            if i >= warmup:
+                mesh.append(ctx.mesh_pass_ms())
+                trace.append(ctx.frame_sun_shadow_ms())
+                nerf.append(ctx.render_stats()["kernel_ms"])
+        q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+        row[key] = {"mesh_pass": q(mesh), "nerf_pass": q(nerf)}
+        if shadow:
+            row[key]["shadow_prep_and_trace"] = q(trace)
+            rec = ctx.frame_sun_shadow(n_pixels)
+            row[key]["pixels_with_shadow_ray"] = round(float(np.any(rec[:, :3] != 0, axis=1).mean()), 4)
+            row[key]["shadow_rays_blocked_above_0.9"] = round(float((rec[:, 3] > 0.9).mean()), 4)
+    ctx.set_sun_nerf_shadow(None)
+    row["mesh_pass_on_over_off"] = round(row["on"]["mesh_pass"]["median_ms"] / row["off"]["mesh_pass"]["median_ms"], 3)
+    row["gbuffer_and_shade_ms"] = round(row["on"]["mesh_pass"]["median_ms"] - row["on"]["shadow_prep_and_trace"]["median_ms"], 4)
+    return row
+
+
+def main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out):
+    out["how"] = ("per shade mode, one run: option off, then on (ngp_set_sun_nerf_shadow, min_transmittance 0.01, t_min 0). mesh_pass: HIP events around the whole mesh "
+                  "pass of the frame (ngp_get_mesh_pass_ms: off = render_mesh_fused; on = G-buffer kernel, prep, ray-list trace, deferred shade); "
+                  "shadow_prep_and_trace: HIP events around prep + trace inside it (ngp_get_frame_sun_shadow_ms); nerf_pass: the frame's NeRF launch "
+                  "(ngp_get_render_stats kernel_ms); gbuffer_and_shade_ms = the difference of the first two medians. Medians of --frames frames after --warmup, "
+                  "with p10 / p90. parent_off_median_ms: the parent commit's profiles/mesh_shade_rate.json, another run on another day.")
+    parent = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "mesh_shade_rate.json")) as f:
+            parent = {k: v["median_ms"] for k, v in json.load(f)["modes"].items()}
+    except (OSError, KeyError, ValueError):
+        pass
+    rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid"),
+            ("ShadeIrradianceVolume_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, 8), ("ShadeIrradianceVolumeVisible_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, -8)]
+    for name, mode, what in rows:
+        if what == "grid":
+            ctx.compute_envmap_grid(8, 8, 64, 32)
+        elif what is not None and what > 0:
+            ctx.compute_irradiance_volume((what,) * 3, (lo, hi), 16, 16)
+        elif what is not None:
+            ctx.compute_irradiance_volume_visibility(16, 16, 5)
+        row = median_on_off(ctx, cam, native.make_opts(render_mode=mode, **geo), args.frames, args.warmup, args.width * args.height)
+        if name in parent:
+            row["parent_off_median_ms"] = parent[name]
+        out["modes"][name] = row
+        print(f"{name:30s} mesh pass off {row['off']['mesh_pass']['median_ms']:.4f} ms, on {row['on']['mesh_pass']['median_ms']:.4f} ms "
+              f"(prep + trace {row['on']['shadow_prep_and_trace']['median_ms']:.4f} ms), NeRF pass {row['on']['nerf_pass']['median_ms']:.4f} ms", flush=True)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -60,10 +123,11 @@ def main():
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--visibility", action="store_true", help="the visibility-weighted volume against Shade and the plain volume, and the maps' compute time")
+    ap.add_argument("--sun-nerf-shadow", action="store_true", help="the mesh pass with the NeRF in front of the frames' sun, off and on, per shade mode")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -82,6 +146,9 @@ def main():
                   "median (and minimum) of --frames frames after --warmup; ratio = median / the Shade median of the same run",
            "width": args.width, "height": args.height, "frames": args.frames, "triangles": int(info["n_tris"]), "modes": {}}
     ctx.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
+    if args.sun_nerf_shadow:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out)
     rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid")]
     rows += [("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r) for r in (8, 32)]
     if args.visibility:  # one run: Shade, then per resolution the plain volume and the same volume with visibility
