@@ -690,8 +690,8 @@ NGP_API int ngp_get_irradiance_sun_shadow_ms(ngp_ctx* ctx, float* ms);
  *   refused when the frame is rendered, with the tracer's message, naming the option. A moving camera with meshes is refused as before.
  * Several devices: the option travels to the peers with the geometry and each device traces the shadow rays of its own tiles;
  *   ngp_get_frame_sun_shadow and ngp_get_frame_sun_shadow_ms read the primary's share only.
- * Stated limits: the NeRF attenuates the sun and is not lit by it; the meshes still throw no shadow onto the NeRF; one directional light; a
- *   hit that sits inside the NeRF's own density shadows itself unless t_min skips it. */
+ * Stated limits: the NeRF attenuates the sun and is not lit by it; the meshes throw no shadow onto the NeRF unless ngp_set_mesh_shadow_on_nerf (the next block) is on;
+ *   one directional light; a hit that sits inside the NeRF's own density shadows itself unless t_min skips it. */
 /* nerf == NULL: off (the default). Refusals as ngp_irradiance_sun_nerf_desc's: NaN min_transmittance; negative or non-finite t_min. */
 NGP_API int ngp_set_sun_nerf_shadow(ngp_ctx* ctx, const ngp_irradiance_sun_nerf_desc* nerf /* nullable */);
 NGP_API int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int* enabled);
@@ -701,6 +701,53 @@ NGP_API int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* 
 NGP_API int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
 /* device time (HIP events) of the shadow rays' prep and trace in the last frame's last sample; 0 after a frame without them */
 NGP_API int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms);
+
+/* sun: the meshes in front of the sun on the NeRF. The block above lets the captured object shadow the inserted meshes; this option lets the
+ * inserted meshes throw the sun's shadow onto the captured scene. Context state, set like ngp_set_sun_nerf_shadow; off by default, and with
+ * it off every frame is the one it was, as bytes.
+ *
+ * Which frames: Geometry mode, meshes loaded, a model loaded, render modes Shade, ShadeEnvMap, ShadeGridEnvMap and ShadeIrradianceVolume
+ *   (with or without visibility). In every other frame (NeRF mode, no meshes, no model) the option is ignored and the frame is the
+ *   option-off frame, as bytes; the G-buffer modes AO / Positions / Depth / Cost / Normals apply to NeRF mode alone.
+ * Each sample of such a frame runs three steps on the frame's stream:
+ *   1. the mesh pass, exactly as with the option off (the fused pass, or the split pass of ngp_set_sun_nerf_shadow when that is on too);
+ *   2. the NeRF launch, unchanged, with its colour output pointed at a zeroed per-pixel scratch instead of the frame: the scratch then holds
+ *      the NeRF's premultiplied n = (r, g, b, a) of a pixel the NeRF wrote and zero bits of any other (a <= 0.001, or culled by the depth
+ *      test against the meshes). The depth buffer, the depth test and the depth writes are those of every frame;
+ *   3. nerf_mesh_shadow_kernel, one thread a pixel:
+ *      n.w == 0: nothing is written, the pixel stays the mesh pass's; the record is (0, 0, 0, 0).
+ *      n.w > 0.2 (the NeRF pass's own rule for writing depth, so the depth buffer holds this ray's depth, the z-depth of its sample of
+ *        largest weight): the pixel owns a surface point p = o + d ((depth - cam_fwd . (o - cam_pos)) / (cam_fwd . d)), (o, d) the ray the
+ *        NeRF pass forms for that pixel and sample (lens, aperture, near distance and sample offset included). s^ =
+ *        normalize(normalize(sun_dir)) as the mesh pass forms it, q = p + bias s^, blocked = a triangle of ANY mesh lies within 100 of q
+ *        along s^ (the sunlit volume's shadow query). f = blocked ? fl(1 - strength) : 1. The record is (p, blocked ? 2 : 1).
+ *      0 < n.w <= 0.2: f = 1, the record is (0, 0, 0, 0).
+ *      The pixel becomes (fl(r f) + m.x k, fl(g f) + m.y k, fl(b f) + m.z k, a + m.w k), m the mesh pass's value of the pixel and
+ *      k = 1 - a: the NeRF pass's own composite, in its order, so f = 1 gives the option-off bits.
+ *   Accumulation and tonemapping follow as in every frame.
+ * strength: the share of the NeRF's own colour that the sun is taken to carry. A photograph does not say what that share is, so it is the
+ *   caller's number (the bindings' True: 0.5). bias: how far q is lifted off p towards the sun (True: 1e-2).
+ * Determinism: no atomics decide a value; frames are bit-identical from run to run. ngp_render_device stays asynchronous.
+ * Statistics: ngp_get_render_stats is the option-off frame's; the new kernel's time is ngp_get_frame_mesh_shadow_ms.
+ * Identities as bytes (colour and depth are the option-off frame's): the option off; strength 0; NeRF mode; no meshes; no model; a model
+ *   without density. Depth is the option-off frame's in every case.
+ * Refusals: a strength that is NaN or outside [0, 1]; a bias that is not finite or is negative; on any context. A refused call leaves the
+ *   option alone.
+ * Several devices: the option travels to the peers with the geometry and each device shadows its own share; ngp_get_frame_mesh_shadow and
+ *   ngp_get_frame_mesh_shadow_ms read the primary's share only.
+ * Stated limits: the shadow is hard-edged and there is one directional light; the NeRF pixel is scaled as a whole at its largest-weight
+ *   sample, there is no per-sample shadowing along the ray; a pixel of alpha <= 0.2 is never shadowed; shadows already baked into the
+ *   photographs are not removed; the NeRF is still not lit by anything. */
+typedef struct ngp_mesh_shadow_on_nerf_desc { float strength; float bias; } ngp_mesh_shadow_on_nerf_desc;
+/* desc == NULL: off (the default) */
+NGP_API int ngp_set_mesh_shadow_on_nerf(ngp_ctx* ctx, const ngp_mesh_shadow_on_nerf_desc* desc /* nullable: off */);
+NGP_API int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_desc* out, int* enabled);
+/* stage entry for tests: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on a multi-device context
+ * the primary's tile-packed share): (p_xyz, 2 blocked / 1 open); zeros where the pixel owns no surface point. n_pixels must be that frame's
+ * extent. Refuses when the last frame did not run the pass. */
+NGP_API int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
+/* device time (HIP events) of nerf_mesh_shadow_kernel in the last frame's last sample; 0 after a frame without it */
+NGP_API int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -1147,4 +1147,54 @@ void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const 
 	if (n) hipLaunchKernelGGL(irradiance_sun_shadow_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, traced, o, st, rgba, shadow_out);
 }
 
+// ---- the meshes in front of the sun on the NeRF (ngp_set_mesh_shadow_on_nerf; contract in include/ngp_hip.h, "sun: the meshes in front of
+// the sun on the NeRF"). The frame's NeRF launch composited over zeros into `nerf` instead of the frame: nerf[idx] = the pixel's premultiplied
+// (r, g, b, a), zero bits where the launch wrote nothing. This kernel finishes shade_ray's composite over the mesh pass's frame_buffer[idx],
+// in shade_ray's order, with the NeRF's colour scaled by f where a mesh stands between the pixel's surface point and the sun. A pixel of
+// alpha > 0.2 owns depth_buffer[idx] (shade_ray's rule), so its surface point lies at that z-depth on the ray init_ray forms for it.
+// record: (p, 2 blocked / 1 open), left as the host cleared it where the pixel owns no surface point.
+__global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShadeParams P, const ModelParams M, const CameraParams C, float4* __restrict__ frame_buffer,
+                                        const float* __restrict__ depth_buffer, const float4* __restrict__ nerf, float4* __restrict__ record, uint32_t shard_index,
+                                        uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias) {
+	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
+	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
+	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
+	if (tile % shard_count != shard_index) return;
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	if (C.moving || idx >= n_pixels) return;
+	const float4 n = nerf[idx];
+	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here: the pixel stays the mesh pass's
+	float f = 1.0f;
+	if (n.w > 0.2f) {
+		const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
+		const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
+		RayState ray;
+		init_ray<false>(M, C, x, y, ray);
+		const float t = (depth_buffer[idx] - dot3(cam_fwd, sub3(ray.o, cam_pos))) / dot3(cam_fwd, ray.d);
+		const f3 p = add3(ray.o, scale3(ray.d, t));
+		const f3 sdir = normalize3(normalize3(ld3(P.sun_dir)));
+		const bool blocked = any_hit(S, add3(p, scale3(sdir, bias)), sdir);
+		if (blocked) f = 1.0f - strength;
+		record[idx] = make_float4(p.x, p.y, p.z, blocked ? 2.0f : 1.0f);
+	}
+	float4 fb = frame_buffer[idx];
+	const float r = n.x * f, g = n.y * f, b = n.z * f, a = n.w;
+	float k = 1.0f - a;
+	fb.x = r + fb.x * k;
+	fb.y = g + fb.y * k;
+	fb.z = b + fb.z * k;
+	fb.w = a + fb.w * k;
+	frame_buffer[idx] = fb;
+}
+
+void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
+                             const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
+                             hipStream_t stream) {
+	dim3 threads(16, 8, 1);
+	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
+	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, blocks, threads, 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, shard_index, shard_count, packed, n_pixels, strength,
+	                   bias);
+}
+
 } // namespace ngp

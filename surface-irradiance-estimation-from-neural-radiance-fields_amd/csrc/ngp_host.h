@@ -149,6 +149,9 @@ void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, con
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
                                 float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
                                 const float2* ray_t, const float4* traced, float4* record, hipStream_t stream); // M5 of launch_render_mesh behind the trace
+void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
+                             const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
+                             hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t stream);
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
@@ -395,6 +398,15 @@ struct ngp_ctx {
 	ngp::Event ev_ss0[HISTORY], ev_ss1[HISTORY]; // around prep + trace of a frame's last sample (ngp_get_frame_sun_shadow_ms)
 	bool hist_sun_shadow[HISTORY] = {};                  // the slot's call was a frame that traced shadow rays
 	size_t ss_n_pixels = 0;                                    // pixels of the last such frame
+	// ---- the meshes in front of the sun on the NeRF (ngp_set_mesh_shadow_on_nerf); a peer's copy follows the primary's with the geometry
+	bool mesh_shadow_on_nerf = false;
+	ngp_mesh_shadow_on_nerf_desc mesh_shadow_on_nerf_desc{};
+	// its per-pixel buffers, allocated when a frame first uses the option and grown like the frame buffers (d_ms_record, allocated last, holds the size of both)
+	ngp::DevArray<float4> d_ms_nerf;   // where the NeRF launch composites instead of the frame: premultiplied (r, g, b, a), zeros where it wrote nothing
+	ngp::DevArray<float4> d_ms_record; // (p, 2 blocked / 1 open) of the last sample (ngp_get_frame_mesh_shadow)
+	ngp::Event ev_ms0[HISTORY], ev_ms1[HISTORY]; // around nerf_mesh_shadow_kernel of a frame's last sample (ngp_get_frame_mesh_shadow_ms)
+	bool hist_mesh_shadow[HISTORY] = {};         // the slot's call was a frame that ran the pass
+	size_t ms_n_pixels = 0;                      // pixels of the last such frame
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a

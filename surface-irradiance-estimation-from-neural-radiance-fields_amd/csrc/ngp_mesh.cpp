@@ -256,6 +256,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->shade = primary->shade;
 	peer->sun_nerf_shadow = primary->sun_nerf_shadow; // each device traces the shadow rays of its own share
 	peer->sun_nerf_shadow_desc = primary->sun_nerf_shadow_desc;
+	peer->mesh_shadow_on_nerf = primary->mesh_shadow_on_nerf; // each device shadows its own share
+	peer->mesh_shadow_on_nerf_desc = primary->mesh_shadow_on_nerf_desc;
 	if (peer->synced_mesh_generation != primary->mesh_generation) {
 		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)

@@ -253,6 +253,21 @@ void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	NGP_HIP_CHECK(hipMemset(ctx->d_ss_d.get(), 0, ctx->d_ss_d.bytes()));
 }
 
+// the per-pixel buffers of a frame whose meshes shadow the NeRF (ngp_set_mesh_shadow_on_nerf): allocated by the first frame that uses the
+// option, grown as ensure_frame_buffers grows
+void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->ev_ms0[0]) {
+		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
+			ctx->ev_ms0[i] = new_event();
+			ctx->ev_ms1[i] = new_event();
+		}
+	}
+	if (n_pixels <= ctx->d_ms_record.size()) return;
+	ctx->d_ms_nerf.reset(), ctx->d_ms_record.reset();
+	ctx->d_ms_nerf.reset(n_pixels);
+	ctx->d_ms_record.reset(n_pixels);
+}
+
 // Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
 void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba_out, float* d_depth_out, hipStream_t stream) {
 	require_device(ctx, "rendering needs an MI355X");
@@ -269,6 +284,12 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 		require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
 		ensure_sun_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
 	}
+	// the meshes in front of the sun on the NeRF: the same frames, in the four shade modes. The NeRF launch composites into a scratch of
+	// its own and one kernel behind it finishes the composite over the mesh pass's pixels, all of it on `stream`; nothing waits.
+	const bool shade_mode = opts.render_mode == NGP_RENDER_SHADE || opts.render_mode == NGP_RENDER_SHADE_ENVMAP || opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ||
+	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
+	const bool mesh_shadow = ctx->mesh_shadow_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
+	if (mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
 	const int spp = opts.spp > 0 ? opts.spp : 1;
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
@@ -344,10 +365,21 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 			}
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
 		}
+		if (mesh_shadow) { // the NeRF launch composites over zeros, apart from the mesh pass's pixels; its depth test and depth writes are every frame's
+			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_nerf.get(), 0, n_pixels * sizeof(float4), stream));
+			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_record.get(), 0, n_pixels * sizeof(float4), stream));
+			F.frame_buffer = ctx->d_ms_nerf.get();
+		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
 		if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
 		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
+		if (mesh_shadow) { // ... and the composite over the mesh pass's pixels follows, scaled where a mesh stands in front of the sun
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ms0[slot], stream)); // (ngp_get_frame_mesh_shadow_ms)
+			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), ctx->d_ms_record.get(), F.shard_index, F.shard_count,
+			                        F.packed, (uint32_t)n_pixels, ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, stream);
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ms1[slot], stream));
+		}
 		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame.get(), ctx->d_accum.get(), (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
 	}
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
@@ -357,6 +389,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->hist_mesh_pass[slot] = have_meshes && !F.direct;
 	ctx->hist_sun_shadow[slot] = sun_shadow;
 	if (sun_shadow) ctx->ss_n_pixels = n_pixels;
+	ctx->hist_mesh_shadow[slot] = mesh_shadow;
+	if (mesh_shadow) ctx->ms_n_pixels = n_pixels;
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -543,6 +577,49 @@ int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
 		if (!ctx->hist_sun_shadow[slot]) return;
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ss0[slot], ctx->ev_ss1[slot]));
+	});
+}
+
+int ngp_set_mesh_shadow_on_nerf(ngp_ctx* ctx, const ngp_mesh_shadow_on_nerf_desc* desc) {
+	return guarded(ctx, [&] {
+		if (desc) {
+			if (!(desc->strength >= 0.0f && desc->strength <= 1.0f)) throw std::runtime_error("invalid mesh shadow descriptor: strength must lie in [0, 1]");
+			if (!std::isfinite(desc->bias) || desc->bias < 0.0f) throw std::runtime_error("invalid mesh shadow descriptor: bias must be finite and >= 0");
+		}
+		ctx->mesh_shadow_on_nerf = desc != nullptr;
+		ctx->mesh_shadow_on_nerf_desc = desc ? *desc : ngp_mesh_shadow_on_nerf_desc{};
+	});
+}
+
+int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = ctx->mesh_shadow_on_nerf_desc;
+		*enabled = ctx->mesh_shadow_on_nerf ? 1 : 0;
+	});
+}
+
+int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls || !ctx->hist_mesh_shadow[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame ran no mesh shadow pass (ngp_set_mesh_shadow_on_nerf)");
+		if (n_pixels != ctx->ms_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ms_n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ms_record.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = 0.f;
+		if (!ctx->n_calls) return;
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		if (!ctx->hist_mesh_shadow[slot]) return;
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ms0[slot], ctx->ev_ms1[slot]));
 	});
 }
 

@@ -261,6 +261,10 @@ PYBIND11_MODULE(pyngp, m) {
 		               "Geometry frames with meshes and a model: the NeRF's density shadows the frames' own sun on mesh pixels (default False)")
 		.def_readwrite("sun_nerf_shadow_min_transmittance", &Testbed::m_sun_nerf_shadow_min_transmittance, "with sun_nerf_shadow: the shadow rays' transmittance floor (0.01)")
 		.def_readwrite("sun_nerf_shadow_t_min", &Testbed::m_sun_nerf_shadow_t_min, "with sun_nerf_shadow: the NeRF is ignored within this distance of the surface (0)")
+		.def_readwrite("mesh_shadow_on_nerf", &Testbed::m_mesh_shadow_on_nerf,
+		               "Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (default False)")
+		.def_readwrite("mesh_shadow_on_nerf_strength", &Testbed::m_mesh_shadow_on_nerf_strength, "with mesh_shadow_on_nerf: the share of a shadowed NeRF pixel's colour the shadow takes away (0.5)")
+		.def_readwrite("mesh_shadow_on_nerf_bias", &Testbed::m_mesh_shadow_on_nerf_bias, "with mesh_shadow_on_nerf: how far the shadow ray's origin is lifted off the NeRF's surface point towards the sun (1e-2)")
 		.def_readwrite("irradiance_volume_sun_nerf_shadow", &Testbed::m_irradiance_volume_sun_nerf_shadow,
 		               "with irradiance_volume_sun: the NeRF's density shadows that sun in the default volume (render_min_transmittance, t_min 0)")
 		.def_readwrite("irradiance_volume_sun_radiance", &Testbed::m_irradiance_volume_sun_radiance, "what a surface facing the sun receives in a sunlit volume; default: the frames' sun colour")

@@ -496,6 +496,10 @@ public:
 			const ngp_irradiance_sun_nerf_desc ns{m_sun_nerf_shadow_min_transmittance, m_sun_nerf_shadow_t_min};
 			check(ngp_set_sun_nerf_shadow(m_ctx, m_sun_nerf_shadow ? &ns : nullptr));
 		}
+		{ // the meshes in front of the sun on the NeRF (off: NULL)
+			const ngp_mesh_shadow_on_nerf_desc ms{m_mesh_shadow_on_nerf_strength, m_mesh_shadow_on_nerf_bias};
+			check(ngp_set_mesh_shadow_on_nerf(m_ctx, m_mesh_shadow_on_nerf ? &ms : nullptr));
+		}
 		check(ngp_render(m_ctx, &cam, &o, out, depth_out));
 	}
 	// irradiance probe pre-pass: what src/main.cu:185-188 calls before the render loop in ShadeEnvMap mode
@@ -609,6 +613,8 @@ public:
 	bool m_irradiance_volume_sun = false; // that default volume also holds the sun's first bounce off the meshes (the frame's sun: m_sun_dir, the radiance below, bias 1e-3)
 	bool m_sun_nerf_shadow = false; // Geometry frames with meshes and a model: the NeRF's density stands in front of the frames' own sun on mesh pixels (ngp_set_sun_nerf_shadow)
 	float m_sun_nerf_shadow_min_transmittance = 0.01f, m_sun_nerf_shadow_t_min = 0.f; // ... traced down to this transmittance, ignoring the NeRF within t_min of the surface
+	bool m_mesh_shadow_on_nerf = false; // Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (ngp_set_mesh_shadow_on_nerf)
+	float m_mesh_shadow_on_nerf_strength = 0.5f, m_mesh_shadow_on_nerf_bias = 1e-2f; // ... taking this share of a shadowed NeRF pixel's colour away, from a point lifted this far towards the sun
 	bool m_irradiance_volume_sun_nerf_shadow = false; // ... with the NeRF's density in front of that sun (render_min_transmittance, t_min 0); looked at with m_irradiance_volume_sun alone
 	std::array<float, 3> m_irradiance_volume_sun_radiance{255.f / 255.0f * 4.f, 225.f / 255.0f * 4.f, 195.f / 255.0f * 4.f}; // the frames' suncol (mesh_kernels.hip)
 	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)

@@ -121,6 +121,10 @@ class IrradianceSunNerfDesc(C.Structure):
     _fields_ = [("min_transmittance", C.c_float), ("t_min", C.c_float)]
 
 
+class MeshShadowOnNerfDesc(C.Structure):
+    _fields_ = [("strength", C.c_float), ("bias", C.c_float)]
+
+
 SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
 
 
@@ -266,6 +270,10 @@ def load_library():
     L.ngp_get_sun_nerf_shadow.argtypes = [vp, C.POINTER(IrradianceSunNerfDesc), C.POINTER(C.c_int)]
     L.ngp_get_frame_sun_shadow.argtypes = [vp, vp, C.c_size_t]
     L.ngp_get_frame_sun_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_set_mesh_shadow_on_nerf.argtypes = [vp, C.POINTER(MeshShadowOnNerfDesc)]
+    L.ngp_get_mesh_shadow_on_nerf.argtypes = [vp, C.POINTER(MeshShadowOnNerfDesc), C.POINTER(C.c_int)]
+    L.ngp_get_frame_mesh_shadow.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_mesh_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -904,6 +912,39 @@ class Context:
         """device time of the shadow rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
         ms = C.c_float(0)
         self._check(self.L.ngp_get_frame_sun_shadow_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def set_mesh_shadow_on_nerf(self, shadow=True):
+        """the meshes in front of the sun on the NeRF (Geometry frames with meshes and a model, the four shade modes): None or False switches
+        it off (the default), True takes strength 0.5 and bias 1e-2, a dict gives strength and bias"""
+        if shadow is None or shadow is False:
+            self._check(self.L.ngp_set_mesh_shadow_on_nerf(self.h, None))
+            return
+        if shadow is True:
+            shadow = {}
+        if not isinstance(shadow, dict) or set(shadow) - {"strength", "bias"}:
+            raise ValueError("mesh_shadow_on_nerf: True, False, None or a dict of strength and bias")
+        d = MeshShadowOnNerfDesc()
+        d.strength, d.bias = float(shadow.get("strength", 0.5)), float(shadow.get("bias", 1e-2))
+        self._check(self.L.ngp_set_mesh_shadow_on_nerf(self.h, C.byref(d)))
+
+    def mesh_shadow_on_nerf(self):
+        """None while the option is off, else dict(strength=, bias=) as set"""
+        d, on = MeshShadowOnNerfDesc(), C.c_int(0)
+        self._check(self.L.ngp_get_mesh_shadow_on_nerf(self.h, C.byref(d), C.byref(on)))
+        return dict(strength=d.strength, bias=d.bias) if on.value else None
+
+    def frame_mesh_shadow(self, n_pixels):
+        """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (p xyz, 2 blocked / 1 open) of the NeRF's
+        surface point under the meshes' shadow; zeros where the pixel owns none. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros((int(n_pixels), 4), np.float32)
+        self._check(self.L.ngp_get_frame_mesh_shadow(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def frame_mesh_shadow_ms(self):
+        """device time of the mesh shadow kernel in the last frame's last sample, ms; 0 after a frame without it"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_frame_mesh_shadow_ms(self.h, C.byref(ms)))
         return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):

@@ -11,6 +11,11 @@ sharpness 2^5, default D) at 8^3 and 32^3 probes in one run, and the wall time o
 With --sun-nerf-shadow: per shade mode, in one run, the mesh pass with the option off (render_mesh_fused) and on (G-buffer kernel, prep and
 ray-list trace of one shadow ray a local pixel, deferred shade kernel; ngp_set_sun_nerf_shadow at its defaults), of the latter the prep and
 trace alone (ngp_get_frame_sun_shadow_ms), the frame's NeRF pass (kernel_ms) beside them, and how many pixels own a shadow ray.
+    python tools/mesh_shade_rate.py --mesh-shadow-on-nerf [--out profiles/mesh_shadow_on_nerf_rate.json]
+
+With --mesh-shadow-on-nerf: Shade-mode frames with the meshes' shadow on the NeRF off and on (ngp_set_mesh_shadow_on_nerf at its defaults),
+the calls alternating: the whole frame on the device (frame_ms), its NeRF pass (kernel_ms), its mesh pass, the new kernel alone
+(ngp_get_frame_mesh_shadow_ms), and how many pixels own a surface point and how many of those a mesh shadows.
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -116,6 +121,38 @@ def main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out):
     ctx.close()
 
 
+def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
+    out["how"] = ("Shade-mode Geometry frames, the option off and on (ngp_set_mesh_shadow_on_nerf, strength 0.5, bias 1e-2) in alternating calls of one run. frame: HIP "
+                  "events around the whole frame (ngp_get_render_stats frame_ms); nerf_pass: its NeRF launch (kernel_ms); mesh_pass: ngp_get_mesh_pass_ms; "
+                  "mesh_shadow_kernel: HIP events around nerf_mesh_shadow_kernel (ngp_get_frame_mesh_shadow_ms). Medians of --frames frames each after --warmup, with p10 / p90.")
+    opts = native.make_opts(render_mode=native.RENDER_SHADE, **geo)
+    ts = {key: {"frame": [], "nerf_pass": [], "mesh_pass": [], "mesh_shadow_kernel": []} for key in ("off", "on")}
+    for i in range(args.warmup + args.frames):
+        for key, shadow in (("off", None), ("on", True)):
+            ctx.set_mesh_shadow_on_nerf(shadow)
+            ctx.render(cam, opts)
+            if i >= args.warmup:
+                st = ctx.render_stats()
+                ts[key]["frame"].append(st["frame_ms"])
+                ts[key]["nerf_pass"].append(st["kernel_ms"])
+                ts[key]["mesh_pass"].append(ctx.mesh_pass_ms())
+                ts[key]["mesh_shadow_kernel"].append(ctx.frame_mesh_shadow_ms())
+    rec = ctx.frame_mesh_shadow(args.width * args.height)  # (the last call was an on frame)
+    ctx.set_mesh_shadow_on_nerf(None)
+    q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+    row = {key: {k: q(v) for k, v in t.items()} for key, t in ts.items()}
+    row["pixels_with_surface_point"] = round(float((rec[:, 3] != 0).mean()), 4)
+    row["pixels_blocked"] = round(float((rec[:, 3] == 2).mean()), 4)
+    row["frame_on_minus_off_ms"] = round(row["on"]["frame"]["median_ms"] - row["off"]["frame"]["median_ms"], 4)
+    out["modes"]["Shade"] = row
+    print(f"frame off {row['off']['frame']['median_ms']:.4f} ms, on {row['on']['frame']['median_ms']:.4f} ms (mesh shadow kernel {row['on']['mesh_shadow_kernel']['median_ms']:.4f} ms, "
+          f"NeRF pass off {row['off']['nerf_pass']['median_ms']:.4f} / on {row['on']['nerf_pass']['median_ms']:.4f} ms), owners {row['pixels_with_surface_point']}, blocked {row['pixels_blocked']}", flush=True)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -124,10 +161,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--visibility", action="store_true", help="the visibility-weighted volume against Shade and the plain volume, and the maps' compute time")
     ap.add_argument("--sun-nerf-shadow", action="store_true", help="the mesh pass with the NeRF in front of the frames' sun, off and on, per shade mode")
+    ap.add_argument("--mesh-shadow-on-nerf", action="store_true", help="Shade frames with the meshes' shadow on the NeRF, off and on in alternating calls")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -149,6 +187,9 @@ def main():
     if args.sun_nerf_shadow:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out)
+    if args.mesh_shadow_on_nerf:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out)
     rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid")]
     rows += [("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r) for r in (8, 32)]
     if args.visibility:  # one run: Shade, then per resolution the plain volume and the same volume with visibility
