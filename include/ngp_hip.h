@@ -737,7 +737,7 @@ NGP_API int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms);
  *   ngp_get_frame_mesh_shadow_ms read the primary's share only.
  * Stated limits: the shadow is hard-edged and there is one directional light; the NeRF pixel is scaled as a whole at its largest-weight
  *   sample, there is no per-sample shadowing along the ray; a pixel of alpha <= 0.2 is never shadowed; shadows already baked into the
- *   photographs are not removed; the NeRF is still not lit by anything. */
+ *   photographs are not removed; the ambient light on the NeRF changes only with ngp_set_ambient_change_on_nerf (the next block). */
 typedef struct ngp_mesh_shadow_on_nerf_desc { float strength; float bias; } ngp_mesh_shadow_on_nerf_desc;
 /* desc == NULL: off (the default) */
 NGP_API int ngp_set_mesh_shadow_on_nerf(ngp_ctx* ctx, const ngp_mesh_shadow_on_nerf_desc* desc /* nullable: off */);
@@ -748,6 +748,59 @@ NGP_API int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_de
 NGP_API int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
 /* device time (HIP events) of nerf_mesh_shadow_kernel in the last frame's last sample; 0 after a frame without it */
 NGP_API int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms);
+
+/* ambient: what the inserted meshes change in the ambient light on the NeRF (differential rendering). The context holds a second SH9
+ * volume, the REFERENCE volume: the scene before anything was inserted. With the option on, a NeRF pixel that owns a surface point has its
+ * colour scaled, per channel, by g = E_after(p, N) / E_before(p, N): "after" the context's own volume (ngp_compute_irradiance_volume* /
+ * ngp_set_irradiance_volume), "before" the reference, N the NeRF's own normal at p. Off by default, and with it off every frame is the
+ * one it was, as bytes.
+ *
+ * The reference volume is data, held exactly like the context's volume: on the primary device, never recomputed behind the caller's back,
+ *   not stored in snapshots, copied to the peers with the geometry (a generation counter of its own). It has no visibility maps.
+ *   ngp_compute_reference_irradiance_volume: V_0 of the SH9 block above, traced over the lattice of desc with occlude_by_meshes forced to
+ *   0 whatever desc->sh says; no bounces, no sun. The context's own volume is untouched. ngp_set_ / ngp_get_ / ngp_clear_reference_
+ *   irradiance_volume: as ngp_set_ / ngp_get_ / ngp_clear_irradiance_volume, with their refusals and messages.
+ * The ratio at (p, N^), N^ = N / |N|. Both lookups are the plain ngp_irradiance_volume_at lookup: (E_after, W_after) in the context's
+ *   volume, (E_before, W_before) in the reference. The visibility maps are not used. Per channel
+ *     a = max(E_after, 0), b = E_before, g = (b > min_irradiance) ? min(a / b, max_gain) : 1
+ *   state 1, "no estimate", when W_after = 0 or W_before = 0: g = (1, 1, 1); state 2 otherwise.
+ *   IDENTITY: identical records in the two volumes (the same lattice and box) give a / b = 1 exactly on every channel, whatever N is: one
+ *   device function evaluates both lookups, a and b are then the same bits, and a correctly rounded quotient of equal numbers is 1. So the
+ *   two volumes should be computed with the same lattice, box and ray counts, and away from the meshes, where their records agree, the
+ *   option changes nothing.
+ * min_irradiance: below it the reference is taken to say nothing about the channel (the bindings' True: 1e-3). max_gain: the cap on g
+ *   (True: 4). Refused: values that are not finite, min_irradiance < 0, max_gain < 1; on any context; a refused call leaves the option alone.
+ * Which frames: those of ngp_set_mesh_shadow_on_nerf (Geometry mode, meshes, a model, the four shade modes); every other frame ignores the
+ *   option and is the option-off frame as bytes. Such a frame is refused when either volume is missing (the message names it), and for
+ *   Frequency / Identity (wide) models: the normals kernel runs the grid encoding's gradient.
+ * Each sample, on the frame's stream, nothing waits: (1) the mesh pass; (2) the NeRF launch into the zeroed scratch n of the block above;
+ *   (3) nerf_surface_normals_kernel: a pixel with n.w > 0.2 owns p exactly as in the block above; N = -(grad / aabb_diag) / |grad /
+ *   aabb_diag|, grad the density-gradient stage (ngp_density_gradient) at the warped p: the marching-cubes export's rule. A zero or
+ *   non-finite length gives state 1. N is the raw gradient: neither smoothed nor flipped towards the viewer; (4) nerf_ambient_ratio_
+ *   kernel, one thread a pixel: g as above, n.rgb <- fl(n.rgb g) in the scratch; (5) the closing composite: nerf_mesh_shadow_kernel when
+ *   ngp_set_mesh_shadow_on_nerf is on too (the pixel is fl(fl(n g) f) + m k), else the same expression with f = 1 and no shadow query. g = 1
+ *   and f = 1 give the option-off bits. Depth, alpha and ngp_get_render_stats are the option-off frame's.
+ * The record: 12 floats a pixel: p (3), state (0 not an owner, 1 no estimate, 2 scaled), N (3), W_after, g (3), W_before.
+ * Stated limits: the pixel is scaled as a whole at its largest-weight sample, pixels of alpha <= 0.2 are untouched; the normal is the raw
+ *   density gradient; the lookup is plain, so light leaks through thin inserted walls as it does for the meshes without visibility; SH9
+ *   holds no sharp contact shadow; grid-encoded models only; shadows and interreflections already in the photographs stay. */
+typedef struct ngp_ambient_change_desc { float min_irradiance; float max_gain; } ngp_ambient_change_desc;
+NGP_API int ngp_compute_reference_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc);
+NGP_API int ngp_set_reference_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh /* probes x 28 */);
+NGP_API int ngp_get_reference_irradiance_volume(ngp_ctx* ctx, ngp_irradiance_volume_desc* desc_out, float* sh_out /* nullable, probes x 28 */);
+NGP_API int ngp_clear_reference_irradiance_volume(ngp_ctx* ctx);
+/* desc == NULL: off (the default) */
+NGP_API int ngp_set_ambient_change_on_nerf(ngp_ctx* ctx, const ngp_ambient_change_desc* desc /* nullable: off */);
+NGP_API int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, int* enabled);
+/* stage entry for tests and tools: (g rgb, state) at explicit points and normals. Refuses without either volume, a zero or non-finite
+ * normal, a non-finite position. */
+NGP_API int ngp_irradiance_volume_ratio(ngp_ctx* ctx, uint32_t n, const float* positions /* n x 3 */, const float* normals /* n x 3 */,
+                                        const ngp_ambient_change_desc* desc, float* out /* n x 4 */);
+/* per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on a multi-device context the primary's
+ * tile-packed share): the 12-float record. n_pixels must be that frame's extent. Refuses when the last frame did not run the pass. */
+NGP_API int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out /* n_pixels x 12 */, size_t n_pixels);
+/* device time (HIP events) around the two new kernels in the last frame's last sample; 0 after a frame without them */
+NGP_API int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -34,9 +34,7 @@ NGP_DEV f3 mc_position(const McLattice& L, float qx, float qy, float qz) {
 	return mk3(L.r2l[0] * lx + L.r2l[1] * ly + L.r2l[2] * lz, L.r2l[3] * lx + L.r2l[4] * ly + L.r2l[5] * lz,
 	           L.r2l[6] * lx + L.r2l[7] * ly + L.r2l[8] * lz);
 }
-NGP_DEV f3 mc_warp(const ModelParams& M, f3 p) { // warp_position (nerf_device.cuh), as density_grid_samples_kernel forms it
-	return div3(sub3(p, mk3(M.aabb_min[0], M.aabb_min[1], M.aabb_min[2])), mk3(M.aabb_diag[0], M.aabb_diag[1], M.aabb_diag[2]));
-}
+// (mc_warp, warp_position, lives in render_common.h: the frames' surface-normal pass forms its positions with it too)
 
 // the values at flat indices base .. base + 4 (zero beyond the lattice): a float4 when base is 16-byte aligned
 NGP_DEV void mc_load5(const float* __restrict__ d, uint32_t n, uint32_t base, float (&v)[5]) {
@@ -302,11 +300,7 @@ __global__ void mc_vertex_attributes_kernel(const ModelParams M, uint32_t n, con
                                             float* __restrict__ C) {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= n) return;
-	// d logit / d ngp position = d logit / d warped position / aabb_diag; the density is increasing in its logit
-	const float gx = grad01[3 * t] / M.aabb_diag[0], gy = grad01[3 * t + 1] / M.aabb_diag[1], gz = grad01[3 * t + 2] / M.aabb_diag[2];
-	const float len = sqrtf(gx * gx + gy * gy + gz * gz);
-	const bool ok = len > 0.0f && isfinite(len);
-	N[3 * t] = ok ? -gx / len : 0.0f; N[3 * t + 1] = ok ? -gy / len : 0.0f; N[3 * t + 2] = ok ? -gz / len : 0.0f;
+	density_normal(M, grad01 + 3 * t, N + 3 * t); // (render_common.h: the rule the frames' surface-normal pass shares)
 	union { uint16_t u; half_t h; } cv;
 	for (int c = 0; c < 3; ++c) {
 		cv.u = net[4 * (size_t)t + c];

@@ -1153,6 +1153,16 @@ void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const 
 // in shade_ray's order, with the NeRF's colour scaled by f where a mesh stands between the pixel's surface point and the sun. A pixel of
 // alpha > 0.2 owns depth_buffer[idx] (shade_ray's rule), so its surface point lies at that z-depth on the ray init_ray forms for it.
 // record: (p, 2 blocked / 1 open), left as the host cleared it where the pixel owns no surface point.
+// shade_ray's composite of the NeRF's premultiplied n, its colour scaled by f, over the mesh pass's pixel fb, in shade_ray's order
+NGP_DEV float4 nerf_over_mesh(float4 fb, float4 n, float f) {
+	const float r = n.x * f, g = n.y * f, b = n.z * f, a = n.w;
+	float k = 1.0f - a;
+	fb.x = r + fb.x * k;
+	fb.y = g + fb.y * k;
+	fb.z = b + fb.z * k;
+	fb.w = a + fb.w * k;
+	return fb;
+}
 __global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShadeParams P, const ModelParams M, const CameraParams C, float4* __restrict__ frame_buffer,
                                         const float* __restrict__ depth_buffer, const float4* __restrict__ nerf, float4* __restrict__ record, uint32_t shard_index,
                                         uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias) {
@@ -1167,25 +1177,13 @@ __global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShade
 	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here: the pixel stays the mesh pass's
 	float f = 1.0f;
 	if (n.w > 0.2f) {
-		const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
-		const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
-		RayState ray;
-		init_ray<false>(M, C, x, y, ray);
-		const float t = (depth_buffer[idx] - dot3(cam_fwd, sub3(ray.o, cam_pos))) / dot3(cam_fwd, ray.d);
-		const f3 p = add3(ray.o, scale3(ray.d, t));
+		const f3 p = nerf_surface_point(M, C, x, y, depth_buffer[idx]); // (render_common.h: the one definition of p)
 		const f3 sdir = normalize3(normalize3(ld3(P.sun_dir)));
 		const bool blocked = any_hit(S, add3(p, scale3(sdir, bias)), sdir);
 		if (blocked) f = 1.0f - strength;
 		record[idx] = make_float4(p.x, p.y, p.z, blocked ? 2.0f : 1.0f);
 	}
-	float4 fb = frame_buffer[idx];
-	const float r = n.x * f, g = n.y * f, b = n.z * f, a = n.w;
-	float k = 1.0f - a;
-	fb.x = r + fb.x * k;
-	fb.y = g + fb.y * k;
-	fb.z = b + fb.z * k;
-	fb.w = a + fb.w * k;
-	frame_buffer[idx] = fb;
+	frame_buffer[idx] = nerf_over_mesh(frame_buffer[idx], n, f);
 }
 
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
@@ -1195,6 +1193,85 @@ void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P,
 	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
 	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, blocks, threads, 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, shard_index, shard_count, packed, n_pixels, strength,
 	                   bias);
+}
+
+// ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf; contract in include/ngp_hip.h, "ambient").
+// g = E_after / E_before per channel at (p, n^): both lookups are the plain irradiance_volume_lookup (no visibility maps), `after` the
+// context's volume and `before` the reference. a = max(E_after, 0), b = E_before, g = b > min_irradiance ? min(a / b, max_gain) : 1.
+// Returns the state: 1 "no estimate" (W_after = 0 or W_before = 0; g = 1), else 2. Identical records in the two volumes give a and b the
+// same bits (one lookup function, the same statements) and a / b = 1 exactly, whatever n^ is. The one definition: the stage kernel and
+// the frame's ratio kernel both call it.
+NGP_DEV float irradiance_volume_ratio(const IrradianceVolume& after, const IrradianceVolume& before, f3 p, f3 nh, float min_irradiance, float max_gain, float (&g)[3],
+                                      float& W_after, float& W_before) {
+	float Ea[3], Eb[3];
+	irradiance_volume_lookup(after, p, nh, Ea, W_after);
+	irradiance_volume_lookup(before, p, nh, Eb, W_before);
+	g[0] = g[1] = g[2] = 1.0f;
+	if (W_after == 0.0f || W_before == 0.0f) return 1.0f;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const float a = fmaxf(Ea[c], 0.0f), b = Eb[c];
+		if (b > min_irradiance) g[c] = fminf(a / b, max_gain);
+	}
+	return 2.0f;
+}
+// one thread per point: out = (g rgb, state) at the point and its normalised normal (ngp_irradiance_volume_ratio)
+__global__ void irradiance_volume_ratio_kernel(const IrradianceVolume after, const IrradianceVolume before, uint32_t n, const float* __restrict__ positions,
+                                               const float* __restrict__ normals, float min_irradiance, float max_gain, float4* __restrict__ out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	float g[3], Wa, Wb;
+	const float state = irradiance_volume_ratio(after, before, ld3(positions + 3 * (size_t)i), normalize3(ld3(normals + 3 * (size_t)i)), min_irradiance, max_gain, g, Wa, Wb);
+	out[i] = make_float4(g[0], g[1], g[2], state);
+}
+// one thread per pixel of the frame's own order: the record nerf_surface_normals_kernel left is (p, state), (N, 0), (1, 1, 1, 0) where the
+// pixel owns a surface point (state 2: N is a unit normal; 1: the gradient gave none) and zeros elsewhere. Where N stands, g scales the
+// NeRF's colour in the scratch in place and the record becomes (p, state), (N, W_after), (g, W_before).
+__global__ void nerf_ambient_ratio_kernel(const IrradianceVolume after, const IrradianceVolume before, uint32_t n_pixels, float4* __restrict__ nerf,
+                                          float4* __restrict__ record, float min_irradiance, float max_gain) {
+	const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= n_pixels) return;
+	const float4 r0 = record[3 * (size_t)idx];
+	if (r0.w != 2.0f) return;
+	const float4 r1 = record[3 * (size_t)idx + 1];
+	float g[3], Wa, Wb;
+	const float state = irradiance_volume_ratio(after, before, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), min_irradiance, max_gain, g, Wa, Wb);
+	float4 n = nerf[idx];
+	n.x *= g[0]; n.y *= g[1]; n.z *= g[2];
+	nerf[idx] = n;
+	record[3 * (size_t)idx] = make_float4(r0.x, r0.y, r0.z, state);
+	record[3 * (size_t)idx + 1] = make_float4(r1.x, r1.y, r1.z, Wa);
+	record[3 * (size_t)idx + 2] = make_float4(g[0], g[1], g[2], Wb);
+}
+// the closing composite of such a frame while ngp_set_mesh_shadow_on_nerf is off: nerf_mesh_shadow_kernel's expression with f = 1, no
+// traversal and no record
+__global__ void nerf_composite_kernel(const CameraParams C, float4* __restrict__ frame_buffer, const float4* __restrict__ nerf, uint32_t shard_index, uint32_t shard_count,
+                                      int packed, uint32_t n_pixels) {
+	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
+	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
+	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
+	if (tile % shard_count != shard_index) return;
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	if (C.moving || idx >= n_pixels) return;
+	const float4 n = nerf[idx];
+	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here: the pixel stays the mesh pass's
+	frame_buffer[idx] = nerf_over_mesh(frame_buffer[idx], n, 1.0f);
+}
+
+void launch_irradiance_volume_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n, const float* positions, const float* normals, float min_irradiance,
+                                    float max_gain, float4* out, hipStream_t stream) {
+	if (n) hipLaunchKernelGGL(irradiance_volume_ratio_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, after, before, n, positions, normals, min_irradiance, max_gain, out);
+}
+void launch_nerf_ambient_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n_pixels, float4* nerf, float4* record, float min_irradiance,
+                               float max_gain, hipStream_t stream) {
+	if (n_pixels) hipLaunchKernelGGL(nerf_ambient_ratio_kernel, dim3((n_pixels + 127) / 128), dim3(128), 0, stream, after, before, n_pixels, nerf, record, min_irradiance, max_gain);
+}
+void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels,
+                           hipStream_t stream) {
+	dim3 threads(16, 8, 1);
+	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
+	hipLaunchKernelGGL(nerf_composite_kernel, blocks, threads, 0, stream, C, frame_buffer, nerf, shard_index, shard_count, packed, n_pixels);
 }
 
 } // namespace ngp

@@ -1003,6 +1003,64 @@ __global__ __launch_bounds__(BLOCK) void density_gradient_kernel(const ModelPara
 	}
 }
 
+// ngp_set_ambient_change_on_nerf (contract in include/ngp_hip.h, "ambient"): the NeRF's normal at the surface point of every pixel that
+// owns one. A wave covers one 8 x 8 tile of the camera (tile -> shard and the packed layout as in the mesh kernels; lane = the pixel's slot
+// (x & 7) + 8 (y & 7)). `nerf` is the frame's NeRF launch composited over zeros; a pixel of alpha > 0.2 owns p = nerf_surface_point at
+// depth_buffer[idx], the p of nerf_mesh_shadow_kernel. The wave then runs density_gradient_kernel's 16-sample passes at mc_warp(M, p) --
+// pass q serves the pixels of lanes 16 q .. 16 q + 15 and is skipped when none of them is an owner -- and forms N by the marching-cubes
+// export's rule (density_normal). record, 3 float4 a pixel: (p, 2 / 1 where the gradient gives no normal), (N, 0), (1, 1, 1, 0); left as
+// the host cleared it where the pixel owns no point. Grid-encoded models only (the host refuses the wide ones).
+__global__ __launch_bounds__(BLOCK) void nerf_surface_normals_kernel(const ModelParams M, const CameraParams C, const float* __restrict__ depth_buffer,
+                                                                     const float4* __restrict__ nerf, float4* __restrict__ record, uint32_t shard_index,
+                                                                     uint32_t shard_count, int packed, uint32_t n_pixels, uint32_t n_tiles) {
+	if (C.moving) return; // (the host refuses a moving camera with meshes; said first, the static camera's ray set-up is all that is compiled in)
+	__shared__ uint4 s_w[FRAG_R0 * 64];
+	__shared__ LevelInfo s_lv[N_LEVELS];
+	for (int i = threadIdx.x; i < FRAG_R0 * 64; i += BLOCK) s_w[i] = M.wfrags[i];
+	if (threadIdx.x < N_LEVELS) s_lv[threadIdx.x] = M.levels[threadIdx.x];
+	__syncthreads();
+	const int lane = threadIdx.x & 63, c = lane & 15, hq = lane >> 4;
+	const uint32_t tiles_x = ((uint32_t)C.width + 7u) >> 3;
+	const uint32_t tile = (blockIdx.x * BLOCK + threadIdx.x) >> 6; // (wave-uniform)
+	const uint32_t x = (tile % tiles_x) * 8u + ((uint32_t)lane & 7u), y = (tile / tiles_x) * 8u + ((uint32_t)lane >> 3);
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (uint32_t)lane : x + (uint32_t)C.width * y;
+	const bool mine = tile < n_tiles && tile % shard_count == shard_index && x < (uint32_t)C.width && y < (uint32_t)C.height && idx < n_pixels;
+	const bool owner = mine && nerf[idx].w > 0.2f;
+	const unsigned long long owners = __ballot(owner);
+	if (owners == 0ull) return;
+	f3 p = mk3(0.f, 0.f, 0.f), w = mk3(0.5f, 0.5f, 0.5f); // (a lane without a point rides along at the cube's centre)
+	if (owner) {
+		p = nerf_surface_point(M, C, x, y, depth_buffer[idx]);
+		w = mc_warp(M, p);
+	}
+	const GridRsrc t_grid = make_grid_rsrc(M.grid, M.grid_bytes), t_xgrid = make_grid_rsrc(M.xgrid, M.xgrid_bytes);
+	float g[3] = {0.f, 0.f, 0.f};
+	for (int q = 0; q < 4; ++q) {
+		if (((owners >> (16 * q)) & 0xffffull) == 0ull) continue; // (wave-uniform)
+		const int src = 16 * q + c;
+		const float sx = __shfl(w.x, src, 64), sy = __shfl(w.y, src, 64), sz = __shfl(w.z, src, 64);
+		EncodeInFlight e;
+		encode_issue(t_grid, t_xgrid, s_lv, hq, sx, sy, sz, e);
+		const half8 enc = encode_finish(e);
+		DensityGrad dg = density_gradient_pass(s_w, M.wfrags, lane, e, enc, s_lv[hq].scale, s_lv[hq + 4].scale, M.density_linear != 0);
+#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			dg.g[k] += __shfl_xor(dg.g[k], 16, 64);
+			dg.g[k] += __shfl_xor(dg.g[k], 32, 64);
+		}
+		if (hq == q) { // (every quarter holds the sum: the lane whose own pixel this pass served keeps it)
+#pragma unroll
+			for (int k = 0; k < 3; ++k) g[k] = dg.g[k] * (1.0f / 128.0f);
+		}
+	}
+	if (!owner) return;
+	float N[3];
+	const bool ok = density_normal(M, g, N);
+	record[3 * (size_t)idx] = make_float4(p.x, p.y, p.z, ok ? 2.0f : 1.0f);
+	record[3 * (size_t)idx + 1] = make_float4(N[0], N[1], N[2], 0.0f);
+	record[3 * (size_t)idx + 2] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Density-grid refresh: generate_grid_samples_nerf_nonuniform + NerfNetwork::density +
 // splat_grid_samples_nerf_max_nearest_neighbor in one kernel (src/testbed_nerf.cu:185-232, 2812-2852). A wave owns
@@ -1410,6 +1468,13 @@ void launch_build_normals_fragments(uint4* wfrags, hipStream_t stream) {
 void launch_density_gradient(const ModelParams& M, uint32_t n, const float* pos01, float* out, hipStream_t stream) {
 	if (n == 0) return;
 	hipLaunchKernelGGL(density_gradient_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, M, n, pos01, out);
+}
+void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const float* depth_buffer, const float4* nerf, float4* record, uint32_t shard_index,
+                                 uint32_t shard_count, int packed, uint32_t n_pixels, hipStream_t stream) {
+	const uint32_t n_tiles = (((uint32_t)C.width + 7u) >> 3) * (((uint32_t)C.height + 7u) >> 3); // one wave a tile, BLOCK / 64 tiles a block
+	if (n_tiles == 0) return;
+	hipLaunchKernelGGL(nerf_surface_normals_kernel, dim3((n_tiles + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, M, C, depth_buffer, nerf, record, shard_index, shard_count,
+	                   packed, n_pixels, n_tiles);
 }
 void launch_density_grid_update(const ModelParams& M, uint32_t n_samples, const Pcg32& rng, uint32_t step, uint32_t n_cascades, float thresh, const float* grid,
                                 float* grid_tmp, hipStream_t stream) {

@@ -152,6 +152,16 @@ void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
+// ngp_set_ambient_change_on_nerf: the NeRF's normal at every owner pixel's surface point (record: 3 float4 a pixel), then g = E_after / E_before
+// there, n.rgb scaled in place; launch_nerf_composite closes the frame when the meshes' shadow on the NeRF is off (f = 1, no traversal)
+void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const float* depth_buffer, const float4* nerf, float4* record, uint32_t shard_index,
+                                 uint32_t shard_count, int packed, uint32_t n_pixels, hipStream_t stream);
+void launch_nerf_ambient_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n_pixels, float4* nerf, float4* record, float min_irradiance,
+                               float max_gain, hipStream_t stream);
+void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels,
+                           hipStream_t stream);
+void launch_irradiance_volume_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n, const float* positions, const float* normals, float min_irradiance,
+                                    float max_gain, float4* out, hipStream_t stream);
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
 void launch_probe_reduce(const ProbeParams& P, float4* envmap, hipStream_t stream);
 void launch_irradiance(const ProbeParams& P, const float4* envmap, uint32_t n, const float* normals, float4* out, hipStream_t stream);
@@ -356,6 +366,10 @@ struct ngp_ctx {
 	// ---- its probes' distance maps (ngp_compute_irradiance_volume_visibility / ngp_set_irradiance_volume_visibility): data like the volume, dropped with it
 	ngp::DevArray<float2> d_sh_visibility; // 64 float2 a probe, probe-major; empty: no visibility (a peer holds a replica like the volume's)
 	ngp_irradiance_visibility_desc sh_visibility_desc{}; // max_distance holds D
+	// ---- the reference SH9 volume, the scene before the meshes (ngp_compute_reference_irradiance_volume / ngp_set_reference_irradiance_volume):
+	// data like d_sh_volume, without visibility maps (a peer holds a replica for ambient-change frames: sync_peer_geometry)
+	ngp::DevArray<float4> d_sh_reference;
+	ngp_irradiance_volume_desc sh_reference_desc{};
 
 	// ---- environment map behind the NeRF (m_envmap.inference_view(), testbed.h:1297-1316)
 	ngp::DevArray<float4> d_bg_envmap;
@@ -407,6 +421,14 @@ struct ngp_ctx {
 	ngp::Event ev_ms0[HISTORY], ev_ms1[HISTORY]; // around nerf_mesh_shadow_kernel of a frame's last sample (ngp_get_frame_mesh_shadow_ms)
 	bool hist_mesh_shadow[HISTORY] = {};         // the slot's call was a frame that ran the pass
 	size_t ms_n_pixels = 0;                      // pixels of the last such frame
+	// ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf); a peer's copy follows the primary's with the geometry
+	bool ambient_change_on_nerf = false;
+	ngp_ambient_change_desc ambient_change_desc{};
+	// its per-pixel record, allocated when a frame first uses the option and grown like the frame buffers (the scratch is d_ms_nerf)
+	ngp::DevArray<float4> d_ac_record; // 3 float4 a pixel: (p, state), (N, W_after), (g, W_before) of the last sample (ngp_get_frame_ambient_change)
+	ngp::Event ev_ac0[HISTORY], ev_ac1[HISTORY]; // around the normals and ratio kernels of a frame's last sample (ngp_get_frame_ambient_change_ms)
+	bool hist_ambient_change[HISTORY] = {};      // the slot's call was a frame that ran the pass
+	size_t ac_n_pixels = 0;                      // pixels of the last such frame
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a
@@ -433,6 +455,7 @@ struct ngp_ctx {
 	uint64_t mesh_generation = 0, synced_mesh_generation = 0;           // the mesh list / BVHs changed (Geometry mode)
 	uint64_t probe_generation = 0, synced_probe_generation = 0;         // the irradiance probe textures were (re)computed
 	uint64_t sh_volume_generation = 0, synced_sh_volume_generation = 0; // the SH9 irradiance volume or its visibility was computed, set or cleared
+	uint64_t sh_reference_generation = 0, synced_sh_reference_generation = 0; // the reference SH9 volume was computed, set or cleared
 	ngp::DevArray<float4> d_pack_rgba;   // this device's tiles of the current frame, tile-packed
 	ngp::DevArray<float> d_pack_depth;   // (allocated last: its size is that of both)
 	ngp::DevArray<float4> d_gather_rgba; // primary: [device][slots * 64]
@@ -594,6 +617,12 @@ inline IrradianceVolume irradiance_volume_from(const ngp_irradiance_volume_desc&
 	return V;
 }
 inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) { return irradiance_volume_from(ctx->sh_volume_desc, ctx->d_sh_volume.get()); }
+// the refusals of an ngp_ambient_change_desc (ngp_set_ambient_change_on_nerf, ngp_irradiance_volume_ratio)
+inline void check_ambient_change_desc(const ngp_ambient_change_desc& d) {
+	if (!std::isfinite(d.min_irradiance) || d.min_irradiance < 0.0f) throw std::runtime_error("invalid ambient change descriptor: min_irradiance must be finite and >= 0");
+	if (!std::isfinite(d.max_gain) || d.max_gain < 1.0f) throw std::runtime_error("invalid ambient change descriptor: max_gain must be finite and >= 1");
+}
+inline IrradianceVolume sh_reference_of(const ngp_ctx* ctx) { return irradiance_volume_from(ctx->sh_reference_desc, ctx->d_sh_reference.get()); }
 inline IrradianceVolumeVisible sh_volume_visible_of(const ngp_ctx* ctx) {
 	IrradianceVolumeVisible A{};
 	A.V = sh_volume_of(ctx);

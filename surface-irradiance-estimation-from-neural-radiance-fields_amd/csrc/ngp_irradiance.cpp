@@ -285,6 +285,10 @@ SunLight check_sunlit(const ngp_irradiance_bounce_desc* bounce, const ngp_irradi
 void require_volume(const ngp_ctx* ctx) {
 	if (!ctx->d_sh_volume) throw std::runtime_error("no irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
 }
+void require_reference(const ngp_ctx* ctx) {
+	if (!ctx->d_sh_reference)
+		throw std::runtime_error("no reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
+}
 void require_visibility(const ngp_ctx* ctx) {
 	if (!ctx->d_sh_visibility)
 		throw std::runtime_error("no irradiance visibility: call ngp_compute_irradiance_volume_visibility or ngp_set_irradiance_volume_visibility first");
@@ -425,6 +429,17 @@ void drop_volume(ngp_ctx* ctx) {
 	ctx->sh_volume_desc = ngp_irradiance_volume_desc{};
 	drop_visibility(ctx);
 }
+// the reference volume (the scene before the meshes): records for the lattice of d; it has no maps
+void commit_reference(ngp_ctx* ctx, DevArray<float4>& sh, const ngp_irradiance_volume_desc& d) {
+	ctx->d_sh_reference = std::move(sh);
+	ctx->sh_reference_desc = d;
+	++ctx->sh_reference_generation;
+}
+void drop_reference(ngp_ctx* ctx) {
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	ctx->d_sh_reference.reset();
+	ctx->sh_reference_desc = ngp_irradiance_volume_desc{};
+}
 // D of a volume whose descriptor asks for the default: 1.5 x the diagonal of one lattice cell, an axis of one probe counting with extent
 // 0; 1.5 x the box diagonal when every axis has one probe
 float default_max_distance(const ngp_irradiance_volume_desc& v) {
@@ -535,9 +550,10 @@ void sun_pass_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const n
 
 // the volume of desc: V_0 traced through the NeRF, then the sun's first bounce off the meshes S = V_0 + R_sun (`sun` nullable: none, S =
 // V_0; `nerf` nullable: the NeRF's density does not shadow the sun), then `bounce` (nullable: none) passes V_b = S + R(V_{b-1}) looked up through the distance maps of `visibility` (nullable: none,
-// and none kept). The context's volume is replaced once every launch has succeeded.
+// and none kept). The context's volume is replaced once every launch has succeeded; `reference`: the context's reference volume instead
+// (ngp_compute_reference_irradiance_volume: V_0 alone, its caller passes no pass and a descriptor that does not occlude), the volume untouched.
 void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const ngp_irradiance_bounce_desc* bounce, const ngp_irradiance_visibility_desc* visibility,
-                    const SunLight* sun = nullptr, const ngp_irradiance_sun_nerf_desc* nerf = nullptr) {
+                    const SunLight* sun = nullptr, const ngp_irradiance_sun_nerf_desc* nerf = nullptr, bool reference = false) {
 	require_probe_model(ctx, "SH irradiance probes");
 	const uint64_t probes = check_volume_lattice(desc);
 	const uint32_t K = check_sh_desc(probes, &desc->sh);
@@ -569,8 +585,21 @@ void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const 
 		bounce_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, al, A.V, visibility ? &A : nullptr, alpha.get(), nullptr, nullptr, v0.get(), next);
 		prev = next;
 	}
+	if (reference) return commit_reference(ctx, v0, *desc);
 	commit_volume(ctx, n_bounces == 0 ? v0 : n_bounces % 2u ? odd : even, *desc); // (the previous volume stays in place when a launch throws)
 	if (visibility) commit_visibility(ctx, maps, *visibility, D);
+}
+
+// a caller's records for the lattice of desc, checked and on the device (ngp_set_irradiance_volume, ngp_set_reference_irradiance_volume)
+DevArray<float4> upload_volume_records(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh) {
+	const uint64_t probes = check_volume_lattice(desc);
+	if (!sh) throw std::runtime_error("null argument");
+	for (size_t i = 0; i < 4 * SH_FLOAT4 * (size_t)probes; ++i)
+		if (!std::isfinite(sh[i])) throw std::runtime_error("irradiance volume: value " + std::to_string(i % 28) + " of probe " + std::to_string(i / 28) + " is not finite");
+	DevArray<float4> d;
+	d.upload(reinterpret_cast<const float4*>(sh), SH_FLOAT4 * (size_t)probes);
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old records)
+	return d;
 }
 
 } // namespace
@@ -897,13 +926,7 @@ int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms) {
 int ngp_set_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh) {
 	return guarded(ctx, [&] {
 		require_device(ctx);
-		const uint64_t probes = check_volume_lattice(desc);
-		if (!sh) throw std::runtime_error("null argument");
-		for (size_t i = 0; i < 4 * SH_FLOAT4 * (size_t)probes; ++i)
-			if (!std::isfinite(sh[i])) throw std::runtime_error("irradiance volume: value " + std::to_string(i % 28) + " of probe " + std::to_string(i / 28) + " is not finite");
-		DevArray<float4> d;
-		d.upload(reinterpret_cast<const float4*>(sh), SH_FLOAT4 * (size_t)probes);
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a lookup still in flight reads the old records)
+		DevArray<float4> d = upload_volume_records(ctx, desc, sh);
 		commit_volume(ctx, d, *desc);
 	});
 }
@@ -927,6 +950,62 @@ int ngp_clear_irradiance_volume(ngp_ctx* ctx) {
 			drop_volume(p);
 			p->synced_sh_volume_generation = ctx->sh_volume_generation;
 		}
+	});
+}
+
+int ngp_compute_reference_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc) {
+	return guarded(ctx, [&] {
+		if (!desc) throw std::runtime_error("null argument");
+		ngp_irradiance_volume_desc d = *desc;
+		d.sh.occlude_by_meshes = 0; // the scene before anything was inserted, whatever the caller's descriptor says
+		compute_volume(ctx, &d, nullptr, nullptr, nullptr, nullptr, true);
+	});
+}
+
+int ngp_set_reference_irradiance_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const float* sh) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		DevArray<float4> d = upload_volume_records(ctx, desc, sh);
+		commit_reference(ctx, d, *desc);
+	});
+}
+
+int ngp_get_reference_irradiance_volume(ngp_ctx* ctx, ngp_irradiance_volume_desc* desc_out, float* sh_out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_reference(ctx);
+		if (desc_out) *desc_out = ctx->sh_reference_desc;
+		if (sh_out) download(ctx, sh_out, ctx->d_sh_reference.get(), ctx->d_sh_reference.size() * sizeof(float4));
+	});
+}
+
+int ngp_clear_reference_irradiance_volume(ngp_ctx* ctx) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		drop_reference(ctx);
+		++ctx->sh_reference_generation;
+		for (ngp_ctx* p : ctx->peers) { // the replicas go too
+			DeviceGuard g(p->device);
+			drop_reference(p);
+			p->synced_sh_reference_generation = ctx->sh_reference_generation;
+		}
+	});
+}
+
+int ngp_irradiance_volume_ratio(ngp_ctx* ctx, uint32_t n, const float* positions, const float* normals, const ngp_ambient_change_desc* desc, float* out) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		require_volume(ctx);
+		require_reference(ctx);
+		if (!desc) throw std::runtime_error("null argument");
+		check_ambient_change_desc(*desc);
+		if (n == 0) return;
+		if (!positions || !normals || !out) throw std::runtime_error("null argument");
+		check_positions(n, positions);
+		check_normals(n, normals);
+		lookup_rgbw(ctx, n, positions, normals, out, [&](const float* d_p, const float* d_n, float4* d_o) {
+			launch_irradiance_volume_ratio(sh_volume_of(ctx), sh_reference_of(ctx), n, d_p, d_n, desc->min_irradiance, desc->max_gain, d_o, ctx->stream);
+		});
 	});
 }
 

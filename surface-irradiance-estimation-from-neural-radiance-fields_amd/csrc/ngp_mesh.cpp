@@ -258,6 +258,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->sun_nerf_shadow_desc = primary->sun_nerf_shadow_desc;
 	peer->mesh_shadow_on_nerf = primary->mesh_shadow_on_nerf; // each device shadows its own share
 	peer->mesh_shadow_on_nerf_desc = primary->mesh_shadow_on_nerf_desc;
+	peer->ambient_change_on_nerf = primary->ambient_change_on_nerf; // each device scales its own share
+	peer->ambient_change_desc = primary->ambient_change_desc;
 	if (peer->synced_mesh_generation != primary->mesh_generation) {
 		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)
@@ -316,6 +318,22 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 		peer->sh_visibility_desc = primary->sh_visibility_desc;
 		peer->sh_volume_desc = primary->sh_volume_desc;
 		peer->synced_sh_volume_generation = primary->sh_volume_generation;
+	}
+	if (peer->synced_sh_reference_generation != primary->sh_reference_generation) { // the reference volume, as the volume above (it has no maps)
+		const size_t n = primary->d_sh_reference.size();
+		{
+			DeviceGuard g(peer->device);
+			NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // frames on the peer still read the old records
+			peer->d_sh_reference.reset();
+			if (n) peer->d_sh_reference.reset(n);
+		}
+		if (n) {
+			NGP_HIP_CHECK(hipStreamSynchronize(primary->stream));
+			DeviceGuard g(peer->device);
+			NGP_HIP_CHECK(hipMemcpyPeer(peer->d_sh_reference.get(), peer->device, primary->d_sh_reference.get(), primary->device, n * sizeof(float4)));
+		}
+		peer->sh_reference_desc = primary->sh_reference_desc;
+		peer->synced_sh_reference_generation = primary->sh_reference_generation;
 	}
 }
 } // namespace ngp

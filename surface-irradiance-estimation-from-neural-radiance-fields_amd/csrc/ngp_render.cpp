@@ -268,6 +268,21 @@ void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ctx->d_ms_record.reset(n_pixels);
 }
 
+// the per-pixel record of a frame whose NeRF pixels follow the meshes' change of the ambient light (ngp_set_ambient_change_on_nerf): allocated
+// by the first frame that uses the option, grown as ensure_frame_buffers grows. The scratch is ensure_mesh_shadow_buffers' d_ms_nerf.
+void ensure_ambient_change_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	ensure_mesh_shadow_buffers(ctx, n_pixels);
+	if (!ctx->ev_ac0[0]) {
+		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
+			ctx->ev_ac0[i] = new_event();
+			ctx->ev_ac1[i] = new_event();
+		}
+	}
+	if (3 * n_pixels <= ctx->d_ac_record.size()) return;
+	ctx->d_ac_record.reset();
+	ctx->d_ac_record.reset(3 * n_pixels);
+}
+
 // Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
 void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts, float4* d_rgba_out, float* d_depth_out, hipStream_t stream) {
 	require_device(ctx, "rendering needs an MI355X");
@@ -290,6 +305,17 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
 	const bool mesh_shadow = ctx->mesh_shadow_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
 	if (mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
+	// what the meshes change in the ambient light on the NeRF: the same frames. Behind the NeRF launch into the scratch, one kernel forms the
+	// NeRF's normal at every owner pixel's surface point and one scales the pixel by E_after / E_before there, ahead of the closing composite.
+	const bool ambient_change = ctx->ambient_change_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
+	if (ambient_change) {
+		if (!ctx->d_sh_volume) throw std::runtime_error("ambient_change_on_nerf frames need the irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+		if (!ctx->d_sh_reference)
+			throw std::runtime_error("ambient_change_on_nerf frames need the reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
+		if (ctx->M.wide.width) throw std::runtime_error("ambient_change_on_nerf frames need a grid-encoded model (ngp_set_ambient_change_on_nerf)");
+		ensure_ambient_change_buffers(ctx, n_pixels ? n_pixels : 1);
+	}
+	const bool scratch = mesh_shadow || ambient_change; // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
 	const int spp = opts.spp > 0 ? opts.spp : 1;
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
@@ -365,15 +391,24 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 			}
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
 		}
-		if (mesh_shadow) { // the NeRF launch composites over zeros, apart from the mesh pass's pixels; its depth test and depth writes are every frame's
+		if (scratch) { // the NeRF launch composites over zeros, apart from the mesh pass's pixels; its depth test and depth writes are every frame's
 			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_nerf.get(), 0, n_pixels * sizeof(float4), stream));
-			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_record.get(), 0, n_pixels * sizeof(float4), stream));
+			if (mesh_shadow) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_record.get(), 0, n_pixels * sizeof(float4), stream));
+			if (ambient_change) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ac_record.get(), 0, 3 * n_pixels * sizeof(float4), stream));
 			F.frame_buffer = ctx->d_ms_nerf.get();
 		}
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
 		if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
 		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
 		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
+		if (ambient_change) { // the scratch's colour follows the ambient light: normals at the owners' surface points, then g = E_after / E_before
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ac0[slot], stream)); // (ngp_get_frame_ambient_change_ms)
+			launch_nerf_surface_normals(M, C, F.depth_buffer, ctx->d_ms_nerf.get(), ctx->d_ac_record.get(), F.shard_index, F.shard_count, F.packed, (uint32_t)n_pixels, stream);
+			launch_nerf_ambient_ratio(sh_volume_of(ctx), sh_reference_of(ctx), (uint32_t)n_pixels, ctx->d_ms_nerf.get(), ctx->d_ac_record.get(), ctx->ambient_change_desc.min_irradiance,
+			                          ctx->ambient_change_desc.max_gain, stream);
+			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ac1[slot], stream));
+			if (!mesh_shadow) launch_nerf_composite(C, ctx->d_frame.get(), ctx->d_ms_nerf.get(), F.shard_index, F.shard_count, F.packed, (uint32_t)n_pixels, stream); // f = 1, no traversal
+		}
 		if (mesh_shadow) { // ... and the composite over the mesh pass's pixels follows, scaled where a mesh stands in front of the sun
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ms0[slot], stream)); // (ngp_get_frame_mesh_shadow_ms)
 			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), ctx->d_ms_record.get(), F.shard_index, F.shard_count,
@@ -391,6 +426,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	if (sun_shadow) ctx->ss_n_pixels = n_pixels;
 	ctx->hist_mesh_shadow[slot] = mesh_shadow;
 	if (mesh_shadow) ctx->ms_n_pixels = n_pixels;
+	ctx->hist_ambient_change[slot] = ambient_change;
+	if (ambient_change) ctx->ac_n_pixels = n_pixels;
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -620,6 +657,47 @@ int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) {
 		if (!ctx->hist_mesh_shadow[slot]) return;
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ms0[slot], ctx->ev_ms1[slot]));
+	});
+}
+
+int ngp_set_ambient_change_on_nerf(ngp_ctx* ctx, const ngp_ambient_change_desc* desc) {
+	return guarded(ctx, [&] {
+		if (desc) check_ambient_change_desc(*desc);
+		ctx->ambient_change_on_nerf = desc != nullptr;
+		ctx->ambient_change_desc = desc ? *desc : ngp_ambient_change_desc{};
+	});
+}
+
+int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = ctx->ambient_change_desc;
+		*enabled = ctx->ambient_change_on_nerf ? 1 : 0;
+	});
+}
+
+int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls || !ctx->hist_ambient_change[(ctx->n_calls - 1) % ngp_ctx::HISTORY])
+			throw std::runtime_error("the last frame ran no ambient change pass (ngp_set_ambient_change_on_nerf)");
+		if (n_pixels != ctx->ac_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ac_n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ac_record.get(), 3 * n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = 0.f;
+		if (!ctx->n_calls) return;
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		if (!ctx->hist_ambient_change[slot]) return;
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ac0[slot], ctx->ev_ac1[slot]));
 	});
 }
 

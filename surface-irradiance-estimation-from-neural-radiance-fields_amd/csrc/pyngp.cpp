@@ -265,6 +265,28 @@ PYBIND11_MODULE(pyngp, m) {
 		               "Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (default False)")
 		.def_readwrite("mesh_shadow_on_nerf_strength", &Testbed::m_mesh_shadow_on_nerf_strength, "with mesh_shadow_on_nerf: the share of a shadowed NeRF pixel's colour the shadow takes away (0.5)")
 		.def_readwrite("mesh_shadow_on_nerf_bias", &Testbed::m_mesh_shadow_on_nerf_bias, "with mesh_shadow_on_nerf: how far the shadow ray's origin is lifted off the NeRF's surface point towards the sun (1e-2)")
+		.def_readwrite("ambient_change_on_nerf", &Testbed::m_ambient_change_on_nerf,
+		               "Geometry frames with meshes and a model: every NeRF pixel that owns a surface point is scaled by E_after / E_before there, the irradiance volume "
+		               "over the reference volume; a missing volume is computed before the frame (default False)")
+		.def_readwrite("ambient_change_on_nerf_min_irradiance", &Testbed::m_ambient_change_on_nerf_min_irradiance, "with ambient_change_on_nerf: a channel whose reference irradiance is not above this keeps its colour (1e-3)")
+		.def_readwrite("ambient_change_on_nerf_max_gain", &Testbed::m_ambient_change_on_nerf_max_gain, "with ambient_change_on_nerf: the cap on the ratio (4)")
+		.def("compute_reference_irradiance_volume", [](Testbed& t, const std::array<uint32_t, 3>& res, py::object aabb, uint32_t n_u, uint32_t n_v) {
+			const std::vector<float> box = aabb6_arg(aabb);
+			std::vector<float> sh;
+			std::array<float, 6> used{};
+			{
+				py::gil_scoped_release nogil;
+				sh = t.compute_reference_irradiance_volume(res, box.empty() ? nullptr : box.data(), n_u, n_v, used.data());
+			}
+			py::array_t<float> a({(py::ssize_t)res[2], (py::ssize_t)res[1], (py::ssize_t)res[0], (py::ssize_t)28});
+			if (!sh.empty()) memcpy(a.mutable_data(), sh.data(), sh.size() * sizeof(float));
+			py::dict d;
+			d["sh"] = a;
+			d["aabb"] = py::make_tuple(std::array<float, 3>{used[0], used[1], used[2]}, std::array<float, 3>{used[3], used[4], used[5]});
+			return d;
+		}, py::arg("resolution"), py::arg("aabb") = py::none(), py::arg("n_u") = 32, py::arg("n_v") = 32,
+		   "This project's own: the reference volume of ambient_change_on_nerf, the scene before the meshes: the lattice of compute_irradiance_volume traced with the meshes "
+		   "occluding nothing, kept beside the irradiance volume: {'sh': (rz, ry, rx, 28), 'aabb': (min, max)}")
 		.def_readwrite("irradiance_volume_sun_nerf_shadow", &Testbed::m_irradiance_volume_sun_nerf_shadow,
 		               "with irradiance_volume_sun: the NeRF's density shadows that sun in the default volume (render_min_transmittance, t_min 0)")
 		.def_readwrite("irradiance_volume_sun_radiance", &Testbed::m_irradiance_volume_sun_radiance, "what a surface facing the sun receives in a sunlit volume; default: the frames' sun colour")

@@ -93,6 +93,30 @@ NGP_DEV bool shade_ray(const FrameParams& F, const ProbeParams& P, f3 bg_linear,
 	return true;
 }
 
+// ---- a NeRF pixel's surface point and normal (the passes behind the NeRF launch of a hybrid frame: nerf_mesh_shadow_kernel,
+// nerf_surface_normals_kernel; the marching-cubes export). One definition each.
+// the point at z-depth `depth` on the ray init_ray forms for pixel (x, y): a pixel of alpha > 0.2 owns the depth buffer's value (shade_ray)
+NGP_DEV f3 nerf_surface_point(const ModelParams& M, const CameraParams& C, uint32_t x, uint32_t y, float depth) {
+	const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
+	const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
+	RayState ray;
+	init_ray<false>(M, C, x, y, ray);
+	const float t = (depth - dot3(cam_fwd, sub3(ray.o, cam_pos))) / dot3(cam_fwd, ray.d);
+	return add3(ray.o, scale3(ray.d, t));
+}
+NGP_DEV f3 mc_warp(const ModelParams& M, f3 p) { // warp_position (nerf_device.cuh), as density_grid_samples_kernel forms it
+	return div3(sub3(p, mk3(M.aabb_min[0], M.aabb_min[1], M.aabb_min[2])), mk3(M.aabb_diag[0], M.aabb_diag[1], M.aabb_diag[2]));
+}
+// the surface normal from d logit / d warped position: d logit / d ngp position = that / aabb_diag, the density is increasing in its logit,
+// so N = -(grad / diag) / |grad / diag|; false (N = 0) where the length is zero or not finite
+NGP_DEV bool density_normal(const ModelParams& M, const float* __restrict__ grad, float* __restrict__ N) {
+	const float gx = grad[0] / M.aabb_diag[0], gy = grad[1] / M.aabb_diag[1], gz = grad[2] / M.aabb_diag[2];
+	const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+	const bool ok = len > 0.0f && isfinite(len);
+	N[0] = ok ? -gx / len : 0.0f; N[1] = ok ? -gy / len : 0.0f; N[2] = ok ? -gz / len : 0.0f;
+	return ok;
+}
+
 // K10 / K11 / K12: init_rays_from_{center, center_outward, multiple_center}_with_payload_kernel_nerf
 // (src/testbed_nerf.cu:1559-1773) for probe ray q (= the reference's payload index `mulidx`)
 NGP_DEV float halton(uint32_t base, uint32_t idx) { // random_val.cuh:338-350

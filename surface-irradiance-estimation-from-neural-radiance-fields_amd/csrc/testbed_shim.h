@@ -431,12 +431,24 @@ public:
 			if (m_render_mode == ERenderMode::ShadeGridEnvMap && !m_envmap_grid_ready) computeEnvmapGrid();
 			if (m_render_mode == ERenderMode::ShadeEnvMap && !m_envmap_ready) computeEnvmapMultipleMain();
 			// ShadeIrradianceVolume: a context without a volume gets the default one; a volume the caller set or computed is never replaced
-			if (m_render_mode == ERenderMode::ShadeIrradianceVolume && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0) {
+			// ambient_change_on_nerf needs that volume too, in every shade mode, and the reference volume beside it: whichever the context lacks is
+			// computed here (the C ABI refuses instead), the reference over the lattice and with the ray counts of the volume the context then holds
+			bool ambient_missing = false;
+			if (m_ambient_change_on_nerf && shade_family && (ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0 || ngp_get_reference_irradiance_volume(m_ctx, nullptr, nullptr) != 0)) {
+				ngp_model_desc md{};
+				ambient_missing = ngp_get_model(m_ctx, &md) == 0; // (without a model the frame ignores the option: nothing to compute)
+			}
+			if ((m_render_mode == ERenderMode::ShadeIrradianceVolume || ambient_missing) && ngp_get_irradiance_volume(m_ctx, nullptr, nullptr) != 0) {
 				// (bounces: the visibility is computed inside that call, ahead of the passes that look the volume up through it)
 				const bool vis_in_bounces = m_irradiance_volume_visibility && m_irradiance_volume_bounces > 0;
 				compute_irradiance_volume({m_irradiance_volume_res, m_irradiance_volume_res, m_irradiance_volume_res}, nullptr, 32, 32, true, nullptr, m_irradiance_volume_bounces, nullptr,
 				                          vis_in_bounces, m_irradiance_volume_sun, m_irradiance_volume_sun && m_irradiance_volume_sun_nerf_shadow);
 				if (m_irradiance_volume_visibility && !vis_in_bounces) compute_irradiance_volume_visibility(); // (the default volume alone: a caller's volume keeps what the caller gave it)
+			}
+			if (ambient_missing && ngp_get_reference_irradiance_volume(m_ctx, nullptr, nullptr) != 0) {
+				ngp_irradiance_volume_desc d{};
+				check(ngp_get_irradiance_volume(m_ctx, &d, nullptr));
+				check(ngp_compute_reference_irradiance_volume(m_ctx, &d));
 			}
 		}
 		ngp_camera cam{};
@@ -499,6 +511,10 @@ public:
 		{ // the meshes in front of the sun on the NeRF (off: NULL)
 			const ngp_mesh_shadow_on_nerf_desc ms{m_mesh_shadow_on_nerf_strength, m_mesh_shadow_on_nerf_bias};
 			check(ngp_set_mesh_shadow_on_nerf(m_ctx, m_mesh_shadow_on_nerf ? &ms : nullptr));
+		}
+		{ // what the meshes change in the ambient light on the NeRF (off: NULL)
+			const ngp_ambient_change_desc ac{m_ambient_change_on_nerf_min_irradiance, m_ambient_change_on_nerf_max_gain};
+			check(ngp_set_ambient_change_on_nerf(m_ctx, m_ambient_change_on_nerf ? &ac : nullptr));
 		}
 		check(ngp_render(m_ctx, &cam, &o, out, depth_out));
 	}
@@ -577,6 +593,20 @@ public:
 		if (aabb6_out) { memcpy(aabb6_out, d.aabb_min, 12); memcpy(aabb6_out + 3, d.aabb_max, 12); }
 		return out;
 	}
+	// the reference volume of ambient_change_on_nerf, the scene before the meshes: a lattice of res probes over aabb6 (nullptr: the render
+	// aabb), V_0 traced with the meshes occluding nothing and kept in the context; returns the records and the box as above
+	std::vector<float> compute_reference_irradiance_volume(const std::array<uint32_t, 3>& res, const float* aabb6 = nullptr, uint32_t n_u = 32, uint32_t n_v = 32,
+	                                                       float* aabb6_out = nullptr) {
+		ngp_irradiance_volume_desc d{};
+		const float* box = aabb6 ? aabb6 : m_render_aabb.data();
+		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
+		d.sh = ngp_irradiance_sh_desc{n_u, n_v, nerf.render_min_transmittance, 0};
+		check(ngp_compute_reference_irradiance_volume(m_ctx, &d));
+		std::vector<float> out((size_t)res[0] * res[1] * res[2] * 28);
+		check(ngp_get_reference_irradiance_volume(m_ctx, &d, out.data()));
+		if (aabb6_out) { memcpy(aabb6_out, d.aabb_min, 12); memcpy(aabb6_out + 3, d.aabb_max, 12); }
+		return out;
+	}
 	// the volume the context holds (computed here, by a ShadeIrradianceVolume render or set through the C ABI): its records, resolution and box
 	std::vector<float> get_irradiance_volume(std::array<uint32_t, 3>& res_out, float* aabb6_out) {
 		ngp_irradiance_volume_desc d{};
@@ -615,6 +645,8 @@ public:
 	float m_sun_nerf_shadow_min_transmittance = 0.01f, m_sun_nerf_shadow_t_min = 0.f; // ... traced down to this transmittance, ignoring the NeRF within t_min of the surface
 	bool m_mesh_shadow_on_nerf = false; // Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (ngp_set_mesh_shadow_on_nerf)
 	float m_mesh_shadow_on_nerf_strength = 0.5f, m_mesh_shadow_on_nerf_bias = 1e-2f; // ... taking this share of a shadowed NeRF pixel's colour away, from a point lifted this far towards the sun
+	bool m_ambient_change_on_nerf = false; // Geometry frames with meshes and a model: NeRF pixels follow what the meshes change in the ambient light, E_after / E_before (ngp_set_ambient_change_on_nerf)
+	float m_ambient_change_on_nerf_min_irradiance = 1e-3f, m_ambient_change_on_nerf_max_gain = 4.f; // ... where the reference holds more than this, by at most this factor
 	bool m_irradiance_volume_sun_nerf_shadow = false; // ... with the NeRF's density in front of that sun (render_min_transmittance, t_min 0); looked at with m_irradiance_volume_sun alone
 	std::array<float, 3> m_irradiance_volume_sun_radiance{255.f / 255.0f * 4.f, 225.f / 255.0f * 4.f, 195.f / 255.0f * 4.f}; // the frames' suncol (mesh_kernels.hip)
 	uint32_t m_irradiance_volume_bounces = 0; // passes of diffuse interreflection off the meshes in that default volume (albedo: the base colour squared)

@@ -125,6 +125,10 @@ class MeshShadowOnNerfDesc(C.Structure):
     _fields_ = [("strength", C.c_float), ("bias", C.c_float)]
 
 
+class AmbientChangeDesc(C.Structure):
+    _fields_ = [("min_irradiance", C.c_float), ("max_gain", C.c_float)]
+
+
 SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
 
 
@@ -274,6 +278,15 @@ def load_library():
     L.ngp_get_mesh_shadow_on_nerf.argtypes = [vp, C.POINTER(MeshShadowOnNerfDesc), C.POINTER(C.c_int)]
     L.ngp_get_frame_mesh_shadow.argtypes = [vp, vp, C.c_size_t]
     L.ngp_get_frame_mesh_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_compute_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc)]
+    L.ngp_get_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
+    L.ngp_set_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
+    L.ngp_clear_reference_irradiance_volume.argtypes = [vp]
+    L.ngp_set_ambient_change_on_nerf.argtypes = [vp, C.POINTER(AmbientChangeDesc)]
+    L.ngp_get_ambient_change_on_nerf.argtypes = [vp, C.POINTER(AmbientChangeDesc), C.POINTER(C.c_int)]
+    L.ngp_irradiance_volume_ratio.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(AmbientChangeDesc), vp]
+    L.ngp_get_frame_ambient_change.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_ambient_change_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -945,6 +958,82 @@ class Context:
         """device time of the mesh shadow kernel in the last frame's last sample, ms; 0 after a frame without it"""
         ms = C.c_float(0)
         self._check(self.L.ngp_get_frame_mesh_shadow_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    # ---------------------------------------------------------------- the meshes' change of the ambient light on the NeRF (include/ngp_hip.h, "ambient")
+    @staticmethod
+    def _ambient_desc(change):
+        if change is True:
+            change = {}
+        if not isinstance(change, dict) or set(change) - {"min_irradiance", "max_gain"}:
+            raise ValueError("ambient_change_on_nerf: True, False, None or a dict of min_irradiance and max_gain")
+        d = AmbientChangeDesc()
+        d.min_irradiance, d.max_gain = float(change.get("min_irradiance", 1e-3)), float(change.get("max_gain", 4.0))
+        return d
+
+    def set_ambient_change_on_nerf(self, change=True):
+        """scale every NeRF pixel that owns a surface point by E_after / E_before there (Geometry frames with meshes and a model, the four
+        shade modes; needs the irradiance volume and the reference volume): None or False switches it off (the default), True takes
+        min_irradiance 1e-3 and max_gain 4, a dict gives them"""
+        if change is None or change is False:
+            self._check(self.L.ngp_set_ambient_change_on_nerf(self.h, None))
+            return
+        d = self._ambient_desc(change)
+        self._check(self.L.ngp_set_ambient_change_on_nerf(self.h, C.byref(d)))
+
+    def ambient_change_on_nerf(self):
+        """None while the option is off, else dict(min_irradiance=, max_gain=) as set"""
+        d, on = AmbientChangeDesc(), C.c_int(0)
+        self._check(self.L.ngp_get_ambient_change_on_nerf(self.h, C.byref(d), C.byref(on)))
+        return dict(min_irradiance=d.min_irradiance, max_gain=d.max_gain) if on.value else None
+
+    def compute_reference_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, min_transmittance=0.01):
+        """trace the reference volume, the scene before the meshes: V_0 over the lattice with the meshes occluding nothing, no bounces, no
+        sun; it stays on the device (reference_irradiance_volume) and the context's own volume is untouched"""
+        d = self._volume_desc(resolution, aabb, self._sh_desc(n_u, n_v, False, min_transmittance))
+        self._check(self.L.ngp_compute_reference_irradiance_volume(self.h, C.byref(d)))
+
+    def set_reference_irradiance_volume(self, sh, aabb, n_u=0, n_v=0, min_transmittance=0.01):
+        """a caller's own reference records (rz, ry, rx, 28) over aabb = (min, max)"""
+        sh = np.ascontiguousarray(sh, np.float32)
+        if sh.ndim != 4 or sh.shape[3] != 28:
+            raise ValueError("records: (rz, ry, rx, 28)")
+        d = self._volume_desc(sh.shape[2::-1], aabb, self._sh_desc(n_u, n_v, False, min_transmittance))
+        self._check(self.L.ngp_set_reference_irradiance_volume(self.h, C.byref(d), _p(sh)))
+
+    def reference_irradiance_volume(self):
+        """(desc, records (rz, ry, rx, 28)) of the reference volume"""
+        d = IrradianceVolumeDesc()
+        self._check(self.L.ngp_get_reference_irradiance_volume(self.h, C.byref(d), None))
+        sh = np.zeros((d.res[2], d.res[1], d.res[0], 28), np.float32)
+        self._check(self.L.ngp_get_reference_irradiance_volume(self.h, C.byref(d), _p(sh)))
+        return d, sh
+
+    def clear_reference_irradiance_volume(self):
+        self._check(self.L.ngp_clear_reference_irradiance_volume(self.h))
+
+    def irradiance_volume_ratio(self, positions, normals, min_irradiance=1e-3, max_gain=4.0):
+        """(n, 4) = g rgb, state (1 no estimate, 2 scaled): E_after / E_before per channel, the context's volume over its reference volume"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != n.shape:
+            raise ValueError("positions and normals: n x 3 each")
+        d = self._ambient_desc(dict(min_irradiance=min_irradiance, max_gain=max_gain))
+        out = np.zeros((p.shape[0], 4), np.float32)
+        self._check(self.L.ngp_irradiance_volume_ratio(self.h, p.shape[0], _p(p), _p(n), C.byref(d), _p(out)))
+        return out
+
+    def frame_ambient_change(self, n_pixels):
+        """(n_pixels, 12): per pixel of the last frame's last sample, in the frame's pixel order: p (3), state (0 not an owner, 1 no estimate,
+        2 scaled), N (3), W_after, g (3), W_before. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros((int(n_pixels), 12), np.float32)
+        self._check(self.L.ngp_get_frame_ambient_change(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def frame_ambient_change_ms(self):
+        """device time of the normals and ratio kernels in the last frame's last sample, ms; 0 after a frame without them"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_frame_ambient_change_ms(self.h, C.byref(ms)))
         return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):

@@ -16,6 +16,13 @@ trace alone (ngp_get_frame_sun_shadow_ms), the frame's NeRF pass (kernel_ms) bes
 With --mesh-shadow-on-nerf: Shade-mode frames with the meshes' shadow on the NeRF off and on (ngp_set_mesh_shadow_on_nerf at its defaults),
 the calls alternating: the whole frame on the device (frame_ms), its NeRF pass (kernel_ms), its mesh pass, the new kernel alone
 (ngp_get_frame_mesh_shadow_ms), and how many pixels own a surface point and how many of those a mesh shadows.
+    python tools/mesh_shade_rate.py --ambient-change-on-nerf [--out profiles/ambient_change_on_nerf_rate.json]
+
+With --ambient-change-on-nerf: Shade-mode frames with ngp_set_ambient_change_on_nerf off and on (its defaults), the calls alternating, in
+two views: the one above, and one in which the NeRF fills the frame (the model alone over a far floor: the normals kernel's cost follows
+the number of pixels that own a surface point). The volumes: 8^3 probes over the scene box, 16 x 16 rays, the context's with the meshes
+occluding, sunlit and one bounce, the reference beside it. Per view: the whole frame (frame_ms), its NeRF pass (kernel_ms), its mesh pass,
+the two new kernels together (ngp_get_frame_ambient_change_ms), and how many pixels own a surface point and how many were scaled.
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -153,6 +160,53 @@ def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
     ctx.close()
 
 
+def main_ambient_change_on_nerf(args, ctx, native, synthetic, cam, geo, lo, hi, out):
+    out["how"] = ("Shade-mode Geometry frames, the option off and on (ngp_set_ambient_change_on_nerf, min_irradiance 1e-3, max_gain 4) in alternating calls of one run, per view. "
+                  "frame: HIP events around the whole frame (ngp_get_render_stats frame_ms); nerf_pass: its NeRF launch (kernel_ms); mesh_pass: ngp_get_mesh_pass_ms; "
+                  "ambient_kernels: HIP events around nerf_surface_normals_kernel and nerf_ambient_ratio_kernel (ngp_get_frame_ambient_change_ms). "
+                  "Medians of --frames frames each after --warmup, with p10 / p90. Volumes: 8^3 probes over the scene box, 16 x 16 rays; the context's sunlit with one bounce.")
+    # the second view: the model alone over a far floor, seen from close by, so that the NeRF fills the frame
+    fill = native.Context(0)
+    fill.set_model(synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19))
+    fill.add_mesh((scene()[0][0] * np.float32([8.0, 0.05, 8.0])).astype(np.float32), (0.5, -3.0, 0.5))
+    fill.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
+    flo, fhi = fill.mesh_info(-1)["aabb"]
+    fill_cam = native.make_camera(look_at((0.5, 0.9, -0.8), (0.5, 0.45, 0.5), up=(0.0, 1.0, 0.0)), args.width, args.height, (0.9 * args.width,) * 2)
+    opts = native.make_opts(render_mode=native.RENDER_SHADE, **geo)
+    q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+    for name, c, view, box in (("meshes_view", ctx, cam, (lo, hi)), ("nerf_fills_the_frame", fill, fill_cam, (flo, fhi))):
+        c.compute_irradiance_volume((8,) * 3, box, 16, 16, bounces=1, sun=dict(direction=(1.0, 1.0, 1.0)))
+        c.compute_reference_irradiance_volume((8,) * 3, box, 16, 16)
+        ts = {key: {"frame": [], "nerf_pass": [], "mesh_pass": [], "ambient_kernels": []} for key in ("off", "on")}
+        for i in range(args.warmup + args.frames):
+            for key, change in (("off", None), ("on", True)):
+                c.set_ambient_change_on_nerf(change)
+                c.render(view, opts)
+                if i >= args.warmup:
+                    st = c.render_stats()
+                    ts[key]["frame"].append(st["frame_ms"])
+                    ts[key]["nerf_pass"].append(st["kernel_ms"])
+                    ts[key]["mesh_pass"].append(c.mesh_pass_ms())
+                    ts[key]["ambient_kernels"].append(c.frame_ambient_change_ms())
+        rec = c.frame_ambient_change(args.width * args.height)  # (the last call was an on frame)
+        c.set_ambient_change_on_nerf(None)
+        row = {key: {k: q(v) for k, v in t.items()} for key, t in ts.items()}
+        owner = rec[:, 3] != 0
+        row["pixels_with_surface_point"] = round(float(owner.mean()), 4)
+        row["pixels_scaled"] = round(float((rec[:, 3] == 2).mean()), 4)
+        row["g_min_max"] = [round(float(rec[owner, 8:11].min()), 4), round(float(rec[owner, 8:11].max()), 4)] if owner.any() else None
+        row["frame_on_minus_off_ms"] = round(row["on"]["frame"]["median_ms"] - row["off"]["frame"]["median_ms"], 4)
+        out["modes"][name] = row
+        print(f"{name}: frame off {row['off']['frame']['median_ms']:.4f} ms, on {row['on']['frame']['median_ms']:.4f} ms (ambient kernels {row['on']['ambient_kernels']['median_ms']:.4f} ms, "
+              f"NeRF pass off {row['off']['nerf_pass']['median_ms']:.4f} / on {row['on']['nerf_pass']['median_ms']:.4f} ms), owners {row['pixels_with_surface_point']}, "
+              f"scaled {row['pixels_scaled']}, g {row['g_min_max']}", flush=True)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    fill.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -162,10 +216,11 @@ def main():
     ap.add_argument("--visibility", action="store_true", help="the visibility-weighted volume against Shade and the plain volume, and the maps' compute time")
     ap.add_argument("--sun-nerf-shadow", action="store_true", help="the mesh pass with the NeRF in front of the frames' sun, off and on, per shade mode")
     ap.add_argument("--mesh-shadow-on-nerf", action="store_true", help="Shade frames with the meshes' shadow on the NeRF, off and on in alternating calls")
+    ap.add_argument("--ambient-change-on-nerf", action="store_true", help="Shade frames with the meshes' change of the ambient light on the NeRF, off and on in alternating calls, in two views")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -190,6 +245,9 @@ def main():
     if args.mesh_shadow_on_nerf:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out)
+    if args.ambient_change_on_nerf:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_ambient_change_on_nerf(args, ctx, native, synthetic, cam, geo, lo, hi, out)
     rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid")]
     rows += [("ShadeIrradianceVolume_%d" % r, native.RENDER_SHADE_IRRADIANCE_VOLUME, r) for r in (8, 32)]
     if args.visibility:  # one run: Shade, then per resolution the plain volume and the same volume with visibility
