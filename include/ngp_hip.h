@@ -563,7 +563,7 @@ NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const flo
  * Determinism: no atomics; bit-identical from run to run and for any chunking. With N = 0, every albedo channel 0, no meshes loaded or
  *   occlude_by_meshes == 0 no pass runs and the records are V_0's as bytes.
  * Limits: N <= 16; every albedo channel finite and in [0, 1]; each refused with a message that names the field.
- * Out of scope: glossy transport; a NeRF surface lit by the meshes; probes inside closed
+ * Out of scope: glossy transport in the volume (the frames' own mirror ray is ngp_set_mesh_reflection, below); a NeRF surface lit by the meshes; probes inside closed
  *   meshes (they stay dead: a room built of meshes alone gets nothing); bounces for the lat-long probe tables.
  * Refusals: those of the volume and visibility sections; ngp_irradiance_sh_bounce without a volume ("no irradiance volume") and with
  *   use_visible without visibility ("no irradiance visibility"); a non-finite alpha. */
@@ -801,6 +801,61 @@ NGP_API int ngp_irradiance_volume_ratio(ngp_ctx* ctx, uint32_t n, const float* p
 NGP_API int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out /* n_pixels x 12 */, size_t n_pixels);
 /* device time (HIP events) around the two new kernels in the last frame's last sample; 0 after a frame without them */
 NGP_API int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms);
+
+/* mesh reflection: the inserted meshes mirror the NeRF, one reflection ray a pixel. The mesh BRDF's GGX lobe, Fresnel term, metallic and
+ * specular answer to the sun alone; with this option a mesh pixel also receives what the captured scene sends along its mirror direction.
+ * Context state, set like ngp_set_sun_nerf_shadow; off by default, and with it off every frame is the one it was, as bytes.
+ *
+ * Which frames: Geometry mode, meshes loaded, a model loaded, render modes Shade, ShadeEnvMap, ShadeGridEnvMap and ShadeIrradianceVolume
+ *   (with or without visibility). Every other frame ignores the option and is the option-off frame as bytes. Such a frame takes the split
+ *   mesh pass of ngp_set_sun_nerf_shadow (G-buffer, ray-list trace, deferred shade) with a second ray list, on the frame's stream.
+ * Which pixels own a reflection ray: for each sample of the frame, a pixel that is covered (its hit position lies inside the scene box) AND
+ *   whose primary ray found a triangle. The second condition is this block's own: a pixel whose ray chose no mesh is covered too, with
+ *   normal = dir, and its mirror ray would run straight back at the camera; it owns no ray.
+ * The ray, from the float32 values the pass holds: n^ = normalize(ff), ff the winding normal turned against the primary ray as the mesh pass
+ *   forms it; c = -(n^ . primary_dir); origin q = pos + 1e-3 n^, the very value the sun block calls q; direction r = primary_dir + (2 c) n^;
+ *   t_range = (t_min, t_hit), t_hit the closest triangle over ALL meshes from q along normalize(r), +inf without one: the rule of
+ *   ngp_irradiance_rays with occlude_by_meshes, not the one-mesh rule of the frames' shadow ray. It is traced with the semantics of
+ *   ngp_trace_nerf_rays: the tracer normalises the direction; the render box in force is the inflated mesh box; no background; a ray cut at
+ *   t_hit is shaded like one that left the box. The result (rgb_r, alpha_r) is linear and premultiplied.
+ * The colour, behind the mesh pass's BRDF and only where alpha_r > 0, in float32 and in this order:
+ *     Cspec0 = mix3(specular * 0.08 * (1, 1, 1), base^2, metallic)      (the BRDF's own Cspec0 with its tint at 0)
+ *     F = mix3(Cspec0, (1, 1, 1), SchlickFresnel(c))
+ *     color += fl(fl(F (.) rgb_r) strength)
+ *   A pixel with alpha_r = 0, or without a ray, keeps the bits it would have had; so do depth, coverage, the ambient term, sharding and
+ *   packing, and the NeRF pass that follows. With ngp_set_sun_nerf_shadow off the shadow trace is not run and T_s = 1; with it on, each
+ *   list is traced on its own and each record is that of the frame with only that option on, as bytes.
+ * Determinism: no atomics decide a value; frames are bit-identical from run to run. Everything runs on the frame's stream and
+ *   ngp_render_device stays asynchronous.
+ * Statistics: ngp_get_render_stats reports the frame's NeRF pass alone; the tracer's counters go to a block of the context's own. The time of
+ *   prep + trace is ngp_get_frame_mesh_reflection_ms, inside ngp_get_mesh_pass_ms.
+ * Identities as bytes (the frame is the option-off frame): the option off; strength 0 (no trace is run); NeRF mode; no meshes; no model
+ *   (meshes only); a t_min of at least the box diagonal; a model that is empty along every reflection ray.
+ * Refusals: a NaN min_transmittance, a negative or non-finite t_min, a negative or non-finite strength, on any context; a refused call leaves
+ *   the option as it was. A model the ray-list tracer does not serve is refused when the frame is rendered, naming the option. The stage
+ *   entries refuse a host-only context ("no HIP device"). A moving camera with meshes is refused as before.
+ * Several devices: the option travels to the peers with the geometry and each device traces the rays of its own tiles;
+ *   ngp_get_frame_mesh_reflection and ngp_get_frame_mesh_reflection_ms read the primary's share only.
+ * Stated limits: mirror direction only: roughness does not blur the reflection, and strength is the caller's handle on that. Meshes do not
+ *   appear in reflections: a ray cut by a mesh carries what the NeRF put in front of the hit, and black behind it. No environment map or
+ *   sky fills the reflection where alpha_r < 1. The reflected NeRF is the captured one: the shadow and the ambient change of
+ *   ngp_set_mesh_shadow_on_nerf / ngp_set_ambient_change_on_nerf are not applied to it. A surface inside the NeRF's own density reflects
+ *   that density unless t_min skips it. The NeRF does not reflect the meshes. */
+typedef struct ngp_mesh_reflection_desc {
+	float strength;          /* the factor on the reflected radiance; finite, >= 0 (the bindings' True: 1). 0: the frame is the option-off frame */
+	float min_transmittance; /* as in ngp_trace_nerf_rays (<= 0 selects 0.01); NaN refused (True: 0.01) */
+	float t_min;             /* the NeRF is ignored within t_min of q along the mirror direction; finite, >= 0 (True: 0) */
+} ngp_mesh_reflection_desc;
+/* desc == NULL: off (the default) */
+NGP_API int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc /* nullable: off */);
+NGP_API int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* enabled);
+/* stage entry for tests and tools: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on a
+ * multi-device context the primary's tile-packed share), 12 floats: q (3), t_hit, r (3) as handed to the tracer before it is normalised,
+ * 0, rgb_r (3), alpha_r; zeros where the pixel owns no ray. n_pixels must be that frame's extent. Refuses when the last frame traced no
+ * reflection rays. */
+NGP_API int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out /* n_pixels x 12 */, size_t n_pixels);
+/* device time (HIP events) of the reflection rays' prep and trace in the last frame's last sample; 0 after a frame without them */
+NGP_API int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -92,7 +92,9 @@ NGP_DEV void bvh4_ray_intersect(const TriangleBvhNode* __restrict__ nodes, const
 //  - a ray whose line enters no box within MAX_DIST is left untouched. render_mesh_fused then finds its position, the camera's,
 //    inside the scene box and shades the pixel with alpha 1, depth 0 and N = the ray's direction (NdotV = -1: the ambient term alone);
 //  - a traced ray that hits nothing ends at pos + MAX_DIST * dir, its direction unchanged.
-NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
+// hit: the traversal found a triangle (idx > -1). A ray that chose no mesh, or hit nothing in the one it chose, has none.
+NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir, bool& hit) {
+	hit = false;
 	float mint = MAX_DIST;
 	int mesh_idx = -1;
 	for (uint32_t m = 0; m < S.n_meshes; ++m) {
@@ -112,7 +114,12 @@ NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
 		const Triangle& tri = M.tris[idx];
 		f3 a = ld3(tri.a);
 		dir = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
+		hit = true;
 	}
+}
+NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
+	bool hit;
+	trace_mesh(S, pos, dir, hit);
 }
 
 // the closest triangle hit of a ray over ALL meshes (trace_mesh's rule is another: one mesh, chosen by box entry): its t, +inf without a
@@ -517,7 +524,7 @@ void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, cons
 // sun"). render_mesh_fused split around a ray-list trace: M1-M4 leave a G-buffer and one shadow-ray entry per local pixel, in idx order and
 // not compacted; the tracer walks the list; M5 shades from the G-buffer with shadow scaled by what the tracer let through. The statements
 // are render_mesh_fused's, in its order, on the same leaf functions, so a pixel whose T_s is 1 gets the fused kernel's bits.
-// G-buffer of n pixels, three planes of n float4: (pos, shadow), (raw normal, covered), (primary_dir, 0).
+// G-buffer of n pixels, three planes of n float4: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle).
 
 __global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, float* __restrict__ depth_buffer, uint32_t shard_index,
                                     uint32_t shard_count, int packed, float t_min, uint32_t n_pixels, float4* __restrict__ gbuf, float* __restrict__ ray_o,
@@ -563,7 +570,8 @@ __global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadePara
 	const f3 primary_dir = dir;
 	// M2
 	f3 normal = dir;
-	trace_mesh(S, pos, normal);
+	bool hit;
+	trace_mesh(S, pos, normal, hit);
 	// M3
 	float shadow;
 	f3 q;
@@ -585,18 +593,72 @@ __global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadePara
 	if (!has) q = mk3(0.f, 0.f, 0.f);
 	gbuf[idx] = make_float4(pos.x, pos.y, pos.z, shadow);
 	gbuf[(size_t)n_pixels + idx] = make_float4(normal.x, normal.y, normal.z, covered ? 1.0f : 0.0f);
-	gbuf[2 * (size_t)n_pixels + idx] = make_float4(primary_dir.x, primary_dir.y, primary_dir.z, 0.0f);
+	gbuf[2 * (size_t)n_pixels + idx] = make_float4(primary_dir.x, primary_dir.y, primary_dir.z, hit ? 1.0f : 0.0f);
 	ray_o[3 * (size_t)idx] = q.x; ray_o[3 * (size_t)idx + 1] = q.y; ray_o[3 * (size_t)idx + 2] = q.z;
 	ray_t[idx] = has ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
 	if (covered) depth_buffer[idx] = dot3(cam_fwd, sub3(pos, cam_pos));
 }
 
-// M5 from the G-buffer. traced: the tracer's rgba of the pixel's list entry; a pixel has a shadow ray where ray_t.y != 0 (the prep step
-// moves ray_t.x alone). record: (q, alpha_s), zeros without a shadow ray (ngp_get_frame_sun_shadow).
+// ---- the NeRF mirrored in the meshes (ngp_set_mesh_reflection; contract in include/ngp_hip.h, "mesh reflection"). A second use of the split
+// pass: one mirror ray a pixel whose primary ray found a triangle inside the scene box, in a ray list of its own, traced like the shadow list.
+
+// the mirror ray of a G-buffer pixel, in one fixed order: n^ = normalize(ff), ff M3's winding normal turned against the primary ray;
+// c = -(n^ . primary_dir); q = pos + 1e-3 n^ (M3's view_pos, the shadow list's q, as bits); r = primary_dir + (2 c) n^, not normalised
+NGP_DEV void mirror_ray(f3 pos, f3 normal, f3 primary_dir, f3& q, f3& r, float& c) {
+	float nd = dot3(normal, primary_dir);
+	f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f);
+	f3 nh = normalize3(ff);
+	c = -dot3(nh, primary_dir);
+	q = add3(pos, scale3(nh, 1e-3f));
+	r = add3(primary_dir, scale3(nh, 2.0f * c));
+}
+
+// what a pixel's mirror ray adds to its colour: strength F (.) rgb_r, F = mix3(Cspec0, 1, SchlickFresnel(c)), Cspec0 the BRDF's with its tint at 0
+NGP_DEV f3 mirror_term(const MeshShadeParams& P, float c, f3 rgb_r, float strength) {
+	const f3 one = mk3(1.0f, 1.0f, 1.0f);
+	f3 base = ld3(P.basecolor);
+	f3 Cspec0 = mix3(scale3(scale3(one, P.specular), 0.08f), mul3(base, base), P.metallic);
+	f3 F = mix3(Cspec0, one, SchlickFresnel(c));
+	return scale3(mul3(F, rgb_r), strength);
+}
+
+// one thread a pixel, mesh_gbuffer_kernel's indexing: the pixel's entry of the reflection list, in idx order and not compacted. A pixel owns a
+// ray where it is covered and its primary ray found a triangle (plane 2's w); t = (t_min, the closest triangle over ALL meshes from q along
+// normalize(r), +inf without one), ngp_irradiance_rays' rule. Every other entry is dead: origin 0, direction +z, t = (0, 0).
+__global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const CameraParams C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min,
+                                            uint32_t n_pixels, const float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d,
+                                            float2* __restrict__ ray_t) {
+	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
+	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
+	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
+	if (tile % shard_count != shard_index) return;
+	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	if (C.moving || idx >= n_pixels) return;
+	f3 q = mk3(0.f, 0.f, 0.f), r = mk3(0.f, 0.f, 1.f);
+	float2 t = make_float2(0.f, 0.f);
+	const float4 g1 = gbuf[(size_t)n_pixels + idx];
+	if (g1.w != 0.0f) { // (a pixel that is not covered may hold a stale plane 2)
+		const float4 g2 = gbuf[2 * (size_t)n_pixels + idx];
+		if (g2.w != 0.0f) {
+			const float4 g0 = gbuf[idx];
+			float c;
+			mirror_ray(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), q, r, c);
+			t = make_float2(t_min, closest_hit(S, q, normalize3(r)));
+		}
+	}
+	ray_o[3 * (size_t)idx] = q.x; ray_o[3 * (size_t)idx + 1] = q.y; ray_o[3 * (size_t)idx + 2] = q.z;
+	ray_d[3 * (size_t)idx] = r.x; ray_d[3 * (size_t)idx + 1] = r.y; ray_d[3 * (size_t)idx + 2] = r.z;
+	ray_t[idx] = t;
+}
+
+// M5 from the G-buffer. traced (nullable: no shadow trace was run, T_s = 1): the tracer's rgba of the pixel's list entry; a pixel has a shadow
+// ray where ray_t.y != 0 (the prep step moves ray_t.x alone). record: (q, alpha_s), zeros without a shadow ray (ngp_get_frame_sun_shadow).
+// R: the mirror ray's radiance is added behind evaluate_shading where alpha_r > 0; every other pixel keeps its bits.
 template <typename Ambient>
 __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer, uint32_t shard_index,
                                            uint32_t shard_count, int packed, uint32_t n_pixels, const float4* __restrict__ gbuf, const float* __restrict__ ray_o,
-                                           const float2* __restrict__ ray_t, const float4* __restrict__ traced, float4* __restrict__ record) {
+                                           const float2* __restrict__ ray_t, const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R) {
 	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
 	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
 	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
@@ -605,9 +667,12 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
 	if (C.moving || idx >= n_pixels) return;
 	const float4 g1 = gbuf[(size_t)n_pixels + idx];
-	const bool has = g1.w != 0.0f && ray_t[idx].y != 0.0f;
+	const bool has = traced && g1.w != 0.0f && ray_t[idx].y != 0.0f;
 	const float alpha_s = has ? traced[idx].w : 0.0f;
-	record[idx] = has ? make_float4(ray_o[3 * (size_t)idx], ray_o[3 * (size_t)idx + 1], ray_o[3 * (size_t)idx + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
+	if (traced) record[idx] = has ? make_float4(ray_o[3 * (size_t)idx], ray_o[3 * (size_t)idx + 1], ray_o[3 * (size_t)idx + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
+	// a pixel owns a mirror ray by mesh_reflection_rays_kernel's rule: covered, and its primary ray found a triangle
+	const bool mirror = R.traced && g1.w != 0.0f && gbuf[2 * (size_t)n_pixels + idx].w != 0.0f;
+	if (R.traced && !mirror) R.record[3 * (size_t)idx] = R.record[3 * (size_t)idx + 1] = R.record[3 * (size_t)idx + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
 	if (g1.w == 0.0f) return;
 	const float4 g0 = gbuf[idx], g2 = gbuf[2 * (size_t)n_pixels + idx];
 	const f3 pos = mk3(g0.x, g0.y, g0.z), normal = mk3(g1.x, g1.y, g1.z), primary_dir = mk3(g2.x, g2.y, g2.z);
@@ -639,6 +704,16 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 	}
 	f3 color = evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen,
 	                            0.f, P.clearcoat, P.clearcoat_gloss, sun, scale3(normalize3(primary_dir), -1.0f), N);
+	if (mirror) {
+		f3 q, r;
+		float c;
+		mirror_ray(pos, normal, primary_dir, q, r, c); // (the list's bits: one device function forms them in both kernels)
+		const float4 tr = R.traced[idx];
+		R.record[3 * (size_t)idx] = make_float4(R.ray_o[3 * (size_t)idx], R.ray_o[3 * (size_t)idx + 1], R.ray_o[3 * (size_t)idx + 2], R.ray_t[idx].y);
+		R.record[3 * (size_t)idx + 1] = make_float4(r.x, r.y, r.z, 0.0f);
+		R.record[3 * (size_t)idx + 2] = tr;
+		if (tr.w > 0.0f) color = add3(color, mirror_term(P, c, mk3(tr.x, tr.y, tr.z), R.strength));
+	}
 	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
 }
 
@@ -651,12 +726,18 @@ void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, con
 }
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
                                 float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
-                                const float2* ray_t, const float4* traced, float4* record, hipStream_t stream) {
+                                const float2* ray_t, const float4* traced, float4* record, const MeshReflectionList& R, hipStream_t stream) {
 	dim3 threads(16, 8, 1);
 	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	if (VV) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, P, *VV, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
-	else if (V) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolume>, blocks, threads, 0, stream, P, *V, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
-	else hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceMap>, blocks, threads, 0, stream, P, I, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record);
+	if (VV) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, P, *VV, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
+	else if (V) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolume>, blocks, threads, 0, stream, P, *V, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
+	else hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceMap>, blocks, threads, 0, stream, P, I, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
+}
+void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min, uint32_t n_pixels,
+                                 const float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
+	dim3 threads(16, 8, 1);
+	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
+	hipLaunchKernelGGL(mesh_reflection_rays_kernel, blocks, threads, 0, stream, S, C, shard_index, shard_count, packed, t_min, n_pixels, gbuf, ray_o, ray_d, ray_t);
 }
 
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)

@@ -148,7 +148,10 @@ void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, con
                          float t_min, uint32_t n_pixels, float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
                                 float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
-                                const float2* ray_t, const float4* traced, float4* record, hipStream_t stream); // M5 of launch_render_mesh behind the trace
+                                const float2* ray_t, const float4* traced, float4* record, const MeshReflectionList& R,
+                                hipStream_t stream); // M5 of launch_render_mesh behind the trace(s); traced == nullptr: no shadow trace was run (T_s = 1, no record)
+void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min, uint32_t n_pixels,
+                                 const float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // the G-buffer's mirror rays (ngp_set_mesh_reflection)
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
@@ -403,7 +406,7 @@ struct ngp_ctx {
 	bool sun_nerf_shadow = false;
 	ngp_irradiance_sun_nerf_desc sun_nerf_shadow_desc{};
 	// its per-pixel scratch, allocated when a frame first uses the option and grown like the frame buffers (d_ss_record, allocated last, holds the size of all)
-	ngp::DevArray<float4> d_ss_gbuf;   // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, 0)
+	ngp::DevArray<float4> d_ss_gbuf;   // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle)
 	ngp::DevArray<float> d_ss_o, d_ss_d; // the shadow-ray list, one entry a local pixel
 	ngp::DevArray<float2> d_ss_t;
 	ngp::DevArray<float4> d_ss_traced; // the tracer's rgba of the list
@@ -429,6 +432,19 @@ struct ngp_ctx {
 	ngp::Event ev_ac0[HISTORY], ev_ac1[HISTORY]; // around the normals and ratio kernels of a frame's last sample (ngp_get_frame_ambient_change_ms)
 	bool hist_ambient_change[HISTORY] = {};      // the slot's call was a frame that ran the pass
 	size_t ac_n_pixels = 0;                      // pixels of the last such frame
+	// ---- the NeRF mirrored in the meshes (ngp_set_mesh_reflection); a peer's copy follows the primary's with the geometry
+	bool mesh_reflection = false;
+	ngp_mesh_reflection_desc mesh_reflection_desc{};
+	// its per-pixel scratch, allocated when a frame first uses the option and grown like the frame buffers (d_mr_record, allocated last, holds
+	// the size of all). The G-buffer and the shadow list its frames fill are the sun shadow's (d_ss_*).
+	ngp::DevArray<float> d_mr_o, d_mr_d; // the reflection-ray list, one entry a local pixel
+	ngp::DevArray<float2> d_mr_t;
+	ngp::DevArray<float4> d_mr_traced; // the tracer's rgba of the list
+	ngp::DevArray<float4> d_mr_record; // 3 float4 a pixel: (q, t_hit), (r, 0), (rgb_r, alpha_r) of the last sample (ngp_get_frame_mesh_reflection)
+	ngp::DevArray<unsigned long long> d_mr_results; // where the reflection trace's counters go: the slot's results stay the NeRF pass's
+	ngp::Event ev_mr0[HISTORY], ev_mr1[HISTORY]; // around prep + trace of a frame's last sample (ngp_get_frame_mesh_reflection_ms)
+	bool hist_mesh_reflection[HISTORY] = {};     // the slot's call was a frame that traced reflection rays
+	size_t mr_n_pixels = 0;                      // pixels of the last such frame
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a

@@ -233,5 +233,12 @@ struct IrradianceVolumeVisible { // the volume and its probes' distance maps: pr
 	float D;           // the distance the maps were capped at
 	float normal_bias; // the point a probe is looked at from: p + normal_bias n^
 };
+struct MeshReflectionList { // the reflection ray list of a frame as the deferred mesh shade sees it (ngp_set_mesh_reflection); traced == nullptr: off
+	const float* ray_o;   // one entry a local pixel, in the frame's pixel order, not compacted
+	const float2* ray_t;
+	const float4* traced; // the tracer's premultiplied rgba of the list
+	float4* record;       // 3 float4 a pixel: (q, t_hit), (r, 0), (rgb_r, alpha_r); zeros without a ray (ngp_get_frame_mesh_reflection)
+	float strength;
+};
 
 } // namespace ngp

@@ -260,6 +260,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->mesh_shadow_on_nerf_desc = primary->mesh_shadow_on_nerf_desc;
 	peer->ambient_change_on_nerf = primary->ambient_change_on_nerf; // each device scales its own share
 	peer->ambient_change_desc = primary->ambient_change_desc;
+	peer->mesh_reflection = primary->mesh_reflection; // each device traces the mirror rays of its own share
+	peer->mesh_reflection_desc = primary->mesh_reflection_desc;
 	if (peer->synced_mesh_generation != primary->mesh_generation) {
 		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)

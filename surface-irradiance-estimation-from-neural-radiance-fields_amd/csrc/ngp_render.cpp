@@ -253,6 +253,30 @@ void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	NGP_HIP_CHECK(hipMemset(ctx->d_ss_d.get(), 0, ctx->d_ss_d.bytes()));
 }
 
+// the per-pixel scratch of a frame whose meshes mirror the NeRF (ngp_set_mesh_reflection): allocated by the first frame that uses the option,
+// grown as ensure_frame_buffers grows. The G-buffer and the shadow list such a frame fills are ensure_sun_shadow_buffers'.
+void ensure_mesh_reflection_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	ensure_sun_shadow_buffers(ctx, n_pixels);
+	if (!ctx->d_mr_results) {
+		ctx->d_mr_results.reset(8);
+		NGP_HIP_CHECK(hipMemset(ctx->d_mr_results.get(), 0, 8 * sizeof(unsigned long long)));
+		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
+			ctx->ev_mr0[i] = new_event();
+			ctx->ev_mr1[i] = new_event();
+		}
+	}
+	if (3 * n_pixels <= ctx->d_mr_record.size()) return;
+	ctx->d_mr_o.reset(), ctx->d_mr_d.reset(), ctx->d_mr_t.reset(), ctx->d_mr_traced.reset(), ctx->d_mr_record.reset();
+	ctx->d_mr_o.reset(3 * n_pixels);
+	ctx->d_mr_d.reset(3 * n_pixels);
+	ctx->d_mr_t.reset(n_pixels);
+	ctx->d_mr_traced.reset(n_pixels);
+	ctx->d_mr_record.reset(3 * n_pixels);
+	// (list entries no pixel of a frame owns are dead through their t alone; their o and d are never garbage)
+	NGP_HIP_CHECK(hipMemset(ctx->d_mr_o.get(), 0, ctx->d_mr_o.bytes()));
+	NGP_HIP_CHECK(hipMemset(ctx->d_mr_d.get(), 0, ctx->d_mr_d.bytes()));
+}
+
 // the per-pixel buffers of a frame whose meshes shadow the NeRF (ngp_set_mesh_shadow_on_nerf): allocated by the first frame that uses the
 // option, grown as ensure_frame_buffers grows
 void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
@@ -303,6 +327,14 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	// its own and one kernel behind it finishes the composite over the mesh pass's pixels, all of it on `stream`; nothing waits.
 	const bool shade_mode = opts.render_mode == NGP_RENDER_SHADE || opts.render_mode == NGP_RENDER_SHADE_ENVMAP || opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ||
 	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
+	// the NeRF mirrored in the meshes: the same frames, in the four shade modes, through the split mesh pass with a ray list of its own
+	// (strength 0 adds nothing: no trace is run and the frame takes the path it would take with the option off)
+	const bool reflection = ctx->mesh_reflection && ctx->mesh_reflection_desc.strength > 0.0f && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() &&
+	                        ctx->model_loaded && shade_mode;
+	if (reflection) {
+		require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
+		ensure_mesh_reflection_buffers(ctx, n_pixels ? n_pixels : 1);
+	}
 	const bool mesh_shadow = ctx->mesh_shadow_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
 	if (mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
 	// what the meshes change in the ambient light on the NeRF: the same frames. Behind the NeRF launch into the scratch, one kernel forms the
@@ -371,21 +403,38 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 			const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
 			const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
 			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[slot], stream)); // (ngp_get_mesh_pass_ms)
-			if (sun_shadow) { // G-buffer -> prep -> trace -> deferred shade; the trace borrows the slot's queue ahead of the NeRF launch and reports into a block of its own
+			if (sun_shadow || reflection) { // G-buffer -> per list: prep -> trace -> deferred shade; a trace borrows the slot's queue ahead of the NeRF launch and reports into a block of its own
 				const uint32_t n = (uint32_t)n_pixels;
 				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_t.get(), 0, n_pixels * sizeof(float2), stream)); // entries no pixel owns stay dead
-				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_record.get(), 0, n_pixels * sizeof(float4), stream));
+				if (sun_shadow) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_record.get(), 0, n_pixels * sizeof(float4), stream));
 				launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, F.depth_buffer, F.shard_index, F.shard_count, F.packed, ctx->sun_nerf_shadow_desc.t_min, n, ctx->d_ss_gbuf.get(),
 				                    ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), stream);
-				if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss0[slot], stream)); // (ngp_get_frame_sun_shadow_ms)
-				launch_ray_list_prep(M, n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), true, stream);
-				FrameParams FT{};
-				tracer_frame_params(ctx, slot, ctx->sun_nerf_shadow_desc.min_transmittance, FT);
-				FT.results = ctx->d_ss_results.get();
-				if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), nullptr), false, stream); // (a shard without tiles traces nothing)
-				if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss1[slot], stream));
+				if (sun_shadow) {
+					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss0[slot], stream)); // (ngp_get_frame_sun_shadow_ms)
+					launch_ray_list_prep(M, n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), true, stream);
+					FrameParams FT{};
+					tracer_frame_params(ctx, slot, ctx->sun_nerf_shadow_desc.min_transmittance, FT);
+					FT.results = ctx->d_ss_results.get();
+					if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), nullptr), false, stream); // (a shard without tiles traces nothing)
+					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss1[slot], stream));
+				}
+				MeshReflectionList R{};
+				if (reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
+					NGP_HIP_CHECK(hipMemsetAsync(ctx->d_mr_t.get(), 0, n_pixels * sizeof(float2), stream)); // entries no pixel owns stay dead
+					NGP_HIP_CHECK(hipMemsetAsync(ctx->d_mr_record.get(), 0, 3 * n_pixels * sizeof(float4), stream));
+					launch_mesh_reflection_rays(ctx->mesh_scene, C, F.shard_index, F.shard_count, F.packed, ctx->mesh_reflection_desc.t_min, n, ctx->d_ss_gbuf.get(), ctx->d_mr_o.get(),
+					                            ctx->d_mr_d.get(), ctx->d_mr_t.get(), stream);
+					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mr0[slot], stream)); // (ngp_get_frame_mesh_reflection_ms)
+					launch_ray_list_prep(M, n, ctx->d_mr_o.get(), ctx->d_mr_d.get(), ctx->d_mr_t.get(), true, stream);
+					FrameParams FT{};
+					tracer_frame_params(ctx, slot, ctx->mesh_reflection_desc.min_transmittance, FT);
+					FT.results = ctx->d_mr_results.get();
+					if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_mr_o.get(), ctx->d_mr_d.get(), ctx->d_mr_t.get(), ctx->d_mr_traced.get(), nullptr), false, stream);
+					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mr1[slot], stream));
+					R = MeshReflectionList{ctx->d_mr_o.get(), ctx->d_mr_t.get(), ctx->d_mr_traced.get(), ctx->d_mr_record.get(), ctx->mesh_reflection_desc.strength};
+				}
 				launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.shard_index, F.shard_count, F.packed, n,
-				                           ctx->d_ss_gbuf.get(), ctx->d_ss_o.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), ctx->d_ss_record.get(), stream);
+				                           ctx->d_ss_gbuf.get(), ctx->d_ss_o.get(), ctx->d_ss_t.get(), sun_shadow ? ctx->d_ss_traced.get() : nullptr, ctx->d_ss_record.get(), R, stream);
 			} else {
 				launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
 			}
@@ -424,6 +473,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->hist_mesh_pass[slot] = have_meshes && !F.direct;
 	ctx->hist_sun_shadow[slot] = sun_shadow;
 	if (sun_shadow) ctx->ss_n_pixels = n_pixels;
+	ctx->hist_mesh_reflection[slot] = reflection;
+	if (reflection) ctx->mr_n_pixels = n_pixels;
 	ctx->hist_mesh_shadow[slot] = mesh_shadow;
 	if (mesh_shadow) ctx->ms_n_pixels = n_pixels;
 	ctx->hist_ambient_change[slot] = ambient_change;
@@ -614,6 +665,51 @@ int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
 		if (!ctx->hist_sun_shadow[slot]) return;
 		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
 		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ss0[slot], ctx->ev_ss1[slot]));
+	});
+}
+
+int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc) {
+	return guarded(ctx, [&] {
+		if (desc) {
+			if (!std::isfinite(desc->strength) || desc->strength < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: strength must be finite and >= 0");
+			if (std::isnan(desc->min_transmittance)) throw std::runtime_error("invalid mesh reflection descriptor: min_transmittance is NaN");
+			if (!std::isfinite(desc->t_min) || desc->t_min < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: t_min must be finite and >= 0");
+		}
+		ctx->mesh_reflection = desc != nullptr;
+		ctx->mesh_reflection_desc = desc ? *desc : ngp_mesh_reflection_desc{};
+	});
+}
+
+int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = ctx->mesh_reflection_desc;
+		*enabled = ctx->mesh_reflection ? 1 : 0;
+	});
+}
+
+int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls || !ctx->hist_mesh_reflection[(ctx->n_calls - 1) % ngp_ctx::HISTORY])
+			throw std::runtime_error("the last frame traced no reflection rays (ngp_set_mesh_reflection)");
+		if (n_pixels != ctx->mr_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->mr_n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_mr_record.get(), 3 * n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+	});
+}
+
+int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = 0.f;
+		if (!ctx->n_calls) return;
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		if (!ctx->hist_mesh_reflection[slot]) return;
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_mr0[slot], ctx->ev_mr1[slot]));
 	});
 }
 

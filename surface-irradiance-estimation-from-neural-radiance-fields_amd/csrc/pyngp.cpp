@@ -270,6 +270,11 @@ PYBIND11_MODULE(pyngp, m) {
 		               "over the reference volume; a missing volume is computed before the frame (default False)")
 		.def_readwrite("ambient_change_on_nerf_min_irradiance", &Testbed::m_ambient_change_on_nerf_min_irradiance, "with ambient_change_on_nerf: a channel whose reference irradiance is not above this keeps its colour (1e-3)")
 		.def_readwrite("ambient_change_on_nerf_max_gain", &Testbed::m_ambient_change_on_nerf_max_gain, "with ambient_change_on_nerf: the cap on the ratio (4)")
+		.def_readwrite("mesh_reflection", &Testbed::m_mesh_reflection,
+		               "This project's own: Geometry frames with meshes and a model, the four shade modes: a mesh pixel whose primary ray found a triangle adds strength * F * (the NeRF's radiance along its mirror direction) (default False)")
+		.def_readwrite("mesh_reflection_strength", &Testbed::m_mesh_reflection_strength, "with mesh_reflection: the factor on the reflected radiance (1)")
+		.def_readwrite("mesh_reflection_min_transmittance", &Testbed::m_mesh_reflection_min_transmittance, "with mesh_reflection: the reflection rays' transmittance floor (0.01)")
+		.def_readwrite("mesh_reflection_t_min", &Testbed::m_mesh_reflection_t_min, "with mesh_reflection: the NeRF is ignored within this distance of the surface (0)")
 		.def("compute_reference_irradiance_volume", [](Testbed& t, const std::array<uint32_t, 3>& res, py::object aabb, uint32_t n_u, uint32_t n_v) {
 			const std::vector<float> box = aabb6_arg(aabb);
 			std::vector<float> sh;

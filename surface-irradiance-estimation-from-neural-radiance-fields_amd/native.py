@@ -129,6 +129,10 @@ class AmbientChangeDesc(C.Structure):
     _fields_ = [("min_irradiance", C.c_float), ("max_gain", C.c_float)]
 
 
+class MeshReflectionDesc(C.Structure):
+    _fields_ = [("strength", C.c_float), ("min_transmittance", C.c_float), ("t_min", C.c_float)]
+
+
 SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
 
 
@@ -287,6 +291,10 @@ def load_library():
     L.ngp_irradiance_volume_ratio.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(AmbientChangeDesc), vp]
     L.ngp_get_frame_ambient_change.argtypes = [vp, vp, C.c_size_t]
     L.ngp_get_frame_ambient_change_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_set_mesh_reflection.argtypes = [vp, C.POINTER(MeshReflectionDesc)]
+    L.ngp_get_mesh_reflection.argtypes = [vp, C.POINTER(MeshReflectionDesc), C.POINTER(C.c_int)]
+    L.ngp_get_frame_mesh_reflection.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_mesh_reflection_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -1034,6 +1042,40 @@ class Context:
         """device time of the normals and ratio kernels in the last frame's last sample, ms; 0 after a frame without them"""
         ms = C.c_float(0)
         self._check(self.L.ngp_get_frame_ambient_change_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    # ---------------------------------------------------------------- the NeRF mirrored in the meshes (include/ngp_hip.h, "mesh reflection")
+    def set_mesh_reflection(self, reflection=True):
+        """one reflection ray a mesh pixel through the NeRF (Geometry frames with meshes and a model, the four shade modes): None or False
+        switches it off (the default), True takes strength 1, min_transmittance 0.01 and t_min 0, a dict gives them"""
+        if reflection is None or reflection is False:
+            self._check(self.L.ngp_set_mesh_reflection(self.h, None))
+            return
+        if reflection is True:
+            reflection = {}
+        if not isinstance(reflection, dict) or set(reflection) - {"strength", "min_transmittance", "t_min"}:
+            raise ValueError("mesh_reflection: True, False, None or a dict of strength, min_transmittance and t_min")
+        d = MeshReflectionDesc()
+        d.strength, d.min_transmittance, d.t_min = float(reflection.get("strength", 1.0)), float(reflection.get("min_transmittance", 0.01)), float(reflection.get("t_min", 0.0))
+        self._check(self.L.ngp_set_mesh_reflection(self.h, C.byref(d)))
+
+    def mesh_reflection(self):
+        """None while the option is off, else dict(strength=, min_transmittance=, t_min=) as set"""
+        d, on = MeshReflectionDesc(), C.c_int(0)
+        self._check(self.L.ngp_get_mesh_reflection(self.h, C.byref(d), C.byref(on)))
+        return dict(strength=d.strength, min_transmittance=d.min_transmittance, t_min=d.t_min) if on.value else None
+
+    def frame_mesh_reflection(self, n_pixels):
+        """(n_pixels, 12): per pixel of the last frame's last sample, in the frame's pixel order: q (3), t_hit, r (3) before the tracer
+        normalises it, 0, rgb_r (3), alpha_r; zeros where the pixel owns no ray. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros((int(n_pixels), 12), np.float32)
+        self._check(self.L.ngp_get_frame_mesh_reflection(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def frame_mesh_reflection_ms(self):
+        """device time of the reflection rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_frame_mesh_reflection_ms(self.h, C.byref(ms)))
         return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):

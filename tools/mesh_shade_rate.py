@@ -23,6 +23,12 @@ two views: the one above, and one in which the NeRF fills the frame (the model a
 the number of pixels that own a surface point). The volumes: 8^3 probes over the scene box, 16 x 16 rays, the context's with the meshes
 occluding, sunlit and one bounce, the reference beside it. Per view: the whole frame (frame_ms), its NeRF pass (kernel_ms), its mesh pass,
 the two new kernels together (ngp_get_frame_ambient_change_ms), and how many pixels own a surface point and how many were scaled.
+    python tools/mesh_shade_rate.py --mesh-reflection [--out profiles/mesh_reflection_rate.json]
+
+With --mesh-reflection: per shade mode, in one run, the mesh pass with ngp_set_mesh_reflection off (render_mesh_fused) and on at its defaults
+(G-buffer kernel, reflection-ray kernel, prep and ray-list trace of one mirror ray a local pixel, deferred shade kernel), of the latter the
+prep and trace alone (ngp_get_frame_mesh_reflection_ms), the frame's NeRF pass beside them, and how many pixels own a ray, how many of the
+rays a mesh cuts and how many see the NeRF.
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -128,6 +134,69 @@ def main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out):
     ctx.close()
 
 
+def median_reflection_on_off(ctx, cam, opts, frames, warmup, n_pixels):
+    """median_on_off for ngp_set_mesh_reflection: the option off, then on, in one run"""
+    row = {}
+    for key, reflection in (("off", None), ("on", True)):
+        ctx.set_mesh_reflection(reflection)
+        mesh, trace, nerf = [], [], []
+        for i in range(warmup + frames):
+            ctx.render(cam, opts)
+            if i >= warmup:
+                mesh.append(ctx.mesh_pass_ms())
+                trace.append(ctx.frame_mesh_reflection_ms())
+                nerf.append(ctx.render_stats()["kernel_ms"])
+        q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+        row[key] = {"mesh_pass": q(mesh), "nerf_pass": q(nerf)}
+        if reflection:
+            row[key]["reflection_prep_and_trace"] = q(trace)
+            rec = ctx.frame_mesh_reflection(n_pixels)
+            owns = np.any(rec[:, 4:7] != 0, axis=1)
+            row[key]["pixels_with_reflection_ray"] = round(float(owns.mean()), 4)
+            row[key]["rays_cut_by_a_mesh"] = round(float((owns & np.isfinite(rec[:, 3])).mean()), 4)
+            row[key]["rays_with_alpha_above_0"] = round(float((rec[:, 11] > 0).mean()), 4)
+            row[key]["rays_with_alpha_above_0.9"] = round(float((rec[:, 11] > 0.9).mean()), 4)
+    ctx.set_mesh_reflection(None)
+    row["mesh_pass_on_over_off"] = round(row["on"]["mesh_pass"]["median_ms"] / row["off"]["mesh_pass"]["median_ms"], 3)
+    row["gbuffer_rays_and_shade_ms"] = round(row["on"]["mesh_pass"]["median_ms"] - row["on"]["reflection_prep_and_trace"]["median_ms"], 4)
+    return row
+
+
+def main_mesh_reflection(args, ctx, native, cam, geo, lo, hi, out):
+    out["how"] = ("per shade mode, one run: option off, then on (ngp_set_mesh_reflection, strength 1, min_transmittance 0.01, t_min 0). mesh_pass: HIP events around the whole "
+                  "mesh pass of the frame (ngp_get_mesh_pass_ms: off = render_mesh_fused; on = G-buffer kernel, reflection-ray kernel, prep, ray-list trace, deferred shade); "
+                  "reflection_prep_and_trace: HIP events around prep + trace inside it (ngp_get_frame_mesh_reflection_ms); nerf_pass: the frame's NeRF launch "
+                  "(ngp_get_render_stats kernel_ms); gbuffer_rays_and_shade_ms = the difference of the first two medians. Medians of --frames frames after --warmup, "
+                  "with p10 / p90. sun_shadow_run_off: the off figures of profiles/mesh_shade_sun_shadow_rate.json, another run on another day.")
+    earlier = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "mesh_shade_sun_shadow_rate.json")) as f:
+            earlier = {k: v["off"]["mesh_pass"] for k, v in json.load(f)["modes"].items()}
+    except (OSError, KeyError, ValueError):
+        pass
+    rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid"),
+            ("ShadeIrradianceVolume_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, 8), ("ShadeIrradianceVolumeVisible_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, -8)]
+    for name, mode, what in rows:
+        if what == "grid":
+            ctx.compute_envmap_grid(8, 8, 64, 32)
+        elif what is not None and what > 0:
+            ctx.compute_irradiance_volume((what,) * 3, (lo, hi), 16, 16)
+        elif what is not None:
+            ctx.compute_irradiance_volume_visibility(16, 16, 5)
+        row = median_reflection_on_off(ctx, cam, native.make_opts(render_mode=mode, **geo), args.frames, args.warmup, args.width * args.height)
+        if name in earlier:
+            row["sun_shadow_run_off"] = earlier[name]
+            row["off_inside_that_runs_p10_p90"] = bool(earlier[name]["p10_ms"] <= row["off"]["mesh_pass"]["median_ms"] <= earlier[name]["p90_ms"])
+        out["modes"][name] = row
+        print(f"{name:30s} mesh pass off {row['off']['mesh_pass']['median_ms']:.4f} ms, on {row['on']['mesh_pass']['median_ms']:.4f} ms "
+              f"(prep + trace {row['on']['reflection_prep_and_trace']['median_ms']:.4f} ms, the rest {row['gbuffer_rays_and_shade_ms']:.4f} ms), NeRF pass {row['on']['nerf_pass']['median_ms']:.4f} ms, "
+              f"owners {row['on']['pixels_with_reflection_ray']}, alpha > 0: {row['on']['rays_with_alpha_above_0']}", flush=True)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
 def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
     out["how"] = ("Shade-mode Geometry frames, the option off and on (ngp_set_mesh_shadow_on_nerf, strength 0.5, bias 1e-2) in alternating calls of one run. frame: HIP "
                   "events around the whole frame (ngp_get_render_stats frame_ms); nerf_pass: its NeRF launch (kernel_ms); mesh_pass: ngp_get_mesh_pass_ms; "
@@ -217,10 +286,11 @@ def main():
     ap.add_argument("--sun-nerf-shadow", action="store_true", help="the mesh pass with the NeRF in front of the frames' sun, off and on, per shade mode")
     ap.add_argument("--mesh-shadow-on-nerf", action="store_true", help="Shade frames with the meshes' shadow on the NeRF, off and on in alternating calls")
     ap.add_argument("--ambient-change-on-nerf", action="store_true", help="Shade frames with the meshes' change of the ambient light on the NeRF, off and on in alternating calls, in two views")
+    ap.add_argument("--mesh-reflection", action="store_true", help="the mesh pass with the NeRF mirrored in the meshes, off and on, per shade mode")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -242,6 +312,9 @@ def main():
     if args.sun_nerf_shadow:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out)
+    if args.mesh_reflection:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_mesh_reflection(args, ctx, native, cam, geo, lo, hi, out)
     if args.mesh_shadow_on_nerf:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out)
