@@ -117,10 +117,6 @@ NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir, bool& hit) {
 		hit = true;
 	}
 }
-NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir) {
-	bool hit;
-	trace_mesh(S, pos, dir, hit);
-}
 
 // the closest triangle hit of a ray over ALL meshes (trace_mesh's rule is another: one mesh, chosen by box entry): its t, +inf without a
 // hit. mesh / tri (nullable) receive the hit's mesh and triangle; they are left alone without a hit. What the irradiance ray generators see.
@@ -412,31 +408,24 @@ NGP_DEV void irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, 
 	}
 }
 
-// render_geometry_mesh (src/testbed_geometry_training.cu:2202-2320), Shade mode, floor disabled, one thread per pixel. The ambient source
-// is fixed at compile time by the type of A: IrradianceMap (the sky term, or the probe table(s) when A.irradiance is set),
-// IrradianceVolume (ShadeIrradianceVolume: max(E(pos, N), 0) / pi from the SH9 lattice, 0 where every probe around pos is dead) or
-// IrradianceVolumeVisible (the same mode while the context holds the probes' distance maps: the visibility-weighted estimate).
-template <typename Ambient>
-__global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer,
-                                  float* __restrict__ depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	// camera-tile sharding: same 8x8 tile -> rank mapping as the NeRF pass
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	// tile-packed layout: local tile q = tile / shard_count, slot = (x & 7) + 8 * (y & 7)
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving) return; // (a moving camera is a NeRF-mode feature here; the host refuses the combination)
-	const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
-	const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
-	// M1: init_rays_with_payload_kernel_mesh_geometry (:488-579)
+// ---- the frames' mesh pass: render_geometry_mesh (src/testbed_geometry_training.cu:2202-2320), Shade mode, floor disabled, one thread per
+// pixel (frame_pixel, render_common.h). Its stages M1-M5 are the three functions below, the one definition of each: render_mesh_fused runs
+// them back to back, the split pass (mesh_gbuffer_kernel, mesh_shade_deferred_kernel) runs the same functions in the same order around the
+// ray-list traces, so a split-pass pixel whose T_s is 1 gets the fused kernel's bits.
+// The three take the kernels' parameter structs by value, as closest_hit does: through references the fused kernel reloads twice as many
+// spilled scalar registers and its pass measures 3 us longer.
+NGP_DEV void st3(float* p, f3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+NGP_DEV f3 shadow_ray_dir(const MeshShadeParams& P) { return normalize3(normalize3(ld3(P.sun_dir))); } // (M3 normalises m_sun_dir twice)
+NGP_DEV float camera_depth(const CameraParams& C, f3 pos) { return dot3(mk3(C.m[6], C.m[7], C.m[8]), sub3(pos, mk3(C.m[9], C.m[10], C.m[11]))); }
+
+// M1: init_rays_with_payload_kernel_mesh_geometry (:488-579): pixel (x, y)'s ray through the lens and the aperture, advanced to the scene
+// box: pos, and the unit dir. false: the lens gives the pixel no direction (it keeps MAX_DEPTH and an empty frame)
+NGP_DEV bool mesh_primary_ray(const MeshSceneParams S, const CameraParams C, uint32_t x, uint32_t y, f3& pos, f3& dir) {
 	float u = ((float)x + C.pixel_offset[0]) / (float)C.width;
 	float v = ((float)y + C.pixel_offset[1]) / (float)C.height;
-	f3 dir;
 	lens_direction(C, u, v, dir);
 	dir = m3_mulv(C.m, dir);
-	f3 origin = cam_pos;
+	f3 origin = mk3(C.m[9], C.m[10], C.m[11]);
 	if (C.aperture_size != 0.0f) {
 		float o3[3] = {origin.x, origin.y, origin.z}, d3[3] = {dir.x, dir.y, dir.z}, cm[6];
 		for (int i = 0; i < 6; ++i) cm[i] = C.m[i];
@@ -445,33 +434,41 @@ __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams
 		dir = mk3(d3[0], d3[1], d3[2]);
 	}
 	origin = add3(origin, scale3(dir, C.near_distance));
-	depth_buffer[idx] = MAX_DEPTH;
-	if (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f) return;
+	if (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f) return false;
 	dir = normalize3(dir);
 	float t = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, origin, dir), 0.0f);
-	f3 pos = add3(origin, scale3(dir, t + 1e-6f));
-	const f3 primary_dir = dir;
-	// M2 on every ray; the normal buffer starts out holding the ray direction (trace_mesh_bvh :2140-2155)
-	f3 normal = dir;
-	trace_mesh(S, pos, normal);
-	// M3: prepare_shadow_rays_geometry (:222-271)
+	pos = add3(origin, scale3(dir, t + 1e-6f));
+	return true;
+}
+
+// M2 on every ray (the normal buffer starts out holding the ray direction, trace_mesh_bvh :2140-2155), M3 prepare_shadow_rays_geometry
+// (:222-271) and M4 write_shadow_ray_result_geometry (:273-278, min_visibility == 1). pos: the primary ray's start in, its end out; hit: it
+// found a triangle; q: where the shadow ray leaves the surface, before M3 advances it to the scene box (the split pass starts the NeRF's
+// shadow ray and the mirror ray there); shadow: 1 where no mesh stands between q and the sun, else 0.
+NGP_DEV void mesh_trace_shadow(const MeshSceneParams S, const MeshShadeParams P, f3 primary_dir, f3& pos, f3& normal, bool& hit, f3& q, float& shadow) {
+	normal = primary_dir;
+	trace_mesh(S, pos, normal, hit);
+	const f3 sdir = shadow_ray_dir(P);
+	float nd = dot3(normal, primary_dir);
+	f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f); // faceforward(n, dir, n)
+	f3 view_pos = add3(pos, scale3(normalize3(ff), 1e-3f));
+	q = view_pos;
+	float st = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, view_pos, sdir) + 1e-6f, 0.0f);
+	view_pos = add3(view_pos, scale3(sdir, st));
+	f3 spos = view_pos;
+	f3 sn = box_contains(S.scene_min, S.scene_max, view_pos) ? sdir : primary_dir; // dead shadow rays keep the copied payload.dir
+	bool shadow_hit;
+	trace_mesh(S, spos, sn, shadow_hit);
+	shadow = box_contains(S.scene_min, S.scene_max, spos) ? 0.0f : 1.0f;
+}
+
+// M5: shade_kernel_mesh_geometry (:280-355) at a covered pixel. The ambient source is fixed at compile time by the type of A: IrradianceMap
+// (the sky term, or the probe table(s) when A.irradiance is set), IrradianceVolume (ShadeIrradianceVolume: max(E(pos, N), 0) / pi from the
+// SH9 lattice, 0 where every probe around pos is dead) or IrradianceVolumeVisible (the same mode while the context holds the probes'
+// distance maps: the visibility-weighted estimate).
+template <typename Ambient>
+NGP_DEV f3 mesh_shade(const MeshShadeParams P, const Ambient A, f3 pos, f3 normal, f3 primary_dir, float shadow) {
 	const f3 sun = normalize3(ld3(P.sun_dir));
-	float shadow;
-	{
-		float nd = dot3(normal, primary_dir);
-		f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f); // faceforward(n, dir, n)
-		f3 view_pos = add3(pos, scale3(normalize3(ff), 1e-3f));
-		f3 sdir = normalize3(sun);
-		float st = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, view_pos, sdir) + 1e-6f, 0.0f);
-		view_pos = add3(view_pos, scale3(sdir, st));
-		f3 spos = view_pos;
-		f3 sn = box_contains(S.scene_min, S.scene_max, view_pos) ? sdir : primary_dir; // dead shadow rays keep the copied payload.dir
-		trace_mesh(S, spos, sn);
-		// M4: write_shadow_ray_result_geometry (:273-278), min_visibility == 1
-		shadow = box_contains(S.scene_min, S.scene_max, spos) ? 0.0f : 1.0f;
-	}
-	// M5: shade_kernel_mesh_geometry (:280-355)
-	if (!box_contains(S.scene_min, S.scene_max, pos)) return;
 	f3 N = normalize3(normal);
 	f3 up = normalize3(ld3(P.up_dir));
 	float skyam = -dot3(N, up) * 0.5f + 0.5f;
@@ -479,25 +476,38 @@ __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams
 	f3 skycol = scale3(scale3(mk3(195.f / 255.0f, 215.f / 255.0f, 255.f / 255.0f), 4.f), skyam);
 	f3 base = ld3(P.basecolor);
 	f3 ambc;
-	if constexpr (std::is_same<Ambient, IrradianceVolume>::value) { // the blend's accumulators are live from here on only: both traversals are over
-		float E[3], W;
-		irradiance_volume_lookup(A, pos, N, E, W);
-		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F); // (SH9 rings: E may dip below zero)
-	} else if constexpr (std::is_same<Ambient, IrradianceVolumeVisible>::value) {
-		float E[3], W;
-		irradiance_volume_lookup_visible(A, pos, N, E, W);
-		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
-	} else {
+	if constexpr (std::is_same<Ambient, IrradianceMap>::value) {
 		ambc = mul3(ld3(P.ambientcolor), skycol);
 		if (A.irradiance) { // ShadeEnvMap / ShadeGridEnvMap: ambient light = E(N)/pi from the NeRF-derived irradiance table(s)
 			f3 E = irradiance_lookup(A, pos, N);
 			ambc = mk3(E.x / PI_F, E.y / PI_F, E.z / PI_F);
 		}
+	} else { // the blend's accumulators are live from here on only: both traversals are over
+		float E[3], W;
+		if constexpr (std::is_same<Ambient, IrradianceVolume>::value) irradiance_volume_lookup(A, pos, N, E, W);
+		else irradiance_volume_lookup_visible(A, pos, N, E, W);
+		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F); // (SH9 rings: E may dip below zero)
 	}
-	f3 color = evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen,
-	                            0.f, P.clearcoat, P.clearcoat_gloss, sun, scale3(normalize3(primary_dir), -1.0f), N);
+	return evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen, 0.f, P.clearcoat, P.clearcoat_gloss, sun,
+	                        scale3(normalize3(primary_dir), -1.0f), N);
+}
+
+// the whole pass in one kernel: primary hit, sun shadow ray and BRDF stay in registers
+template <typename Ambient>
+__global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                  float4* __restrict__ frame_buffer, float* __restrict__ depth_buffer) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
+	depth_buffer[idx] = MAX_DEPTH;
+	f3 pos, primary_dir, normal, q;
+	if (!mesh_primary_ray(S, C, x, y, pos, primary_dir)) return;
+	bool hit;
+	float shadow;
+	mesh_trace_shadow(S, P, primary_dir, pos, normal, hit, q, shadow);
+	if (!box_contains(S.scene_min, S.scene_max, pos)) return;
+	f3 color = mesh_shade(P, A, pos, normal, primary_dir, shadow);
 	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
-	depth_buffer[idx] = dot3(cam_fwd, sub3(pos, cam_pos));
+	depth_buffer[idx] = camera_depth(C, pos);
 }
 
 // stage kernel: M2 alone (mesh_raytrace_kernel)
@@ -505,102 +515,43 @@ __global__ void trace_mesh_rays_kernel(const MeshSceneParams S, uint32_t n, floa
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	f3 p = ld3(positions + 3 * (size_t)i), d = ld3(directions + 3 * (size_t)i);
-	trace_mesh(S, p, d);
-	positions[3 * (size_t)i] = p.x; positions[3 * (size_t)i + 1] = p.y; positions[3 * (size_t)i + 2] = p.z;
-	directions[3 * (size_t)i] = d.x; directions[3 * (size_t)i + 1] = d.y; directions[3 * (size_t)i + 2] = d.z;
+	bool hit;
+	trace_mesh(S, p, d, hit);
+	st3(positions + 3 * (size_t)i, p);
+	st3(directions + 3 * (size_t)i, d);
 }
 
-// V != nullptr: the ambient light comes from the SH9 volume (ShadeIrradianceVolume) and I is not looked at; VV != nullptr: from the volume
-// weighted by its probes' visibility, and neither V nor I is looked at
-void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
-                        const CameraParams& C, float4* frame_buffer, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed, hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	if (VV) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolumeVisible>, blocks, threads, 0, stream, S, P, *VV, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
-	else if (V) hipLaunchKernelGGL(render_mesh_fused<IrradianceVolume>, blocks, threads, 0, stream, S, P, *V, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
-	else hipLaunchKernelGGL(render_mesh_fused<IrradianceMap>, blocks, threads, 0, stream, S, P, I, C, frame_buffer, depth_buffer, shard_index, shard_count, packed);
-}
-// ---- the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow; contract in include/ngp_hip.h, "sun: the NeRF in front of the frames'
-// sun"). render_mesh_fused split around a ray-list trace: M1-M4 leave a G-buffer and one shadow-ray entry per local pixel, in idx order and
-// not compacted; the tracer walks the list; M5 shades from the G-buffer with shadow scaled by what the tracer let through. The statements
-// are render_mesh_fused's, in its order, on the same leaf functions, so a pixel whose T_s is 1 gets the fused kernel's bits.
+// ---- the split pass (ngp_set_sun_nerf_shadow, ngp_set_mesh_reflection; contracts in include/ngp_hip.h, "sun: the NeRF in front of the
+// frames' sun" and "mesh reflection"): M1-M4 leave a G-buffer and one shadow-ray entry per local pixel, in idx order and not compacted; the
+// tracer walks the list(s); M5 shades from the G-buffer with shadow scaled by what the tracer let through.
 // G-buffer of n pixels, three planes of n float4: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle).
-
-__global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, float* __restrict__ depth_buffer, uint32_t shard_index,
-                                    uint32_t shard_count, int packed, float t_min, uint32_t n_pixels, float4* __restrict__ gbuf, float* __restrict__ ray_o,
-                                    float* __restrict__ ray_d, float2* __restrict__ ray_t) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving || idx >= n_pixels) return;
-	const f3 cam_fwd = mk3(C.m[6], C.m[7], C.m[8]);
-	const f3 cam_pos = mk3(C.m[9], C.m[10], C.m[11]);
-	// M1
-	float u = ((float)x + C.pixel_offset[0]) / (float)C.width;
-	float v = ((float)y + C.pixel_offset[1]) / (float)C.height;
-	f3 dir;
-	lens_direction(C, u, v, dir);
-	dir = m3_mulv(C.m, dir);
-	f3 origin = cam_pos;
-	if (C.aperture_size != 0.0f) {
-		float o3[3] = {origin.x, origin.y, origin.z}, d3[3] = {dir.x, dir.y, dir.z}, cm[6];
-		for (int i = 0; i < 6; ++i) cm[i] = C.m[i];
-		apply_aperture(cm, C.aperture_size, C.focus_z, C.spp, (uint32_t)(int)(u * (float)C.width) * 19349663u + (uint32_t)(int)(v * (float)C.height) * 96925573u, o3, d3);
-		origin = mk3(o3[0], o3[1], o3[2]);
-		dir = mk3(d3[0], d3[1], d3[2]);
-	}
-	origin = add3(origin, scale3(dir, C.near_distance));
+__global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, const FrameLayout L, float* __restrict__ depth_buffer, float t_min,
+                                    float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
 	depth_buffer[idx] = MAX_DEPTH;
-	const f3 sun = normalize3(ld3(P.sun_dir));
-	const f3 sdir = normalize3(sun);
 	// the dead entry irradiance_sun_shadow_rays_kernel writes: origin 0, the sun's direction, t = (0, 0)
-	ray_d[3 * (size_t)idx] = sdir.x; ray_d[3 * (size_t)idx + 1] = sdir.y; ray_d[3 * (size_t)idx + 2] = sdir.z;
-	if (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f) {
-		gbuf[(size_t)n_pixels + idx] = make_float4(0.f, 0.f, 0.f, 0.f); // not covered
-		ray_o[3 * (size_t)idx] = 0.f; ray_o[3 * (size_t)idx + 1] = 0.f; ray_o[3 * (size_t)idx + 2] = 0.f;
+	st3(ray_d + 3 * (size_t)idx, shadow_ray_dir(P));
+	f3 pos, primary_dir, normal, q;
+	if (!mesh_primary_ray(S, C, x, y, pos, primary_dir)) {
+		gbuf[(size_t)L.n_pixels + idx] = make_float4(0.f, 0.f, 0.f, 0.f); // not covered
+		st3(ray_o + 3 * (size_t)idx, mk3(0.f, 0.f, 0.f));
 		ray_t[idx] = make_float2(0.f, 0.f);
 		return;
 	}
-	dir = normalize3(dir);
-	float t = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, origin, dir), 0.0f);
-	f3 pos = add3(origin, scale3(dir, t + 1e-6f));
-	const f3 primary_dir = dir;
-	// M2
-	f3 normal = dir;
 	bool hit;
-	trace_mesh(S, pos, normal, hit);
-	// M3
 	float shadow;
-	f3 q;
-	{
-		float nd = dot3(normal, primary_dir);
-		f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f);
-		f3 view_pos = add3(pos, scale3(normalize3(ff), 1e-3f));
-		q = view_pos; // the NeRF shadow ray starts where the mesh shadow ray does, before that one is advanced to the scene box
-		float st = fmaxf(aabb_ray_entry(S.scene_min, S.scene_max, view_pos, sdir) + 1e-6f, 0.0f);
-		view_pos = add3(view_pos, scale3(sdir, st));
-		f3 spos = view_pos;
-		f3 sn = box_contains(S.scene_min, S.scene_max, view_pos) ? sdir : primary_dir;
-		trace_mesh(S, spos, sn);
-		// M4
-		shadow = box_contains(S.scene_min, S.scene_max, spos) ? 0.0f : 1.0f;
-	}
+	mesh_trace_shadow(S, P, primary_dir, pos, normal, hit, q, shadow);
 	const bool covered = box_contains(S.scene_min, S.scene_max, pos);
-	const bool has = covered && shadow == 1.0f;
+	const bool has = covered && shadow == 1.0f; // the NeRF's shadow ray starts at q, where the mesh shadow ray does
 	if (!has) q = mk3(0.f, 0.f, 0.f);
 	gbuf[idx] = make_float4(pos.x, pos.y, pos.z, shadow);
-	gbuf[(size_t)n_pixels + idx] = make_float4(normal.x, normal.y, normal.z, covered ? 1.0f : 0.0f);
-	gbuf[2 * (size_t)n_pixels + idx] = make_float4(primary_dir.x, primary_dir.y, primary_dir.z, hit ? 1.0f : 0.0f);
-	ray_o[3 * (size_t)idx] = q.x; ray_o[3 * (size_t)idx + 1] = q.y; ray_o[3 * (size_t)idx + 2] = q.z;
+	gbuf[(size_t)L.n_pixels + idx] = make_float4(normal.x, normal.y, normal.z, covered ? 1.0f : 0.0f);
+	gbuf[2 * (size_t)L.n_pixels + idx] = make_float4(primary_dir.x, primary_dir.y, primary_dir.z, hit ? 1.0f : 0.0f);
+	st3(ray_o + 3 * (size_t)idx, q);
 	ray_t[idx] = has ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
-	if (covered) depth_buffer[idx] = dot3(cam_fwd, sub3(pos, cam_pos));
+	if (covered) depth_buffer[idx] = camera_depth(C, pos);
 }
-
-// ---- the NeRF mirrored in the meshes (ngp_set_mesh_reflection; contract in include/ngp_hip.h, "mesh reflection"). A second use of the split
-// pass: one mirror ray a pixel whose primary ray found a triangle inside the scene box, in a ray list of its own, traced like the shadow list.
 
 // the mirror ray of a G-buffer pixel, in one fixed order: n^ = normalize(ff), ff M3's winding normal turned against the primary ray;
 // c = -(n^ . primary_dir); q = pos + 1e-3 n^ (M3's view_pos, the shadow list's q, as bits); r = primary_dir + (2 c) n^, not normalised
@@ -622,24 +573,18 @@ NGP_DEV f3 mirror_term(const MeshShadeParams& P, float c, f3 rgb_r, float streng
 	return scale3(mul3(F, rgb_r), strength);
 }
 
-// one thread a pixel, mesh_gbuffer_kernel's indexing: the pixel's entry of the reflection list, in idx order and not compacted. A pixel owns a
-// ray where it is covered and its primary ray found a triangle (plane 2's w); t = (t_min, the closest triangle over ALL meshes from q along
-// normalize(r), +inf without one), ngp_irradiance_rays' rule. Every other entry is dead: origin 0, direction +z, t = (0, 0).
-__global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const CameraParams C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min,
-                                            uint32_t n_pixels, const float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d,
-                                            float2* __restrict__ ray_t) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving || idx >= n_pixels) return;
+// the pixel's entry of the reflection list, in idx order and not compacted. A pixel owns a ray where it is covered and its primary ray found
+// a triangle (plane 2's w); t = (t_min, the closest triangle over ALL meshes from q along normalize(r), +inf without one), ngp_irradiance_rays'
+// rule. Every other entry is dead: origin 0, direction +z, t = (0, 0).
+__global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const CameraParams C, const FrameLayout L, float t_min, const float4* __restrict__ gbuf,
+                                            float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
 	f3 q = mk3(0.f, 0.f, 0.f), r = mk3(0.f, 0.f, 1.f);
 	float2 t = make_float2(0.f, 0.f);
-	const float4 g1 = gbuf[(size_t)n_pixels + idx];
+	const float4 g1 = gbuf[(size_t)L.n_pixels + idx];
 	if (g1.w != 0.0f) { // (a pixel that is not covered may hold a stale plane 2)
-		const float4 g2 = gbuf[2 * (size_t)n_pixels + idx];
+		const float4 g2 = gbuf[2 * (size_t)L.n_pixels + idx];
 		if (g2.w != 0.0f) {
 			const float4 g0 = gbuf[idx];
 			float c;
@@ -647,8 +592,8 @@ __global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const Camer
 			t = make_float2(t_min, closest_hit(S, q, normalize3(r)));
 		}
 	}
-	ray_o[3 * (size_t)idx] = q.x; ray_o[3 * (size_t)idx + 1] = q.y; ray_o[3 * (size_t)idx + 2] = q.z;
-	ray_d[3 * (size_t)idx] = r.x; ray_d[3 * (size_t)idx + 1] = r.y; ray_d[3 * (size_t)idx + 2] = r.z;
+	st3(ray_o + 3 * (size_t)idx, q);
+	st3(ray_d + 3 * (size_t)idx, r);
 	ray_t[idx] = t;
 }
 
@@ -656,54 +601,24 @@ __global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const Camer
 // ray where ray_t.y != 0 (the prep step moves ray_t.x alone). record: (q, alpha_s), zeros without a shadow ray (ngp_get_frame_sun_shadow).
 // R: the mirror ray's radiance is added behind evaluate_shading where alpha_r > 0; every other pixel keeps its bits.
 template <typename Ambient>
-__global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, float4* __restrict__ frame_buffer, uint32_t shard_index,
-                                           uint32_t shard_count, int packed, uint32_t n_pixels, const float4* __restrict__ gbuf, const float* __restrict__ ray_o,
-                                           const float2* __restrict__ ray_t, const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving || idx >= n_pixels) return;
-	const float4 g1 = gbuf[(size_t)n_pixels + idx];
+__global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
+                                           const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
+                                           const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
+	const float4 g1 = gbuf[(size_t)L.n_pixels + idx];
 	const bool has = traced && g1.w != 0.0f && ray_t[idx].y != 0.0f;
 	const float alpha_s = has ? traced[idx].w : 0.0f;
 	if (traced) record[idx] = has ? make_float4(ray_o[3 * (size_t)idx], ray_o[3 * (size_t)idx + 1], ray_o[3 * (size_t)idx + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
 	// a pixel owns a mirror ray by mesh_reflection_rays_kernel's rule: covered, and its primary ray found a triangle
-	const bool mirror = R.traced && g1.w != 0.0f && gbuf[2 * (size_t)n_pixels + idx].w != 0.0f;
+	const bool mirror = R.traced && g1.w != 0.0f && gbuf[2 * (size_t)L.n_pixels + idx].w != 0.0f;
 	if (R.traced && !mirror) R.record[3 * (size_t)idx] = R.record[3 * (size_t)idx + 1] = R.record[3 * (size_t)idx + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
 	if (g1.w == 0.0f) return;
-	const float4 g0 = gbuf[idx], g2 = gbuf[2 * (size_t)n_pixels + idx];
+	const float4 g0 = gbuf[idx], g2 = gbuf[2 * (size_t)L.n_pixels + idx];
 	const f3 pos = mk3(g0.x, g0.y, g0.z), normal = mk3(g1.x, g1.y, g1.z), primary_dir = mk3(g2.x, g2.y, g2.z);
 	float shadow = g0.w;
 	if (has) shadow = shadow * fmaxf(1.0f - alpha_s, 0.0f); // T_s
-	const f3 sun = normalize3(ld3(P.sun_dir));
-	// M5
-	f3 N = normalize3(normal);
-	f3 up = normalize3(ld3(P.up_dir));
-	float skyam = -dot3(N, up) * 0.5f + 0.5f;
-	f3 suncol = scale3(scale3(mk3(255.f / 255.0f, 225.f / 255.0f, 195.f / 255.0f), 4.f), shadow);
-	f3 skycol = scale3(scale3(mk3(195.f / 255.0f, 215.f / 255.0f, 255.f / 255.0f), 4.f), skyam);
-	f3 base = ld3(P.basecolor);
-	f3 ambc;
-	if constexpr (std::is_same<Ambient, IrradianceVolume>::value) {
-		float E[3], W;
-		irradiance_volume_lookup(A, pos, N, E, W);
-		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
-	} else if constexpr (std::is_same<Ambient, IrradianceVolumeVisible>::value) {
-		float E[3], W;
-		irradiance_volume_lookup_visible(A, pos, N, E, W);
-		ambc = mk3(fmaxf(E[0], 0.0f) / PI_F, fmaxf(E[1], 0.0f) / PI_F, fmaxf(E[2], 0.0f) / PI_F);
-	} else {
-		ambc = mul3(ld3(P.ambientcolor), skycol);
-		if (A.irradiance) {
-			f3 E = irradiance_lookup(A, pos, N);
-			ambc = mk3(E.x / PI_F, E.y / PI_F, E.z / PI_F);
-		}
-	}
-	f3 color = evaluate_shading(mul3(base, base), ambc, suncol, P.metallic, P.subsurface, P.specular, P.roughness, 0.f, P.sheen,
-	                            0.f, P.clearcoat, P.clearcoat_gloss, sun, scale3(normalize3(primary_dir), -1.0f), N);
+	f3 color = mesh_shade(P, A, pos, normal, primary_dir, shadow);
 	if (mirror) {
 		f3 q, r;
 		float c;
@@ -717,27 +632,40 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
 }
 
-// the two halves of launch_render_mesh around the caller's trace of (ray_o, ray_d, ray_t); n_pixels: the extent of every per-pixel buffer
-void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
-                         float t_min, uint32_t n_pixels, float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	hipLaunchKernelGGL(mesh_gbuffer_kernel, blocks, threads, 0, stream, S, P, C, depth_buffer, shard_index, shard_count, packed, t_min, n_pixels, gbuf, ray_o, ray_d, ray_t);
+// the launch geometry of every frame_pixel kernel: blocks of 16 x 8 threads over the camera
+static dim3 pixel_threads() { return dim3(16, 8, 1); }
+static dim3 pixel_blocks(const CameraParams& C) { return dim3((C.width + 15) / 16, (C.height + 7) / 8, 1); }
+// calls f with the ambient source of a mesh shade. VV != nullptr: the SH9 volume weighted by its probes' visibility, and neither V nor I is
+// looked at; else V != nullptr: the volume (ShadeIrradianceVolume), and I is not looked at; else I
+template <typename F>
+void with_ambient(const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, F&& f) {
+	if (VV) f(*VV);
+	else if (V) f(*V);
+	else f(I);
+}
+
+void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
+                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer, hipStream_t stream) {
+	with_ambient(I, V, VV, [&](const auto& A) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(render_mesh_fused<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, frame_buffer, depth_buffer);
+	});
+}
+// the two halves of launch_render_mesh around the caller's trace of (ray_o, ray_d, ray_t)
+void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, const FrameLayout& L, float* depth_buffer, float t_min, float4* gbuf,
+                         float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
+	hipLaunchKernelGGL(mesh_gbuffer_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t);
 }
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
-                                float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
-                                const float2* ray_t, const float4* traced, float4* record, const MeshReflectionList& R, hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	if (VV) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, P, *VV, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
-	else if (V) hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceVolume>, blocks, threads, 0, stream, P, *V, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
-	else hipLaunchKernelGGL(mesh_shade_deferred_kernel<IrradianceMap>, blocks, threads, 0, stream, P, I, C, frame_buffer, shard_index, shard_count, packed, n_pixels, gbuf, ray_o, ray_t, traced, record, R);
+                                const FrameLayout& L, float4* frame_buffer, const float4* gbuf, const float* ray_o, const float2* ray_t, const float4* traced, float4* record,
+                                const MeshReflectionList& R, hipStream_t stream) {
+	with_ambient(I, V, VV, [&](const auto& A) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_shade_deferred_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, P, A, C, L, frame_buffer, gbuf, ray_o,
+		                   ray_t, traced, record, R);
+	});
 }
-void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min, uint32_t n_pixels,
-                                 const float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	hipLaunchKernelGGL(mesh_reflection_rays_kernel, blocks, threads, 0, stream, S, C, shard_index, shard_count, packed, t_min, n_pixels, gbuf, ray_o, ray_d, ray_t);
+void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
+                                 float2* ray_t, hipStream_t stream) {
+	hipLaunchKernelGGL(mesh_reflection_rays_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, C, L, t_min, gbuf, ray_o, ray_d, ray_t);
 }
 
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)
@@ -1245,21 +1173,16 @@ NGP_DEV float4 nerf_over_mesh(float4 fb, float4 n, float f) {
 	return fb;
 }
 __global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShadeParams P, const ModelParams M, const CameraParams C, float4* __restrict__ frame_buffer,
-                                        const float* __restrict__ depth_buffer, const float4* __restrict__ nerf, float4* __restrict__ record, uint32_t shard_index,
-                                        uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving || idx >= n_pixels) return;
+                                        const float* __restrict__ depth_buffer, const float4* __restrict__ nerf, float4* __restrict__ record, const FrameLayout L,
+                                        float strength, float bias) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
 	const float4 n = nerf[idx];
 	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here: the pixel stays the mesh pass's
 	float f = 1.0f;
 	if (n.w > 0.2f) {
 		const f3 p = nerf_surface_point(M, C, x, y, depth_buffer[idx]); // (render_common.h: the one definition of p)
-		const f3 sdir = normalize3(normalize3(ld3(P.sun_dir)));
+		const f3 sdir = shadow_ray_dir(P);
 		const bool blocked = any_hit(S, add3(p, scale3(sdir, bias)), sdir);
 		if (blocked) f = 1.0f - strength;
 		record[idx] = make_float4(p.x, p.y, p.z, blocked ? 2.0f : 1.0f);
@@ -1268,12 +1191,8 @@ __global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShade
 }
 
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
-                             const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
-                             hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, blocks, threads, 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, shard_index, shard_count, packed, n_pixels, strength,
-	                   bias);
+                             const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias, hipStream_t stream) {
+	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, L, strength, bias);
 }
 
 // ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf; contract in include/ngp_hip.h, "ambient").
@@ -1326,15 +1245,9 @@ __global__ void nerf_ambient_ratio_kernel(const IrradianceVolume after, const Ir
 }
 // the closing composite of such a frame while ngp_set_mesh_shadow_on_nerf is off: nerf_mesh_shadow_kernel's expression with f = 1, no
 // traversal and no record
-__global__ void nerf_composite_kernel(const CameraParams C, float4* __restrict__ frame_buffer, const float4* __restrict__ nerf, uint32_t shard_index, uint32_t shard_count,
-                                      int packed, uint32_t n_pixels) {
-	uint32_t x = threadIdx.x + blockDim.x * blockIdx.x;
-	uint32_t y = threadIdx.y + blockDim.y * blockIdx.y;
-	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return;
-	uint32_t tile = (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3);
-	if (tile % shard_count != shard_index) return;
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
-	if (C.moving || idx >= n_pixels) return;
+__global__ void nerf_composite_kernel(const CameraParams C, float4* __restrict__ frame_buffer, const float4* __restrict__ nerf, const FrameLayout L) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
 	const float4 n = nerf[idx];
 	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here: the pixel stays the mesh pass's
 	frame_buffer[idx] = nerf_over_mesh(frame_buffer[idx], n, 1.0f);
@@ -1348,11 +1261,8 @@ void launch_nerf_ambient_ratio(const IrradianceVolume& after, const IrradianceVo
                                float max_gain, hipStream_t stream) {
 	if (n_pixels) hipLaunchKernelGGL(nerf_ambient_ratio_kernel, dim3((n_pixels + 127) / 128), dim3(128), 0, stream, after, before, n_pixels, nerf, record, min_irradiance, max_gain);
 }
-void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels,
-                           hipStream_t stream) {
-	dim3 threads(16, 8, 1);
-	dim3 blocks((C.width + 15) / 16, (C.height + 7) / 8, 1);
-	hipLaunchKernelGGL(nerf_composite_kernel, blocks, threads, 0, stream, C, frame_buffer, nerf, shard_index, shard_count, packed, n_pixels);
+void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, const FrameLayout& L, hipStream_t stream) {
+	hipLaunchKernelGGL(nerf_composite_kernel, pixel_blocks(C), pixel_threads(), 0, stream, C, frame_buffer, nerf, L);
 }
 
 } // namespace ngp

@@ -1011,8 +1011,8 @@ __global__ __launch_bounds__(BLOCK) void density_gradient_kernel(const ModelPara
 // export's rule (density_normal). record, 3 float4 a pixel: (p, 2 / 1 where the gradient gives no normal), (N, 0), (1, 1, 1, 0); left as
 // the host cleared it where the pixel owns no point. Grid-encoded models only (the host refuses the wide ones).
 __global__ __launch_bounds__(BLOCK) void nerf_surface_normals_kernel(const ModelParams M, const CameraParams C, const float* __restrict__ depth_buffer,
-                                                                     const float4* __restrict__ nerf, float4* __restrict__ record, uint32_t shard_index,
-                                                                     uint32_t shard_count, int packed, uint32_t n_pixels, uint32_t n_tiles) {
+                                                                     const float4* __restrict__ nerf, float4* __restrict__ record, const FrameLayout L,
+                                                                     uint32_t n_tiles) {
 	if (C.moving) return; // (the host refuses a moving camera with meshes; said first, the static camera's ray set-up is all that is compiled in)
 	__shared__ uint4 s_w[FRAG_R0 * 64];
 	__shared__ LevelInfo s_lv[N_LEVELS];
@@ -1023,8 +1023,8 @@ __global__ __launch_bounds__(BLOCK) void nerf_surface_normals_kernel(const Model
 	const uint32_t tiles_x = ((uint32_t)C.width + 7u) >> 3;
 	const uint32_t tile = (blockIdx.x * BLOCK + threadIdx.x) >> 6; // (wave-uniform)
 	const uint32_t x = (tile % tiles_x) * 8u + ((uint32_t)lane & 7u), y = (tile / tiles_x) * 8u + ((uint32_t)lane >> 3);
-	const uint32_t idx = packed ? (tile / shard_count) * 64u + (uint32_t)lane : x + (uint32_t)C.width * y;
-	const bool mine = tile < n_tiles && tile % shard_count == shard_index && x < (uint32_t)C.width && y < (uint32_t)C.height && idx < n_pixels;
+	uint32_t idx = 0;
+	const bool mine = tile < n_tiles && frame_tile_pixel(L, C, tile, x, y, idx); // (the pixel's slot (x & 7) + 8 (y & 7) is the lane)
 	const bool owner = mine && nerf[idx].w > 0.2f;
 	const unsigned long long owners = __ballot(owner);
 	if (owners == 0ull) return;
@@ -1469,12 +1469,11 @@ void launch_density_gradient(const ModelParams& M, uint32_t n, const float* pos0
 	if (n == 0) return;
 	hipLaunchKernelGGL(density_gradient_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, M, n, pos01, out);
 }
-void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const float* depth_buffer, const float4* nerf, float4* record, uint32_t shard_index,
-                                 uint32_t shard_count, int packed, uint32_t n_pixels, hipStream_t stream) {
+void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const FrameLayout& L, const float* depth_buffer, const float4* nerf, float4* record,
+                                 hipStream_t stream) {
 	const uint32_t n_tiles = (((uint32_t)C.width + 7u) >> 3) * (((uint32_t)C.height + 7u) >> 3); // one wave a tile, BLOCK / 64 tiles a block
 	if (n_tiles == 0) return;
-	hipLaunchKernelGGL(nerf_surface_normals_kernel, dim3((n_tiles + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, M, C, depth_buffer, nerf, record, shard_index, shard_count,
-	                   packed, n_pixels, n_tiles);
+	hipLaunchKernelGGL(nerf_surface_normals_kernel, dim3((n_tiles + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, M, C, depth_buffer, nerf, record, L, n_tiles);
 }
 void launch_density_grid_update(const ModelParams& M, uint32_t n_samples, const Pcg32& rng, uint32_t step, uint32_t n_cascades, float thresh, const float* grid,
                                 float* grid_tmp, hipStream_t stream) {

@@ -141,28 +141,28 @@ void launch_coarse_occupancy(const uint8_t* bitfield, uint32_t* coarse, hipStrea
 void launch_accumulate_tonemap(uint32_t n_pixels, const float4* frame_buffer, float4* accumulate_buffer, float sample_count, const float* background,
                                float exposure, int to_srgb, int color_space, float4* rgba_out, hipStream_t stream);
 
+// the frame's one-thread-a-pixel passes; L: the pixels the launch owns and the extent of every per-pixel buffer (FrameLayout, ngp_kernels.h)
 void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
-                        const CameraParams& C, float4* frame_buffer, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
+                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer,
                         hipStream_t stream); // V: the ShadeIrradianceVolume instantiation; VV: the one that weights the probes by visibility
-void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, float* depth_buffer, uint32_t shard_index, uint32_t shard_count, int packed,
-                         float t_min, uint32_t n_pixels, float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
+void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, const FrameLayout& L, float* depth_buffer, float t_min, float4* gbuf,
+                         float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
-                                float4* frame_buffer, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, const float4* gbuf, const float* ray_o,
-                                const float2* ray_t, const float4* traced, float4* record, const MeshReflectionList& R,
+                                const FrameLayout& L, float4* frame_buffer, const float4* gbuf, const float* ray_o, const float2* ray_t, const float4* traced, float4* record,
+                                const MeshReflectionList& R,
                                 hipStream_t stream); // M5 of launch_render_mesh behind the trace(s); traced == nullptr: no shadow trace was run (T_s = 1, no record)
-void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, uint32_t shard_index, uint32_t shard_count, int packed, float t_min, uint32_t n_pixels,
-                                 const float4* gbuf, float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // the G-buffer's mirror rays (ngp_set_mesh_reflection)
+void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
+                                 float2* ray_t, hipStream_t stream); // the G-buffer's mirror rays (ngp_set_mesh_reflection)
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
-                             const float4* nerf, float4* record, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels, float strength, float bias,
+                             const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
 // ngp_set_ambient_change_on_nerf: the NeRF's normal at every owner pixel's surface point (record: 3 float4 a pixel), then g = E_after / E_before
 // there, n.rgb scaled in place; launch_nerf_composite closes the frame when the meshes' shadow on the NeRF is off (f = 1, no traversal)
-void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const float* depth_buffer, const float4* nerf, float4* record, uint32_t shard_index,
-                                 uint32_t shard_count, int packed, uint32_t n_pixels, hipStream_t stream);
+void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const FrameLayout& L, const float* depth_buffer, const float4* nerf, float4* record,
+                                 hipStream_t stream);
 void launch_nerf_ambient_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n_pixels, float4* nerf, float4* record, float min_irradiance,
                                float max_gain, hipStream_t stream);
-void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, uint32_t shard_index, uint32_t shard_count, int packed, uint32_t n_pixels,
-                           hipStream_t stream);
+void launch_nerf_composite(const CameraParams& C, float4* frame_buffer, const float4* nerf, const FrameLayout& L, hipStream_t stream);
 void launch_irradiance_volume_ratio(const IrradianceVolume& after, const IrradianceVolume& before, uint32_t n, const float* positions, const float* normals, float min_irradiance,
                                     float max_gain, float4* out, hipStream_t stream);
 void launch_trace_probe(const ModelParams& M, const FrameParams& F, const ProbeParams& P, int n_cus, hipStream_t stream);
@@ -310,6 +310,67 @@ struct TrainState {
 	bool batch_ready = false;
 	TrainStepParams last_step{};
 };
+
+constexpr int FRAME_HISTORY = 256; // the render calls whose slot, events and flags a context keeps (ngp_ctx::HISTORY)
+
+// What an optional pass of a frame keeps for its getters (ngp_get_frame_*, ngp_get_frame_*_ms): the per-pixel record of the frame's last
+// sample, events around the pass in that sample, and which calls of the ring ran it. Everything is allocated when a frame first uses the
+// option and grown as ensure_frame_buffers grows (releasing device memory waits for the device: nothing goes under a frame in flight). The
+// record is allocated last and holds the size of the option's scratch too: ensure() says that n_pixels do not fit, the caller then
+// releases all of its scratch, allocates it anew and calls grow().
+struct FramePass {
+	explicit FramePass(uint32_t stride) : stride(stride) {}
+	uint32_t stride; // float4 a pixel of the record
+	DevArray<float4> record;
+	Event ev0[FRAME_HISTORY], ev1[FRAME_HISTORY];
+	bool hist[FRAME_HISTORY] = {}; // the slot's call was a frame that ran the pass
+	size_t n_pixels = 0;           // pixels of the last such frame
+	bool ensure(size_t n) {
+		if (!ev1[FRAME_HISTORY - 1]) {
+			for (int i = 0; i < FRAME_HISTORY; ++i) {
+				ev0[i] = new_event();
+				ev1[i] = new_event();
+			}
+		}
+		if ((size_t)stride * n <= record.size()) return false;
+		record.reset();
+		return true;
+	}
+	void grow(size_t n) { record.reset((size_t)stride * n); }
+	void clear(size_t n, hipStream_t stream) const { NGP_HIP_CHECK(hipMemsetAsync(record.get(), 0, (size_t)stride * n * sizeof(float4), stream)); }
+	// around the pass; the events of a frame's last sample are the ones read_ms reads
+	void begin(int slot, hipStream_t stream, bool last) const { if (last) NGP_HIP_CHECK(hipEventRecord(ev0[slot], stream)); }
+	void end(int slot, hipStream_t stream, bool last) const { if (last) NGP_HIP_CHECK(hipEventRecord(ev1[slot], stream)); }
+	void ran(int slot, bool on, size_t n) {
+		hist[slot] = on;
+		if (on) n_pixels = n;
+	}
+	// ngp_render.cpp: the last frame's record (`none`: the refusal after a frame without the pass) and the pass's device time (0 after such a frame)
+	void read_record(ngp_ctx* ctx, float* out, size_t n, const char* none) const;
+	void read_ms(ngp_ctx* ctx, float* ms) const;
+};
+
+// a ray list for the ray-list tracer with one entry a local pixel of a frame, in the frame's pixel order and not compacted
+struct RayList {
+	DevArray<float> o, d;
+	DevArray<float2> t;
+	DevArray<float4> traced;                    // the tracer's rgba of the list
+	DevArray<unsigned long long> results;       // where the trace's counters go: the slot's results stay the NeRF pass's
+	void release() { o.reset(), d.reset(), t.reset(), traced.reset(); }
+	void allocate(size_t n) {
+		if (!results) {
+			results.reset(8);
+			NGP_HIP_CHECK(hipMemset(results.get(), 0, results.bytes()));
+		}
+		o.reset(3 * n);
+		d.reset(3 * n);
+		t.reset(n);
+		traced.reset(n);
+		// (list entries no pixel of a frame owns -- another shard's, a partial tile's -- are dead through their t alone; their o and d are never garbage)
+		NGP_HIP_CHECK(hipMemset(o.get(), 0, o.bytes()));
+		NGP_HIP_CHECK(hipMemset(d.get(), 0, d.bytes()));
+	}
+};
 } // namespace ngp
 
 struct ngp_ctx {
@@ -385,7 +446,7 @@ struct ngp_ctx {
 	ngp::DevArray<float4> d_rgba;
 	// a ring of per-call slots of 80 B: accumulators [alive, hit, samples], {tile queue, exited waves}, results [alive, hit, samples, device ticks], start stamp.
 	// Zeroed once; every launch's last wave leaves its slot's first four words zero again (nerf_kernels.hip fused_body)
-	static constexpr int HISTORY = 256;
+	static constexpr int HISTORY = ngp::FRAME_HISTORY;
 	static constexpr size_t SLOT_BYTES = 128;
 	ngp::DevArray<char> d_sync;
 	void bind_slot(ngp::FrameParams& F, int slot) const {
@@ -405,46 +466,29 @@ struct ngp_ctx {
 	// ---- the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow); a peer's copy follows the primary's with the geometry
 	bool sun_nerf_shadow = false;
 	ngp_irradiance_sun_nerf_desc sun_nerf_shadow_desc{};
-	// its per-pixel scratch, allocated when a frame first uses the option and grown like the frame buffers (d_ss_record, allocated last, holds the size of all)
-	ngp::DevArray<float4> d_ss_gbuf;   // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle)
-	ngp::DevArray<float> d_ss_o, d_ss_d; // the shadow-ray list, one entry a local pixel
-	ngp::DevArray<float2> d_ss_t;
-	ngp::DevArray<float4> d_ss_traced; // the tracer's rgba of the list
-	ngp::DevArray<float4> d_ss_record; // (q, alpha_s) of the last sample (ngp_get_frame_sun_shadow)
-	ngp::DevArray<unsigned long long> d_ss_results; // where the shadow trace's counters go: the slot's results stay the NeRF pass's
-	ngp::Event ev_ss0[HISTORY], ev_ss1[HISTORY]; // around prep + trace of a frame's last sample (ngp_get_frame_sun_shadow_ms)
-	bool hist_sun_shadow[HISTORY] = {};                  // the slot's call was a frame that traced shadow rays
-	size_t ss_n_pixels = 0;                                    // pixels of the last such frame
+	// (q, alpha_s) a pixel of the last sample (ngp_get_frame_sun_shadow); events around prep + trace (ngp_get_frame_sun_shadow_ms). Its scratch:
+	ngp::FramePass pass_sun_shadow{1};
+	ngp::DevArray<float4> d_ss_gbuf; // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle)
+	ngp::RayList ss_rays;            // the shadow-ray list
 	// ---- the meshes in front of the sun on the NeRF (ngp_set_mesh_shadow_on_nerf); a peer's copy follows the primary's with the geometry
 	bool mesh_shadow_on_nerf = false;
 	ngp_mesh_shadow_on_nerf_desc mesh_shadow_on_nerf_desc{};
-	// its per-pixel buffers, allocated when a frame first uses the option and grown like the frame buffers (d_ms_record, allocated last, holds the size of both)
-	ngp::DevArray<float4> d_ms_nerf;   // where the NeRF launch composites instead of the frame: premultiplied (r, g, b, a), zeros where it wrote nothing
-	ngp::DevArray<float4> d_ms_record; // (p, 2 blocked / 1 open) of the last sample (ngp_get_frame_mesh_shadow)
-	ngp::Event ev_ms0[HISTORY], ev_ms1[HISTORY]; // around nerf_mesh_shadow_kernel of a frame's last sample (ngp_get_frame_mesh_shadow_ms)
-	bool hist_mesh_shadow[HISTORY] = {};         // the slot's call was a frame that ran the pass
-	size_t ms_n_pixels = 0;                      // pixels of the last such frame
+	// (p, 2 blocked / 1 open) a pixel of the last sample (ngp_get_frame_mesh_shadow); events around nerf_mesh_shadow_kernel (ngp_get_frame_mesh_shadow_ms)
+	ngp::FramePass pass_mesh_shadow{1};
+	ngp::DevArray<float4> d_ms_nerf; // its scratch, where the NeRF launch composites instead of the frame: premultiplied (r, g, b, a), zeros where it wrote nothing
 	// ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf); a peer's copy follows the primary's with the geometry
 	bool ambient_change_on_nerf = false;
 	ngp_ambient_change_desc ambient_change_desc{};
-	// its per-pixel record, allocated when a frame first uses the option and grown like the frame buffers (the scratch is d_ms_nerf)
-	ngp::DevArray<float4> d_ac_record; // 3 float4 a pixel: (p, state), (N, W_after), (g, W_before) of the last sample (ngp_get_frame_ambient_change)
-	ngp::Event ev_ac0[HISTORY], ev_ac1[HISTORY]; // around the normals and ratio kernels of a frame's last sample (ngp_get_frame_ambient_change_ms)
-	bool hist_ambient_change[HISTORY] = {};      // the slot's call was a frame that ran the pass
-	size_t ac_n_pixels = 0;                      // pixels of the last such frame
+	// (p, state), (N, W_after), (g, W_before) a pixel of the last sample (ngp_get_frame_ambient_change); events around the normals and ratio kernels
+	// (ngp_get_frame_ambient_change_ms). The scratch is the mesh shadow's d_ms_nerf.
+	ngp::FramePass pass_ambient_change{3};
 	// ---- the NeRF mirrored in the meshes (ngp_set_mesh_reflection); a peer's copy follows the primary's with the geometry
 	bool mesh_reflection = false;
 	ngp_mesh_reflection_desc mesh_reflection_desc{};
-	// its per-pixel scratch, allocated when a frame first uses the option and grown like the frame buffers (d_mr_record, allocated last, holds
-	// the size of all). The G-buffer and the shadow list its frames fill are the sun shadow's (d_ss_*).
-	ngp::DevArray<float> d_mr_o, d_mr_d; // the reflection-ray list, one entry a local pixel
-	ngp::DevArray<float2> d_mr_t;
-	ngp::DevArray<float4> d_mr_traced; // the tracer's rgba of the list
-	ngp::DevArray<float4> d_mr_record; // 3 float4 a pixel: (q, t_hit), (r, 0), (rgb_r, alpha_r) of the last sample (ngp_get_frame_mesh_reflection)
-	ngp::DevArray<unsigned long long> d_mr_results; // where the reflection trace's counters go: the slot's results stay the NeRF pass's
-	ngp::Event ev_mr0[HISTORY], ev_mr1[HISTORY]; // around prep + trace of a frame's last sample (ngp_get_frame_mesh_reflection_ms)
-	bool hist_mesh_reflection[HISTORY] = {};     // the slot's call was a frame that traced reflection rays
-	size_t mr_n_pixels = 0;                      // pixels of the last such frame
+	// (q, t_hit), (r, 0), (rgb_r, alpha_r) a pixel of the last sample (ngp_get_frame_mesh_reflection); events around prep + trace
+	// (ngp_get_frame_mesh_reflection_ms). The G-buffer and the shadow list its frames fill are the sun shadow's (d_ss_gbuf, ss_rays).
+	ngp::FramePass pass_mesh_reflection{3};
+	ngp::RayList mr_rays; // its scratch: the reflection-ray list
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a

@@ -138,6 +138,14 @@ struct CameraParams {
 	int32_t moving;
 };
 
+// which pixels of the camera a launch of a frame's one-thread-a-pixel passes owns and where they go (frame_pixel, render_common.h): the
+// 8 x 8 camera tiles are dealt round-robin to shard_count ranks; packed: pixel (local tile q, slot s) sits at 64 q + s, else at x + W y
+struct FrameLayout {
+	uint32_t shard_index, shard_count;
+	uint32_t n_pixels; // the extent of every per-pixel buffer: the rank's tile share times 64 (packed) or the whole image
+	int32_t packed;
+};
+
 struct FrameParams {
 	float4* frame_buffer;
 	float* depth_buffer;

@@ -229,82 +229,197 @@ void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ctx->d_rgba.reset(n_pixels);
 }
 
-// the per-pixel scratch of a frame with the NeRF in front of its sun (ngp_set_sun_nerf_shadow): allocated by the first frame that uses the
-// option, grown as ensure_frame_buffers grows (releasing device memory waits for the device: nothing goes under a frame in flight)
-void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	if (!ctx->d_ss_results) {
-		ctx->d_ss_results.reset(8);
-		NGP_HIP_CHECK(hipMemset(ctx->d_ss_results.get(), 0, 8 * sizeof(unsigned long long)));
-		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-			ctx->ev_ss0[i] = new_event();
-			ctx->ev_ss1[i] = new_event();
-		}
-	}
-	if (n_pixels <= ctx->d_ss_record.size()) return;
-	ctx->d_ss_gbuf.reset(), ctx->d_ss_o.reset(), ctx->d_ss_d.reset(), ctx->d_ss_t.reset(), ctx->d_ss_traced.reset(), ctx->d_ss_record.reset();
+void FramePass::read_record(ngp_ctx* ctx, float* out, size_t n, const char* none) const {
+	require_device(ctx);
+	if (!out) throw std::runtime_error("null argument");
+	if (!ctx->n_calls || !hist[(ctx->n_calls - 1) % FRAME_HISTORY]) throw std::runtime_error(none);
+	if (n != n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(n_pixels) + " pixels on this device");
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+	NGP_HIP_CHECK(hipMemcpy(out, record.get(), stride * n * sizeof(float4), hipMemcpyDeviceToHost));
+}
+void FramePass::read_ms(ngp_ctx* ctx, float* ms) const {
+	require_device(ctx);
+	if (!ms) throw std::runtime_error("null argument");
+	*ms = 0.f;
+	if (!ctx->n_calls) return;
+	const int slot = (int)((ctx->n_calls - 1) % FRAME_HISTORY);
+	if (!hist[slot]) return;
+	NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+	NGP_HIP_CHECK(hipEventElapsedTime(ms, ev0[slot], ev1[slot]));
+}
+
+// ---- the optional passes' buffers. Who owns what: the G-buffer and the shadow list are the sun shadow's, and a frame with mirror rays
+// fills them too; the scratch d_ms_nerf is the mesh shadow's, and a frame with the ambient change composites into it too.
+static void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->pass_sun_shadow.ensure(n_pixels)) return;
+	ctx->d_ss_gbuf.reset(), ctx->ss_rays.release(); // all go before the new ones come
 	ctx->d_ss_gbuf.reset(3 * n_pixels);
-	ctx->d_ss_o.reset(3 * n_pixels);
-	ctx->d_ss_d.reset(3 * n_pixels);
-	ctx->d_ss_t.reset(n_pixels);
-	ctx->d_ss_traced.reset(n_pixels);
-	ctx->d_ss_record.reset(n_pixels);
-	// (list entries no pixel of a frame owns -- another shard's, a partial tile's -- are dead through their t alone; their o and d are never garbage)
-	NGP_HIP_CHECK(hipMemset(ctx->d_ss_o.get(), 0, ctx->d_ss_o.bytes()));
-	NGP_HIP_CHECK(hipMemset(ctx->d_ss_d.get(), 0, ctx->d_ss_d.bytes()));
+	ctx->ss_rays.allocate(n_pixels);
+	ctx->pass_sun_shadow.grow(n_pixels);
 }
-
-// the per-pixel scratch of a frame whose meshes mirror the NeRF (ngp_set_mesh_reflection): allocated by the first frame that uses the option,
-// grown as ensure_frame_buffers grows. The G-buffer and the shadow list such a frame fills are ensure_sun_shadow_buffers'.
-void ensure_mesh_reflection_buffers(ngp_ctx* ctx, size_t n_pixels) {
+static void ensure_mesh_reflection_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ensure_sun_shadow_buffers(ctx, n_pixels);
-	if (!ctx->d_mr_results) {
-		ctx->d_mr_results.reset(8);
-		NGP_HIP_CHECK(hipMemset(ctx->d_mr_results.get(), 0, 8 * sizeof(unsigned long long)));
-		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-			ctx->ev_mr0[i] = new_event();
-			ctx->ev_mr1[i] = new_event();
-		}
-	}
-	if (3 * n_pixels <= ctx->d_mr_record.size()) return;
-	ctx->d_mr_o.reset(), ctx->d_mr_d.reset(), ctx->d_mr_t.reset(), ctx->d_mr_traced.reset(), ctx->d_mr_record.reset();
-	ctx->d_mr_o.reset(3 * n_pixels);
-	ctx->d_mr_d.reset(3 * n_pixels);
-	ctx->d_mr_t.reset(n_pixels);
-	ctx->d_mr_traced.reset(n_pixels);
-	ctx->d_mr_record.reset(3 * n_pixels);
-	// (list entries no pixel of a frame owns are dead through their t alone; their o and d are never garbage)
-	NGP_HIP_CHECK(hipMemset(ctx->d_mr_o.get(), 0, ctx->d_mr_o.bytes()));
-	NGP_HIP_CHECK(hipMemset(ctx->d_mr_d.get(), 0, ctx->d_mr_d.bytes()));
+	if (!ctx->pass_mesh_reflection.ensure(n_pixels)) return;
+	ctx->mr_rays.release();
+	ctx->mr_rays.allocate(n_pixels);
+	ctx->pass_mesh_reflection.grow(n_pixels);
 }
-
-// the per-pixel buffers of a frame whose meshes shadow the NeRF (ngp_set_mesh_shadow_on_nerf): allocated by the first frame that uses the
-// option, grown as ensure_frame_buffers grows
-void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	if (!ctx->ev_ms0[0]) {
-		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-			ctx->ev_ms0[i] = new_event();
-			ctx->ev_ms1[i] = new_event();
-		}
-	}
-	if (n_pixels <= ctx->d_ms_record.size()) return;
-	ctx->d_ms_nerf.reset(), ctx->d_ms_record.reset();
+static void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->pass_mesh_shadow.ensure(n_pixels)) return;
 	ctx->d_ms_nerf.reset(n_pixels);
-	ctx->d_ms_record.reset(n_pixels);
+	ctx->pass_mesh_shadow.grow(n_pixels);
+}
+static void ensure_ambient_change_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	ensure_mesh_shadow_buffers(ctx, n_pixels);
+	if (ctx->pass_ambient_change.ensure(n_pixels)) ctx->pass_ambient_change.grow(n_pixels);
 }
 
-// the per-pixel record of a frame whose NeRF pixels follow the meshes' change of the ambient light (ngp_set_ambient_change_on_nerf): allocated
-// by the first frame that uses the option, grown as ensure_frame_buffers grows. The scratch is ensure_mesh_shadow_buffers' d_ms_nerf.
-void ensure_ambient_change_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	ensure_mesh_shadow_buffers(ctx, n_pixels);
-	if (!ctx->ev_ac0[0]) {
-		for (int i = 0; i < ngp_ctx::HISTORY; ++i) {
-			ctx->ev_ac0[i] = new_event();
-			ctx->ev_ac1[i] = new_event();
-		}
+// Which passes a frame runs. The four options apply to a hybrid frame -- Geometry mode, meshes and a model (always the general path) --
+// and all but the sun shadow to the four shade modes alone. Resolved once a call, with the options' refusals and buffers, before
+// anything is enqueued; all of a frame's work then goes onto its stream and nothing waits.
+struct FramePlan {
+	bool have_meshes = false;    // a Geometry frame with meshes: it has a mesh pass
+	bool sun_shadow = false;     // the NeRF in front of the frames' sun: the mesh pass is split around one ray-list trace per sample
+	bool reflection = false;     // the NeRF mirrored in the meshes: the split mesh pass with a ray list of its own
+	bool mesh_shadow = false;    // the meshes in front of the sun on the NeRF: one kernel behind the NeRF launch finishes its composite
+	bool ambient_change = false; // the meshes' change of the ambient light on the NeRF: normals at the owners' surface points, then g = E_after / E_before
+	bool split() const { return sun_shadow || reflection; }
+	bool scratch() const { return mesh_shadow || ambient_change; } // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
+};
+static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_pixels) {
+	FramePlan p;
+	p.have_meshes = opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty();
+	const bool hybrid = p.have_meshes && ctx->model_loaded;
+	const bool shade_mode = opts.render_mode == NGP_RENDER_SHADE || opts.render_mode == NGP_RENDER_SHADE_ENVMAP || opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ||
+	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
+	p.sun_shadow = ctx->sun_nerf_shadow && hybrid;
+	if (p.sun_shadow) {
+		require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
+		ensure_sun_shadow_buffers(ctx, n_pixels);
 	}
-	if (3 * n_pixels <= ctx->d_ac_record.size()) return;
-	ctx->d_ac_record.reset();
-	ctx->d_ac_record.reset(3 * n_pixels);
+	// (strength 0 adds nothing: no trace is run and the frame takes the path it would take with the option off)
+	p.reflection = ctx->mesh_reflection && ctx->mesh_reflection_desc.strength > 0.0f && hybrid && shade_mode;
+	if (p.reflection) {
+		require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
+		ensure_mesh_reflection_buffers(ctx, n_pixels);
+	}
+	p.mesh_shadow = ctx->mesh_shadow_on_nerf && hybrid && shade_mode;
+	if (p.mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels);
+	p.ambient_change = ctx->ambient_change_on_nerf && hybrid && shade_mode;
+	if (p.ambient_change) {
+		if (!ctx->d_sh_volume) throw std::runtime_error("ambient_change_on_nerf frames need the irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+		if (!ctx->d_sh_reference)
+			throw std::runtime_error("ambient_change_on_nerf frames need the reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
+		if (ctx->M.wide.width) throw std::runtime_error("ambient_change_on_nerf frames need a grid-encoded model (ngp_set_ambient_change_on_nerf)");
+		ensure_ambient_change_buffers(ctx, n_pixels);
+	}
+	return p;
+}
+
+// what the steps of one sample share
+struct FrameCall {
+	ngp_ctx* ctx;
+	FramePlan plan;
+	FrameLayout L;
+	int slot;
+	hipStream_t stream;
+};
+
+// one ray list of a sample's split mesh pass: clear, `fill` (the kernel that writes the pixels' entries), and with `trace` prep -> trace,
+// between the pass's events. The trace borrows the slot's queue ahead of the NeRF launch and reports into the list's own results.
+template <typename Fill>
+static void trace_pixel_rays(const FrameCall& f, const ModelParams& M, const RayList& rays, const FramePass& pass, bool trace, float min_transmittance, bool last, Fill&& fill) {
+	const uint32_t n = f.L.n_pixels;
+	NGP_HIP_CHECK(hipMemsetAsync(rays.t.get(), 0, (size_t)n * sizeof(float2), f.stream)); // entries no pixel owns stay dead
+	if (trace) pass.clear(n, f.stream);
+	fill();
+	if (!trace) return;
+	pass.begin(f.slot, f.stream, last);
+	launch_ray_list_prep(M, n, rays.o.get(), rays.d.get(), rays.t.get(), true, f.stream);
+	FrameParams FT{};
+	tracer_frame_params(f.ctx, f.slot, min_transmittance, FT);
+	FT.results = rays.results.get();
+	if (n) launch_probe_trace(f.ctx, M, FT, ray_list_params(n, rays.o.get(), rays.d.get(), rays.t.get(), rays.traced.get(), nullptr), false, f.stream); // (a shard without tiles traces nothing)
+	pass.end(f.slot, f.stream, last);
+}
+
+// the mesh pass of a sample into d_frame and the depth buffer: fused, or G-buffer -> per list: prep -> trace -> deferred shade
+static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const ModelParams& M, const CameraParams& C, const FrameParams& F, bool last) {
+	ngp_ctx* ctx = f.ctx;
+	IrradianceMap I{};
+	if (opts.render_mode == NGP_RENDER_SHADE_ENVMAP) {
+		if (!ctx->d_irradiance || ctx->env_probe.mode == 3) throw std::runtime_error("render_mode ShadeEnvMap needs ngp_compute_envmap first");
+		I = irradiance_map_of(ctx);
+	} else if (opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP) {
+		if (!ctx->d_irradiance || ctx->env_probe.mode != 3) throw std::runtime_error("render_mode ShadeGridEnvMap needs ngp_compute_envmap_grid first");
+		I = irradiance_map_of(ctx);
+	}
+	IrradianceVolume V{};
+	const bool volume = opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
+	if (volume) {
+		if (!ctx->d_sh_volume) throw std::runtime_error("render_mode ShadeIrradianceVolume needs ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
+		V = sh_volume_of(ctx);
+	}
+	const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
+	const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
+	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[f.slot], f.stream)); // (ngp_get_mesh_pass_ms)
+	if (f.plan.split()) {
+		const RayList& ss = ctx->ss_rays;
+		trace_pixel_rays(f, M, ss, ctx->pass_sun_shadow, f.plan.sun_shadow, ctx->sun_nerf_shadow_desc.min_transmittance, last, [&] {
+			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), f.stream);
+		});
+		MeshReflectionList R{};
+		if (f.plan.reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
+			const RayList& mr = ctx->mr_rays;
+			trace_pixel_rays(f, M, mr, ctx->pass_mesh_reflection, true, ctx->mesh_reflection_desc.min_transmittance, last, [&] {
+				launch_mesh_reflection_rays(ctx->mesh_scene, C, f.L, ctx->mesh_reflection_desc.t_min, ctx->d_ss_gbuf.get(), mr.o.get(), mr.d.get(), mr.t.get(), f.stream);
+			});
+			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->pass_mesh_reflection.record.get(), ctx->mesh_reflection_desc.strength};
+		}
+		launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), ctx->d_ss_gbuf.get(), ss.o.get(), ss.t.get(),
+		                           f.plan.sun_shadow ? ss.traced.get() : nullptr, ctx->pass_sun_shadow.record.get(), R, f.stream);
+	} else {
+		launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), F.depth_buffer, f.stream);
+	}
+	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[f.slot], f.stream));
+}
+
+// the NeRF launch of sample s: into the frame, or with plan.scratch() over zeros into d_ms_nerf, apart from the mesh pass's pixels (its depth
+// test and depth writes are every frame's)
+static void nerf_pass(const FrameCall& f, const ModelParams& M, const CameraParams& C, FrameParams& F, int s, bool last) {
+	ngp_ctx* ctx = f.ctx;
+	if (f.plan.scratch()) {
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_nerf.get(), 0, (size_t)f.L.n_pixels * sizeof(float4), f.stream));
+		if (f.plan.mesh_shadow) ctx->pass_mesh_shadow.clear(f.L.n_pixels, f.stream);
+		if (f.plan.ambient_change) ctx->pass_ambient_change.clear(f.L.n_pixels, f.stream);
+		F.frame_buffer = ctx->d_ms_nerf.get();
+	}
+	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[f.slot], f.stream));
+	if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, f.stream); // persistent grid sized by the launcher
+	else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, f.stream)); // meshes only: no NeRF launch reports counters
+	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[f.slot], f.stream));
+}
+
+// what closes a sample whose NeRF launch went into the scratch: the scratch's colour follows the ambient light, then its composite over the
+// mesh pass's pixels, scaled where a mesh stands in front of the sun (or plain: f = 1, no traversal)
+static void closing_passes(const FrameCall& f, const ModelParams& M, const CameraParams& C, const FrameParams& F, bool last) {
+	ngp_ctx* ctx = f.ctx;
+	if (f.plan.ambient_change) {
+		const FramePass& pass = ctx->pass_ambient_change;
+		pass.begin(f.slot, f.stream, last);
+		launch_nerf_surface_normals(M, C, f.L, F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.stream);
+		launch_nerf_ambient_ratio(sh_volume_of(ctx), sh_reference_of(ctx), f.L.n_pixels, ctx->d_ms_nerf.get(), pass.record.get(), ctx->ambient_change_desc.min_irradiance,
+		                          ctx->ambient_change_desc.max_gain, f.stream);
+		pass.end(f.slot, f.stream, last);
+		if (!f.plan.mesh_shadow) launch_nerf_composite(C, ctx->d_frame.get(), ctx->d_ms_nerf.get(), f.L, f.stream);
+	}
+	if (f.plan.mesh_shadow) {
+		const FramePass& pass = ctx->pass_mesh_shadow;
+		pass.begin(f.slot, f.stream, last);
+		launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L,
+		                        ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
+		pass.end(f.slot, f.stream, last);
+	}
 }
 
 // Testbed::render_frame (src/testbed.cu:4694-4721) for opts->spp samples; the final image lands in d_rgba_out.
@@ -316,38 +431,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	// frame-buffer extent: the whole image, or only this shard's tiles in tile-packed order
 	const size_t n_pixels = opts.packed_output ? (size_t)tile_share(cam.width, cam.height, opts.shard_index, shard_count_of(opts)) * 64 : (size_t)cam.width * cam.height;
 	ensure_frame_buffers(ctx, n_pixels ? n_pixels : 1);
-	// the NeRF in front of the frames' sun: a Geometry frame with meshes and a model (always the general path). The mesh pass is split
-	// around one ray-list trace per sample, all of it on `stream`; nothing waits.
-	const bool sun_shadow = ctx->sun_nerf_shadow && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded;
-	if (sun_shadow) {
-		require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
-		ensure_sun_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
-	}
-	// the meshes in front of the sun on the NeRF: the same frames, in the four shade modes. The NeRF launch composites into a scratch of
-	// its own and one kernel behind it finishes the composite over the mesh pass's pixels, all of it on `stream`; nothing waits.
-	const bool shade_mode = opts.render_mode == NGP_RENDER_SHADE || opts.render_mode == NGP_RENDER_SHADE_ENVMAP || opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ||
-	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
-	// the NeRF mirrored in the meshes: the same frames, in the four shade modes, through the split mesh pass with a ray list of its own
-	// (strength 0 adds nothing: no trace is run and the frame takes the path it would take with the option off)
-	const bool reflection = ctx->mesh_reflection && ctx->mesh_reflection_desc.strength > 0.0f && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() &&
-	                        ctx->model_loaded && shade_mode;
-	if (reflection) {
-		require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
-		ensure_mesh_reflection_buffers(ctx, n_pixels ? n_pixels : 1);
-	}
-	const bool mesh_shadow = ctx->mesh_shadow_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
-	if (mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels ? n_pixels : 1);
-	// what the meshes change in the ambient light on the NeRF: the same frames. Behind the NeRF launch into the scratch, one kernel forms the
-	// NeRF's normal at every owner pixel's surface point and one scales the pixel by E_after / E_before there, ahead of the closing composite.
-	const bool ambient_change = ctx->ambient_change_on_nerf && opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty() && ctx->model_loaded && shade_mode;
-	if (ambient_change) {
-		if (!ctx->d_sh_volume) throw std::runtime_error("ambient_change_on_nerf frames need the irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
-		if (!ctx->d_sh_reference)
-			throw std::runtime_error("ambient_change_on_nerf frames need the reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
-		if (ctx->M.wide.width) throw std::runtime_error("ambient_change_on_nerf frames need a grid-encoded model (ngp_set_ambient_change_on_nerf)");
-		ensure_ambient_change_buffers(ctx, n_pixels ? n_pixels : 1);
-	}
-	const bool scratch = mesh_shadow || ambient_change; // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
+	const FramePlan plan = plan_frame(ctx, opts, n_pixels ? n_pixels : 1);
 	const int spp = opts.spp > 0 ? opts.spp : 1;
 	const int slot = (int)(ctx->n_calls % ngp_ctx::HISTORY);
 	// Call k reuses the queue word, exit counter and accumulators of call k - HISTORY, which may have been issued on another stream and,
@@ -358,7 +442,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	FrameParams F{};
 	ModelParams M = ctx->M;
 	make_frame_params(ctx, cam, opts, d_depth_out, slot, spp, stream, F, M);
-	const bool have_meshes = opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty();
+	const FrameCall f{ctx, plan, FrameLayout{F.shard_index, F.shard_count, (uint32_t)n_pixels, F.packed}, slot, stream};
 
 	order_after_model(ctx, stream); // a training step / grid refresh / peer copy that updated what this frame reads (a device-side wait)
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame0[slot], stream));
@@ -385,100 +469,20 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 		NGP_HIP_CHECK(hipMemsetAsync(F.depth_buffer, 0, n_pixels * sizeof(float), stream));
 		F.add_results = s > 0 ? 1 : 0; // the call's counters are the sums over its samples per pixel
 		const bool last = s == spp - 1;
-		if (have_meshes) {
-			IrradianceMap I{};
-			if (opts.render_mode == NGP_RENDER_SHADE_ENVMAP) {
-				if (!ctx->d_irradiance || ctx->env_probe.mode == 3) throw std::runtime_error("render_mode ShadeEnvMap needs ngp_compute_envmap first");
-				I = irradiance_map_of(ctx);
-			} else if (opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP) {
-				if (!ctx->d_irradiance || ctx->env_probe.mode != 3) throw std::runtime_error("render_mode ShadeGridEnvMap needs ngp_compute_envmap_grid first");
-				I = irradiance_map_of(ctx);
-			}
-			IrradianceVolume V{};
-			const bool volume = opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
-			if (volume) {
-				if (!ctx->d_sh_volume) throw std::runtime_error("render_mode ShadeIrradianceVolume needs ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
-				V = sh_volume_of(ctx);
-			}
-			const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
-			const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[slot], stream)); // (ngp_get_mesh_pass_ms)
-			if (sun_shadow || reflection) { // G-buffer -> per list: prep -> trace -> deferred shade; a trace borrows the slot's queue ahead of the NeRF launch and reports into a block of its own
-				const uint32_t n = (uint32_t)n_pixels;
-				NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_t.get(), 0, n_pixels * sizeof(float2), stream)); // entries no pixel owns stay dead
-				if (sun_shadow) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ss_record.get(), 0, n_pixels * sizeof(float4), stream));
-				launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, F.depth_buffer, F.shard_index, F.shard_count, F.packed, ctx->sun_nerf_shadow_desc.t_min, n, ctx->d_ss_gbuf.get(),
-				                    ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), stream);
-				if (sun_shadow) {
-					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss0[slot], stream)); // (ngp_get_frame_sun_shadow_ms)
-					launch_ray_list_prep(M, n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), true, stream);
-					FrameParams FT{};
-					tracer_frame_params(ctx, slot, ctx->sun_nerf_shadow_desc.min_transmittance, FT);
-					FT.results = ctx->d_ss_results.get();
-					if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_ss_o.get(), ctx->d_ss_d.get(), ctx->d_ss_t.get(), ctx->d_ss_traced.get(), nullptr), false, stream); // (a shard without tiles traces nothing)
-					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ss1[slot], stream));
-				}
-				MeshReflectionList R{};
-				if (reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
-					NGP_HIP_CHECK(hipMemsetAsync(ctx->d_mr_t.get(), 0, n_pixels * sizeof(float2), stream)); // entries no pixel owns stay dead
-					NGP_HIP_CHECK(hipMemsetAsync(ctx->d_mr_record.get(), 0, 3 * n_pixels * sizeof(float4), stream));
-					launch_mesh_reflection_rays(ctx->mesh_scene, C, F.shard_index, F.shard_count, F.packed, ctx->mesh_reflection_desc.t_min, n, ctx->d_ss_gbuf.get(), ctx->d_mr_o.get(),
-					                            ctx->d_mr_d.get(), ctx->d_mr_t.get(), stream);
-					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mr0[slot], stream)); // (ngp_get_frame_mesh_reflection_ms)
-					launch_ray_list_prep(M, n, ctx->d_mr_o.get(), ctx->d_mr_d.get(), ctx->d_mr_t.get(), true, stream);
-					FrameParams FT{};
-					tracer_frame_params(ctx, slot, ctx->mesh_reflection_desc.min_transmittance, FT);
-					FT.results = ctx->d_mr_results.get();
-					if (n) launch_probe_trace(ctx, M, FT, ray_list_params(n, ctx->d_mr_o.get(), ctx->d_mr_d.get(), ctx->d_mr_t.get(), ctx->d_mr_traced.get(), nullptr), false, stream);
-					if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mr1[slot], stream));
-					R = MeshReflectionList{ctx->d_mr_o.get(), ctx->d_mr_t.get(), ctx->d_mr_traced.get(), ctx->d_mr_record.get(), ctx->mesh_reflection_desc.strength};
-				}
-				launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.shard_index, F.shard_count, F.packed, n,
-				                           ctx->d_ss_gbuf.get(), ctx->d_ss_o.get(), ctx->d_ss_t.get(), sun_shadow ? ctx->d_ss_traced.get() : nullptr, ctx->d_ss_record.get(), R, stream);
-			} else {
-				launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, ctx->d_frame.get(), F.depth_buffer, F.shard_index, F.shard_count, F.packed, stream);
-			}
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[slot], stream));
-		}
-		if (scratch) { // the NeRF launch composites over zeros, apart from the mesh pass's pixels; its depth test and depth writes are every frame's
-			NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_nerf.get(), 0, n_pixels * sizeof(float4), stream));
-			if (mesh_shadow) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_record.get(), 0, n_pixels * sizeof(float4), stream));
-			if (ambient_change) NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ac_record.get(), 0, 3 * n_pixels * sizeof(float4), stream));
-			F.frame_buffer = ctx->d_ms_nerf.get();
-		}
-		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[slot], stream));
-		if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, stream); // persistent grid sized by the launcher
-		else if (s == 0) NGP_HIP_CHECK(hipMemsetAsync(F.results, 0, 24, stream)); // meshes only: no NeRF launch reports counters
-		if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern1[slot], stream));
-		if (ambient_change) { // the scratch's colour follows the ambient light: normals at the owners' surface points, then g = E_after / E_before
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ac0[slot], stream)); // (ngp_get_frame_ambient_change_ms)
-			launch_nerf_surface_normals(M, C, F.depth_buffer, ctx->d_ms_nerf.get(), ctx->d_ac_record.get(), F.shard_index, F.shard_count, F.packed, (uint32_t)n_pixels, stream);
-			launch_nerf_ambient_ratio(sh_volume_of(ctx), sh_reference_of(ctx), (uint32_t)n_pixels, ctx->d_ms_nerf.get(), ctx->d_ac_record.get(), ctx->ambient_change_desc.min_irradiance,
-			                          ctx->ambient_change_desc.max_gain, stream);
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ac1[slot], stream));
-			if (!mesh_shadow) launch_nerf_composite(C, ctx->d_frame.get(), ctx->d_ms_nerf.get(), F.shard_index, F.shard_count, F.packed, (uint32_t)n_pixels, stream); // f = 1, no traversal
-		}
-		if (mesh_shadow) { // ... and the composite over the mesh pass's pixels follows, scaled where a mesh stands in front of the sun
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ms0[slot], stream)); // (ngp_get_frame_mesh_shadow_ms)
-			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), ctx->d_ms_record.get(), F.shard_index, F.shard_count,
-			                        F.packed, (uint32_t)n_pixels, ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, stream);
-			if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_ms1[slot], stream));
-		}
+		if (plan.have_meshes) mesh_pass(f, opts, M, C, F, last);
+		nerf_pass(f, M, C, F, s, last);
+		closing_passes(f, M, C, F, last);
 		launch_accumulate_tonemap((uint32_t)n_pixels, ctx->d_frame.get(), ctx->d_accum.get(), (float)s, opts.background, opts.exposure, opts.to_srgb, opts.color_space, last ? d_rgba_out : nullptr, stream);
 	}
 	NGP_HIP_CHECK(hipEventRecord(ctx->ev_frame1[slot], stream));
 	NGP_HIP_CHECK(hipGetLastError());
 	ctx->last_stream = stream;
 	ctx->hist_n_rays[slot] = (uint64_t)F.n_local_tiles * 64u * (uint64_t)spp;
-	ctx->hist_mesh_pass[slot] = have_meshes && !F.direct;
-	ctx->hist_sun_shadow[slot] = sun_shadow;
-	if (sun_shadow) ctx->ss_n_pixels = n_pixels;
-	ctx->hist_mesh_reflection[slot] = reflection;
-	if (reflection) ctx->mr_n_pixels = n_pixels;
-	ctx->hist_mesh_shadow[slot] = mesh_shadow;
-	if (mesh_shadow) ctx->ms_n_pixels = n_pixels;
-	ctx->hist_ambient_change[slot] = ambient_change;
-	if (ambient_change) ctx->ac_n_pixels = n_pixels;
+	ctx->hist_mesh_pass[slot] = plan.have_meshes && !F.direct;
+	ctx->pass_sun_shadow.ran(slot, plan.sun_shadow, n_pixels);
+	ctx->pass_mesh_reflection.ran(slot, plan.reflection, n_pixels);
+	ctx->pass_mesh_shadow.ran(slot, plan.mesh_shadow, n_pixels);
+	ctx->pass_ambient_change.ran(slot, plan.ambient_change, n_pixels);
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -644,30 +648,6 @@ int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int
 	});
 }
 
-int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!out) throw std::runtime_error("null argument");
-		if (!ctx->n_calls || !ctx->hist_sun_shadow[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)");
-		if (n_pixels != ctx->ss_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ss_n_pixels) + " pixels on this device");
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ss_record.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
-	});
-}
-
-int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!ms) throw std::runtime_error("null argument");
-		*ms = 0.f;
-		if (!ctx->n_calls) return;
-		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
-		if (!ctx->hist_sun_shadow[slot]) return;
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ss0[slot], ctx->ev_ss1[slot]));
-	});
-}
-
 int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc) {
 	return guarded(ctx, [&] {
 		if (desc) {
@@ -685,31 +665,6 @@ int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* en
 		if (!out || !enabled) throw std::runtime_error("null argument");
 		*out = ctx->mesh_reflection_desc;
 		*enabled = ctx->mesh_reflection ? 1 : 0;
-	});
-}
-
-int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!out) throw std::runtime_error("null argument");
-		if (!ctx->n_calls || !ctx->hist_mesh_reflection[(ctx->n_calls - 1) % ngp_ctx::HISTORY])
-			throw std::runtime_error("the last frame traced no reflection rays (ngp_set_mesh_reflection)");
-		if (n_pixels != ctx->mr_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->mr_n_pixels) + " pixels on this device");
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_mr_record.get(), 3 * n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
-	});
-}
-
-int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!ms) throw std::runtime_error("null argument");
-		*ms = 0.f;
-		if (!ctx->n_calls) return;
-		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
-		if (!ctx->hist_mesh_reflection[slot]) return;
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_mr0[slot], ctx->ev_mr1[slot]));
 	});
 }
 
@@ -732,30 +687,6 @@ int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_desc* out,
 	});
 }
 
-int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!out) throw std::runtime_error("null argument");
-		if (!ctx->n_calls || !ctx->hist_mesh_shadow[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame ran no mesh shadow pass (ngp_set_mesh_shadow_on_nerf)");
-		if (n_pixels != ctx->ms_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ms_n_pixels) + " pixels on this device");
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ms_record.get(), n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
-	});
-}
-
-int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!ms) throw std::runtime_error("null argument");
-		*ms = 0.f;
-		if (!ctx->n_calls) return;
-		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
-		if (!ctx->hist_mesh_shadow[slot]) return;
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ms0[slot], ctx->ev_ms1[slot]));
-	});
-}
-
 int ngp_set_ambient_change_on_nerf(ngp_ctx* ctx, const ngp_ambient_change_desc* desc) {
 	return guarded(ctx, [&] {
 		if (desc) check_ambient_change_desc(*desc);
@@ -772,29 +703,30 @@ int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, i
 	});
 }
 
-int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!out) throw std::runtime_error("null argument");
-		if (!ctx->n_calls || !ctx->hist_ambient_change[(ctx->n_calls - 1) % ngp_ctx::HISTORY])
-			throw std::runtime_error("the last frame ran no ambient change pass (ngp_set_ambient_change_on_nerf)");
-		if (n_pixels != ctx->ac_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->ac_n_pixels) + " pixels on this device");
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_ac_record.get(), 3 * n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
-	});
+// what the last frame's optional passes left (FramePass, ngp_host.h)
+int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] { ctx->pass_sun_shadow.read_record(ctx, out, n_pixels, "the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)"); });
 }
-
+int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] { ctx->pass_sun_shadow.read_ms(ctx, ms); });
+}
+int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_record(ctx, out, n_pixels, "the last frame traced no reflection rays (ngp_set_mesh_reflection)"); });
+}
+int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_ms(ctx, ms); });
+}
+int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] { ctx->pass_mesh_shadow.read_record(ctx, out, n_pixels, "the last frame ran no mesh shadow pass (ngp_set_mesh_shadow_on_nerf)"); });
+}
+int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] { ctx->pass_mesh_shadow.read_ms(ctx, ms); });
+}
+int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] { ctx->pass_ambient_change.read_record(ctx, out, n_pixels, "the last frame ran no ambient change pass (ngp_set_ambient_change_on_nerf)"); });
+}
 int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!ms) throw std::runtime_error("null argument");
-		*ms = 0.f;
-		if (!ctx->n_calls) return;
-		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
-		if (!ctx->hist_ambient_change[slot]) return;
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ac0[slot], ctx->ev_ac1[slot]));
-	});
+	return guarded(ctx, [&] { ctx->pass_ambient_change.read_ms(ctx, ms); });
 }
 
 int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {

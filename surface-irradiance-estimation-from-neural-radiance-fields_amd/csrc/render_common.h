@@ -93,6 +93,25 @@ NGP_DEV bool shade_ray(const FrameParams& F, const ProbeParams& P, f3 bg_linear,
 	return true;
 }
 
+// ---- the pixel map of a frame's passes around the NeRF launch (mesh_kernels.hip; nerf_surface_normals_kernel). One definition.
+// Does layout L own pixel (x, y) of camera tile `tile`, and at which idx of the per-pixel buffers? The tile -> rank mapping and the packed
+// layout are the NeRF pass's (FrameParams). idx < n_pixels holds for every owned pixel (n_pixels is the rank's tile share times 64, or the
+// whole image): the test only keeps a launch whose layout and buffers disagree inside its buffers. A moving camera owns nothing (a
+// NeRF-mode feature; the host refuses the combination).
+NGP_DEV bool frame_tile_pixel(const FrameLayout& L, const CameraParams& C, uint32_t tile, uint32_t x, uint32_t y, uint32_t& idx) {
+	if (x >= (uint32_t)C.width || y >= (uint32_t)C.height) return false;
+	const uint32_t shard_count = L.shard_count;
+	if (tile % shard_count != L.shard_index) return false;
+	idx = L.packed ? (tile / shard_count) * 64u + (x & 7u) + 8u * (y & 7u) : x + (uint32_t)C.width * y;
+	return !C.moving && idx < L.n_pixels;
+}
+// one thread a pixel, blocks of 16 x 8 threads (pixel_blocks, mesh_kernels.hip): the thread's pixel
+NGP_DEV bool frame_pixel(const FrameLayout& L, const CameraParams& C, uint32_t& x, uint32_t& y, uint32_t& idx) {
+	x = threadIdx.x + blockDim.x * blockIdx.x;
+	y = threadIdx.y + blockDim.y * blockIdx.y;
+	return frame_tile_pixel(L, C, (y >> 3) * (((uint32_t)C.width + 7u) >> 3) + (x >> 3), x, y, idx);
+}
+
 // ---- a NeRF pixel's surface point and normal (the passes behind the NeRF launch of a hybrid frame: nerf_mesh_shadow_kernel,
 // nerf_surface_normals_kernel; the marching-cubes export). One definition each.
 // the point at z-depth `depth` on the ray init_ray forms for pixel (x, y): a pixel of alpha > 0.2 owns the depth buffer's value (shade_ray)

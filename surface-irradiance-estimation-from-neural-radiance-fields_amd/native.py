@@ -910,6 +910,18 @@ class Context:
         self._check(self.L.ngp_get_irradiance_sun_shadow_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def _frame_record(self, fn, n_pixels, stride):
+        """(n_pixels, stride): the record an optional pass of the last frame left, through its getter fn"""
+        out = np.zeros((int(n_pixels), stride), np.float32)
+        self._check(fn(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def _frame_pass_ms(self, fn):
+        """device time of an optional pass in the last frame's last sample, ms, through its getter fn"""
+        ms = C.c_float(0)
+        self._check(fn(self.h, C.byref(ms)))
+        return ms.value
+
     def set_sun_nerf_shadow(self, shadow=True):
         """the NeRF's density in front of the frames' sun on mesh pixels (Geometry frames with meshes and a model): None or False switches it
         off (the default), True takes min_transmittance 0.01 and t_min 0, a dict or a tuple gives min_transmittance and t_min"""
@@ -925,15 +937,11 @@ class Context:
     def frame_sun_shadow(self, n_pixels):
         """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (q xyz, alpha_s) of its shadow ray through the
         NeRF; zeros where the pixel had none. On a multi-device context the primary's tile-packed share."""
-        out = np.zeros((int(n_pixels), 4), np.float32)
-        self._check(self.L.ngp_get_frame_sun_shadow(self.h, _p(out), int(n_pixels)))
-        return out
+        return self._frame_record(self.L.ngp_get_frame_sun_shadow, n_pixels, 4)
 
     def frame_sun_shadow_ms(self):
         """device time of the shadow rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
-        ms = C.c_float(0)
-        self._check(self.L.ngp_get_frame_sun_shadow_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._frame_pass_ms(self.L.ngp_get_frame_sun_shadow_ms)
 
     def set_mesh_shadow_on_nerf(self, shadow=True):
         """the meshes in front of the sun on the NeRF (Geometry frames with meshes and a model, the four shade modes): None or False switches
@@ -958,15 +966,11 @@ class Context:
     def frame_mesh_shadow(self, n_pixels):
         """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (p xyz, 2 blocked / 1 open) of the NeRF's
         surface point under the meshes' shadow; zeros where the pixel owns none. On a multi-device context the primary's tile-packed share."""
-        out = np.zeros((int(n_pixels), 4), np.float32)
-        self._check(self.L.ngp_get_frame_mesh_shadow(self.h, _p(out), int(n_pixels)))
-        return out
+        return self._frame_record(self.L.ngp_get_frame_mesh_shadow, n_pixels, 4)
 
     def frame_mesh_shadow_ms(self):
         """device time of the mesh shadow kernel in the last frame's last sample, ms; 0 after a frame without it"""
-        ms = C.c_float(0)
-        self._check(self.L.ngp_get_frame_mesh_shadow_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._frame_pass_ms(self.L.ngp_get_frame_mesh_shadow_ms)
 
     # ---------------------------------------------------------------- the meshes' change of the ambient light on the NeRF (include/ngp_hip.h, "ambient")
     @staticmethod
@@ -1034,15 +1038,11 @@ class Context:
     def frame_ambient_change(self, n_pixels):
         """(n_pixels, 12): per pixel of the last frame's last sample, in the frame's pixel order: p (3), state (0 not an owner, 1 no estimate,
         2 scaled), N (3), W_after, g (3), W_before. On a multi-device context the primary's tile-packed share."""
-        out = np.zeros((int(n_pixels), 12), np.float32)
-        self._check(self.L.ngp_get_frame_ambient_change(self.h, _p(out), int(n_pixels)))
-        return out
+        return self._frame_record(self.L.ngp_get_frame_ambient_change, n_pixels, 12)
 
     def frame_ambient_change_ms(self):
         """device time of the normals and ratio kernels in the last frame's last sample, ms; 0 after a frame without them"""
-        ms = C.c_float(0)
-        self._check(self.L.ngp_get_frame_ambient_change_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._frame_pass_ms(self.L.ngp_get_frame_ambient_change_ms)
 
     # ---------------------------------------------------------------- the NeRF mirrored in the meshes (include/ngp_hip.h, "mesh reflection")
     def set_mesh_reflection(self, reflection=True):
@@ -1068,15 +1068,11 @@ class Context:
     def frame_mesh_reflection(self, n_pixels):
         """(n_pixels, 12): per pixel of the last frame's last sample, in the frame's pixel order: q (3), t_hit, r (3) before the tracer
         normalises it, 0, rgb_r (3), alpha_r; zeros where the pixel owns no ray. On a multi-device context the primary's tile-packed share."""
-        out = np.zeros((int(n_pixels), 12), np.float32)
-        self._check(self.L.ngp_get_frame_mesh_reflection(self.h, _p(out), int(n_pixels)))
-        return out
+        return self._frame_record(self.L.ngp_get_frame_mesh_reflection, n_pixels, 12)
 
     def frame_mesh_reflection_ms(self):
         """device time of the reflection rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
-        ms = C.c_float(0)
-        self._check(self.L.ngp_get_frame_mesh_reflection_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._frame_pass_ms(self.L.ngp_get_frame_mesh_reflection_ms)
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
         """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass

@@ -146,6 +146,51 @@ def test_deferred_pass_is_the_fused_pass(mode, hybrid, native):
         hybrid.set_geometry_opts()
 
 
+@pytest.mark.parametrize("lens", ["aperture", "fisheye"])
+def test_deferred_pass_is_the_fused_pass_through_every_lens(lens, hybrid, bare, native):
+    """test_deferred_pass_is_the_fused_pass where the primary ray is more than a pinhole's and the pixel map more than whole tiles: a thin
+    lens (aperture_size > 0, a positive focus_z) and an OpenCV fisheye, 52 x 36 (a multiple of neither 8 nor 16), whole and as three
+    tile-packed shards put together as in test_shards_and_packed_shards_cover_the_frame. With every shadow ray beyond the box the split
+    pass's frame is the fused pass's as bytes, colour and depth, in both layouts. The comparison must not be one of empty frames: a primary ray
+    has to find a triangle at a quarter of the pixels at least. They are counted in the frame of the meshes alone through the same camera,
+    where no NeRF writes a depth: a depth of 0.01 or more, below MAX_DEPTH (a ray that chooses no mesh ends where it starts, at a depth
+    under 1e-6, test_nerf_mesh_shadow_gpu.py's `behind`). mesh_reference.trace on these cameras' rays at pixel centres gives 782 of 1872
+    for the fisheye and 808 to 817 for the thin lens, over draws of the point on the lens disk, its rim included; the pinhole's 812."""
+    import torch
+
+    w, h, world = 52, 36, 3
+    kw = {"aperture": dict(aperture_size=0.05, focus_z=1.5), "fisheye": dict(lens_mode=native.LENS_OPENCV_FISHEYE, lens_params=(0.05, -0.01, 0.003, -0.0005))}[lens]
+    cam = _cam(native, w=w, h=h, **kw)
+    tile, slot = _tiles(w, h)
+    src = (tile // world) * 64 + slot
+    got = {}
+    hybrid.set_geometry_opts(**RICH)
+    try:
+        for name, shadow in (("off", None), ("far", FAR)):
+            hybrid.set_sun_nerf_shadow(shadow)
+            full, full_depth = hybrid.render(cam, _opts(native), want_depth=True)
+            packed, packed_depth = np.zeros_like(full), np.zeros_like(full_depth)
+            for r in range(world):
+                mine = tile % world == r
+                n = native.load_library().ngp_packed_tiles(w, h, r, world) * 64
+                rgba = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+                dep = torch.zeros((n,), dtype=torch.float32, device="cuda")
+                hybrid.render_device(cam, _opts(native, shard_index=r, shard_count=world, packed_output=True), rgba.data_ptr(), dep.data_ptr(), None)
+                torch.cuda.synchronize()
+                packed[mine], packed_depth[mine] = rgba.cpu().numpy()[src[mine]], dep.cpu().numpy()[src[mine]]
+            got[name] = (full, full_depth), (packed, packed_depth)
+    finally:
+        hybrid.set_sun_nerf_shadow(None)
+        hybrid.set_geometry_opts()
+    (off, off_packed), (far, far_packed) = got["off"], got["far"]
+    mesh_depth = _render(bare, native, None, cam=cam)[1]
+    hit = (mesh_depth >= np.float32(0.01)) & (mesh_depth < mref.MAX_DEPTH)
+    assert hit.sum() >= w * h // 4, "%s: a triangle at %d of %d pixels" % (lens, hit.sum(), w * h)
+    assert np.all(off[0][hit, 3] > 0) and np.unique(off[0][hit, 0]).size > 100  # the hybrid frame's mesh pixels: covered, and shaded
+    assert _same(far, off) and _same(far_packed, off_packed)
+    assert _same(off_packed, off)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the record
 def test_record_matches_tracer_reference_and_oracle(hybrid, frames, native, oracle, scene_unit):
     """(a) alpha_s is ngp_trace_nerf_rays' alpha of (q_out, s^, (t_min, inf)) as bytes, for two descriptors; (b) q = 0 and alpha_s = 0
