@@ -836,8 +836,9 @@ NGP_API int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms);
  *   entries refuse a host-only context ("no HIP device"). A moving camera with meshes is refused as before.
  * Several devices: the option travels to the peers with the geometry and each device traces the rays of its own tiles;
  *   ngp_get_frame_mesh_reflection and ngp_get_frame_mesh_reflection_ms read the primary's share only.
- * Stated limits: mirror direction only: roughness does not blur the reflection, and strength is the caller's handle on that. Meshes do not
- *   appear in reflections: a ray cut by a mesh carries what the NeRF put in front of the hit, and black behind it. No environment map or
+ * Stated limits: mirror direction only: roughness does not blur the reflection, and strength is the caller's handle on that. Without
+ *   ngp_set_mesh_reflection_meshes (below) meshes do not appear in reflections: a ray cut by a mesh carries what the NeRF put in front of
+ *   the hit, and black behind it. No environment map or
  *   sky fills the reflection where alpha_r < 1. The reflected NeRF is the captured one: the shadow and the ambient change of
  *   ngp_set_mesh_shadow_on_nerf / ngp_set_ambient_change_on_nerf are not applied to it. A surface inside the NeRF's own density reflects
  *   that density unless t_min skips it. The NeRF does not reflect the meshes. */
@@ -856,6 +857,41 @@ NGP_API int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out,
 NGP_API int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out /* n_pixels x 12 */, size_t n_pixels);
 /* device time (HIP events) of the reflection rays' prep and trace in the last frame's last sample; 0 after a frame without them */
 NGP_API int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms);
+
+/* mesh reflection, the meshes in it: a mirror ray that a mesh cuts has its hit shaded by the mesh pass's own M5, composited behind the NeRF
+ * along the ray. A sub-option of the mesh reflection: context state, off by default. It acts while ngp_set_mesh_reflection is on with
+ * strength > 0 in a frame the reflection serves; every other frame ignores it. All values are float32, in this order, under
+ * -ffp-contract=off.
+ *
+ * Who owns a hit: a pixel that owns a mirror ray (the rule above) whose t_hit is finite.
+ * The hit: r^ = normalize3(r) as the reflection forms it for closest_hit; (mesh, tri) what closest_hit reports for that call;
+ *   p2 = q + r^ t_hit; n2 = normalize3(cross(b - a, c - a)) of that triangle, the raw winding normal as the mesh trace leaves it, so the
+ *   shade gets what the frames' own trace would have given it.
+ * Its sun: ff2 = n2 turned against r^ (n2 where n2 . r^ < 0, else -n2); q2 = p2 + 1e-3 normalize3(ff2); shadow2 = 0 where a triangle of ANY
+ *   mesh lies within MAX_DIST of q2 along the frames' shadow direction, else 1. This is the all-meshes rule of ngp_set_mesh_shadow_on_nerf,
+ *   not the one-mesh rule of the frames' own shadow ray. ngp_set_sun_nerf_shadow does not reach the hit: the NeRF throws no shadow on a
+ *   mirrored mesh.
+ * Its colour: C2 = the mesh pass's shade at (p2, n2) viewed along r^ with shadow2: the frame's own ambient source (sky term, probe table(s),
+ *   SH9 volume, visible volume) and the one material of the context. C2 carries no mirror ray of its own: one bounce only.
+ * The pixel: L = rgb_r + fl(max(1 - alpha_r, 0) C2); color += fl(fl(F (.) L) strength), F the term above; added where alpha_r > 0 or the ray
+ *   owns a hit. A ray without a hit (t_hit = +inf) keeps exactly the bits it has with the sub-option off; a hit with alpha_r = 0 gives L = C2.
+ * Identities as bytes (the frame is that of the same options without the sub-option): the sub-option off; on with the reflection off, at
+ *   strength 0, in NeRF mode, without meshes, or without a model; on in a scene where no mirror ray is cut.
+ * Records: the 12-float record of ngp_get_frame_mesh_reflection does not change by a bit (it is the tracer's rgb_r and alpha_r); neither do
+ *   depth, coverage, the NeRF pass, the sun-shadow record and ngp_get_render_stats.
+ * Determinism: no atomics; frames are bit-identical from run to run. One kernel on the frame's stream between the reflection list's fill
+ *   and its prep step, inside the time of ngp_get_frame_mesh_reflection_ms; nothing waits on the host.
+ * Several devices: the flag travels to the peers with the geometry; ngp_get_frame_mesh_reflection_hits reads the primary's share only.
+ * Stated limits: one bounce; mirror direction only; no sky where alpha_r < 1 and nothing is hit; no NeRF shadow on the mirrored hit; the hit is
+ *   not ambient-changed by ngp_set_ambient_change_on_nerf; the NeRF still does not reflect the meshes. */
+NGP_API int ngp_set_mesh_reflection_meshes(ngp_ctx* ctx, int on);
+NGP_API int ngp_get_mesh_reflection_meshes(ngp_ctx* ctx, int* on);
+/* stage entry for tests and tools: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (as ngp_get_frame_mesh_reflection),
+ * 8 floats: p2 (3), shadow2, C2 (3), 1; zeros where the pixel owns no hit. n_pixels must be that frame's extent. Refuses when the last frame
+ * shaded no reflection hits. */
+NGP_API int ngp_get_frame_mesh_reflection_hits(ngp_ctx* ctx, float* out /* n_pixels x 8 */, size_t n_pixels);
+/* device time (HIP events) of the hit-shade kernel in the last frame's last sample; 0 after a frame without it */
+NGP_API int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms);
 
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),

@@ -575,13 +575,15 @@ NGP_DEV f3 mirror_term(const MeshShadeParams& P, float c, f3 rgb_r, float streng
 
 // the pixel's entry of the reflection list, in idx order and not compacted. A pixel owns a ray where it is covered and its primary ray found
 // a triangle (plane 2's w); t = (t_min, the closest triangle over ALL meshes from q along normalize(r), +inf without one), ngp_irradiance_rays'
-// rule. Every other entry is dead: origin 0, direction +z, t = (0, 0).
+// rule. Every other entry is dead: origin 0, direction +z, t = (0, 0). hit_ids (nullable: ngp_set_mesh_reflection_meshes is off) receives the
+// (mesh, triangle) of that closest hit, (-1, -1) where the pixel owns no ray or its ray is not cut.
 __global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const CameraParams C, const FrameLayout L, float t_min, const float4* __restrict__ gbuf,
-                                            float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+                                            float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t, int2* __restrict__ hit_ids) {
 	uint32_t x, y, idx;
 	if (!frame_pixel(L, C, x, y, idx)) return;
 	f3 q = mk3(0.f, 0.f, 0.f), r = mk3(0.f, 0.f, 1.f);
 	float2 t = make_float2(0.f, 0.f);
+	int mesh = -1, tri = -1;
 	const float4 g1 = gbuf[(size_t)L.n_pixels + idx];
 	if (g1.w != 0.0f) { // (a pixel that is not covered may hold a stale plane 2)
 		const float4 g2 = gbuf[2 * (size_t)L.n_pixels + idx];
@@ -589,17 +591,20 @@ __global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const Camer
 			const float4 g0 = gbuf[idx];
 			float c;
 			mirror_ray(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), q, r, c);
-			t = make_float2(t_min, closest_hit(S, q, normalize3(r)));
+			t = make_float2(t_min, closest_hit(S, q, normalize3(r), &mesh, &tri));
 		}
 	}
 	st3(ray_o + 3 * (size_t)idx, q);
 	st3(ray_d + 3 * (size_t)idx, r);
 	ray_t[idx] = t;
+	if (hit_ids) hit_ids[idx] = make_int2(mesh, tri);
 }
 
 // M5 from the G-buffer. traced (nullable: no shadow trace was run, T_s = 1): the tracer's rgba of the pixel's list entry; a pixel has a shadow
 // ray where ray_t.y != 0 (the prep step moves ray_t.x alone). record: (q, alpha_s), zeros without a shadow ray (ngp_get_frame_sun_shadow).
-// R: the mirror ray's radiance is added behind evaluate_shading where alpha_r > 0; every other pixel keeps its bits.
+// R: the mirror ray's radiance is added behind evaluate_shading where alpha_r > 0; every other pixel keeps its bits. With R.hits
+// (ngp_set_mesh_reflection_meshes) a ray that a mesh cuts carries L = rgb_r + max(1 - alpha_r, 0) C2, C2 the hit's own M5 from
+// mesh_reflection_hit_shade_kernel, and adds it whatever alpha_r is; a ray without a hit keeps the bits it has with R.hits null.
 template <typename Ambient>
 __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
                                            const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
@@ -627,7 +632,14 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 		R.record[3 * (size_t)idx] = make_float4(R.ray_o[3 * (size_t)idx], R.ray_o[3 * (size_t)idx + 1], R.ray_o[3 * (size_t)idx + 2], R.ray_t[idx].y);
 		R.record[3 * (size_t)idx + 1] = make_float4(r.x, r.y, r.z, 0.0f);
 		R.record[3 * (size_t)idx + 2] = tr;
-		if (tr.w > 0.0f) color = add3(color, mirror_term(P, c, mk3(tr.x, tr.y, tr.z), R.strength));
+		f3 Lr = mk3(tr.x, tr.y, tr.z);
+		bool cut = false; // the ray owns a shaded mesh hit: its colour stands behind the NeRF along the ray
+		if (R.hits) {
+			const float4 h1 = R.hits[2 * (size_t)idx + 1];
+			cut = h1.w != 0.0f;
+			if (cut) Lr = add3(Lr, scale3(mk3(h1.x, h1.y, h1.z), fmaxf(1.0f - tr.w, 0.0f)));
+		}
+		if (tr.w > 0.0f || cut) color = add3(color, mirror_term(P, c, Lr, R.strength));
 	}
 	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
 }
@@ -664,8 +676,8 @@ void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I
 	});
 }
 void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
-                                 float2* ray_t, hipStream_t stream) {
-	hipLaunchKernelGGL(mesh_reflection_rays_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, C, L, t_min, gbuf, ray_o, ray_d, ray_t);
+                                 float2* ray_t, int2* hit_ids, hipStream_t stream) {
+	hipLaunchKernelGGL(mesh_reflection_rays_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, C, L, t_min, gbuf, ray_o, ray_d, ray_t, hit_ids);
 }
 
 // stage kernel: the irradiance lookup at explicit surface points (ngp_irradiance_at)
@@ -1193,6 +1205,47 @@ __global__ void nerf_mesh_shadow_kernel(const MeshSceneParams S, const MeshShade
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias, hipStream_t stream) {
 	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, L, strength, bias);
+}
+
+// ---- the meshes seen by the mirror ray (ngp_set_mesh_reflection_meshes; contract in include/ngp_hip.h, "mesh reflection"). One thread a
+// pixel on the frame's pixel map, between mesh_reflection_rays_kernel and the list's prep step: ray_d still holds r as mirror_ray formed it
+// and ray_t = (t_min, t_hit), so normalize3(r) has the bits closest_hit was given. A pixel owns a hit where hit_ids names a mesh. For it:
+// p2 = q + r^ t_hit; n2 the triangle's raw winding normal (trace_mesh's expression, what M2 hands M5); q2 = p2 + 1e-3 normalize(n2 turned
+// against r^) (M3's lift); shadow2 = 0 where any mesh stands between q2 and the sun (nerf_mesh_shadow_kernel's all-meshes rule, not M3's
+// one-mesh rule), else 1; C2 = M5 at (p2, n2) viewed along r^. hits: (p2, shadow2), (C2, 1); zeros for every other pixel.
+// A kernel of its own: a second M5 inside mesh_shade_deferred_kernel would hold two lookups' accumulators at once.
+template <typename Ambient>
+__global__ void mesh_reflection_hit_shade_kernel(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                                 const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float2* __restrict__ ray_t,
+                                                 const int2* __restrict__ hit_ids, float4* __restrict__ hits) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
+	float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;
+	const int2 id = hit_ids[idx];
+	if (id.x > -1) {
+		const f3 q = ld3(ray_o + 3 * (size_t)idx);
+		const f3 rh = normalize3(ld3(ray_d + 3 * (size_t)idx));
+		const f3 p2 = add3(q, scale3(rh, ray_t[idx].y));
+		const Triangle& tri = S.meshes[id.x].tris[id.y];
+		const f3 a = ld3(tri.a);
+		const f3 n2 = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
+		const f3 ff2 = dot3(n2, rh) < 0.0f ? n2 : scale3(n2, -1.0f);
+		const f3 q2 = add3(p2, scale3(normalize3(ff2), 1e-3f));
+		const float shadow2 = any_hit(S, q2, shadow_ray_dir(P)) ? 0.0f : 1.0f;
+		const f3 C2 = mesh_shade(P, A, p2, n2, rh, shadow2);
+		h0 = make_float4(p2.x, p2.y, p2.z, shadow2);
+		h1 = make_float4(C2.x, C2.y, C2.z, 1.0f);
+	}
+	hits[2 * (size_t)idx] = h0;
+	hits[2 * (size_t)idx + 1] = h1;
+}
+void launch_mesh_reflection_hit_shade(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
+                                      const CameraParams& C, const FrameLayout& L, const float* ray_o, const float* ray_d, const float2* ray_t, const int2* hit_ids, float4* hits,
+                                      hipStream_t stream) {
+	with_ambient(I, V, VV, [&](const auto& A) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_reflection_hit_shade_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, ray_o, ray_d,
+		                   ray_t, hit_ids, hits);
+	});
 }
 
 // ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf; contract in include/ngp_hip.h, "ambient").

@@ -152,7 +152,13 @@ void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I
                                 const MeshReflectionList& R,
                                 hipStream_t stream); // M5 of launch_render_mesh behind the trace(s); traced == nullptr: no shadow trace was run (T_s = 1, no record)
 void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
-                                 float2* ray_t, hipStream_t stream); // the G-buffer's mirror rays (ngp_set_mesh_reflection)
+                                 float2* ray_t, int2* hit_ids,
+                                 hipStream_t stream); // the G-buffer's mirror rays (ngp_set_mesh_reflection); hit_ids (nullable): each ray's closest (mesh, triangle)
+// ngp_set_mesh_reflection_meshes: M5 at the mesh hit of every cut mirror ray, on the list as launch_mesh_reflection_rays left it (before its
+// prep step); hits: 2 float4 a pixel, (p2, shadow2), (C2, 1)
+void launch_mesh_reflection_hit_shade(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
+                                      const CameraParams& C, const FrameLayout& L, const float* ray_o, const float* ray_d, const float2* ray_t, const int2* hit_ids, float4* hits,
+                                      hipStream_t stream);
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
@@ -489,6 +495,11 @@ struct ngp_ctx {
 	// (ngp_get_frame_mesh_reflection_ms). The G-buffer and the shadow list its frames fill are the sun shadow's (d_ss_gbuf, ss_rays).
 	ngp::FramePass pass_mesh_reflection{3};
 	ngp::RayList mr_rays; // its scratch: the reflection-ray list
+	// ... and the meshes in it (ngp_set_mesh_reflection_meshes): (p2, shadow2), (C2, 1) a pixel of the last sample
+	// (ngp_get_frame_mesh_reflection_hits); events around mesh_reflection_hit_shade_kernel, inside the reflection pass's
+	bool mesh_reflection_meshes = false;
+	ngp::FramePass pass_mesh_reflection_hits{2};
+	ngp::DevArray<int2> d_mr_hit_ids; // its scratch: the (mesh, triangle) each mirror ray is cut at, (-1, -1) without a hit
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a

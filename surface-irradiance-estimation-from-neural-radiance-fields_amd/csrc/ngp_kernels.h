@@ -247,6 +247,7 @@ struct MeshReflectionList { // the reflection ray list of a frame as the deferre
 	const float4* traced; // the tracer's premultiplied rgba of the list
 	float4* record;       // 3 float4 a pixel: (q, t_hit), (r, 0), (rgb_r, alpha_r); zeros without a ray (ngp_get_frame_mesh_reflection)
 	float strength;
+	const float4* hits;   // nullable (ngp_set_mesh_reflection_meshes off): 2 float4 a pixel from mesh_reflection_hit_shade_kernel: (p2, shadow2), (C2, 1); zeros without a hit
 };
 
 } // namespace ngp

@@ -77,7 +77,7 @@ void usage() {
 	             "             [--irradiance_volume_res N] [--irradiance_volume_visibility] [--irradiance_volume_bounces N] [--irradiance_volume_sun]\n"
 	             "             [--irradiance_volume_sun_nerf_shadow] [--sun_nerf_shadow [--sun_nerf_shadow_t_min X]]\n"
 	             "             [--mesh_shadow_on_nerf [--mesh_shadow_on_nerf_strength X]] [--ambient_change_on_nerf]\n"
-	             "             [--mesh_reflection [--mesh_reflection_strength X]]\n"
+	             "             [--mesh_reflection [--mesh_reflection_strength X] [--mesh_reflection_meshes]]\n"
 	             "             [--exposure E] [--n_steps N] [--save_snapshot OUT.ingp] [--network CONFIG.json]\n"
 	             "             [--save_mesh OUT.obj|OUT.ply [--marching_cubes_res N] [--marching_cubes_density_thresh T]] [--no-gui] [--no-train] [--version]\n"
 	             "             [--video_camera_path PATH.json --video_output DIR/%04d.png [--video_n_seconds S] [--video_fps F] [--video_spp N]]\n";
@@ -93,7 +93,7 @@ int main(int argc, char** argv) {
 		float mc_thresh = 2.5f;
 		std::string scene, snapshot, screenshot, shot_transforms, shot_dir, render_mode = "Shade", save_snapshot, network, video_path, video_output = "video_%04d.png";
 		int width = 1920, height = 1080, spp = 1, volume_res = 8, volume_bounces = 0, n_steps = -1, video_seconds = 1, video_fps = 60, video_spp = 8;
-		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false, sun_nerf_shadow = false, mesh_shadow_on_nerf = false, ambient_change_on_nerf = false, mesh_reflection = false;
+		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false, sun_nerf_shadow = false, mesh_shadow_on_nerf = false, ambient_change_on_nerf = false, mesh_reflection = false, mesh_reflection_meshes = false;
 		float exposure = 0.f, sun_nerf_shadow_t_min = 0.f, mesh_shadow_on_nerf_strength = 0.5f, mesh_reflection_strength = 1.f;
 		for (int i = 1; i < argc; ++i) {
 			std::string a = argv[i];
@@ -122,6 +122,7 @@ int main(int argc, char** argv) {
 			else if (a == "--mesh_shadow_on_nerf_strength") mesh_shadow_on_nerf_strength = (float)std::atof(val().c_str()); // ... taking this share of a shadowed pixel's colour away
 			else if (a == "--ambient_change_on_nerf") ambient_change_on_nerf = true; // Geometry frames: NeRF pixels follow what the meshes change in the ambient light (the two volumes are computed before the frame)
 			else if (a == "--mesh_reflection") mesh_reflection = true; // Geometry frames: the meshes mirror the NeRF, one reflection ray a pixel
+			else if (a == "--mesh_reflection_meshes") mesh_reflection_meshes = true; // ... and the mirror rays see the meshes too: a cut ray's hit is shaded
 			else if (a == "--mesh_reflection_strength") mesh_reflection_strength = (float)std::atof(val().c_str()); // ... scaled by this factor
 			else if (a == "--irradiance_volume_sun") volume_sun = true; // ... and the sun's first bounce off the meshes, the frame's sun
 			else if (a == "--exposure") exposure = (float)std::atof(val().c_str());
@@ -157,6 +158,7 @@ int main(int argc, char** argv) {
 		testbed.m_ambient_change_on_nerf = ambient_change_on_nerf;
 		testbed.m_mesh_reflection = mesh_reflection;
 		testbed.m_mesh_reflection_strength = mesh_reflection_strength;
+		testbed.m_mesh_reflection_meshes = mesh_reflection_meshes;
 		for (auto& f : files) {
 			std::cerr << "Loading file " << f << "\n";
 			testbed.load_file(f);

@@ -262,6 +262,7 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->ambient_change_desc = primary->ambient_change_desc;
 	peer->mesh_reflection = primary->mesh_reflection; // each device traces the mirror rays of its own share
 	peer->mesh_reflection_desc = primary->mesh_reflection_desc;
+	peer->mesh_reflection_meshes = primary->mesh_reflection_meshes; // ... and shades the hits of its own share
 	if (peer->synced_mesh_generation != primary->mesh_generation) {
 		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)

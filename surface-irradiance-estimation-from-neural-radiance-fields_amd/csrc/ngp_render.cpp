@@ -264,6 +264,12 @@ static void ensure_mesh_reflection_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ctx->mr_rays.allocate(n_pixels);
 	ctx->pass_mesh_reflection.grow(n_pixels);
 }
+static void ensure_mesh_reflection_hit_buffers(ngp_ctx* ctx, size_t n_pixels) {
+	if (!ctx->pass_mesh_reflection_hits.ensure(n_pixels)) return;
+	ctx->d_mr_hit_ids.reset();
+	ctx->d_mr_hit_ids.reset(n_pixels);
+	ctx->pass_mesh_reflection_hits.grow(n_pixels);
+}
 static void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	if (!ctx->pass_mesh_shadow.ensure(n_pixels)) return;
 	ctx->d_ms_nerf.reset(n_pixels);
@@ -281,6 +287,7 @@ struct FramePlan {
 	bool have_meshes = false;    // a Geometry frame with meshes: it has a mesh pass
 	bool sun_shadow = false;     // the NeRF in front of the frames' sun: the mesh pass is split around one ray-list trace per sample
 	bool reflection = false;     // the NeRF mirrored in the meshes: the split mesh pass with a ray list of its own
+	bool reflection_meshes = false; // ... and the meshes in it: the cut rays' hits are shaded between the list's fill and its prep
 	bool mesh_shadow = false;    // the meshes in front of the sun on the NeRF: one kernel behind the NeRF launch finishes its composite
 	bool ambient_change = false; // the meshes' change of the ambient light on the NeRF: normals at the owners' surface points, then g = E_after / E_before
 	bool split() const { return sun_shadow || reflection; }
@@ -303,6 +310,8 @@ static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_
 		require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
 		ensure_mesh_reflection_buffers(ctx, n_pixels);
 	}
+	p.reflection_meshes = p.reflection && ctx->mesh_reflection_meshes;
+	if (p.reflection_meshes) ensure_mesh_reflection_hit_buffers(ctx, n_pixels);
 	p.mesh_shadow = ctx->mesh_shadow_on_nerf && hybrid && shade_mode;
 	if (p.mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels);
 	p.ambient_change = ctx->ambient_change_on_nerf && hybrid && shade_mode;
@@ -325,16 +334,19 @@ struct FrameCall {
 	hipStream_t stream;
 };
 
-// one ray list of a sample's split mesh pass: clear, `fill` (the kernel that writes the pixels' entries), and with `trace` prep -> trace,
-// between the pass's events. The trace borrows the slot's queue ahead of the NeRF launch and reports into the list's own results.
-template <typename Fill>
-static void trace_pixel_rays(const FrameCall& f, const ModelParams& M, const RayList& rays, const FramePass& pass, bool trace, float min_transmittance, bool last, Fill&& fill) {
+// one ray list of a sample's split mesh pass: clear, `fill` (the kernel that writes the pixels' entries), and with `trace` `before_prep`
+// (what reads the list as `fill` left it: the prep step normalises d in place and moves t.x) -> prep -> trace, between the pass's events.
+// The trace borrows the slot's queue ahead of the NeRF launch and reports into the list's own results.
+template <typename Fill, typename BeforePrep>
+static void trace_pixel_rays(const FrameCall& f, const ModelParams& M, const RayList& rays, const FramePass& pass, bool trace, float min_transmittance, bool last, Fill&& fill,
+                             BeforePrep&& before_prep) {
 	const uint32_t n = f.L.n_pixels;
 	NGP_HIP_CHECK(hipMemsetAsync(rays.t.get(), 0, (size_t)n * sizeof(float2), f.stream)); // entries no pixel owns stay dead
 	if (trace) pass.clear(n, f.stream);
 	fill();
 	if (!trace) return;
 	pass.begin(f.slot, f.stream, last);
+	before_prep();
 	launch_ray_list_prep(M, n, rays.o.get(), rays.d.get(), rays.t.get(), true, f.stream);
 	FrameParams FT{};
 	tracer_frame_params(f.ctx, f.slot, min_transmittance, FT);
@@ -367,14 +379,24 @@ static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const Mod
 		const RayList& ss = ctx->ss_rays;
 		trace_pixel_rays(f, M, ss, ctx->pass_sun_shadow, f.plan.sun_shadow, ctx->sun_nerf_shadow_desc.min_transmittance, last, [&] {
 			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), f.stream);
-		});
+		}, [] {});
 		MeshReflectionList R{};
 		if (f.plan.reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
 			const RayList& mr = ctx->mr_rays;
 			trace_pixel_rays(f, M, mr, ctx->pass_mesh_reflection, true, ctx->mesh_reflection_desc.min_transmittance, last, [&] {
-				launch_mesh_reflection_rays(ctx->mesh_scene, C, f.L, ctx->mesh_reflection_desc.t_min, ctx->d_ss_gbuf.get(), mr.o.get(), mr.d.get(), mr.t.get(), f.stream);
+				launch_mesh_reflection_rays(ctx->mesh_scene, C, f.L, ctx->mesh_reflection_desc.t_min, ctx->d_ss_gbuf.get(), mr.o.get(), mr.d.get(), mr.t.get(),
+				                            f.plan.reflection_meshes ? ctx->d_mr_hit_ids.get() : nullptr, f.stream);
+			}, [&] {
+				if (!f.plan.reflection_meshes) return;
+				const FramePass& hits = ctx->pass_mesh_reflection_hits; // (the kernel writes every pixel it owns; the clear covers the others)
+				hits.clear(f.L.n_pixels, f.stream);
+				hits.begin(f.slot, f.stream, last);
+				launch_mesh_reflection_hit_shade(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, mr.o.get(), mr.d.get(), mr.t.get(),
+				                                 ctx->d_mr_hit_ids.get(), hits.record.get(), f.stream);
+				hits.end(f.slot, f.stream, last);
 			});
-			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->pass_mesh_reflection.record.get(), ctx->mesh_reflection_desc.strength};
+			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->pass_mesh_reflection.record.get(), ctx->mesh_reflection_desc.strength,
+			                       f.plan.reflection_meshes ? ctx->pass_mesh_reflection_hits.record.get() : nullptr};
 		}
 		launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), ctx->d_ss_gbuf.get(), ss.o.get(), ss.t.get(),
 		                           f.plan.sun_shadow ? ss.traced.get() : nullptr, ctx->pass_sun_shadow.record.get(), R, f.stream);
@@ -481,6 +503,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->hist_mesh_pass[slot] = plan.have_meshes && !F.direct;
 	ctx->pass_sun_shadow.ran(slot, plan.sun_shadow, n_pixels);
 	ctx->pass_mesh_reflection.ran(slot, plan.reflection, n_pixels);
+	ctx->pass_mesh_reflection_hits.ran(slot, plan.reflection_meshes, n_pixels);
 	ctx->pass_mesh_shadow.ran(slot, plan.mesh_shadow, n_pixels);
 	ctx->pass_ambient_change.ran(slot, plan.ambient_change, n_pixels);
 	ctx->last_was_multi = false;
@@ -660,6 +683,15 @@ int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc) 
 	});
 }
 
+int ngp_set_mesh_reflection_meshes(ngp_ctx* ctx, int on) {
+	return guarded(ctx, [&] { ctx->mesh_reflection_meshes = on != 0; });
+}
+int ngp_get_mesh_reflection_meshes(ngp_ctx* ctx, int* on) {
+	return guarded(ctx, [&] {
+		if (!on) throw std::runtime_error("null argument");
+		*on = ctx->mesh_reflection_meshes ? 1 : 0;
+	});
+}
 int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* enabled) {
 	return guarded(ctx, [&] {
 		if (!out || !enabled) throw std::runtime_error("null argument");
@@ -712,6 +744,14 @@ int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
 }
 int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) {
 	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_record(ctx, out, n_pixels, "the last frame traced no reflection rays (ngp_set_mesh_reflection)"); });
+}
+int ngp_get_frame_mesh_reflection_hits(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		ctx->pass_mesh_reflection_hits.read_record(ctx, out, n_pixels, "the last frame shaded no reflection hits (ngp_set_mesh_reflection_meshes)");
+	});
+}
+int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] { ctx->pass_mesh_reflection_hits.read_ms(ctx, ms); });
 }
 int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) {
 	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_ms(ctx, ms); });

@@ -272,6 +272,8 @@ PYBIND11_MODULE(pyngp, m) {
 		.def_readwrite("ambient_change_on_nerf_max_gain", &Testbed::m_ambient_change_on_nerf_max_gain, "with ambient_change_on_nerf: the cap on the ratio (4)")
 		.def_readwrite("mesh_reflection", &Testbed::m_mesh_reflection,
 		               "This project's own: Geometry frames with meshes and a model, the four shade modes: a mesh pixel whose primary ray found a triangle adds strength * F * (the NeRF's radiance along its mirror direction) (default False)")
+		.def_readwrite("mesh_reflection_meshes", &Testbed::m_mesh_reflection_meshes,
+		               "with mesh_reflection: a mirror ray that a mesh cuts carries that mesh's own shade at the hit, behind the NeRF along the ray (default False)")
 		.def_readwrite("mesh_reflection_strength", &Testbed::m_mesh_reflection_strength, "with mesh_reflection: the factor on the reflected radiance (1)")
 		.def_readwrite("mesh_reflection_min_transmittance", &Testbed::m_mesh_reflection_min_transmittance, "with mesh_reflection: the reflection rays' transmittance floor (0.01)")
 		.def_readwrite("mesh_reflection_t_min", &Testbed::m_mesh_reflection_t_min, "with mesh_reflection: the NeRF is ignored within this distance of the surface (0)")

@@ -519,6 +519,7 @@ public:
 		{ // the NeRF mirrored in the meshes (off: NULL)
 			const ngp_mesh_reflection_desc mr{m_mesh_reflection_strength, m_mesh_reflection_min_transmittance, m_mesh_reflection_t_min};
 			check(ngp_set_mesh_reflection(m_ctx, m_mesh_reflection ? &mr : nullptr));
+			check(ngp_set_mesh_reflection_meshes(m_ctx, m_mesh_reflection_meshes ? 1 : 0));
 		}
 		check(ngp_render(m_ctx, &cam, &o, out, depth_out));
 	}
@@ -650,6 +651,7 @@ public:
 	bool m_mesh_shadow_on_nerf = false; // Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (ngp_set_mesh_shadow_on_nerf)
 	float m_mesh_shadow_on_nerf_strength = 0.5f, m_mesh_shadow_on_nerf_bias = 1e-2f; // ... taking this share of a shadowed NeRF pixel's colour away, from a point lifted this far towards the sun
 	bool m_mesh_reflection = false; // Geometry frames with meshes and a model: one reflection ray a mesh pixel through the NeRF (ngp_set_mesh_reflection)
+	bool m_mesh_reflection_meshes = false; // ... and a mirror ray that a mesh cuts shows that mesh, shaded, behind the NeRF (ngp_set_mesh_reflection_meshes)
 	float m_mesh_reflection_strength = 1.f, m_mesh_reflection_min_transmittance = 0.01f, m_mesh_reflection_t_min = 0.f; // ... its factor, traced down to this transmittance, ignoring the NeRF within t_min of the surface
 	bool m_ambient_change_on_nerf = false; // Geometry frames with meshes and a model: NeRF pixels follow what the meshes change in the ambient light, E_after / E_before (ngp_set_ambient_change_on_nerf)
 	float m_ambient_change_on_nerf_min_irradiance = 1e-3f, m_ambient_change_on_nerf_max_gain = 4.f; // ... where the reference holds more than this, by at most this factor

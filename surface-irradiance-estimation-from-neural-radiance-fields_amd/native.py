@@ -295,6 +295,10 @@ def load_library():
     L.ngp_get_mesh_reflection.argtypes = [vp, C.POINTER(MeshReflectionDesc), C.POINTER(C.c_int)]
     L.ngp_get_frame_mesh_reflection.argtypes = [vp, vp, C.c_size_t]
     L.ngp_get_frame_mesh_reflection_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_set_mesh_reflection_meshes.argtypes = [vp, C.c_int]
+    L.ngp_get_mesh_reflection_meshes.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ngp_get_frame_mesh_reflection_hits.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_mesh_reflection_hits_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_reset_network.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.ngp_default_training_opts.argtypes = [C.POINTER(TrainingOpts)]; L.ngp_default_training_opts.restype = None
     L.ngp_set_training_opts.argtypes = [vp, C.POINTER(TrainingOpts)]
@@ -1073,6 +1077,27 @@ class Context:
     def frame_mesh_reflection_ms(self):
         """device time of the reflection rays' prep and trace in the last frame's last sample, ms; 0 after a frame without them"""
         return self._frame_pass_ms(self.L.ngp_get_frame_mesh_reflection_ms)
+
+    def set_mesh_reflection_meshes(self, on=True):
+        """with set_mesh_reflection on: a mirror ray that a mesh cuts has its hit shaded by the mesh pass's own shade, composited behind the
+        NeRF along the ray (off by default)"""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("mesh_reflection_meshes: True or False")
+        self._check(self.L.ngp_set_mesh_reflection_meshes(self.h, 1 if on else 0))
+
+    def mesh_reflection_meshes(self):
+        on = C.c_int(0)
+        self._check(self.L.ngp_get_mesh_reflection_meshes(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def frame_mesh_reflection_hits(self, n_pixels):
+        """(n_pixels, 8): per pixel of the last frame's last sample, in the frame's pixel order: p2 (3), shadow2, C2 (3), 1; zeros where the
+        pixel's mirror ray is not cut by a mesh. On a multi-device context the primary's tile-packed share."""
+        return self._frame_record(self.L.ngp_get_frame_mesh_reflection_hits, n_pixels, 8)
+
+    def frame_mesh_reflection_hits_ms(self):
+        """device time of the hit-shade kernel in the last frame's last sample, ms; 0 after a frame without it"""
+        return self._frame_pass_ms(self.L.ngp_get_frame_mesh_reflection_hits_ms)
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
         """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass

@@ -29,6 +29,12 @@ With --mesh-reflection: per shade mode, in one run, the mesh pass with ngp_set_m
 (G-buffer kernel, reflection-ray kernel, prep and ray-list trace of one mirror ray a local pixel, deferred shade kernel), of the latter the
 prep and trace alone (ngp_get_frame_mesh_reflection_ms), the frame's NeRF pass beside them, and how many pixels own a ray, how many of the
 rays a mesh cuts and how many see the NeRF.
+    python tools/mesh_shade_rate.py --mesh-reflection-meshes [--out profiles/mesh_reflection_meshes_rate.json]
+
+With --mesh-reflection-meshes: per shade mode and view, in one process, ngp_set_mesh_reflection on with ngp_set_mesh_reflection_meshes off and
+then on: the mesh pass, the reflection's prep and trace (which holds the new kernel), the hit-shade kernel alone
+(ngp_get_frame_mesh_reflection_hits_ms), and the share of the rays that own a hit. Two views: the one above, whose mirror rays are hardly
+ever cut, and a low view over a floor with a wall behind the model, whose floor mirrors the wall.
 
 Times: HIP events around the mesh pass's launch in the frame's stream (ngp_get_mesh_pass_ms), median over --frames frames after --warmup.
 The frames are Geometry-mode frames of the benchmark's model (bench.py) with the meshes; the tables and the volumes are traced in it, the
@@ -197,6 +203,67 @@ def main_mesh_reflection(args, ctx, native, cam, geo, lo, hi, out):
     ctx.close()
 
 
+def main_mesh_reflection_meshes(args, ctx, native, synthetic, cam, geo, lo, hi, out):
+    out["how"] = ("per view and shade mode, one process: ngp_set_mesh_reflection on (strength 1, min_transmittance 0.01, t_min 0) with ngp_set_mesh_reflection_meshes off, then on. "
+                  "mesh_pass: HIP events around the whole mesh pass (ngp_get_mesh_pass_ms); reflection_prep_and_trace: ngp_get_frame_mesh_reflection_ms, which holds the new "
+                  "kernel; hit_shade_kernel: HIP events around mesh_reflection_hit_shade_kernel alone (ngp_get_frame_mesh_reflection_hits_ms). Medians of --frames frames after "
+                  "--warmup, with p10 / p90. rays_with_a_hit: of all pixels; hits_of_the_rays: of the pixels that own a ray. Views: overhead, the other modes' view; "
+                  "low_floor_and_wall: a floor under the model and a wall behind it, seen from low over the floor.")
+    low = native.Context(0)
+    low.set_model(synthetic.make_scene(aabb_scale=1, seed=1234, log2_hashmap_size=19))
+    cube = scene()[0][0]
+    low.add_mesh((cube * np.float32([4.0, 0.04, 4.0])).astype(np.float32), (0.0, -0.6, 0.0))
+    low.add_mesh((cube * np.float32([0.04, 1.0, 1.0])).astype(np.float32), (0.95, 0.4, 0.0))
+    low.set_geometry_opts(sun_dir=(-1.0, 1.0, -0.3), ambientcolor=(0.3, 0.2, 0.1))
+    llo, lhi = low.mesh_info(-1)["aabb"]
+    low_cam = native.make_camera(look_at((-0.35, 1.3, -0.35), (0.3, -0.1, 0.3), up=(0.0, 1.0, 0.0)), args.width, args.height, (60.0 * args.width / 64.0,) * 2)
+    rows = [("Shade", native.RENDER_SHADE, None), ("ShadeGridEnvMap", native.RENDER_SHADE_GRID_ENVMAP, "grid"),
+            ("ShadeIrradianceVolume_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, 8), ("ShadeIrradianceVolumeVisible_8", native.RENDER_SHADE_IRRADIANCE_VOLUME, -8)]
+    q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+    n_pixels = args.width * args.height
+    for view, c, view_cam, box in (("overhead", ctx, cam, (lo, hi)), ("low_floor_and_wall", low, low_cam, (llo, lhi))):
+        out["modes"][view] = {}
+        c.set_mesh_reflection(True)
+        for name, mode, what in rows:
+            if what == "grid":
+                c.compute_envmap_grid(8, 8, 64, 32)
+            elif what is not None and what > 0:
+                c.compute_irradiance_volume((what,) * 3, box, 16, 16)
+            elif what is not None:
+                c.compute_irradiance_volume_visibility(16, 16, 5)
+            opts = native.make_opts(render_mode=mode, **geo)
+            row = {}
+            for key, meshes in (("meshes_off", False), ("meshes_on", True)):
+                c.set_mesh_reflection_meshes(meshes)
+                mesh, trace, hits = [], [], []
+                for i in range(args.warmup + args.frames):
+                    c.render(view_cam, opts)
+                    if i >= args.warmup:
+                        mesh.append(c.mesh_pass_ms())
+                        trace.append(c.frame_mesh_reflection_ms())
+                        hits.append(c.frame_mesh_reflection_hits_ms())
+                row[key] = {"mesh_pass": q(mesh), "reflection_prep_and_trace": q(trace)}
+                if meshes:
+                    row[key]["hit_shade_kernel"] = q(hits)
+                    owns = np.any(c.frame_mesh_reflection(n_pixels)[:, 4:7] != 0, axis=1)
+                    hit = c.frame_mesh_reflection_hits(n_pixels)[:, 7] != 0
+                    row["pixels_with_reflection_ray"] = round(float(owns.mean()), 4)
+                    row["rays_with_a_hit"] = round(float(hit.mean()), 4)
+                    row["hits_of_the_rays"] = round(float(hit.sum() / max(1, owns.sum())), 4)
+            c.set_mesh_reflection_meshes(False)
+            row["mesh_pass_on_minus_off_ms"] = round(row["meshes_on"]["mesh_pass"]["median_ms"] - row["meshes_off"]["mesh_pass"]["median_ms"], 4)
+            out["modes"][view][name] = row
+            print(f"{view:20s} {name:30s} mesh pass {row['meshes_off']['mesh_pass']['median_ms']:.4f} -> {row['meshes_on']['mesh_pass']['median_ms']:.4f} ms, prep + trace "
+                  f"{row['meshes_off']['reflection_prep_and_trace']['median_ms']:.4f} -> {row['meshes_on']['reflection_prep_and_trace']['median_ms']:.4f} ms, hit-shade kernel "
+                  f"{row['meshes_on']['hit_shade_kernel']['median_ms']:.4f} ms, owners {row['pixels_with_reflection_ray']}, of them with a hit {row['hits_of_the_rays']}", flush=True)
+        c.set_mesh_reflection(None)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    low.close()
+    ctx.close()
+
+
 def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
     out["how"] = ("Shade-mode Geometry frames, the option off and on (ngp_set_mesh_shadow_on_nerf, strength 0.5, bias 1e-2) in alternating calls of one run. frame: HIP "
                   "events around the whole frame (ngp_get_render_stats frame_ms); nerf_pass: its NeRF launch (kernel_ms); mesh_pass: ngp_get_mesh_pass_ms; "
@@ -287,10 +354,11 @@ def main():
     ap.add_argument("--mesh-shadow-on-nerf", action="store_true", help="Shade frames with the meshes' shadow on the NeRF, off and on in alternating calls")
     ap.add_argument("--ambient-change-on-nerf", action="store_true", help="Shade frames with the meshes' change of the ambient light on the NeRF, off and on in alternating calls, in two views")
     ap.add_argument("--mesh-reflection", action="store_true", help="the mesh pass with the NeRF mirrored in the meshes, off and on, per shade mode")
+    ap.add_argument("--mesh-reflection-meshes", action="store_true", help="the mesh reflection with the meshes in it, off and on, per shade mode, in two views")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "mesh_reflection_meshes_rate.json" if args.mesh_reflection_meshes else "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -312,6 +380,9 @@ def main():
     if args.sun_nerf_shadow:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out)
+    if args.mesh_reflection_meshes:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_mesh_reflection_meshes(args, ctx, native, synthetic, cam, geo, lo, hi, out)
     if args.mesh_reflection:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_mesh_reflection(args, ctx, native, cam, geo, lo, hi, out)
