@@ -735,7 +735,7 @@ NGP_API int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms);
  *   option alone.
  * Several devices: the option travels to the peers with the geometry and each device shadows its own share; ngp_get_frame_mesh_shadow and
  *   ngp_get_frame_mesh_shadow_ms read the primary's share only.
- * Stated limits: the shadow is hard-edged and there is one directional light; the NeRF pixel is scaled as a whole at its largest-weight
+ * Stated limits: the shadow is hard-edged unless ngp_set_sun_disk (below) is on, and there is one directional light; the NeRF pixel is scaled as a whole at its largest-weight
  *   sample, there is no per-sample shadowing along the ray; a pixel of alpha <= 0.2 is never shadowed; shadows already baked into the
  *   photographs are not removed; the ambient light on the NeRF changes only with ngp_set_ambient_change_on_nerf (the next block). */
 typedef struct ngp_mesh_shadow_on_nerf_desc { float strength; float bias; } ngp_mesh_shadow_on_nerf_desc;
@@ -748,6 +748,56 @@ NGP_API int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_de
 NGP_API int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
 /* device time (HIP events) of nerf_mesh_shadow_kernel in the last frame's last sample; 0 after a frame without it */
 NGP_API int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms);
+
+/* sun: the sun's disk. Every sun shadow above is one boolean a pixel, and on a mesh pixel the mesh pass's shadow ray sees one mesh only
+ * (M3's rule). This option gives the directional light an angular radius: K shadow rays a pixel are spread over the disk and tested against
+ * ALL meshes (the sunlit volume's query: a triangle of any mesh within 100 along the ray), and the open fraction takes the boolean's place
+ * wherever a mesh can stand in front of the sun. Context state, set like ngp_set_sun_nerf_shadow; off by default, and with it off every
+ * frame is the one it was, as bytes.
+ *
+ * The table of a sample, formed in double and rounded to float once; K = n_rays, s = the spp index of the sample (ngp_camera::spp_index +
+ *   the sample's number in the call, what the sample's pixel offset is drawn with):
+ *     s^ = sun_dir / |sun_dir|; a = the coordinate axis where |s^_j| is smallest, the lowest index on ties;
+ *     u = (a x s^) / |a x s^|, v = s^ x u;
+ *     r_k = sqrt((k + 0.5) / K) for K > 1, r_0 = 0 for K = 1;
+ *     phi_k = k pi (3 - sqrt 5) + 2 pi frac(s 0.6180339887498949);
+ *     d_k = unit(s^ + tan(angular_radius) r_k (cos phi_k u + sin phi_k v)).
+ *   Every pixel of a sample uses the same table, successive samples use rotated ones. The kernels receive the K float directions by value
+ *   in their arguments (no copy in the stream, no synchronisation) and use them as they are, without renormalising.
+ *   ngp_sun_disk_directions returns that table; it is host arithmetic and works on a host-only context.
+ * Mesh pixels, in every Geometry frame with meshes, with or without a model: the frame takes the split mesh pass (G-buffer -> lists ->
+ *   deferred shade; meshes alone fill the shadow list without tracing it) and mesh_sun_disk_kernel runs behind mesh_gbuffer_kernel, before
+ *   the shadow list's prep step. A pixel owns a disk where it is covered and its primary ray found a triangle. q = pos + 1e-3 normalize(ff),
+ *   the shadow list's origin as bits; count = the number of k with a triangle of any mesh within 100 of q along d_k;
+ *   V = (K - count) / K, exact in float, takes the place of M4's shadow in the G-buffer, so the deferred shade's sun colour is scaled by
+ *   fl(V T_s). The pixel's shadow-list entry is rewritten: live (origin q, t = (t_min, +inf), the central direction it had) where V > 0,
+ *   dead otherwise, so with ngp_set_sun_nerf_shadow on the NeRF's shadow ray is still one ray along the sun's centre, from every pixel a
+ *   part of the disk reaches. A covered pixel without a triangle keeps M4's value.
+ * NeRF pixels, where ngp_set_mesh_shadow_on_nerf is on too: owner, p and q = p + bias s^ are that block's; count as above from q;
+ *   f = fl(1 - fl(strength fl(count / K))); the composite is that block's. Its record's w becomes 1 + count / K: 1 is open and 2 is blocked
+ *   as before. count = K gives the hard pass's f as bits. Without the disk the pass runs the kernel it ran before.
+ * Identities as bytes: the option off; no meshes; NeRF mode. With the disk on, strength 0 gives the NeRF pixels of
+ *   ngp_set_mesh_shadow_on_nerf off. Frames and records are bit-identical from run to run: no atomics, and a pixel's count does not depend
+ *   on which other pixels its wave holds.
+ * Refusals, on any context, leaving the option alone: an angular_radius that is not finite, negative or above 0.5 rad; n_rays outside
+ *   {1, 2, 4, 8, 16}. ngp_sun_disk_directions also refuses a sun_dir that is not finite or has no length, and needs the option on.
+ * Several devices: the option travels to the peers with the geometry; ngp_get_frame_sun_disk and ngp_get_frame_sun_disk_ms read the
+ *   primary's share only.
+ * Stated limits: the SH9 volume's sun pass stays hard-edged; the mirrored hit's shadow2 (ngp_set_mesh_reflection_meshes) stays hard-edged;
+ *   the NeRF's own shadow ray stays one central ray; the pattern is the same for every pixel of a sample, so at 1 spp a wide penumbra
+ *   shows K + 1 levels as bands; there is still one light. */
+typedef struct ngp_sun_disk_desc { float angular_radius; /* rad, in [0, 0.5]; the real sun: 0.00465 */ uint32_t n_rays; /* 1, 2, 4, 8 or 16 */ } ngp_sun_disk_desc;
+/* desc == NULL: off (the default) */
+NGP_API int ngp_set_sun_disk(ngp_ctx* ctx, const ngp_sun_disk_desc* desc /* nullable: off */);
+NGP_API int ngp_get_sun_disk(ngp_ctx* ctx, ngp_sun_disk_desc* out, int* enabled);
+/* the table the frame's sample of spp index `spp_index` uses under the sun direction sun_dir: 3 n_rays floats */
+NGP_API int ngp_sun_disk_directions(ngp_ctx* ctx, const float* sun_dir /* 3 */, uint32_t spp_index, float* out /* 3 n_rays */);
+/* stage entry for tests: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on a multi-device context
+ * the primary's tile-packed share): (q_xyz, 1 + count); zeros where the pixel owns no disk. n_pixels must be that frame's extent. Refuses
+ * when the last frame did not run the pass. */
+NGP_API int ngp_get_frame_sun_disk(ngp_ctx* ctx, float* out /* n_pixels x 4 */, size_t n_pixels);
+/* device time (HIP events) of mesh_sun_disk_kernel in the last frame's last sample; refuses when the last frame did not run the pass */
+NGP_API int ngp_get_frame_sun_disk_ms(ngp_ctx* ctx, float* ms);
 
 /* ambient: what the inserted meshes change in the ambient light on the NeRF (differential rendering). The context holds a second SH9
  * volume, the REFERENCE volume: the scene before anything was inserted. With the option on, a NeRF pixel that owns a surface point has its

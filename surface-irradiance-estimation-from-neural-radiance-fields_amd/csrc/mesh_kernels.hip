@@ -1207,6 +1207,132 @@ void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P,
 	hipLaunchKernelGGL(nerf_mesh_shadow_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, L, strength, bias);
 }
 
+// ---- the sun's disk (ngp_set_sun_disk; contract in include/ngp_hip.h, "sun: the sun's disk"). K shadow rays a pixel along the sample's
+// table D, each tested against ALL meshes (any_hit); the blocked count replaces the boolean on mesh pixels (mesh_sun_disk_kernel, between
+// mesh_gbuffer_kernel and the shadow list's prep step) and on NeRF pixels (nerf_mesh_soft_shadow_kernel, in nerf_mesh_shadow_kernel's place).
+
+// the lane of the n-th set bit of m (n < popcount(m)): a select by halves
+NGP_DEV uint32_t nth_set_lane(unsigned long long m, uint32_t n) {
+	uint32_t pos = 0;
+#pragma unroll
+	for (uint32_t w = 32; w >= 1; w >>= 1) {
+		const uint32_t c = (uint32_t)__popcll((m >> pos) & ((1ull << w) - 1ull));
+		if (n >= c) {
+			n -= c;
+			pos += w;
+		}
+	}
+	return pos;
+}
+
+// count = the number of k < K with any_hit(S, q, d_k), for every lane with owner set; 0 for the others. The one definition of the count:
+// both kernels call it, with every lane of the wave alive (it ballots and shuffles).
+// WAVE: the wave ballots its owners and deals (owner, k) items over its lanes, K adjacent lanes to a pixel, in rounds of 64 / K owners. The
+// K rays of a pixel share an origin and differ by the disk's radius in direction, so a lane group walks the same nodes; a pixel's count is
+// the popcount of its group's slice of the ballot of any_hit: no atomics and no LDS. !WAVE: every owner loops over its K rays. A ray's
+// boolean comes from the same any_hit on the same (q, d_k) bits in both, so the counts are equal by construction.
+// S by value, as in closest_hit.
+template <bool WAVE>
+NGP_DEV uint32_t sun_disk_count(const MeshSceneParams S, const SunDisk& D, bool owner, f3 q) {
+	const uint32_t K = D.n_rays;
+	uint32_t count = 0;
+	if constexpr (!WAVE) {
+		if (owner)
+			for (uint32_t k = 0; k < K; ++k) count += any_hit(S, q, ld3(D.d + 3 * k)) ? 1u : 0u;
+		return count;
+	} else {
+		const unsigned long long owners = __ballot(owner);
+		const uint32_t n_own = (uint32_t)__popcll(owners), lane = __lane_id();
+		const uint32_t per_round = 64u / K, k = lane % K, group = lane / K;
+		const uint32_t my_ord = (uint32_t)__popcll(owners & ((1ull << lane) - 1ull)); // an owner's rank among the wave's owners
+		const f3 dir = ld3(D.d + 3 * k);
+		const unsigned long long slice = (1ull << K) - 1ull; // (K <= 16)
+		for (uint32_t base = 0; base < n_own; base += per_round) { // (wave-uniform bounds: every lane takes every shuffle and ballot)
+			const uint32_t j = base + group;
+			const bool item = j < n_own;
+			const int src = (int)nth_set_lane(owners, item ? j : 0u);
+			const f3 org = mk3(__shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src));
+			const unsigned long long hits = __ballot(item && any_hit(S, org, dir));
+			if (owner && my_ord >= base && my_ord < base + per_round) count = (uint32_t)__popcll((hits >> ((my_ord - base) * K)) & slice);
+		}
+		return count;
+	}
+}
+
+// one thread a pixel on the frame's pixel map. A pixel owns a disk where it is covered (plane 1's w) and its primary ray found a triangle
+// (plane 2's w); q = mirror_ray's q, the shadow list's bits. V = (K - count) / K, exact for these K, goes over plane 0's w; the pixel's entry
+// of the shadow list is rewritten: live (origin q, t = (t_min, +inf), the central direction it has) where V > 0, else dead (origin 0,
+// t = (0, 0)). record: (q, 1 + count); the host cleared it, and every other pixel leaves it so. A covered pixel without a hit keeps M4's.
+template <bool WAVE>
+__global__ void mesh_sun_disk_kernel(const MeshSceneParams S, const CameraParams C, const FrameLayout L, const SunDisk D, float t_min, float4* __restrict__ gbuf,
+                                     float* __restrict__ ray_o, float2* __restrict__ ray_t, float4* __restrict__ record) {
+	uint32_t x, y, idx;
+	const bool mine = frame_pixel(L, C, x, y, idx);
+	bool owner = false;
+	f3 q = mk3(0.f, 0.f, 0.f);
+	if (mine) {
+		const float4 g1 = gbuf[(size_t)L.n_pixels + idx];
+		if (g1.w != 0.0f) { // (a pixel that is not covered may hold a stale plane 2)
+			const float4 g2 = gbuf[2 * (size_t)L.n_pixels + idx];
+			if (g2.w != 0.0f) {
+				const float4 g0 = gbuf[idx];
+				f3 r;
+				float c;
+				mirror_ray(mk3(g0.x, g0.y, g0.z), mk3(g1.x, g1.y, g1.z), mk3(g2.x, g2.y, g2.z), q, r, c);
+				owner = true;
+			}
+		}
+	}
+	const uint32_t count = sun_disk_count<WAVE>(S, D, owner, q);
+	if (!owner) return;
+	const float V = (float)(D.n_rays - count) / (float)D.n_rays;
+	gbuf[idx].w = V;
+	const bool live = V > 0.0f;
+	st3(ray_o + 3 * (size_t)idx, live ? q : mk3(0.f, 0.f, 0.f));
+	ray_t[idx] = live ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
+	record[idx] = make_float4(q.x, q.y, q.z, 1.0f + (float)count);
+}
+
+// nerf_mesh_shadow_kernel with the disk: owner, p and q = p + bias shadow_ray_dir(P) as there; f = 1 - strength (count / K), each operation
+// rounded, so count = K gives that kernel's f as bits and count = 0 its open pixel; record: (p, 1 + count / K).
+template <bool WAVE>
+__global__ void nerf_mesh_soft_shadow_kernel(const MeshSceneParams S, const MeshShadeParams P, const ModelParams M, const CameraParams C, float4* __restrict__ frame_buffer,
+                                             const float* __restrict__ depth_buffer, const float4* __restrict__ nerf, float4* __restrict__ record, const FrameLayout L,
+                                             const SunDisk D, float strength, float bias) {
+	uint32_t x, y, idx;
+	const bool mine = frame_pixel(L, C, x, y, idx);
+	float4 n = make_float4(0.f, 0.f, 0.f, 0.f);
+	if (mine) n = nerf[idx];
+	const bool owner = n.w > 0.2f;
+	f3 p = mk3(0.f, 0.f, 0.f), q = p;
+	if (owner) {
+		p = nerf_surface_point(M, C, x, y, depth_buffer[idx]);
+		q = add3(p, scale3(shadow_ray_dir(P), bias));
+	}
+	const uint32_t count = sun_disk_count<WAVE>(S, D, owner, q);
+	if (n.w == 0.0f) return; // the NeRF pass wrote nothing here (or the pixel is not this launch's): it stays the mesh pass's
+	float f = 1.0f;
+	if (owner) {
+		const float blocked = (float)count / (float)D.n_rays;
+		f = 1.0f - strength * blocked;
+		record[idx] = make_float4(p.x, p.y, p.z, 1.0f + blocked);
+	}
+	frame_buffer[idx] = nerf_over_mesh(frame_buffer[idx], n, f);
+}
+
+// wave: the layout that deals a pixel's rays over adjacent lanes; else one thread a pixel loops over its rays (the same integers)
+void launch_mesh_sun_disk(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, const SunDisk& D, bool wave, float t_min, float4* gbuf, float* ray_o,
+                          float2* ray_t, float4* record, hipStream_t stream) {
+	if (wave) hipLaunchKernelGGL(mesh_sun_disk_kernel<true>, pixel_blocks(C), pixel_threads(), 0, stream, S, C, L, D, t_min, gbuf, ray_o, ray_t, record);
+	else hipLaunchKernelGGL(mesh_sun_disk_kernel<false>, pixel_blocks(C), pixel_threads(), 0, stream, S, C, L, D, t_min, gbuf, ray_o, ray_t, record);
+}
+void launch_nerf_mesh_soft_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer,
+                                  const float* depth_buffer, const float4* nerf, float4* record, const FrameLayout& L, const SunDisk& D, bool wave, float strength, float bias,
+                                  hipStream_t stream) {
+	if (wave) hipLaunchKernelGGL(nerf_mesh_soft_shadow_kernel<true>, pixel_blocks(C), pixel_threads(), 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, L, D, strength, bias);
+	else hipLaunchKernelGGL(nerf_mesh_soft_shadow_kernel<false>, pixel_blocks(C), pixel_threads(), 0, stream, S, P, M, C, frame_buffer, depth_buffer, nerf, record, L, D, strength, bias);
+}
+
 // ---- the meshes seen by the mirror ray (ngp_set_mesh_reflection_meshes; contract in include/ngp_hip.h, "mesh reflection"). One thread a
 // pixel on the frame's pixel map, between mesh_reflection_rays_kernel and the list's prep step: ray_d still holds r as mirror_ray formed it
 // and ray_t = (t_min, t_hit), so normalize3(r) has the bits closest_hit was given. A pixel owns a hit where hit_ids names a mesh. For it:

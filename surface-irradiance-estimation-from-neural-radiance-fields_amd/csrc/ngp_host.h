@@ -162,6 +162,14 @@ void launch_mesh_reflection_hit_shade(const MeshSceneParams& S, const MeshShadeP
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
+// ngp_set_sun_disk: K shadow rays a pixel over the sun's disk against all meshes. On the G-buffer behind launch_mesh_gbuffer: V over plane 0's w,
+// the owners' shadow-list entries rewritten, record (q, 1 + count); and launch_nerf_mesh_shadow with the blocked fraction in the boolean's place.
+// wave: a pixel's rays on adjacent lanes, else one thread a pixel looping over them (the same integers)
+void launch_mesh_sun_disk(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, const SunDisk& D, bool wave, float t_min, float4* gbuf, float* ray_o,
+                          float2* ray_t, float4* record, hipStream_t stream);
+void launch_nerf_mesh_soft_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer,
+                                  const float* depth_buffer, const float4* nerf, float4* record, const FrameLayout& L, const SunDisk& D, bool wave, float strength, float bias,
+                                  hipStream_t stream);
 // ngp_set_ambient_change_on_nerf: the NeRF's normal at every owner pixel's surface point (record: 3 float4 a pixel), then g = E_after / E_before
 // there, n.rgb scaled in place; launch_nerf_composite closes the frame when the meshes' shadow on the NeRF is off (f = 1, no traversal)
 void launch_nerf_surface_normals(const ModelParams& M, const CameraParams& C, const FrameLayout& L, const float* depth_buffer, const float4* nerf, float4* record,
@@ -500,6 +508,11 @@ struct ngp_ctx {
 	bool mesh_reflection_meshes = false;
 	ngp::FramePass pass_mesh_reflection_hits{2};
 	ngp::DevArray<int2> d_mr_hit_ids; // its scratch: the (mesh, triangle) each mirror ray is cut at, (-1, -1) without a hit
+	// ---- the sun's disk (ngp_set_sun_disk); a peer's copy follows the primary's with the geometry. (q, 1 + count) a pixel of the last sample
+	// (ngp_get_frame_sun_disk); events around mesh_sun_disk_kernel (ngp_get_frame_sun_disk_ms). The G-buffer and the shadow list are the sun shadow's.
+	bool sun_disk = false;
+	ngp_sun_disk_desc sun_disk_desc{};
+	ngp::FramePass pass_sun_disk{1};
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a

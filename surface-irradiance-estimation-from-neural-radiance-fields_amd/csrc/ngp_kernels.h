@@ -249,5 +249,10 @@ struct MeshReflectionList { // the reflection ray list of a frame as the deferre
 	float strength;
 	const float4* hits;   // nullable (ngp_set_mesh_reflection_meshes off): 2 float4 a pixel from mesh_reflection_hit_shade_kernel: (p2, shadow2), (C2, 1); zeros without a hit
 };
+constexpr uint32_t SUN_DISK_MAX_RAYS = 16;
+struct SunDisk { // the shadow directions of one sample over the sun's disk (ngp_set_sun_disk), a kernel argument by value: the host's table, used as it is
+	float d[3 * SUN_DISK_MAX_RAYS]; // direction k at d[3 k]; entries from n_rays on are zero
+	uint32_t n_rays;                // 1, 2, 4, 8 or 16: it divides the wave
+};
 
 } // namespace ngp

@@ -77,6 +77,7 @@ void usage() {
 	             "             [--irradiance_volume_res N] [--irradiance_volume_visibility] [--irradiance_volume_bounces N] [--irradiance_volume_sun]\n"
 	             "             [--irradiance_volume_sun_nerf_shadow] [--sun_nerf_shadow [--sun_nerf_shadow_t_min X]]\n"
 	             "             [--mesh_shadow_on_nerf [--mesh_shadow_on_nerf_strength X]] [--ambient_change_on_nerf]\n"
+	             "             [--sun_disk [--sun_disk_angular_radius X] [--sun_disk_rays K]]\n"
 	             "             [--mesh_reflection [--mesh_reflection_strength X] [--mesh_reflection_meshes]]\n"
 	             "             [--exposure E] [--n_steps N] [--save_snapshot OUT.ingp] [--network CONFIG.json]\n"
 	             "             [--save_mesh OUT.obj|OUT.ply [--marching_cubes_res N] [--marching_cubes_density_thresh T]] [--no-gui] [--no-train] [--version]\n"
@@ -94,6 +95,9 @@ int main(int argc, char** argv) {
 		std::string scene, snapshot, screenshot, shot_transforms, shot_dir, render_mode = "Shade", save_snapshot, network, video_path, video_output = "video_%04d.png";
 		int width = 1920, height = 1080, spp = 1, volume_res = 8, volume_bounces = 0, n_steps = -1, video_seconds = 1, video_fps = 60, video_spp = 8;
 		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false, sun_nerf_shadow = false, mesh_shadow_on_nerf = false, ambient_change_on_nerf = false, mesh_reflection = false, mesh_reflection_meshes = false;
+		bool sun_disk = false;
+		float sun_disk_angular_radius = 0.00465f;
+		int sun_disk_rays = 16;
 		float exposure = 0.f, sun_nerf_shadow_t_min = 0.f, mesh_shadow_on_nerf_strength = 0.5f, mesh_reflection_strength = 1.f;
 		for (int i = 1; i < argc; ++i) {
 			std::string a = argv[i];
@@ -118,6 +122,9 @@ int main(int argc, char** argv) {
 			else if (a == "--irradiance_volume_sun_nerf_shadow") volume_sun_nerf_shadow = true; // ... with the NeRF's density in front of that sun (with --irradiance_volume_sun)
 			else if (a == "--sun_nerf_shadow") sun_nerf_shadow = true; // Geometry frames: the NeRF's density shadows the frames' own sun on mesh pixels
 			else if (a == "--sun_nerf_shadow_t_min") sun_nerf_shadow_t_min = (float)std::atof(val().c_str()); // ... ignoring the NeRF within this distance of the surface
+			else if (a == "--sun_disk") sun_disk = true; // Geometry frames with meshes: the sun has a disk, soft mesh shadows on the meshes and (with --mesh_shadow_on_nerf) on the NeRF
+			else if (a == "--sun_disk_angular_radius") sun_disk_angular_radius = (float)std::atof(val().c_str()); // ... of this angular radius, rad
+			else if (a == "--sun_disk_rays") sun_disk_rays = std::atoi(val().c_str()); // ... and this many shadow rays a pixel: 1, 2, 4, 8 or 16
 			else if (a == "--mesh_shadow_on_nerf") mesh_shadow_on_nerf = true; // Geometry frames: the meshes throw the sun's shadow onto the NeRF
 			else if (a == "--mesh_shadow_on_nerf_strength") mesh_shadow_on_nerf_strength = (float)std::atof(val().c_str()); // ... taking this share of a shadowed pixel's colour away
 			else if (a == "--ambient_change_on_nerf") ambient_change_on_nerf = true; // Geometry frames: NeRF pixels follow what the meshes change in the ambient light (the two volumes are computed before the frame)
@@ -154,6 +161,9 @@ int main(int argc, char** argv) {
 		testbed.m_sun_nerf_shadow = sun_nerf_shadow;
 		testbed.m_sun_nerf_shadow_t_min = sun_nerf_shadow_t_min;
 		testbed.m_mesh_shadow_on_nerf = mesh_shadow_on_nerf;
+		testbed.m_sun_disk = sun_disk;
+		testbed.m_sun_disk_angular_radius = sun_disk_angular_radius;
+		testbed.m_sun_disk_rays = (uint32_t)sun_disk_rays;
 		testbed.m_mesh_shadow_on_nerf_strength = mesh_shadow_on_nerf_strength;
 		testbed.m_ambient_change_on_nerf = ambient_change_on_nerf;
 		testbed.m_mesh_reflection = mesh_reflection;

@@ -258,6 +258,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->sun_nerf_shadow_desc = primary->sun_nerf_shadow_desc;
 	peer->mesh_shadow_on_nerf = primary->mesh_shadow_on_nerf; // each device shadows its own share
 	peer->mesh_shadow_on_nerf_desc = primary->mesh_shadow_on_nerf_desc;
+	peer->sun_disk = primary->sun_disk; // each device spreads the shadow rays of its own share
+	peer->sun_disk_desc = primary->sun_disk_desc;
 	peer->ambient_change_on_nerf = primary->ambient_change_on_nerf; // each device scales its own share
 	peer->ambient_change_desc = primary->ambient_change_desc;
 	peer->mesh_reflection = primary->mesh_reflection; // each device traces the mirror rays of its own share

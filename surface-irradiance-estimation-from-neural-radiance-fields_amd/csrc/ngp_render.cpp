@@ -155,6 +155,50 @@ void make_frame_params(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opt
 	}
 }
 
+// the shadow directions of the sample of spp index s over the sun's disk (contract: include/ngp_hip.h, "sun: the sun's disk"): formed in
+// double in this order and rounded to float once. 3 n_rays floats.
+void sun_disk_table(const ngp_sun_disk_desc& desc, const float* sun_dir, uint32_t s, float* out) {
+	const double PI = 3.14159265358979323846;
+	const double x = sun_dir[0], y = sun_dir[1], z = sun_dir[2];
+	const double len = std::sqrt(x * x + y * y + z * z);
+	if (!std::isfinite(len) || !(len > 0.0)) throw std::runtime_error("sun disk: the sun direction must be finite and have a length");
+	const double sh[3] = {x / len, y / len, z / len};
+	int a = 0;
+	for (int j = 1; j < 3; ++j)
+		if (std::fabs(sh[j]) < std::fabs(sh[a])) a = j;
+	const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+	const double c[3] = {e[1] * sh[2] - e[2] * sh[1], e[2] * sh[0] - e[0] * sh[2], e[0] * sh[1] - e[1] * sh[0]};
+	const double cl = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+	const double u[3] = {c[0] / cl, c[1] / cl, c[2] / cl};
+	const double v[3] = {sh[1] * u[2] - sh[2] * u[1], sh[2] * u[0] - sh[0] * u[2], sh[0] * u[1] - sh[1] * u[0]};
+	const double tr = std::tan((double)desc.angular_radius);
+	const double golden = PI * (3.0 - std::sqrt(5.0));
+	const double turn = (double)s * 0.6180339887498949;
+	const double rot = 2.0 * PI * (turn - std::floor(turn));
+	const uint32_t K = desc.n_rays;
+	for (uint32_t k = 0; k < K; ++k) {
+		const double r = K > 1 ? std::sqrt(((double)k + 0.5) / (double)K) : 0.0;
+		const double phi = (double)k * golden + rot;
+		const double cp = std::cos(phi), sp = std::sin(phi), m = tr * r;
+		double w[3];
+		for (int j = 0; j < 3; ++j) w[j] = sh[j] + m * (cp * u[j] + sp * v[j]);
+		const double wl = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+		for (int j = 0; j < 3; ++j) out[3 * k + j] = (float)(w[j] / wl);
+	}
+}
+SunDisk sun_disk_of(const ngp_ctx* ctx, uint32_t spp_index) {
+	SunDisk D{};
+	D.n_rays = ctx->sun_disk_desc.n_rays;
+	sun_disk_table(ctx->sun_disk_desc, ctx->shade.sun_dir, spp_index, D.d);
+	return D;
+}
+// NGP_SUN_DISK_LAYOUT=thread: one thread a pixel loops over its rays instead of the wave dealing them over its lanes (A/B runs,
+// tools/mesh_shade_rate.py --sun-disk; the same integers). Read a frame, so one process can alternate.
+bool sun_disk_wave_layout() {
+	const char* e = getenv("NGP_SUN_DISK_LAYOUT");
+	return !e || strcmp(e, "thread") != 0;
+}
+
 // what can be refused before anything is allocated or enqueued
 void validate_render_request(const ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& opts) {
 	if (cam.width <= 0 || cam.height <= 0 || cam.width > 65536 || cam.height > 65536) throw std::runtime_error("invalid render resolution"); // (tile counts stay inside 32 bits)
@@ -290,7 +334,8 @@ struct FramePlan {
 	bool reflection_meshes = false; // ... and the meshes in it: the cut rays' hits are shaded between the list's fill and its prep
 	bool mesh_shadow = false;    // the meshes in front of the sun on the NeRF: one kernel behind the NeRF launch finishes its composite
 	bool ambient_change = false; // the meshes' change of the ambient light on the NeRF: normals at the owners' surface points, then g = E_after / E_before
-	bool split() const { return sun_shadow || reflection; }
+	bool sun_disk = false;       // the sun's disk: K shadow rays a pixel against all meshes on the G-buffer (meshes alone fill the shadow list without tracing it), and in the mesh shadow's kernel
+	bool split() const { return sun_shadow || reflection || sun_disk; }
 	bool scratch() const { return mesh_shadow || ambient_change; } // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
 };
 static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_pixels) {
@@ -321,6 +366,12 @@ static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_
 			throw std::runtime_error("ambient_change_on_nerf frames need the reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
 		if (ctx->M.wide.width) throw std::runtime_error("ambient_change_on_nerf frames need a grid-encoded model (ngp_set_ambient_change_on_nerf)");
 		ensure_ambient_change_buffers(ctx, n_pixels);
+	}
+	p.sun_disk = ctx->sun_disk && p.have_meshes;
+	if (p.sun_disk) {
+		(void)sun_disk_of(ctx, 0); // (a sun direction without a length is refused here, ahead of the frame's work)
+		ensure_sun_shadow_buffers(ctx, n_pixels);
+		if (ctx->pass_sun_disk.ensure(n_pixels)) ctx->pass_sun_disk.grow(n_pixels);
 	}
 	return p;
 }
@@ -379,6 +430,13 @@ static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const Mod
 		const RayList& ss = ctx->ss_rays;
 		trace_pixel_rays(f, M, ss, ctx->pass_sun_shadow, f.plan.sun_shadow, ctx->sun_nerf_shadow_desc.min_transmittance, last, [&] {
 			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), f.stream);
+			if (!f.plan.sun_disk) return;
+			const FramePass& disk = ctx->pass_sun_disk; // (the kernel writes its owners' records; the clear covers the others)
+			disk.clear(f.L.n_pixels, f.stream);
+			disk.begin(f.slot, f.stream, last);
+			launch_mesh_sun_disk(ctx->mesh_scene, C, f.L, sun_disk_of(ctx, C.spp), sun_disk_wave_layout(), ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(),
+			                     ss.t.get(), disk.record.get(), f.stream);
+			disk.end(f.slot, f.stream, last);
 		}, [] {});
 		MeshReflectionList R{};
 		if (f.plan.reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
@@ -438,8 +496,12 @@ static void closing_passes(const FrameCall& f, const ModelParams& M, const Camer
 	if (f.plan.mesh_shadow) {
 		const FramePass& pass = ctx->pass_mesh_shadow;
 		pass.begin(f.slot, f.stream, last);
-		launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L,
-		                        ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
+		if (f.plan.sun_disk)
+			launch_nerf_mesh_soft_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L, sun_disk_of(ctx, C.spp),
+			                             sun_disk_wave_layout(), ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
+		else
+			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L,
+			                        ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
 		pass.end(f.slot, f.stream, last);
 	}
 }
@@ -506,6 +568,7 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->pass_mesh_reflection_hits.ran(slot, plan.reflection_meshes, n_pixels);
 	ctx->pass_mesh_shadow.ran(slot, plan.mesh_shadow, n_pixels);
 	ctx->pass_ambient_change.ran(slot, plan.ambient_change, n_pixels);
+	ctx->pass_sun_disk.ran(slot, plan.sun_disk, n_pixels);
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -735,7 +798,46 @@ int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, i
 	});
 }
 
+int ngp_set_sun_disk(ngp_ctx* ctx, const ngp_sun_disk_desc* desc) {
+	return guarded(ctx, [&] {
+		if (desc) {
+			if (!std::isfinite(desc->angular_radius) || desc->angular_radius < 0.0f || desc->angular_radius > 0.5f)
+				throw std::runtime_error("invalid sun disk descriptor: angular_radius must be finite and lie in [0, 0.5] rad");
+			const uint32_t k = desc->n_rays;
+			if (!(k == 1 || k == 2 || k == 4 || k == 8 || k == 16)) throw std::runtime_error("invalid sun disk descriptor: n_rays must be 1, 2, 4, 8 or 16");
+		}
+		ctx->sun_disk = desc != nullptr;
+		ctx->sun_disk_desc = desc ? *desc : ngp_sun_disk_desc{};
+	});
+}
+
+int ngp_get_sun_disk(ngp_ctx* ctx, ngp_sun_disk_desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = ctx->sun_disk_desc;
+		*enabled = ctx->sun_disk ? 1 : 0;
+	});
+}
+
+int ngp_sun_disk_directions(ngp_ctx* ctx, const float* sun_dir, uint32_t spp_index, float* out) {
+	return guarded(ctx, [&] {
+		if (!sun_dir || !out) throw std::runtime_error("null argument");
+		if (!ctx->sun_disk) throw std::runtime_error("the sun has no disk: call ngp_set_sun_disk first");
+		sun_disk_table(ctx->sun_disk_desc, sun_dir, spp_index, out);
+	});
+}
+
 // what the last frame's optional passes left (FramePass, ngp_host.h)
+int ngp_get_frame_sun_disk(ngp_ctx* ctx, float* out, size_t n_pixels) {
+	return guarded(ctx, [&] { ctx->pass_sun_disk.read_record(ctx, out, n_pixels, "the last frame ran no sun disk pass (ngp_set_sun_disk)"); });
+}
+int ngp_get_frame_sun_disk_ms(ngp_ctx* ctx, float* ms) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!ctx->n_calls || !ctx->pass_sun_disk.hist[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame ran no sun disk pass (ngp_set_sun_disk)");
+		ctx->pass_sun_disk.read_ms(ctx, ms);
+	});
+}
 int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
 	return guarded(ctx, [&] { ctx->pass_sun_shadow.read_record(ctx, out, n_pixels, "the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)"); });
 }

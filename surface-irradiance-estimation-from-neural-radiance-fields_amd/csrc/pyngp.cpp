@@ -261,6 +261,10 @@ PYBIND11_MODULE(pyngp, m) {
 		               "Geometry frames with meshes and a model: the NeRF's density shadows the frames' own sun on mesh pixels (default False)")
 		.def_readwrite("sun_nerf_shadow_min_transmittance", &Testbed::m_sun_nerf_shadow_min_transmittance, "with sun_nerf_shadow: the shadow rays' transmittance floor (0.01)")
 		.def_readwrite("sun_nerf_shadow_t_min", &Testbed::m_sun_nerf_shadow_t_min, "with sun_nerf_shadow: the NeRF is ignored within this distance of the surface (0)")
+		.def_readwrite("sun_disk", &Testbed::m_sun_disk,
+		               "Geometry frames with meshes: the sun has a disk, sun_disk_rays shadow rays a pixel against all meshes give soft shadows on mesh pixels and, with mesh_shadow_on_nerf, on NeRF pixels (default False)")
+		.def_readwrite("sun_disk_angular_radius", &Testbed::m_sun_disk_angular_radius, "with sun_disk: the disk's angular radius in rad, at most 0.5 (0.00465, the real sun)")
+		.def_readwrite("sun_disk_rays", &Testbed::m_sun_disk_rays, "with sun_disk: shadow rays a pixel, 1, 2, 4, 8 or 16 (16)")
 		.def_readwrite("mesh_shadow_on_nerf", &Testbed::m_mesh_shadow_on_nerf,
 		               "Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (default False)")
 		.def_readwrite("mesh_shadow_on_nerf_strength", &Testbed::m_mesh_shadow_on_nerf_strength, "with mesh_shadow_on_nerf: the share of a shadowed NeRF pixel's colour the shadow takes away (0.5)")

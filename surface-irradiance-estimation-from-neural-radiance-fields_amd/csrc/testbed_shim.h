@@ -508,6 +508,10 @@ public:
 			const ngp_irradiance_sun_nerf_desc ns{m_sun_nerf_shadow_min_transmittance, m_sun_nerf_shadow_t_min};
 			check(ngp_set_sun_nerf_shadow(m_ctx, m_sun_nerf_shadow ? &ns : nullptr));
 		}
+		{ // the sun's disk (off: NULL)
+			const ngp_sun_disk_desc sd{m_sun_disk_angular_radius, m_sun_disk_rays};
+			check(ngp_set_sun_disk(m_ctx, m_sun_disk ? &sd : nullptr));
+		}
 		{ // the meshes in front of the sun on the NeRF (off: NULL)
 			const ngp_mesh_shadow_on_nerf_desc ms{m_mesh_shadow_on_nerf_strength, m_mesh_shadow_on_nerf_bias};
 			check(ngp_set_mesh_shadow_on_nerf(m_ctx, m_mesh_shadow_on_nerf ? &ms : nullptr));
@@ -648,6 +652,9 @@ public:
 	bool m_irradiance_volume_sun = false; // that default volume also holds the sun's first bounce off the meshes (the frame's sun: m_sun_dir, the radiance below, bias 1e-3)
 	bool m_sun_nerf_shadow = false; // Geometry frames with meshes and a model: the NeRF's density stands in front of the frames' own sun on mesh pixels (ngp_set_sun_nerf_shadow)
 	float m_sun_nerf_shadow_min_transmittance = 0.01f, m_sun_nerf_shadow_t_min = 0.f; // ... traced down to this transmittance, ignoring the NeRF within t_min of the surface
+	bool m_sun_disk = false; // Geometry frames with meshes: the sun has a disk, K shadow rays a pixel against all meshes on mesh pixels and (with m_mesh_shadow_on_nerf) on NeRF pixels (ngp_set_sun_disk)
+	float m_sun_disk_angular_radius = 0.00465f; // ... of this angular radius, rad (the real sun's)
+	uint32_t m_sun_disk_rays = 16;              // ... and this many rays: 1, 2, 4, 8 or 16
 	bool m_mesh_shadow_on_nerf = false; // Geometry frames with meshes and a model: the meshes throw the sun's shadow onto the NeRF (ngp_set_mesh_shadow_on_nerf)
 	float m_mesh_shadow_on_nerf_strength = 0.5f, m_mesh_shadow_on_nerf_bias = 1e-2f; // ... taking this share of a shadowed NeRF pixel's colour away, from a point lifted this far towards the sun
 	bool m_mesh_reflection = false; // Geometry frames with meshes and a model: one reflection ray a mesh pixel through the NeRF (ngp_set_mesh_reflection)

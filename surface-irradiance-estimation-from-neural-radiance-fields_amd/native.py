@@ -125,6 +125,13 @@ class MeshShadowOnNerfDesc(C.Structure):
     _fields_ = [("strength", C.c_float), ("bias", C.c_float)]
 
 
+class SunDiskDesc(C.Structure):
+    _fields_ = [("angular_radius", C.c_float), ("n_rays", C.c_uint32)]
+
+
+SUN_ANGULAR_RADIUS = 0.00465  # the real sun's, rad
+
+
 class AmbientChangeDesc(C.Structure):
     _fields_ = [("min_irradiance", C.c_float), ("max_gain", C.c_float)]
 
@@ -282,6 +289,11 @@ def load_library():
     L.ngp_get_mesh_shadow_on_nerf.argtypes = [vp, C.POINTER(MeshShadowOnNerfDesc), C.POINTER(C.c_int)]
     L.ngp_get_frame_mesh_shadow.argtypes = [vp, vp, C.c_size_t]
     L.ngp_get_frame_mesh_shadow_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.ngp_set_sun_disk.argtypes = [vp, C.POINTER(SunDiskDesc)]
+    L.ngp_get_sun_disk.argtypes = [vp, C.POINTER(SunDiskDesc), C.POINTER(C.c_int)]
+    L.ngp_sun_disk_directions.argtypes = [vp, vp, C.c_uint32, vp]
+    L.ngp_get_frame_sun_disk.argtypes = [vp, vp, C.c_size_t]
+    L.ngp_get_frame_sun_disk_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.ngp_compute_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc)]
     L.ngp_get_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
     L.ngp_set_reference_irradiance_volume.argtypes = [vp, C.POINTER(IrradianceVolumeDesc), vp]
@@ -1098,6 +1110,53 @@ class Context:
     def frame_mesh_reflection_hits_ms(self):
         """device time of the hit-shade kernel in the last frame's last sample, ms; 0 after a frame without it"""
         return self._frame_pass_ms(self.L.ngp_get_frame_mesh_reflection_hits_ms)
+
+    def set_sun_disk(self, disk=True):
+        """the sun's disk (Geometry frames with meshes): K shadow rays a pixel over the disk against all meshes, on mesh pixels and, with
+        set_mesh_shadow_on_nerf, on NeRF pixels. None or False switches it off (the default), True takes the real sun's 0.00465 rad and 16
+        rays, a dict gives angular_radius and n_rays (1, 2, 4, 8 or 16)"""
+        if disk is None or disk is False:
+            self._check(self.L.ngp_set_sun_disk(self.h, None))
+            return
+        if disk is True:
+            disk = {}
+        if not isinstance(disk, dict) or set(disk) - {"angular_radius", "n_rays"}:
+            raise ValueError("sun_disk: True, False, None or a dict of angular_radius and n_rays")
+        n_rays = disk.get("n_rays", 16)
+        if int(n_rays) != n_rays or not 0 <= n_rays < 2 ** 32:
+            raise ValueError("sun_disk: n_rays must be 1, 2, 4, 8 or 16")
+        d = SunDiskDesc()
+        d.angular_radius, d.n_rays = float(disk.get("angular_radius", SUN_ANGULAR_RADIUS)), int(n_rays)
+        self._check(self.L.ngp_set_sun_disk(self.h, C.byref(d)))
+
+    def sun_disk(self):
+        """None while the option is off, else dict(angular_radius=, n_rays=) as set"""
+        d, on = SunDiskDesc(), C.c_int(0)
+        self._check(self.L.ngp_get_sun_disk(self.h, C.byref(d), C.byref(on)))
+        return dict(angular_radius=d.angular_radius, n_rays=d.n_rays) if on.value else None
+
+    def sun_disk_directions(self, sun_dir, spp_index=0):
+        """(n_rays, 3) float32: the shadow directions the frame's sample of spp index `spp_index` uses under sun_dir (host arithmetic)"""
+        on = self.sun_disk()
+        if on is None:
+            raise RuntimeError("the sun has no disk: call set_sun_disk first")
+        sd = np.ascontiguousarray(sun_dir, np.float32).reshape(3)
+        out = np.zeros((on["n_rays"], 3), np.float32)
+        self._check(self.L.ngp_sun_disk_directions(self.h, _p(sd), int(spp_index), _p(out)))
+        return out
+
+    def frame_sun_disk(self, n_pixels):
+        """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (q xyz, 1 + the blocked rays' count) of the
+        mesh pixel's disk; zeros where the pixel owns none. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros((int(n_pixels), 4), np.float32)
+        self._check(self.L.ngp_get_frame_sun_disk(self.h, _p(out), int(n_pixels)))
+        return out
+
+    def frame_sun_disk_ms(self):
+        """device time of the sun disk kernel in the last frame's last sample, ms; refused after a frame without it"""
+        ms = C.c_float(0)
+        self._check(self.L.ngp_get_frame_sun_disk_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
         """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass

@@ -12,6 +12,11 @@ With --sun-nerf-shadow: per shade mode, in one run, the mesh pass with the optio
 ray-list trace of one shadow ray a local pixel, deferred shade kernel; ngp_set_sun_nerf_shadow at its defaults), of the latter the prep and
 trace alone (ngp_get_frame_sun_shadow_ms), the frame's NeRF pass (kernel_ms) beside them, and how many pixels own a shadow ray.
     python tools/mesh_shade_rate.py --mesh-shadow-on-nerf [--out profiles/mesh_shadow_on_nerf_rate.json]
+    python tools/mesh_shade_rate.py --sun-disk [--sun-disk-rays K] [--out profiles/sun_disk_rate.json]
+
+With --sun-disk: Shade-mode frames with the meshes' shadow on the NeRF on and the sun's disk (ngp_set_sun_disk) off, on in the wave layout and on
+in the one-thread-a-pixel layout, alternating in one run, for the real sun's radius and for 5 degrees: the frame, the mesh pass, the disk
+kernel and the NeRF shadow kernel.
 
 With --mesh-shadow-on-nerf: Shade-mode frames with the meshes' shadow on the NeRF off and on (ngp_set_mesh_shadow_on_nerf at its defaults),
 the calls alternating: the whole frame on the device (frame_ms), its NeRF pass (kernel_ms), its mesh pass, the new kernel alone
@@ -296,6 +301,60 @@ def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
     ctx.close()
 
 
+def main_sun_disk(args, ctx, native, cam, geo, out):
+    out["how"] = ("Shade-mode Geometry frames with ngp_set_mesh_shadow_on_nerf at its defaults, the sun's disk (ngp_set_sun_disk: the real sun's 0.00465 rad and 5 degrees, "
+                  "--sun-disk-rays rays) off, on with a pixel's rays dealt over adjacent lanes of the wave (wave) and on with one thread a pixel looping over its rays "
+                  "(thread, NGP_SUN_DISK_LAYOUT=thread), in alternating calls of one run. frame: HIP events around the whole frame (ngp_get_render_stats frame_ms); mesh_pass: "
+                  "ngp_get_mesh_pass_ms (with the disk on the split pass: G-buffer, disk kernel, deferred shade); sun_disk_kernel: ngp_get_frame_sun_disk_ms; "
+                  "mesh_shadow_kernel: ngp_get_frame_mesh_shadow_ms (nerf_mesh_shadow_kernel, or nerf_mesh_soft_shadow_kernel with the disk). Medians of --frames frames "
+                  "each after --warmup, with p10 / p90. Nothing is asserted on these.")
+    out["n_rays"] = args.sun_disk_rays
+    opts = native.make_opts(render_mode=native.RENDER_SHADE, **geo)
+    n = args.width * args.height
+    q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+    ctx.set_mesh_shadow_on_nerf(True)
+    for name, radius in (("real_sun", 0.00465), ("five_degrees", 0.0872665)):
+        keys = ("off", "wave", "thread")
+        ts = {key: {"frame": [], "mesh_pass": [], "sun_disk_kernel": [], "mesh_shadow_kernel": []} for key in keys}
+        recs = {}
+        for i in range(args.warmup + args.frames):
+            for key in keys:
+                os.environ["NGP_SUN_DISK_LAYOUT"] = "thread" if key == "thread" else "wave"
+                ctx.set_sun_disk(None if key == "off" else dict(angular_radius=radius, n_rays=args.sun_disk_rays))
+                ctx.render(cam, opts)
+                if i >= args.warmup:
+                    ts[key]["frame"].append(ctx.render_stats()["frame_ms"])
+                    ts[key]["mesh_pass"].append(ctx.mesh_pass_ms())
+                    ts[key]["mesh_shadow_kernel"].append(ctx.frame_mesh_shadow_ms())
+                    if key != "off":
+                        ts[key]["sun_disk_kernel"].append(ctx.frame_sun_disk_ms())
+                if i == args.warmup + args.frames - 1 and key != "off":
+                    recs[key] = (ctx.frame_sun_disk(n), ctx.frame_mesh_shadow(n))
+        row = {key: {k: q(v) for k, v in t.items() if v} for key, t in ts.items()}
+        disk, nerf = recs["wave"]
+        count = np.where(disk[:, 3] != 0, disk[:, 3] - 1, 0)
+        row["layouts_give_equal_records"] = bool(disk.tobytes() == recs["thread"][0].tobytes() and nerf.tobytes() == recs["thread"][1].tobytes())
+        row["mesh_pixels_with_disk"] = round(float((disk[:, 3] != 0).mean()), 4)
+        row["mesh_pixels_partial"] = round(float(((count > 0) & (count < args.sun_disk_rays)).mean()), 4)
+        row["mesh_pixels_full"] = round(float((count == args.sun_disk_rays).mean()), 4)
+        row["nerf_pixels_with_surface_point"] = round(float((nerf[:, 3] != 0).mean()), 4)
+        row["nerf_pixels_partial"] = round(float(((nerf[:, 3] > 1) & (nerf[:, 3] < 2)).mean()), 4)
+        row["nerf_pixels_full"] = round(float((nerf[:, 3] == 2).mean()), 4)
+        for key in ("wave", "thread"):
+            row["frame_%s_minus_off_ms" % key] = round(row[key]["frame"]["median_ms"] - row["off"]["frame"]["median_ms"], 4)
+        out["modes"][name] = row
+        print(f"{name}: frame off {row['off']['frame']['median_ms']:.4f} ms, wave {row['wave']['frame']['median_ms']:.4f} ms, thread {row['thread']['frame']['median_ms']:.4f} ms; disk kernel "
+              f"wave {row['wave']['sun_disk_kernel']['median_ms']:.4f} / thread {row['thread']['sun_disk_kernel']['median_ms']:.4f} ms; NeRF shadow kernel off {row['off']['mesh_shadow_kernel']['median_ms']:.4f} / "
+              f"wave {row['wave']['mesh_shadow_kernel']['median_ms']:.4f} / thread {row['thread']['mesh_shadow_kernel']['median_ms']:.4f} ms; equal records {row['layouts_give_equal_records']}", flush=True)
+    os.environ.pop("NGP_SUN_DISK_LAYOUT", None)
+    ctx.set_sun_disk(None)
+    ctx.set_mesh_shadow_on_nerf(None)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
 def main_ambient_change_on_nerf(args, ctx, native, synthetic, cam, geo, lo, hi, out):
     out["how"] = ("Shade-mode Geometry frames, the option off and on (ngp_set_ambient_change_on_nerf, min_irradiance 1e-3, max_gain 4) in alternating calls of one run, per view. "
                   "frame: HIP events around the whole frame (ngp_get_render_stats frame_ms); nerf_pass: its NeRF launch (kernel_ms); mesh_pass: ngp_get_mesh_pass_ms; "
@@ -355,10 +414,12 @@ def main():
     ap.add_argument("--ambient-change-on-nerf", action="store_true", help="Shade frames with the meshes' change of the ambient light on the NeRF, off and on in alternating calls, in two views")
     ap.add_argument("--mesh-reflection", action="store_true", help="the mesh pass with the NeRF mirrored in the meshes, off and on, per shade mode")
     ap.add_argument("--mesh-reflection-meshes", action="store_true", help="the mesh reflection with the meshes in it, off and on, per shade mode, in two views")
+    ap.add_argument("--sun-disk", action="store_true", help="Shade frames with the sun's disk off and on, both kernel layouts, in alternating calls")
+    ap.add_argument("--sun-disk-rays", type=int, default=16, help="with --sun-disk: shadow rays a pixel (1, 2, 4, 8 or 16)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_reflection_meshes_rate.json" if args.mesh_reflection_meshes else "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "sun_disk_rate.json" if args.sun_disk else "mesh_reflection_meshes_rate.json" if args.mesh_reflection_meshes else "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -377,6 +438,9 @@ def main():
                   "median (and minimum) of --frames frames after --warmup; ratio = median / the Shade median of the same run",
            "width": args.width, "height": args.height, "frames": args.frames, "triangles": int(info["n_tris"]), "modes": {}}
     ctx.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
+    if args.sun_disk:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_sun_disk(args, ctx, native, cam, geo, out)
     if args.sun_nerf_shadow:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_sun_nerf_shadow(args, ctx, native, cam, geo, lo, hi, out)
