@@ -943,6 +943,23 @@ NGP_API int ngp_get_frame_mesh_reflection_hits(ngp_ctx* ctx, float* out /* n_pix
 /* device time (HIP events) of the hit-shade kernel in the last frame's last sample; 0 after a frame without it */
 NGP_API int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms);
 
+/* The six frame options together (ngp_set_sun_nerf_shadow, ngp_set_sun_disk, ngp_set_mesh_reflection, ngp_set_mesh_reflection_meshes,
+ * ngp_set_mesh_shadow_on_nerf, ngp_set_ambient_change_on_nerf). Any set of them may be on; each keeps its own block's rule and these hold
+ * between them, as bytes (tests/test_frame_options_gpu.py renders all 48 sets):
+ *   Depth is the frame's with every option off.
+ *   What a record depends on: ngp_get_frame_mesh_reflection on the reflection alone; ngp_get_frame_mesh_reflection_hits on the reflection and
+ *     its sub-option; ngp_get_frame_ambient_change on the ambient change alone; ngp_get_frame_sun_disk on the disk alone;
+ *     ngp_get_frame_sun_shadow on the sun shadow and on whether the disk is on; ngp_get_frame_mesh_shadow on the meshes' shadow and on whether
+ *     the disk is on. No other option changes a bit of it, and a getter refuses after every frame that did not run its pass.
+ *   The disk and the sun shadow: the shadow list's entry of a pixel that owns a disk is live where V > 0, whatever M4 said of it, and dead where
+ *     V = 0; a live entry is traced from q along the sun's centre and the pixel's sun colour is scaled by fl(V T_s). The mirror ray does not
+ *     look at V: its q, r and t_hit are the G-buffer's position and normal alone, and the mirrored hit's shadow2 is the central ray.
+ *   The ambient change and the meshes' shadow, with or without the disk: the ratio scales the scratch first, then the shadow's kernel (hard or
+ *     soft) composites it: the pixel is fl(fl(n g) f) + m k, f = fl(1 - fl(strength fl(count / K))) with the disk.
+ *   Where the NeRF wrote nothing (n.w == 0) the pixel is the mesh pass's of the same set without the meshes' shadow and the ambient change; where
+ *     the primary ray found no triangle the pixel is that of the same set without the sun shadow, the reflection and its sub-option.
+ *   No state survives a frame: a set gives the same colour, depth and records whichever sets and resolutions were rendered before it. */
+
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),
  * Testbed::train_nerf / train_nerf_step (src/testbed_nerf.cu:2949-3431), training_prep_nerf (:3432-3446). The default
