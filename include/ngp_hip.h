@@ -960,6 +960,42 @@ NGP_API int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms);
  *     the primary ray found no triangle the pixel is that of the same set without the sun shadow, the reflection and its sub-option.
  *   No state survives a frame: a set gives the same colour, depth and records whichever sets and resolutions were rendered before it. */
 
+/* mesh materials: a mesh may own a material, the BRDF part of ngp_geometry_opts; a mesh without one is shaded with the context's
+ * ngp_geometry_opts, as every mesh is by default. The sun and up directions stay the context's. Defaults of a material's fields, as a scene
+ * file's "material" object fills the keys it lacks: basecolor (0.8, 0.8, 0.8), ambientcolor (0, 0, 0), metallic 0, subsurface 0, specular 1,
+ * roughness 0.5, sheen 0, clearcoat 0, clearcoat_gloss 0.
+ *
+ * Which material a shade uses: M5 at a pixel uses the material of the mesh whose triangle the pixel's primary ray hit -- the mesh the mesh trace
+ *   chose, and only where it found a triangle. A covered pixel without a triangle (the ray that enters no box and is shaded at the camera)
+ *   uses the context's. The mirror term's F (ngp_set_mesh_reflection) uses the pixel's material. The mirrored hit's C2
+ *   (ngp_set_mesh_reflection_meshes) uses the material of the mesh the mirror ray hit. Nothing else reads a material: hits, q, depth, shadow
+ *   booleans, disk counts and ray lists never depend on one.
+ * Lifetime: a material belongs to its mesh slot. ngp_clear_meshes and ngp_load_scene drop all of them; a mesh added by ngp_add_mesh or
+ *   ngp_load_mesh_file has none; ngp_set_geometry_opts never touches them. ngp_load_scene gives a "Mesh" entry that carries a "material"
+ *   object that material.
+ * Refusals, each naming the field and leaving the state alone: a mesh index outside [0, ngp_n_meshes); a non-finite field. Both calls work
+ *   on a host-only context.
+ * Identities as bytes: while no mesh owns a material, every frame, depth and record is what it was before materials existed, and the frame
+ *   launches those very kernels. With every mesh owning a copy of the context's material, colour and depth are those bytes too. With any
+ *   materials, depth and every geometric record (ngp_get_frame_sun_shadow, _sun_disk, _mesh_shadow, _ambient_change, _mesh_reflection, and
+ *   (p2, shadow2) of _mesh_reflection_hits) are the no-material frame's bytes.
+ * Determinism: no atomics; frames are bit-identical from run to run. The device table (64 bytes a mesh) is uploaded by ngp_set_mesh_material and
+ *   by the calls that change the mesh list, never inside a frame: ngp_render_device stays asynchronous.
+ * Several devices: the materials travel to the peers with the geometry; ngp_get_frame_mesh_ids reads the primary's share only.
+ * Stated limits: the SH9 volume's bounce and sun passes keep one albedo for all meshes (ngp_irradiance_bounce_desc::albedo); no per-triangle
+ *   or per-OBJ-group materials, no textures, no MTL files; the sun and up directions stay per context. */
+typedef struct ngp_mesh_material {
+	float metallic, subsurface, specular, roughness, sheen, clearcoat, clearcoat_gloss;
+	float basecolor[3], ambientcolor[3];
+} ngp_mesh_material;
+NGP_API int ngp_set_mesh_material(ngp_ctx* ctx, int mesh, const ngp_mesh_material* m /* nullable: back to the context's */);
+/* out (nullable) receives the mesh's own material, or where it owns none the context's BRDF fields; own (nullable) receives 1 or 0 */
+NGP_API int ngp_get_mesh_material(ngp_ctx* ctx, int mesh, ngp_mesh_material* out, int* own);
+/* stage entry for tests and tools: per pixel of the LAST frame's LAST sample, in the frame's own pixel order (packed or not; on several devices
+ * the primary's share), the mesh index of the primary hit, -1 for every other pixel. n_pixels must be that frame's extent. Refuses after a
+ * frame that ran without materials. */
+NGP_API int ngp_get_frame_mesh_ids(ngp_ctx* ctx, int32_t* out /* n_pixels */, size_t n_pixels);
+
 
 /* --- training: Testbed::reset_network (src/testbed.cu:3820-4210), Testbed::train (:4364-4470),
  * Testbed::train_nerf / train_nerf_step (src/testbed_nerf.cu:2949-3431), training_prep_nerf (:3432-3446). The default

@@ -93,8 +93,11 @@ NGP_DEV void bvh4_ray_intersect(const TriangleBvhNode* __restrict__ nodes, const
 //    inside the scene box and shades the pixel with alpha 1, depth 0 and N = the ray's direction (NdotV = -1: the ambient term alone);
 //  - a traced ray that hits nothing ends at pos + MAX_DIST * dir, its direction unchanged.
 // hit: the traversal found a triangle (idx > -1). A ray that chose no mesh, or hit nothing in the one it chose, has none.
-NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir, bool& hit) {
+// WITH_ID (the material instantiations): *mesh_id receives the chosen mesh where the ray hit, else -1; without it mesh_id is not looked at.
+template <bool WITH_ID = false>
+NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir, bool& hit, int* mesh_id = nullptr) {
 	hit = false;
+	if constexpr (WITH_ID) *mesh_id = -1;
 	float mint = MAX_DIST;
 	int mesh_idx = -1;
 	for (uint32_t m = 0; m < S.n_meshes; ++m) {
@@ -115,6 +118,7 @@ NGP_DEV void trace_mesh(const MeshSceneParams& S, f3& pos, f3& dir, bool& hit) {
 		f3 a = ld3(tri.a);
 		dir = normalize3(cross3(sub3(ld3(tri.b), a), sub3(ld3(tri.c), a)));
 		hit = true;
+		if constexpr (WITH_ID) *mesh_id = mesh_idx;
 	}
 }
 
@@ -445,9 +449,11 @@ NGP_DEV bool mesh_primary_ray(const MeshSceneParams S, const CameraParams C, uin
 // (:222-271) and M4 write_shadow_ray_result_geometry (:273-278, min_visibility == 1). pos: the primary ray's start in, its end out; hit: it
 // found a triangle; q: where the shadow ray leaves the surface, before M3 advances it to the scene box (the split pass starts the NeRF's
 // shadow ray and the mirror ray there); shadow: 1 where no mesh stands between q and the sun, else 0.
-NGP_DEV void mesh_trace_shadow(const MeshSceneParams S, const MeshShadeParams P, f3 primary_dir, f3& pos, f3& normal, bool& hit, f3& q, float& shadow) {
+// WITH_ID: *mesh_id receives the mesh of the primary hit, -1 without one (geometry never depends on a material: nothing else changes).
+template <bool WITH_ID = false>
+NGP_DEV void mesh_trace_shadow(const MeshSceneParams S, const MeshShadeParams P, f3 primary_dir, f3& pos, f3& normal, bool& hit, f3& q, float& shadow, int* mesh_id = nullptr) {
 	normal = primary_dir;
-	trace_mesh(S, pos, normal, hit);
+	trace_mesh<WITH_ID>(S, pos, normal, hit, mesh_id);
 	const f3 sdir = shadow_ray_dir(P);
 	float nd = dot3(normal, primary_dir);
 	f3 ff = nd < 0.0f ? normal : scale3(normal, -1.0f); // faceforward(n, dir, n)
@@ -460,6 +466,21 @@ NGP_DEV void mesh_trace_shadow(const MeshSceneParams S, const MeshShadeParams P,
 	bool shadow_hit;
 	trace_mesh(S, spos, sn, shadow_hit);
 	shadow = box_contains(S.scene_min, S.scene_max, spos) ? 0.0f : 1.0f;
+}
+
+// the material a shade at mesh m uses (contract: include/ngp_hip.h, "mesh materials"): the mesh's own record where it owns one, else the
+// context's P; the sun and up directions are P's either way. m = -1 (no triangle: the pixel shaded at the camera): P.
+NGP_DEV MeshShadeParams mesh_material_of(const MeshShadeParams P, const MeshMaterial* __restrict__ table, int m) {
+	MeshShadeParams Q = P;
+	if (m < 0) return Q;
+	const float4* rec = reinterpret_cast<const float4*>(table + m);
+	const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+	if (__float_as_uint(d.y) == 0u) return Q;
+	Q.metallic = a.x; Q.subsurface = a.y; Q.specular = a.z; Q.roughness = a.w;
+	Q.sheen = b.x; Q.clearcoat = b.y; Q.clearcoat_gloss = b.z;
+	Q.basecolor[0] = b.w; Q.basecolor[1] = c.x; Q.basecolor[2] = c.y;
+	Q.ambientcolor[0] = c.z; Q.ambientcolor[1] = c.w; Q.ambientcolor[2] = d.x;
+	return Q;
 }
 
 // M5: shade_kernel_mesh_geometry (:280-355) at a covered pixel. The ambient source is fixed at compile time by the type of A: IrradianceMap
@@ -510,6 +531,29 @@ __global__ void render_mesh_fused(const MeshSceneParams S, const MeshShadeParams
 	depth_buffer[idx] = camera_depth(C, pos);
 }
 
+// render_mesh_fused with materials: the same stages, M5 with the material of the mesh the primary ray hit. ids: the frame's id plane, the mesh
+// of the primary hit, -1 on every other pixel (ngp_get_frame_mesh_ids)
+template <typename Ambient>
+__global__ void render_mesh_fused_materials(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                            float4* __restrict__ frame_buffer, float* __restrict__ depth_buffer, const MeshMaterial* __restrict__ materials,
+                                            int32_t* __restrict__ ids) {
+	uint32_t x, y, idx;
+	if (!frame_pixel(L, C, x, y, idx)) return;
+	depth_buffer[idx] = MAX_DEPTH;
+	ids[idx] = -1;
+	f3 pos, primary_dir, normal, q;
+	if (!mesh_primary_ray(S, C, x, y, pos, primary_dir)) return;
+	bool hit;
+	float shadow;
+	int mesh;
+	mesh_trace_shadow<true>(S, P, primary_dir, pos, normal, hit, q, shadow, &mesh);
+	if (!box_contains(S.scene_min, S.scene_max, pos)) return;
+	ids[idx] = mesh;
+	f3 color = mesh_shade(mesh_material_of(P, materials, mesh), A, pos, normal, primary_dir, shadow);
+	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
+	depth_buffer[idx] = camera_depth(C, pos);
+}
+
 // stage kernel: M2 alone (mesh_raytrace_kernel)
 __global__ void trace_mesh_rays_kernel(const MeshSceneParams S, uint32_t n, float* __restrict__ positions, float* __restrict__ directions) {
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -525,11 +569,14 @@ __global__ void trace_mesh_rays_kernel(const MeshSceneParams S, uint32_t n, floa
 // frames' sun" and "mesh reflection"): M1-M4 leave a G-buffer and one shadow-ray entry per local pixel, in idx order and not compacted; the
 // tracer walks the list(s); M5 shades from the G-buffer with shadow scaled by what the tracer let through.
 // G-buffer of n pixels, three planes of n float4: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle).
-__global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, const FrameLayout L, float* __restrict__ depth_buffer, float t_min,
-                                    float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+// IDS (the material instantiation): the int32 id plane beside the G-buffer receives the mesh of the primary hit, -1 on every other pixel.
+template <bool IDS>
+NGP_DEV void mesh_gbuffer_body(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, const FrameLayout L, float* __restrict__ depth_buffer, float t_min,
+                               float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t, int32_t* __restrict__ ids) {
 	uint32_t x, y, idx;
 	if (!frame_pixel(L, C, x, y, idx)) return;
 	depth_buffer[idx] = MAX_DEPTH;
+	if constexpr (IDS) ids[idx] = -1;
 	// the dead entry irradiance_sun_shadow_rays_kernel writes: origin 0, the sun's direction, t = (0, 0)
 	st3(ray_d + 3 * (size_t)idx, shadow_ray_dir(P));
 	f3 pos, primary_dir, normal, q;
@@ -541,8 +588,12 @@ __global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadePara
 	}
 	bool hit;
 	float shadow;
-	mesh_trace_shadow(S, P, primary_dir, pos, normal, hit, q, shadow);
+	int mesh = -1;
+	mesh_trace_shadow<IDS>(S, P, primary_dir, pos, normal, hit, q, shadow, &mesh);
 	const bool covered = box_contains(S.scene_min, S.scene_max, pos);
+	if constexpr (IDS) {
+		if (covered) ids[idx] = mesh;
+	}
 	const bool has = covered && shadow == 1.0f; // the NeRF's shadow ray starts at q, where the mesh shadow ray does
 	if (!has) q = mk3(0.f, 0.f, 0.f);
 	gbuf[idx] = make_float4(pos.x, pos.y, pos.z, shadow);
@@ -551,6 +602,14 @@ __global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadePara
 	st3(ray_o + 3 * (size_t)idx, q);
 	ray_t[idx] = has ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
 	if (covered) depth_buffer[idx] = camera_depth(C, pos);
+}
+__global__ void mesh_gbuffer_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, const FrameLayout L, float* __restrict__ depth_buffer, float t_min,
+                                    float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t) {
+	mesh_gbuffer_body<false>(S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t, nullptr);
+}
+__global__ void mesh_gbuffer_ids_kernel(const MeshSceneParams S, const MeshShadeParams P, const CameraParams C, const FrameLayout L, float* __restrict__ depth_buffer, float t_min,
+                                        float4* __restrict__ gbuf, float* __restrict__ ray_o, float* __restrict__ ray_d, float2* __restrict__ ray_t, int32_t* __restrict__ ids) {
+	mesh_gbuffer_body<true>(S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t, ids);
 }
 
 // the mirror ray of a G-buffer pixel, in one fixed order: n^ = normalize(ff), ff M3's winding normal turned against the primary ray;
@@ -605,10 +664,12 @@ __global__ void mesh_reflection_rays_kernel(const MeshSceneParams S, const Camer
 // R: the mirror ray's radiance is added behind evaluate_shading where alpha_r > 0; every other pixel keeps its bits. With R.hits
 // (ngp_set_mesh_reflection_meshes) a ray that a mesh cuts carries L = rgb_r + max(1 - alpha_r, 0) C2, C2 the hit's own M5 from
 // mesh_reflection_hit_shade_kernel, and adds it whatever alpha_r is; a ray without a hit keeps the bits it has with R.hits null.
-template <typename Ambient>
-__global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
-                                           const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
-                                           const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R) {
+// MAT (the material instantiation): M5 and mirror_term's F take the material of the pixel's mesh in the id plane (mesh_material_of).
+template <bool MAT, typename Ambient>
+NGP_DEV void mesh_shade_deferred_body(const MeshShadeParams P0, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
+                                      const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
+                                      const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R,
+                                      const MeshMaterial* __restrict__ materials, const int32_t* __restrict__ ids) {
 	uint32_t x, y, idx;
 	if (!frame_pixel(L, C, x, y, idx)) return;
 	const float4 g1 = gbuf[(size_t)L.n_pixels + idx];
@@ -623,6 +684,8 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 	const f3 pos = mk3(g0.x, g0.y, g0.z), normal = mk3(g1.x, g1.y, g1.z), primary_dir = mk3(g2.x, g2.y, g2.z);
 	float shadow = g0.w;
 	if (has) shadow = shadow * fmaxf(1.0f - alpha_s, 0.0f); // T_s
+	MeshShadeParams P = P0;
+	if constexpr (MAT) P = mesh_material_of(P0, materials, ids[idx]);
 	f3 color = mesh_shade(P, A, pos, normal, primary_dir, shadow);
 	if (mirror) {
 		f3 q, r;
@@ -643,6 +706,19 @@ __global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambien
 	}
 	frame_buffer[idx] = make_float4(color.x, color.y, color.z, 1.0f);
 }
+template <typename Ambient>
+__global__ void mesh_shade_deferred_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
+                                           const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
+                                           const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R) {
+	mesh_shade_deferred_body<false>(P, A, C, L, frame_buffer, gbuf, ray_o, ray_t, traced, record, R, nullptr, nullptr);
+}
+template <typename Ambient>
+__global__ void mesh_shade_deferred_materials_kernel(const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L, float4* __restrict__ frame_buffer,
+                                                     const float4* __restrict__ gbuf, const float* __restrict__ ray_o, const float2* __restrict__ ray_t,
+                                                     const float4* __restrict__ traced, float4* __restrict__ record, const MeshReflectionList R,
+                                                     const MeshMaterial* __restrict__ materials, const int32_t* __restrict__ ids) {
+	mesh_shade_deferred_body<true>(P, A, C, L, frame_buffer, gbuf, ray_o, ray_t, traced, record, R, materials, ids);
+}
 
 // the launch geometry of every frame_pixel kernel: blocks of 16 x 8 threads over the camera
 static dim3 pixel_threads() { return dim3(16, 8, 1); }
@@ -657,22 +733,30 @@ void with_ambient(const IrradianceMap& I, const IrradianceVolume* V, const Irrad
 }
 
 void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
-                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer, hipStream_t stream) {
+                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer, const MeshMaterial* materials, int32_t* ids, hipStream_t stream) {
 	with_ambient(I, V, VV, [&](const auto& A) {
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(render_mesh_fused<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, frame_buffer, depth_buffer);
+		if (materials)
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(render_mesh_fused_materials<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, frame_buffer,
+			                   depth_buffer, materials, ids);
+		else hipLaunchKernelGGL(HIP_KERNEL_NAME(render_mesh_fused<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, frame_buffer, depth_buffer);
 	});
 }
 // the two halves of launch_render_mesh around the caller's trace of (ray_o, ray_d, ray_t)
 void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, const FrameLayout& L, float* depth_buffer, float t_min, float4* gbuf,
-                         float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream) {
-	hipLaunchKernelGGL(mesh_gbuffer_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t);
+                         float* ray_o, float* ray_d, float2* ray_t, int32_t* ids, hipStream_t stream) {
+	if (ids) hipLaunchKernelGGL(mesh_gbuffer_ids_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t, ids);
+	else hipLaunchKernelGGL(mesh_gbuffer_kernel, pixel_blocks(C), pixel_threads(), 0, stream, S, P, C, L, depth_buffer, t_min, gbuf, ray_o, ray_d, ray_t);
 }
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
                                 const FrameLayout& L, float4* frame_buffer, const float4* gbuf, const float* ray_o, const float2* ray_t, const float4* traced, float4* record,
-                                const MeshReflectionList& R, hipStream_t stream) {
+                                const MeshReflectionList& R, const MeshMaterial* materials, const int32_t* ids, hipStream_t stream) {
 	with_ambient(I, V, VV, [&](const auto& A) {
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_shade_deferred_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, P, A, C, L, frame_buffer, gbuf, ray_o,
-		                   ray_t, traced, record, R);
+		if (materials)
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_shade_deferred_materials_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, P, A, C, L, frame_buffer,
+			                   gbuf, ray_o, ray_t, traced, record, R, materials, ids);
+		else
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_shade_deferred_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, P, A, C, L, frame_buffer, gbuf, ray_o,
+			                   ray_t, traced, record, R);
 	});
 }
 void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
@@ -1340,10 +1424,11 @@ void launch_nerf_mesh_soft_shadow(const MeshSceneParams& S, const MeshShadeParam
 // against r^) (M3's lift); shadow2 = 0 where any mesh stands between q2 and the sun (nerf_mesh_shadow_kernel's all-meshes rule, not M3's
 // one-mesh rule), else 1; C2 = M5 at (p2, n2) viewed along r^. hits: (p2, shadow2), (C2, 1); zeros for every other pixel.
 // A kernel of its own: a second M5 inside mesh_shade_deferred_kernel would hold two lookups' accumulators at once.
-template <typename Ambient>
-__global__ void mesh_reflection_hit_shade_kernel(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
-                                                 const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float2* __restrict__ ray_t,
-                                                 const int2* __restrict__ hit_ids, float4* __restrict__ hits) {
+// MAT (the material instantiation): C2 takes the material of the mesh the mirror ray hit, hit_ids.x (mesh_material_of).
+template <bool MAT, typename Ambient>
+NGP_DEV void mesh_reflection_hit_shade_body(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                            const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float2* __restrict__ ray_t,
+                                            const int2* __restrict__ hit_ids, float4* __restrict__ hits, const MeshMaterial* __restrict__ materials) {
 	uint32_t x, y, idx;
 	if (!frame_pixel(L, C, x, y, idx)) return;
 	float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;
@@ -1358,19 +1443,37 @@ __global__ void mesh_reflection_hit_shade_kernel(const MeshSceneParams S, const 
 		const f3 ff2 = dot3(n2, rh) < 0.0f ? n2 : scale3(n2, -1.0f);
 		const f3 q2 = add3(p2, scale3(normalize3(ff2), 1e-3f));
 		const float shadow2 = any_hit(S, q2, shadow_ray_dir(P)) ? 0.0f : 1.0f;
-		const f3 C2 = mesh_shade(P, A, p2, n2, rh, shadow2);
+		f3 C2;
+		if constexpr (MAT) C2 = mesh_shade(mesh_material_of(P, materials, id.x), A, p2, n2, rh, shadow2);
+		else C2 = mesh_shade(P, A, p2, n2, rh, shadow2);
 		h0 = make_float4(p2.x, p2.y, p2.z, shadow2);
 		h1 = make_float4(C2.x, C2.y, C2.z, 1.0f);
 	}
 	hits[2 * (size_t)idx] = h0;
 	hits[2 * (size_t)idx + 1] = h1;
 }
+template <typename Ambient>
+__global__ void mesh_reflection_hit_shade_kernel(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                                 const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float2* __restrict__ ray_t,
+                                                 const int2* __restrict__ hit_ids, float4* __restrict__ hits) {
+	mesh_reflection_hit_shade_body<false>(S, P, A, C, L, ray_o, ray_d, ray_t, hit_ids, hits, nullptr);
+}
+template <typename Ambient>
+__global__ void mesh_reflection_hit_shade_materials_kernel(const MeshSceneParams S, const MeshShadeParams P, const Ambient A, const CameraParams C, const FrameLayout L,
+                                                           const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float2* __restrict__ ray_t,
+                                                           const int2* __restrict__ hit_ids, float4* __restrict__ hits, const MeshMaterial* __restrict__ materials) {
+	mesh_reflection_hit_shade_body<true>(S, P, A, C, L, ray_o, ray_d, ray_t, hit_ids, hits, materials);
+}
 void launch_mesh_reflection_hit_shade(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
                                       const CameraParams& C, const FrameLayout& L, const float* ray_o, const float* ray_d, const float2* ray_t, const int2* hit_ids, float4* hits,
-                                      hipStream_t stream) {
+                                      const MeshMaterial* materials, hipStream_t stream) {
 	with_ambient(I, V, VV, [&](const auto& A) {
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_reflection_hit_shade_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, ray_o, ray_d,
-		                   ray_t, hit_ids, hits);
+		if (materials)
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_reflection_hit_shade_materials_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, ray_o,
+			                   ray_d, ray_t, hit_ids, hits, materials);
+		else
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(mesh_reflection_hit_shade_kernel<std::decay_t<decltype(A)>>), pixel_blocks(C), pixel_threads(), 0, stream, S, P, A, C, L, ray_o, ray_d,
+			                   ray_t, hit_ids, hits);
 	});
 }
 

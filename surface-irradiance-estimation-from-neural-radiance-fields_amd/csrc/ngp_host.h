@@ -141,15 +141,17 @@ void launch_coarse_occupancy(const uint8_t* bitfield, uint32_t* coarse, hipStrea
 void launch_accumulate_tonemap(uint32_t n_pixels, const float4* frame_buffer, float4* accumulate_buffer, float sample_count, const float* background,
                                float exposure, int to_srgb, int color_space, float4* rgba_out, hipStream_t stream);
 
-// the frame's one-thread-a-pixel passes; L: the pixels the launch owns and the extent of every per-pixel buffer (FrameLayout, ngp_kernels.h)
+// the frame's one-thread-a-pixel passes; L: the pixels the launch owns and the extent of every per-pixel buffer (FrameLayout, ngp_kernels.h).
+// materials (nullable: no mesh owns a material, the launch is the kernel it was before materials existed): the device table of one
+// MeshMaterial a mesh; with it the material instantiation runs and ids is the frame's int32 id plane (ngp_get_frame_mesh_ids)
 void launch_render_mesh(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
-                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer,
+                        const CameraParams& C, const FrameLayout& L, float4* frame_buffer, float* depth_buffer, const MeshMaterial* materials, int32_t* ids,
                         hipStream_t stream); // V: the ShadeIrradianceVolume instantiation; VV: the one that weights the probes by visibility
 void launch_mesh_gbuffer(const MeshSceneParams& S, const MeshShadeParams& P, const CameraParams& C, const FrameLayout& L, float* depth_buffer, float t_min, float4* gbuf,
-                         float* ray_o, float* ray_d, float2* ray_t, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
+                         float* ray_o, float* ray_d, float2* ray_t, int32_t* ids, hipStream_t stream); // M1-M4 of launch_render_mesh + the shadow-ray list
 void launch_mesh_shade_deferred(const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV, const CameraParams& C,
                                 const FrameLayout& L, float4* frame_buffer, const float4* gbuf, const float* ray_o, const float2* ray_t, const float4* traced, float4* record,
-                                const MeshReflectionList& R,
+                                const MeshReflectionList& R, const MeshMaterial* materials, const int32_t* ids,
                                 hipStream_t stream); // M5 of launch_render_mesh behind the trace(s); traced == nullptr: no shadow trace was run (T_s = 1, no record)
 void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C, const FrameLayout& L, float t_min, const float4* gbuf, float* ray_o, float* ray_d,
                                  float2* ray_t, int2* hit_ids,
@@ -158,7 +160,7 @@ void launch_mesh_reflection_rays(const MeshSceneParams& S, const CameraParams& C
 // prep step); hits: 2 float4 a pixel, (p2, shadow2), (C2, 1)
 void launch_mesh_reflection_hit_shade(const MeshSceneParams& S, const MeshShadeParams& P, const IrradianceMap& I, const IrradianceVolume* V, const IrradianceVolumeVisible* VV,
                                       const CameraParams& C, const FrameLayout& L, const float* ray_o, const float* ray_d, const float2* ray_t, const int2* hit_ids, float4* hits,
-                                      hipStream_t stream);
+                                      const MeshMaterial* materials, hipStream_t stream);
 void launch_nerf_mesh_shadow(const MeshSceneParams& S, const MeshShadeParams& P, const ModelParams& M, const CameraParams& C, float4* frame_buffer, const float* depth_buffer,
                              const float4* nerf, float4* record, const FrameLayout& L, float strength, float bias,
                              hipStream_t stream); // the NeRF pass's composite behind the meshes' shadow on it (ngp_set_mesh_shadow_on_nerf)
@@ -234,6 +236,8 @@ struct HostMesh { // MeshData (mesh.h:18-24) after load_mesh
 	std::vector<TriangleBvhNode> nodes;
 	float bmin[3], bmax[3];
 	float center[3];
+	ngp_mesh_material material{}; // its own material where own_material (ngp_set_mesh_material); a peer's copy follows the primary's
+	bool own_material = false;
 	DevArray<Triangle> d_tris; // (a peer's replica holds these alone: the host vectors stay empty, ngp_mesh.cpp sync_peer_geometry)
 	DevArray<TriangleBvhNode> d_nodes;
 };
@@ -430,6 +434,14 @@ struct ngp_ctx {
 	std::vector<ngp::HostMesh> meshes;
 	ngp::DevArray<ngp::MeshRef> d_meshrefs;
 	ngp::MeshSceneParams mesh_scene{};
+	// ---- mesh materials (ngp_set_mesh_material): the device table of one record a mesh, uploaded when a material or the mesh list changes
+	// (ngp_mesh.cpp upload_mesh_materials); null while no mesh owns one, and frames then launch the kernels they always launched
+	ngp::DevArray<ngp::MeshMaterial> d_mesh_materials;
+	uint32_t n_own_materials = 0;
+	uint64_t material_generation = 0, synced_material_generation = 0; // (a peer's replica follows the primary's: sync_peer_geometry)
+	ngp::DevArray<int32_t> d_mesh_ids;       // the id plane of a frame with materials: the mesh of each pixel's primary hit, -1 elsewhere
+	bool hist_mesh_ids[ngp::FRAME_HISTORY] = {}; // the slot's call was a frame with materials
+	size_t mesh_ids_n_pixels = 0;            // pixels of the last such frame
 	ngp::MeshShadeParams shade{{0.57735026f, 0.57735026f, 0.57735026f}, {0.f, 1.f, 0.f}, 0.f, 0.f, 1.f, 0.5f, 0.f, 0.f, 0.f, {0.8f, 0.8f, 0.8f}, {0.f, 0.f, 0.f}};
 
 	// ---- irradiance probe texture(s) (m_envmap_tex / gridSize, testbed.h:949-950) and E(n) tabulated at their texels

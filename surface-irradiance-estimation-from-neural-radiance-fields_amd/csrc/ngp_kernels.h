@@ -223,6 +223,16 @@ struct MeshShadeParams { // BRDFParams (common.h:167-177) + m_sun_dir / m_up_dir
 	float metallic, subsurface, specular, roughness, sheen, clearcoat, clearcoat_gloss;
 	float basecolor[3], ambientcolor[3];
 };
+// a mesh's own material (ngp_set_mesh_material), one 64-byte record a mesh in the device table, read as four 16-byte loads: ngp_mesh_material's
+// 13 floats in its order, then own (0: the mesh is shaded with the context's MeshShadeParams). The table is uploaded when a material or the mesh
+// list changes, never inside a frame; kernels keep receiving the context's MeshShadeParams by value and select per thread (mesh_material_of).
+struct alignas(16) MeshMaterial {
+	float metallic, subsurface, specular, roughness, sheen, clearcoat, clearcoat_gloss;
+	float basecolor[3], ambientcolor[3];
+	uint32_t own;
+	uint32_t pad[2];
+};
+static_assert(sizeof(MeshMaterial) == 64, "one material record is four 16-byte loads");
 struct IrradianceMap { // E(n) tabulated at the probe texture's texel directions; nullptr = not computed
 	const float4* irradiance; // grid_x * grid_y tables (one when grid_x == 0) of n_theta * n_phi texels
 	uint32_t n_theta, n_phi;

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <limits>
 
@@ -15,11 +16,92 @@ namespace {
 
 using namespace ngp::bvh4; // V3 and its helpers, bounds, build_bvh4
 
+// the device table of the meshes' materials (ngp_kernels.h MeshMaterial), whole, from the host's copies; dropped while no mesh owns one, which is
+// what sends a frame to the kernels without materials. Frames in flight may read the old table: the device is waited for first (a rare event,
+// as the mesh list's own upload is).
+void upload_mesh_materials(ngp_ctx* ctx) {
+	++ctx->material_generation;
+	ctx->n_own_materials = 0;
+	for (const HostMesh& m : ctx->meshes) ctx->n_own_materials += m.own_material ? 1u : 0u;
+	if (ctx->device < 0) return;
+	DeviceGuard g(ctx->device);
+	if (ctx->d_mesh_materials) {
+		NGP_HIP_CHECK(hipDeviceSynchronize());
+		ctx->d_mesh_materials.reset();
+	}
+	if (!ctx->n_own_materials) return;
+	std::vector<MeshMaterial> table(ctx->meshes.size());
+	for (size_t i = 0; i < table.size(); ++i) {
+		static_assert(sizeof(ngp_mesh_material) == 13 * sizeof(float) && offsetof(MeshMaterial, own) == sizeof(ngp_mesh_material), "material record layout");
+		memset(&table[i], 0, sizeof(MeshMaterial));
+		memcpy(&table[i], &ctx->meshes[i].material, sizeof(ngp_mesh_material));
+		table[i].own = ctx->meshes[i].own_material ? 1u : 0u;
+	}
+	ctx->d_mesh_materials.upload(table.data(), table.size());
+}
+
+// the fields of a material in the header's order, for refusals and the scene file's keys; a colour is three floats
+struct MaterialField {
+	const char* name;
+	size_t offset;
+	int n;
+};
+const MaterialField MATERIAL_FIELDS[] = {
+	{"metallic", offsetof(ngp_mesh_material, metallic), 1},   {"subsurface", offsetof(ngp_mesh_material, subsurface), 1},
+	{"specular", offsetof(ngp_mesh_material, specular), 1},   {"roughness", offsetof(ngp_mesh_material, roughness), 1},
+	{"sheen", offsetof(ngp_mesh_material, sheen), 1},         {"clearcoat", offsetof(ngp_mesh_material, clearcoat), 1},
+	{"clearcoat_gloss", offsetof(ngp_mesh_material, clearcoat_gloss), 1},
+	{"basecolor", offsetof(ngp_mesh_material, basecolor), 3}, {"ambientcolor", offsetof(ngp_mesh_material, ambientcolor), 3},
+};
+const float* material_field(const ngp_mesh_material& m, const MaterialField& f) { return (const float*)((const char*)&m + f.offset); }
+ngp_mesh_material default_material() {
+	ngp_mesh_material m{};
+	m.specular = 1.0f;
+	m.roughness = 0.5f;
+	m.basecolor[0] = m.basecolor[1] = m.basecolor[2] = 0.8f;
+	return m;
+}
+void check_material(const ngp_mesh_material& m, const std::string& where) {
+	for (const MaterialField& f : MATERIAL_FIELDS)
+		for (int i = 0; i < f.n; ++i)
+			if (!std::isfinite(material_field(m, f)[i])) throw std::runtime_error(where + "material field '" + f.name + "' is not finite");
+}
+// the "material" object of a scene file's "Mesh" entry: missing keys take the header's defaults
+ngp_mesh_material parse_material(const mj::Value& v, const std::string& where) {
+	if (!v.is_object()) throw std::runtime_error(where + "'material' must be an object");
+	ngp_mesh_material m = default_material();
+	for (const auto& kv : v.obj) {
+		const MaterialField* field = nullptr;
+		for (const MaterialField& f : MATERIAL_FIELDS)
+			if (kv.first == f.name) field = &f;
+		if (!field) throw std::runtime_error(where + "unknown material key '" + kv.first + "'");
+		float* dst = const_cast<float*>(material_field(m, *field));
+		if (field->n == 1) {
+			if (!kv.second.is_number()) throw std::runtime_error(where + "material key '" + kv.first + "' must be a number");
+			dst[0] = (float)kv.second.num();
+		} else {
+			if (!kv.second.is_array() || kv.second.size() != 3) throw std::runtime_error(where + "material key '" + kv.first + "' must be an array of 3 numbers");
+			for (size_t i = 0; i < 3; ++i) {
+				if (!kv.second.at(i).is_number()) throw std::runtime_error(where + "material key '" + kv.first + "' must be an array of 3 numbers");
+				dst[i] = (float)kv.second.at(i).num();
+			}
+		}
+	}
+	check_material(m, where);
+	return m;
+}
+HostMesh& mesh_slot(ngp_ctx* ctx, int mesh) {
+	if (mesh < 0 || mesh >= (int)ctx->meshes.size())
+		throw std::runtime_error("mesh: index " + std::to_string(mesh) + " outside [0, " + std::to_string(ctx->meshes.size()) + ") (ngp_n_meshes)");
+	return ctx->meshes[(size_t)mesh];
+}
+
 // after any change of the mesh list: scene AABB (load_scene :3183-3189) and the device-side MeshRef table
 void rebuild_scene(ngp_ctx* ctx) {
 	++ctx->mesh_generation;
 	ctx->d_meshrefs.reset();
 	ctx->mesh_scene = MeshSceneParams{};
+	upload_mesh_materials(ctx); // (the table follows the list: a slot's material goes with its mesh)
 	if (ctx->meshes.empty()) return;
 	V3 lo = ld(ctx->meshes[0].bmin), hi = ld(ctx->meshes[0].bmax);
 	for (auto& m : ctx->meshes) {
@@ -182,15 +264,28 @@ int ngp_load_scene(ngp_ctx* ctx, const char* json_path) {
 		if (!json.is_object() || json.size() == 0) throw std::runtime_error("Geometry file must contain an array of geometry metadata.");
 		const mj::Value& geometries = json.at("geometry");
 		const std::string base = parent_dir(json_path);
-		ctx->meshes.clear();
+		// the entries' materials are read and refused before the scene is touched
+		std::vector<std::pair<bool, ngp_mesh_material>> materials;
 		for (const mj::Value& g : geometries.arr) {
+			const mj::Value* mat = g.is_object() ? g.find("material") : nullptr;
+			const std::string where = "geometry[" + std::to_string(materials.size()) + "]: ";
+			if (mat && g.contains("type") && g.at("type").is_string() && g.at("type").str() == "Nerf") throw std::runtime_error(where + "'material' applies to a 'Mesh' entry, not to 'Nerf'");
+			materials.emplace_back(mat != nullptr, mat ? parse_material(*mat, where) : ngp_mesh_material{});
+		}
+		ctx->meshes.clear();
+		size_t entry = 0;
+		for (const mj::Value& g : geometries.arr) {
+			const std::pair<bool, ngp_mesh_material>& material = materials[entry++];
 			std::string path = g.at("path").str();
 			if (!path.empty() && path[0] != '/') path = base + "/" + path;
 			const std::string& type = g.at("type").str();
 			float center[3];
 			for (int i = 0; i < 3; ++i) center[i] = (float)g.at("center").at((size_t)i).num();
-			if (type == "Mesh") load_mesh_file_impl(ctx, path, center);
-			else if (type == "Nerf") load_snapshot_path(ctx, path);
+			if (type == "Mesh") {
+				load_mesh_file_impl(ctx, path, center);
+				ctx->meshes.back().own_material = material.first;
+				ctx->meshes.back().material = material.second;
+			} else if (type == "Nerf") load_snapshot_path(ctx, path);
 			else throw std::runtime_error("Geometry type must be either 'Mesh' or 'Nerf'.");
 		}
 		rebuild_scene(ctx);
@@ -230,6 +325,26 @@ int ngp_set_geometry_opts(ngp_ctx* ctx, const ngp_geometry_opts* o) {
 	return 0;
 }
 
+int ngp_set_mesh_material(ngp_ctx* ctx, int mesh, const ngp_mesh_material* m) {
+	return guarded(ctx, [&] {
+		HostMesh& slot = mesh_slot(ctx, mesh);
+		if (m) check_material(*m, "");
+		slot.own_material = m != nullptr;
+		slot.material = m ? *m : ngp_mesh_material{};
+		upload_mesh_materials(ctx);
+	});
+}
+
+int ngp_get_mesh_material(ngp_ctx* ctx, int mesh, ngp_mesh_material* out, int* own) {
+	return guarded(ctx, [&] {
+		const HostMesh& slot = mesh_slot(ctx, mesh);
+		if (own) *own = slot.own_material ? 1 : 0;
+		if (!out) return;
+		if (slot.own_material) *out = slot.material;
+		else memcpy(out, &ctx->shade.metallic, sizeof(ngp_mesh_material)); // (the BRDF part of ngp_geometry_opts has the material's layout)
+	});
+}
+
 int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* directions) {
 	return guarded(ctx, [&] {
 		require_device(ctx);
@@ -265,7 +380,16 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->mesh_reflection = primary->mesh_reflection; // each device traces the mirror rays of its own share
 	peer->mesh_reflection_desc = primary->mesh_reflection_desc;
 	peer->mesh_reflection_meshes = primary->mesh_reflection_meshes; // ... and shades the hits of its own share
-	if (peer->synced_mesh_generation != primary->mesh_generation) {
+	const bool meshes_changed = peer->synced_mesh_generation != primary->mesh_generation;
+	if (!meshes_changed && peer->synced_material_generation != primary->material_generation) { // the materials alone: the slots' copies and the table
+		for (size_t i = 0; i < peer->meshes.size(); ++i) {
+			peer->meshes[i].material = primary->meshes[i].material;
+			peer->meshes[i].own_material = primary->meshes[i].own_material;
+		}
+		upload_mesh_materials(peer);
+	}
+	peer->synced_material_generation = primary->material_generation; // (a new mesh list brings its materials below: rebuild_scene uploads them)
+	if (meshes_changed) {
 		DeviceGuard g(peer->device);
 		NGP_HIP_CHECK(hipStreamSynchronize(peer->stream)); // (a rare event: frames on the peer still trace the old BVHs)
 		peer->meshes.clear();
@@ -274,6 +398,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 			memcpy(c.bmin, m.bmin, sizeof(c.bmin));
 			memcpy(c.bmax, m.bmax, sizeof(c.bmax));
 			memcpy(c.center, m.center, sizeof(c.center));
+			c.material = m.material;
+			c.own_material = m.own_material;
 			c.d_tris.upload(m.tris.data(), m.tris.size());
 			c.d_nodes.upload(m.nodes.data(), m.nodes.size());
 			peer->meshes.push_back(std::move(c));

@@ -335,6 +335,7 @@ struct FramePlan {
 	bool mesh_shadow = false;    // the meshes in front of the sun on the NeRF: one kernel behind the NeRF launch finishes its composite
 	bool ambient_change = false; // the meshes' change of the ambient light on the NeRF: normals at the owners' surface points, then g = E_after / E_before
 	bool sun_disk = false;       // the sun's disk: K shadow rays a pixel against all meshes on the G-buffer (meshes alone fill the shadow list without tracing it), and in the mesh shadow's kernel
+	bool materials = false;      // some mesh owns a material: the mesh pass's material instantiations run and leave the frame's id plane
 	bool split() const { return sun_shadow || reflection || sun_disk; }
 	bool scratch() const { return mesh_shadow || ambient_change; } // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
 };
@@ -372,6 +373,11 @@ static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_
 		(void)sun_disk_of(ctx, 0); // (a sun direction without a length is refused here, ahead of the frame's work)
 		ensure_sun_shadow_buffers(ctx, n_pixels);
 		if (ctx->pass_sun_disk.ensure(n_pixels)) ctx->pass_sun_disk.grow(n_pixels);
+	}
+	p.materials = p.have_meshes && ctx->n_own_materials > 0;
+	if (p.materials && n_pixels > ctx->d_mesh_ids.size()) {
+		ctx->d_mesh_ids.reset();
+		ctx->d_mesh_ids.reset(n_pixels);
 	}
 	return p;
 }
@@ -425,11 +431,15 @@ static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const Mod
 	}
 	const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
 	const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
+	// with materials the kernels select own ? table[mesh] : ctx->shade per thread and write the id plane (entries no pixel owns stay -1)
+	const MeshMaterial* materials = f.plan.materials ? ctx->d_mesh_materials.get() : nullptr;
+	int32_t* ids = f.plan.materials ? ctx->d_mesh_ids.get() : nullptr;
 	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[f.slot], f.stream)); // (ngp_get_mesh_pass_ms)
+	if (ids) NGP_HIP_CHECK(hipMemsetAsync(ids, 0xff, (size_t)f.L.n_pixels * sizeof(int32_t), f.stream));
 	if (f.plan.split()) {
 		const RayList& ss = ctx->ss_rays;
 		trace_pixel_rays(f, M, ss, ctx->pass_sun_shadow, f.plan.sun_shadow, ctx->sun_nerf_shadow_desc.min_transmittance, last, [&] {
-			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), f.stream);
+			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), ids, f.stream);
 			if (!f.plan.sun_disk) return;
 			const FramePass& disk = ctx->pass_sun_disk; // (the kernel writes its owners' records; the clear covers the others)
 			disk.clear(f.L.n_pixels, f.stream);
@@ -450,16 +460,16 @@ static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const Mod
 				hits.clear(f.L.n_pixels, f.stream);
 				hits.begin(f.slot, f.stream, last);
 				launch_mesh_reflection_hit_shade(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, mr.o.get(), mr.d.get(), mr.t.get(),
-				                                 ctx->d_mr_hit_ids.get(), hits.record.get(), f.stream);
+				                                 ctx->d_mr_hit_ids.get(), hits.record.get(), materials, f.stream);
 				hits.end(f.slot, f.stream, last);
 			});
 			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->pass_mesh_reflection.record.get(), ctx->mesh_reflection_desc.strength,
 			                       f.plan.reflection_meshes ? ctx->pass_mesh_reflection_hits.record.get() : nullptr};
 		}
 		launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), ctx->d_ss_gbuf.get(), ss.o.get(), ss.t.get(),
-		                           f.plan.sun_shadow ? ss.traced.get() : nullptr, ctx->pass_sun_shadow.record.get(), R, f.stream);
+		                           f.plan.sun_shadow ? ss.traced.get() : nullptr, ctx->pass_sun_shadow.record.get(), R, materials, ids, f.stream);
 	} else {
-		launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), F.depth_buffer, f.stream);
+		launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), F.depth_buffer, materials, ids, f.stream);
 	}
 	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[f.slot], f.stream));
 }
@@ -569,6 +579,8 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->pass_mesh_shadow.ran(slot, plan.mesh_shadow, n_pixels);
 	ctx->pass_ambient_change.ran(slot, plan.ambient_change, n_pixels);
 	ctx->pass_sun_disk.ran(slot, plan.sun_disk, n_pixels);
+	ctx->hist_mesh_ids[slot] = plan.materials && !F.direct;
+	if (ctx->hist_mesh_ids[slot]) ctx->mesh_ids_n_pixels = n_pixels;
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
@@ -869,6 +881,16 @@ int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) {
 }
 int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms) {
 	return guarded(ctx, [&] { ctx->pass_ambient_change.read_ms(ctx, ms); });
+}
+int ngp_get_frame_mesh_ids(ngp_ctx* ctx, int32_t* out, size_t n_pixels) {
+	return guarded(ctx, [&] {
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls || !ctx->hist_mesh_ids[(ctx->n_calls - 1) % FRAME_HISTORY]) throw std::runtime_error("the last frame ran without mesh materials (ngp_set_mesh_material)");
+		if (n_pixels != ctx->mesh_ids_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->mesh_ids_n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_mesh_ids.get(), n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
+	});
 }
 
 int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {

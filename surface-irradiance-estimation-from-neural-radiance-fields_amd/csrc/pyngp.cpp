@@ -85,6 +85,7 @@ PYBIND11_MODULE(pyngp, m) {
 		.def_readwrite("render_with_lens_distortion", &Testbed::Nerf::render_with_lens_distortion)
 		.def_readonly("training", &Testbed::Nerf::training);
 	py::class_<Testbed::BRDFParams>(testbed, "BRDFParams")
+		.def(py::init<>()) // (a material for set_mesh_material: the defaults of testbed.brdf)
 		.def_readwrite("metallic", &Testbed::BRDFParams::metallic).def_readwrite("subsurface", &Testbed::BRDFParams::subsurface)
 		.def_readwrite("specular", &Testbed::BRDFParams::specular).def_readwrite("roughness", &Testbed::BRDFParams::roughness)
 		.def_readwrite("sheen", &Testbed::BRDFParams::sheen).def_readwrite("clearcoat", &Testbed::BRDFParams::clearcoat)
@@ -276,6 +277,14 @@ PYBIND11_MODULE(pyngp, m) {
 		.def_readwrite("ambient_change_on_nerf_max_gain", &Testbed::m_ambient_change_on_nerf_max_gain, "with ambient_change_on_nerf: the cap on the ratio (4)")
 		.def_readwrite("mesh_reflection", &Testbed::m_mesh_reflection,
 		               "This project's own: Geometry frames with meshes and a model, the four shade modes: a mesh pixel whose primary ray found a triangle adds strength * F * (the NeRF's radiance along its mirror direction) (default False)")
+		.def("set_mesh_material", &Testbed::set_mesh_material, py::arg("mesh"), py::arg("material"),
+		     "Give an inserted mesh its own material (a BRDFParams); a mesh without one is shaded with testbed.brdf. Kept across load_training_data.")
+		.def("clear_mesh_material", &Testbed::clear_mesh_material, py::arg("mesh"), "Shade the mesh with testbed.brdf again.")
+		.def("mesh_material", [](Testbed& t, int mesh) -> py::object {
+			Testbed::BRDFParams b;
+			if (!t.mesh_material(mesh, b)) return py::none();
+			return py::cast(b);
+		}, py::arg("mesh"), "The mesh's own material (a BRDFParams), or None where it is shaded with testbed.brdf.")
 		.def_readwrite("mesh_reflection_meshes", &Testbed::m_mesh_reflection_meshes,
 		               "with mesh_reflection: a mirror ray that a mesh cuts carries that mesh's own shade at the hit, behind the NeRF along the ray (default False)")
 		.def_readwrite("mesh_reflection_strength", &Testbed::m_mesh_reflection_strength, "with mesh_reflection: the factor on the reflected radiance (1)")

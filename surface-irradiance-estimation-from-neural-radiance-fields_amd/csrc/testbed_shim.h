@@ -10,6 +10,7 @@
 #include <array>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <sys/stat.h>
@@ -97,6 +98,9 @@ public:
 		m_data_path = path;
 		if (scene_mode == ETestbedMode::Geometry) {
 			check(ngp_load_scene(m_ctx, path.c_str()));
+			// ngp_load_scene drops every material and gives the entries that carry one the file's; what set_mesh_material gave a slot comes back over it
+			for (const auto& kv : m_mesh_materials)
+				if (kv.first < ngp_n_meshes(m_ctx)) apply_mesh_material(kv.first, kv.second);
 			sync_model_state();
 		} else {
 			check(ngp_load_training_data(m_ctx, path.c_str()));
@@ -674,6 +678,31 @@ public:
 		float metallic = 0.f, subsurface = 0.f, specular = 1.f, roughness = 0.5f, sheen = 0.f, clearcoat = 0.f, clearcoat_gloss = 0.f;
 		std::array<float, 3> basecolor{0.8f, 0.8f, 0.8f}, ambientcolor{0.f, 0.f, 0.f};
 	} brdf;
+	// ---- a mesh's own material (ngp_set_mesh_material): kept per slot and restored after load_scene; a mesh without one is shaded with brdf
+	void set_mesh_material(int mesh, const BRDFParams& b) {
+		apply_mesh_material(mesh, b);
+		m_mesh_materials[mesh] = b;
+	}
+	void clear_mesh_material(int mesh) {
+		check(ngp_set_mesh_material(m_ctx, mesh, nullptr));
+		m_mesh_materials.erase(mesh);
+	}
+	// false: the mesh owns none (a scene file's material counts as the mesh's own)
+	bool mesh_material(int mesh, BRDFParams& out) {
+		ngp_mesh_material m{};
+		int own = 0;
+		check(ngp_get_mesh_material(m_ctx, mesh, &m, &own));
+		out.metallic = m.metallic; out.subsurface = m.subsurface; out.specular = m.specular; out.roughness = m.roughness;
+		out.sheen = m.sheen; out.clearcoat = m.clearcoat; out.clearcoat_gloss = m.clearcoat_gloss;
+		for (int i = 0; i < 3; ++i) { out.basecolor[i] = m.basecolor[i]; out.ambientcolor[i] = m.ambientcolor[i]; }
+		return own != 0;
+	}
+	void apply_mesh_material(int mesh, const BRDFParams& b) {
+		ngp_mesh_material m{b.metallic, b.subsurface, b.specular, b.roughness, b.sheen, b.clearcoat, b.clearcoat_gloss,
+		                    {b.basecolor[0], b.basecolor[1], b.basecolor[2]}, {b.ambientcolor[0], b.ambientcolor[1], b.ambientcolor[2]}};
+		check(ngp_set_mesh_material(m_ctx, mesh, &m));
+	}
+	std::map<int, BRDFParams> m_mesh_materials;
 
 	ngp_ctx* ctx() { return m_ctx; }
 

@@ -75,6 +75,14 @@ class GeometryOpts(C.Structure):
     ]
 
 
+class MeshMaterial(C.Structure):
+    _fields_ = GeometryOpts._fields_[2:]  # (ngp_mesh_material: the BRDF part of ngp_geometry_opts)
+
+
+MATERIAL_DEFAULTS = dict(metallic=0.0, subsurface=0.0, specular=1.0, roughness=0.5, sheen=0.0, clearcoat=0.0, clearcoat_gloss=0.0, basecolor=(0.8, 0.8, 0.8),
+                         ambientcolor=(0.0, 0.0, 0.0))
+
+
 class ProbeDesc(C.Structure):
     _fields_ = [("mode", C.c_int32), ("n_theta", C.c_uint32), ("n_phi", C.c_uint32), ("n_origin", C.c_uint32), ("origin", C.c_float * 3),
                 ("min_transmittance", C.c_float)]
@@ -247,6 +255,9 @@ def load_library():
     L.ngp_get_mesh_bvh.argtypes = [vp, ip, vp, vp]
     L.ngp_set_geometry_opts.argtypes = [vp, C.POINTER(GeometryOpts)]
     L.ngp_trace_mesh_rays.argtypes = [vp, C.c_uint32, vp, vp]
+    L.ngp_set_mesh_material.argtypes = [vp, ip, C.POINTER(MeshMaterial)]
+    L.ngp_get_mesh_material.argtypes = [vp, ip, C.POINTER(MeshMaterial), C.POINTER(C.c_int)]
+    L.ngp_get_frame_mesh_ids.argtypes = [vp, vp, C.c_size_t]
     L.ngp_compute_envmap.argtypes = [vp, C.POINTER(ProbeDesc), vp]
     L.ngp_get_envmap.argtypes = [vp, vp, vp, vp, vp]
     L.ngp_irradiance.argtypes = [vp, C.c_uint32, vp, vp]
@@ -674,6 +685,38 @@ class Context:
         o.sheen, o.clearcoat, o.clearcoat_gloss = sheen, clearcoat, clearcoat_gloss
         if self.L.ngp_set_geometry_opts(self.h, C.byref(o)) != 0:
             raise RuntimeError("ngp_set_geometry_opts failed")
+
+    def set_mesh_material(self, mesh, material=None):
+        """give mesh its own material: a dict with set_geometry_opts' BRDF keywords (metallic, subsurface, specular, roughness, sheen, clearcoat,
+        clearcoat_gloss, basecolor, ambientcolor; a missing one takes that function's default), or None: back to the context's"""
+        if material is None:
+            self._check(self.L.ngp_set_mesh_material(self.h, int(mesh), None))
+            return
+        unknown = set(material) - set(MATERIAL_DEFAULTS)
+        if unknown:
+            raise ValueError("mesh material: unknown key(s) %s" % sorted(unknown))
+        v = dict(MATERIAL_DEFAULTS, **material)
+        m = MeshMaterial()
+        for k in ("metallic", "subsurface", "specular", "roughness", "sheen", "clearcoat", "clearcoat_gloss"):
+            setattr(m, k, v[k])
+        for i in range(3):
+            m.basecolor[i], m.ambientcolor[i] = v["basecolor"][i], v["ambientcolor"][i]
+        self._check(self.L.ngp_set_mesh_material(self.h, int(mesh), C.byref(m)))
+
+    def mesh_material(self, mesh):
+        """the mesh's own material as a dict of set_mesh_material's keys, or None where it is shaded with the context's"""
+        m, own = MeshMaterial(), C.c_int(0)
+        self._check(self.L.ngp_get_mesh_material(self.h, int(mesh), C.byref(m), C.byref(own)))
+        if not own.value:
+            return None
+        return {k: (tuple(getattr(m, k)) if k in ("basecolor", "ambientcolor") else getattr(m, k)) for k in MATERIAL_DEFAULTS}
+
+    def frame_mesh_ids(self, n_pixels):
+        """(n_pixels,) int32: per pixel of the last frame's last sample, in the frame's pixel order, the mesh its primary ray hit, -1 for every
+        other pixel; refuses after a frame that ran without materials. On a multi-device context the primary's tile-packed share."""
+        out = np.zeros(int(n_pixels), np.int32)
+        self._check(self.L.ngp_get_frame_mesh_ids(self.h, _p(out), int(n_pixels)))
+        return out
 
     def trace_mesh_rays(self, positions, directions):
         p = np.ascontiguousarray(positions, np.float32).copy()

@@ -12,6 +12,7 @@ With --sun-nerf-shadow: per shade mode, in one run, the mesh pass with the optio
 ray-list trace of one shadow ray a local pixel, deferred shade kernel; ngp_set_sun_nerf_shadow at its defaults), of the latter the prep and
 trace alone (ngp_get_frame_sun_shadow_ms), the frame's NeRF pass (kernel_ms) beside them, and how many pixels own a shadow ray.
     python tools/mesh_shade_rate.py --mesh-shadow-on-nerf [--out profiles/mesh_shadow_on_nerf_rate.json]
+    python tools/mesh_shade_rate.py --mesh-materials [--out profiles/mesh_materials_rate.json]
     python tools/mesh_shade_rate.py --sun-disk [--sun-disk-rays K] [--out profiles/sun_disk_rate.json]
 
 With --sun-disk: Shade-mode frames with the meshes' shadow on the NeRF on and the sun's disk (ngp_set_sun_disk) off, on in the wave layout and on
@@ -301,6 +302,37 @@ def main_mesh_shadow_on_nerf(args, ctx, native, cam, geo, out):
     ctx.close()
 
 
+def main_mesh_materials(args, ctx, native, cam, geo, out):
+    out["how"] = ("Shade-mode Geometry frames of the meshes over the benchmark's model, no mesh owning a material (off: render_mesh_fused) and every mesh owning one (on: "
+                  "render_mesh_fused_materials, ngp_set_mesh_material) in alternating calls of one run. frame: HIP events around the whole frame (ngp_get_render_stats "
+                  "frame_ms); mesh_pass: ngp_get_mesh_pass_ms, with materials the id plane's memset included. Medians of --frames frames each after --warmup, with p10 / p90. "
+                  "Nothing is asserted on them.")
+    opts = native.make_opts(render_mode=native.RENDER_SHADE, **geo)
+    materials = [dict(basecolor=(0.6, 0.6, 0.65), metallic=0.9, roughness=0.2, ambientcolor=(0.3, 0.2, 0.1)),
+                 dict(basecolor=(0.9, 0.15, 0.1), roughness=0.8, specular=0.5, ambientcolor=(0.3, 0.2, 0.1))]
+    ts = {key: {"frame": [], "mesh_pass": []} for key in ("off", "on")}
+    for i in range(args.warmup + args.frames):
+        for key in ("off", "on"):
+            for m in range(ctx.n_meshes()):
+                ctx.set_mesh_material(m, materials[m % len(materials)] if key == "on" else None)
+            ctx.render(cam, opts)
+            if i >= args.warmup:
+                ts[key]["frame"].append(ctx.render_stats()["frame_ms"])
+                ts[key]["mesh_pass"].append(ctx.mesh_pass_ms())
+    ids = ctx.frame_mesh_ids(args.width * args.height)  # (the last call was an on frame)
+    q = lambda x: {"median_ms": round(float(np.median(x)), 4), "min_ms": round(float(np.min(x)), 4), "p10_ms": round(float(np.percentile(x, 10)), 4), "p90_ms": round(float(np.percentile(x, 90)), 4)}
+    row = {key: {k: q(v) for k, v in t.items()} for key, t in ts.items()}
+    row["pixels_with_a_mesh"] = round(float((ids >= 0).mean()), 4)
+    row["mesh_pass_on_minus_off_ms"] = round(row["on"]["mesh_pass"]["median_ms"] - row["off"]["mesh_pass"]["median_ms"], 4)
+    out["modes"]["Shade"] = row
+    print(f"mesh pass off {row['off']['mesh_pass']['median_ms']:.4f} ms, on {row['on']['mesh_pass']['median_ms']:.4f} ms; frame off {row['off']['frame']['median_ms']:.4f} ms, "
+          f"on {row['on']['frame']['median_ms']:.4f} ms; pixels with a mesh {row['pixels_with_a_mesh']}", flush=True)
+    print(json.dumps(out))
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
 def main_sun_disk(args, ctx, native, cam, geo, out):
     out["how"] = ("Shade-mode Geometry frames with ngp_set_mesh_shadow_on_nerf at its defaults, the sun's disk (ngp_set_sun_disk: the real sun's 0.00465 rad and 5 degrees, "
                   "--sun-disk-rays rays) off, on with a pixel's rays dealt over adjacent lanes of the wave (wave) and on with one thread a pixel looping over its rays "
@@ -414,12 +446,13 @@ def main():
     ap.add_argument("--ambient-change-on-nerf", action="store_true", help="Shade frames with the meshes' change of the ambient light on the NeRF, off and on in alternating calls, in two views")
     ap.add_argument("--mesh-reflection", action="store_true", help="the mesh pass with the NeRF mirrored in the meshes, off and on, per shade mode")
     ap.add_argument("--mesh-reflection-meshes", action="store_true", help="the mesh reflection with the meshes in it, off and on, per shade mode, in two views")
+    ap.add_argument("--mesh-materials", action="store_true", help="Shade frames with no mesh and with every mesh owning a material, in alternating calls")
     ap.add_argument("--sun-disk", action="store_true", help="Shade frames with the sun's disk off and on, both kernel layouts, in alternating calls")
     ap.add_argument("--sun-disk-rays", type=int, default=16, help="with --sun-disk: shadow rays a pixel (1, 2, 4, 8 or 16)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "sun_disk_rate.json" if args.sun_disk else "mesh_reflection_meshes_rate.json" if args.mesh_reflection_meshes else "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
+        args.out = os.path.join(ROOT, "profiles", "mesh_materials_rate.json" if args.mesh_materials else "sun_disk_rate.json" if args.sun_disk else "mesh_reflection_meshes_rate.json" if args.mesh_reflection_meshes else "mesh_reflection_rate.json" if args.mesh_reflection else "ambient_change_on_nerf_rate.json" if args.ambient_change_on_nerf else "mesh_shadow_on_nerf_rate.json" if args.mesh_shadow_on_nerf else "mesh_shade_sun_shadow_rate.json" if args.sun_nerf_shadow else "mesh_shade_visibility_rate.json" if args.visibility else "mesh_shade_rate.json")
     if args.frames < 20:
         raise SystemExit("--frames: at least 20")
     pkg("build").build()
@@ -438,6 +471,9 @@ def main():
                   "median (and minimum) of --frames frames after --warmup; ratio = median / the Shade median of the same run",
            "width": args.width, "height": args.height, "frames": args.frames, "triangles": int(info["n_tris"]), "modes": {}}
     ctx.set_geometry_opts(ambientcolor=(0.3, 0.2, 0.1))
+    if args.mesh_materials:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return main_mesh_materials(args, ctx, native, cam, geo, out)
     if args.sun_disk:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         return main_sun_disk(args, ctx, native, cam, geo, out)
