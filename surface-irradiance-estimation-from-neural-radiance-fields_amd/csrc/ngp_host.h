@@ -331,31 +331,90 @@ struct TrainState {
 
 constexpr int FRAME_HISTORY = 256; // the render calls whose slot, events and flags a context keeps (ngp_ctx::HISTORY)
 
-// What an optional pass of a frame keeps for its getters (ngp_get_frame_*, ngp_get_frame_*_ms): the per-pixel record of the frame's last
-// sample, events around the pass in that sample, and which calls of the ring ran it. Everything is allocated when a frame first uses the
-// option and grown as ensure_frame_buffers grows (releasing device memory waits for the device: nothing goes under a frame in flight). The
-// record is allocated last and holds the size of the option's scratch too: ensure() says that n_pixels do not fit, the caller then
-// releases all of its scratch, allocates it anew and calls grow().
+// ---- the frame options (Geometry frames). Three places hold an option: its settings (FrameOptions), the passes it runs (FRAME_PASSES and
+// ngp_ctx::passes) and the scratch those passes share (the *Scratch groups below). ngp_render.cpp's plan_frame joins them once a call.
+
+// The settings, as the ngp_set_* entries took them: plain data, what a peer of a multi-device context inherits with one assignment
+// (ngp_mesh.cpp sync_peer_geometry). Every device then runs the options' passes over its own share of the frame.
+template <typename Desc>
+struct FrameOption {
+	bool on = false;
+	Desc desc{}; // zeros while off
+};
+struct FrameOptions {
+	FrameOption<ngp_irradiance_sun_nerf_desc> sun_nerf_shadow;        // the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow)
+	FrameOption<ngp_mesh_shadow_on_nerf_desc> mesh_shadow_on_nerf;    // the meshes in front of the sun on the NeRF (ngp_set_mesh_shadow_on_nerf)
+	FrameOption<ngp_ambient_change_desc> ambient_change_on_nerf;      // what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf)
+	FrameOption<ngp_mesh_reflection_desc> mesh_reflection;            // the NeRF mirrored in the meshes (ngp_set_mesh_reflection)
+	bool mesh_reflection_meshes = false;                              // ... and the meshes in it (ngp_set_mesh_reflection_meshes)
+	FrameOption<ngp_sun_disk_desc> sun_disk;                          // the sun's disk (ngp_set_sun_disk)
+};
+// the refusals of the options' descriptors (the ngp_set_* entries; ngp_irradiance.cpp's entries that take the same descriptors)
+inline void check_desc(const ngp_irradiance_sun_nerf_desc& d) {
+	if (std::isnan(d.min_transmittance)) throw std::runtime_error("invalid irradiance sun NeRF descriptor: min_transmittance is NaN");
+	if (!std::isfinite(d.t_min) || d.t_min < 0.0f) throw std::runtime_error("invalid irradiance sun NeRF descriptor: t_min must be finite and >= 0");
+}
+inline void check_desc(const ngp_mesh_shadow_on_nerf_desc& d) {
+	if (!(d.strength >= 0.0f && d.strength <= 1.0f)) throw std::runtime_error("invalid mesh shadow descriptor: strength must lie in [0, 1]");
+	if (!std::isfinite(d.bias) || d.bias < 0.0f) throw std::runtime_error("invalid mesh shadow descriptor: bias must be finite and >= 0");
+}
+inline void check_desc(const ngp_ambient_change_desc& d) {
+	if (!std::isfinite(d.min_irradiance) || d.min_irradiance < 0.0f) throw std::runtime_error("invalid ambient change descriptor: min_irradiance must be finite and >= 0");
+	if (!std::isfinite(d.max_gain) || d.max_gain < 1.0f) throw std::runtime_error("invalid ambient change descriptor: max_gain must be finite and >= 1");
+}
+inline void check_desc(const ngp_mesh_reflection_desc& d) {
+	if (!std::isfinite(d.strength) || d.strength < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: strength must be finite and >= 0");
+	if (std::isnan(d.min_transmittance)) throw std::runtime_error("invalid mesh reflection descriptor: min_transmittance is NaN");
+	if (!std::isfinite(d.t_min) || d.t_min < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: t_min must be finite and >= 0");
+}
+inline void check_desc(const ngp_sun_disk_desc& d) {
+	if (!std::isfinite(d.angular_radius) || d.angular_radius < 0.0f || d.angular_radius > 0.5f)
+		throw std::runtime_error("invalid sun disk descriptor: angular_radius must be finite and lie in [0, 0.5] rad");
+	const uint32_t k = d.n_rays;
+	if (!(k == 1 || k == 2 || k == 4 || k == 8 || k == 16)) throw std::runtime_error("invalid sun disk descriptor: n_rays must be 1, 2, 4, 8 or 16");
+}
+
+// The optional passes of a frame, one row each: the bytes a pixel of the record the pass leaves, the byte the record is cleared to, what the
+// pass's ngp_get_frame_*_ms does after a frame that did not run it, and the refusal of its getters after such a frame.
+enum FramePassId { PASS_SUN_SHADOW, PASS_REFLECTION, PASS_REFLECTION_HITS, PASS_MESH_SHADOW, PASS_AMBIENT_CHANGE, PASS_SUN_DISK, PASS_MESH_IDS, N_FRAME_PASSES };
+enum class PassMs { none, zero, refuses }; // no such getter (and no events); it returns 0; it refuses like the record's getter
+struct FramePassInfo {
+	uint32_t bytes;
+	int fill;
+	PassMs ms;
+	const char* none;
+};
+constexpr FramePassInfo FRAME_PASSES[N_FRAME_PASSES] = {
+	{16, 0, PassMs::zero, "the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)"},         // (q, alpha_s); events around prep + trace
+	{48, 0, PassMs::zero, "the last frame traced no reflection rays (ngp_set_mesh_reflection)"},         // (q, t_hit), (r, 0), (rgb_r, alpha_r); around prep + trace
+	{32, 0, PassMs::zero, "the last frame shaded no reflection hits (ngp_set_mesh_reflection_meshes)"},  // (p2, shadow2), (C2, 1); around the hit shade, inside the reflection's
+	{16, 0, PassMs::zero, "the last frame ran no mesh shadow pass (ngp_set_mesh_shadow_on_nerf)"},       // (p, 2 blocked / 1 open, or 1 + count / K); around the (soft) shadow kernel
+	{48, 0, PassMs::zero, "the last frame ran no ambient change pass (ngp_set_ambient_change_on_nerf)"}, // (p, state), (N, W_after), (g, W_before); around normals + ratio
+	{16, 0, PassMs::refuses, "the last frame ran no sun disk pass (ngp_set_sun_disk)"},                  // (q, 1 + count); around mesh_sun_disk_kernel
+	{4, 0xff, PassMs::none, "the last frame ran without mesh materials (ngp_set_mesh_material)"},        // int32: the mesh of the pixel's primary hit, -1 elsewhere
+};
+
+// What a pass keeps on a device for its getters (ngp_render.cpp read_record, read_ms): the per-pixel record of the frame's last sample, events
+// around the pass in that sample, and which calls of the ring ran it. A scratch group like the ones below (release, allocate, capacity).
 struct FramePass {
-	explicit FramePass(uint32_t stride) : stride(stride) {}
-	uint32_t stride; // float4 a pixel of the record
-	DevArray<float4> record;
+	const FramePassInfo* info = nullptr; // its row of FRAME_PASSES (ngp_ctx's constructor)
+	DevArray<char> record;
+	size_t capacity = 0;
 	Event ev0[FRAME_HISTORY], ev1[FRAME_HISTORY];
 	bool hist[FRAME_HISTORY] = {}; // the slot's call was a frame that ran the pass
 	size_t n_pixels = 0;           // pixels of the last such frame
-	bool ensure(size_t n) {
-		if (!ev1[FRAME_HISTORY - 1]) {
+	void release() { record.reset(); }
+	void allocate(size_t n) {
+		if (info->ms != PassMs::none && !ev1[FRAME_HISTORY - 1]) {
 			for (int i = 0; i < FRAME_HISTORY; ++i) {
 				ev0[i] = new_event();
 				ev1[i] = new_event();
 			}
 		}
-		if ((size_t)stride * n <= record.size()) return false;
-		record.reset();
-		return true;
+		record.reset((size_t)info->bytes * n);
 	}
-	void grow(size_t n) { record.reset((size_t)stride * n); }
-	void clear(size_t n, hipStream_t stream) const { NGP_HIP_CHECK(hipMemsetAsync(record.get(), 0, (size_t)stride * n * sizeof(float4), stream)); }
+	float4* f4() const { return (float4*)record.get(); }
+	void clear(size_t n, hipStream_t stream) const { NGP_HIP_CHECK(hipMemsetAsync(record.get(), info->fill, (size_t)info->bytes * n, stream)); }
 	// around the pass; the events of a frame's last sample are the ones read_ms reads
 	void begin(int slot, hipStream_t stream, bool last) const { if (last) NGP_HIP_CHECK(hipEventRecord(ev0[slot], stream)); }
 	void end(int slot, hipStream_t stream, bool last) const { if (last) NGP_HIP_CHECK(hipEventRecord(ev1[slot], stream)); }
@@ -363,9 +422,6 @@ struct FramePass {
 		hist[slot] = on;
 		if (on) n_pixels = n;
 	}
-	// ngp_render.cpp: the last frame's record (`none`: the refusal after a frame without the pass) and the pass's device time (0 after such a frame)
-	void read_record(ngp_ctx* ctx, float* out, size_t n, const char* none) const;
-	void read_ms(ngp_ctx* ctx, float* ms) const;
 };
 
 // a ray list for the ray-list tracer with one entry a local pixel of a frame, in the frame's pixel order and not compacted
@@ -389,9 +445,40 @@ struct RayList {
 		NGP_HIP_CHECK(hipMemset(d.get(), 0, d.bytes()));
 	}
 };
+
+// The passes' scratch, grouped as the passes share it. A group owns its buffers and says how many pixels they hold; only ngp_render.cpp's
+// ensure_pass_buffers allocates and releases them, by the rule written there (grow_scratch).
+struct GbufferScratch { // the split mesh pass's: frames with the sun shadow, the reflection or the sun's disk fill both
+	DevArray<float4> gbuf; // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle)
+	RayList rays;          // the shadow-ray list
+	size_t capacity = 0;
+	void release() { gbuf.reset(), rays.release(); }
+	void allocate(size_t n) { gbuf.reset(3 * n), rays.allocate(n); }
+};
+struct ReflectionScratch { // the reflection's
+	RayList rays; // the reflection-ray list
+	size_t capacity = 0;
+	void release() { rays.release(); }
+	void allocate(size_t n) { rays.allocate(n); }
+};
+struct ReflectionHitScratch { // the reflection hits'
+	DevArray<int2> ids; // the (mesh, triangle) each mirror ray is cut at, (-1, -1) without a hit
+	size_t capacity = 0;
+	void release() { ids.reset(); }
+	void allocate(size_t n) { ids.reset(n); }
+};
+struct NerfScratch { // the mesh shadow's and the ambient change's
+	DevArray<float4> nerf; // where the NeRF launch composites instead of the frame: premultiplied (r, g, b, a), zeros where it wrote nothing
+	size_t capacity = 0;
+	void release() { nerf.reset(); }
+	void allocate(size_t n) { nerf.reset(n); }
+};
 } // namespace ngp
 
 struct ngp_ctx {
+	ngp_ctx() {
+		for (int i = 0; i < ngp::N_FRAME_PASSES; ++i) passes[i].info = &ngp::FRAME_PASSES[i];
+	}
 	int device = 0;
 	int n_cus = 256;
 	std::string error;
@@ -439,9 +526,6 @@ struct ngp_ctx {
 	ngp::DevArray<ngp::MeshMaterial> d_mesh_materials;
 	uint32_t n_own_materials = 0;
 	uint64_t material_generation = 0, synced_material_generation = 0; // (a peer's replica follows the primary's: sync_peer_geometry)
-	ngp::DevArray<int32_t> d_mesh_ids;       // the id plane of a frame with materials: the mesh of each pixel's primary hit, -1 elsewhere
-	bool hist_mesh_ids[ngp::FRAME_HISTORY] = {}; // the slot's call was a frame with materials
-	size_t mesh_ids_n_pixels = 0;            // pixels of the last such frame
 	ngp::MeshShadeParams shade{{0.57735026f, 0.57735026f, 0.57735026f}, {0.f, 1.f, 0.f}, 0.f, 0.f, 1.f, 0.5f, 0.f, 0.f, 0.f, {0.8f, 0.8f, 0.8f}, {0.f, 0.f, 0.f}};
 
 	// ---- irradiance probe texture(s) (m_envmap_tex / gridSize, testbed.h:949-950) and E(n) tabulated at their texels
@@ -489,42 +573,14 @@ struct ngp_ctx {
 	uint64_t hist_n_rays[HISTORY] = {};
 	ngp::Event ev_mesh0[HISTORY], ev_mesh1[HISTORY]; // around the mesh pass of a frame's last sample (ngp_get_mesh_pass_ms)
 	bool hist_mesh_pass[HISTORY] = {};               // the slot's call was a frame with a mesh pass
-	// ---- the NeRF in front of the frames' sun (ngp_set_sun_nerf_shadow); a peer's copy follows the primary's with the geometry
-	bool sun_nerf_shadow = false;
-	ngp_irradiance_sun_nerf_desc sun_nerf_shadow_desc{};
-	// (q, alpha_s) a pixel of the last sample (ngp_get_frame_sun_shadow); events around prep + trace (ngp_get_frame_sun_shadow_ms). Its scratch:
-	ngp::FramePass pass_sun_shadow{1};
-	ngp::DevArray<float4> d_ss_gbuf; // 3 planes: (pos, shadow), (raw normal, covered), (primary_dir, the primary ray found a triangle)
-	ngp::RayList ss_rays;            // the shadow-ray list
-	// ---- the meshes in front of the sun on the NeRF (ngp_set_mesh_shadow_on_nerf); a peer's copy follows the primary's with the geometry
-	bool mesh_shadow_on_nerf = false;
-	ngp_mesh_shadow_on_nerf_desc mesh_shadow_on_nerf_desc{};
-	// (p, 2 blocked / 1 open) a pixel of the last sample (ngp_get_frame_mesh_shadow); events around nerf_mesh_shadow_kernel (ngp_get_frame_mesh_shadow_ms)
-	ngp::FramePass pass_mesh_shadow{1};
-	ngp::DevArray<float4> d_ms_nerf; // its scratch, where the NeRF launch composites instead of the frame: premultiplied (r, g, b, a), zeros where it wrote nothing
-	// ---- what the meshes change in the ambient light on the NeRF (ngp_set_ambient_change_on_nerf); a peer's copy follows the primary's with the geometry
-	bool ambient_change_on_nerf = false;
-	ngp_ambient_change_desc ambient_change_desc{};
-	// (p, state), (N, W_after), (g, W_before) a pixel of the last sample (ngp_get_frame_ambient_change); events around the normals and ratio kernels
-	// (ngp_get_frame_ambient_change_ms). The scratch is the mesh shadow's d_ms_nerf.
-	ngp::FramePass pass_ambient_change{3};
-	// ---- the NeRF mirrored in the meshes (ngp_set_mesh_reflection); a peer's copy follows the primary's with the geometry
-	bool mesh_reflection = false;
-	ngp_mesh_reflection_desc mesh_reflection_desc{};
-	// (q, t_hit), (r, 0), (rgb_r, alpha_r) a pixel of the last sample (ngp_get_frame_mesh_reflection); events around prep + trace
-	// (ngp_get_frame_mesh_reflection_ms). The G-buffer and the shadow list its frames fill are the sun shadow's (d_ss_gbuf, ss_rays).
-	ngp::FramePass pass_mesh_reflection{3};
-	ngp::RayList mr_rays; // its scratch: the reflection-ray list
-	// ... and the meshes in it (ngp_set_mesh_reflection_meshes): (p2, shadow2), (C2, 1) a pixel of the last sample
-	// (ngp_get_frame_mesh_reflection_hits); events around mesh_reflection_hit_shade_kernel, inside the reflection pass's
-	bool mesh_reflection_meshes = false;
-	ngp::FramePass pass_mesh_reflection_hits{2};
-	ngp::DevArray<int2> d_mr_hit_ids; // its scratch: the (mesh, triangle) each mirror ray is cut at, (-1, -1) without a hit
-	// ---- the sun's disk (ngp_set_sun_disk); a peer's copy follows the primary's with the geometry. (q, 1 + count) a pixel of the last sample
-	// (ngp_get_frame_sun_disk); events around mesh_sun_disk_kernel (ngp_get_frame_sun_disk_ms). The G-buffer and the shadow list are the sun shadow's.
-	bool sun_disk = false;
-	ngp_sun_disk_desc sun_disk_desc{};
-	ngp::FramePass pass_sun_disk{1};
+	// ---- the frame options (FrameOptions, FramePass and the scratch groups above): the settings, a peer's copy of which follows the primary's
+	// with the geometry, and per device the passes' records and the scratch of the passes that share it
+	ngp::FrameOptions options;
+	ngp::FramePass passes[ngp::N_FRAME_PASSES];
+	ngp::GbufferScratch gbuffer_scratch;
+	ngp::ReflectionScratch reflection_scratch;
+	ngp::ReflectionHitScratch reflection_hit_scratch;
+	ngp::NerfScratch nerf_scratch;
 	uint64_t n_calls = 0; // render calls so far; call k uses slot k % HISTORY
 	hipStream_t last_stream = nullptr;
 	// Ordering between frames (any stream) and updates of what they read (render tables after training steps, the occupancy grid after a
@@ -673,7 +729,6 @@ void require_probe_model(ngp_ctx* ctx, const char* what); // the models the trac
 void tracer_frame_params(const ngp_ctx* ctx, int slot, float min_transmittance, FrameParams& F);
 ProbeParams ray_list_params(uint32_t n, const float* o, const float* dir, const float2* t, float4* rgba, float* depth);
 void launch_probe_trace(const ngp_ctx* ctx, const ModelParams& M, FrameParams& F, const ProbeParams& P, bool add_results, hipStream_t stream); // clears P's outputs, then one persistent launch
-void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d); // (nullable)
 // ngp_train.cpp
 void free_training(ngp_ctx* ctx);
 bool probe_image_size(const std::string& path, int& width, int& height);
@@ -713,11 +768,6 @@ inline IrradianceVolume irradiance_volume_from(const ngp_irradiance_volume_desc&
 	return V;
 }
 inline IrradianceVolume sh_volume_of(const ngp_ctx* ctx) { return irradiance_volume_from(ctx->sh_volume_desc, ctx->d_sh_volume.get()); }
-// the refusals of an ngp_ambient_change_desc (ngp_set_ambient_change_on_nerf, ngp_irradiance_volume_ratio)
-inline void check_ambient_change_desc(const ngp_ambient_change_desc& d) {
-	if (!std::isfinite(d.min_irradiance) || d.min_irradiance < 0.0f) throw std::runtime_error("invalid ambient change descriptor: min_irradiance must be finite and >= 0");
-	if (!std::isfinite(d.max_gain) || d.max_gain < 1.0f) throw std::runtime_error("invalid ambient change descriptor: max_gain must be finite and >= 1");
-}
 inline IrradianceVolume sh_reference_of(const ngp_ctx* ctx) { return irradiance_volume_from(ctx->sh_reference_desc, ctx->d_sh_reference.get()); }
 inline IrradianceVolumeVisible sh_volume_visible_of(const ngp_ctx* ctx) {
 	IrradianceVolumeVisible A{};

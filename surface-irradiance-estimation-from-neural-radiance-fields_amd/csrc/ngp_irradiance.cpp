@@ -49,12 +49,6 @@ void launch_probe_trace(const ngp_ctx* ctx, const ModelParams& M, FrameParams& F
 	F.add_results = add_results ? 1 : 0;
 	launch_trace_probe(M, F, P, ctx->n_cus, stream);
 }
-// the NeRF's density in front of the sun (nullable: the meshes alone shadow it)
-void check_sun_nerf(const ngp_irradiance_sun_nerf_desc* d) {
-	if (!d) return;
-	if (std::isnan(d->min_transmittance)) throw std::runtime_error("invalid irradiance sun NeRF descriptor: min_transmittance is NaN");
-	if (!std::isfinite(d->t_min) || d->t_min < 0.0f) throw std::runtime_error("invalid irradiance sun NeRF descriptor: t_min must be finite and >= 0");
-}
 } // namespace ngp
 
 namespace {
@@ -278,7 +272,7 @@ SunLight check_sunlit(const ngp_irradiance_bounce_desc* bounce, const ngp_irradi
 	check_albedo(bounce->albedo);
 	SunLight L{};
 	if (sun) L = check_sun(sun, bounce->albedo);
-	check_sun_nerf(nerf);
+	if (nerf) check_desc(*nerf); // (nullable: the meshes alone shadow the sun)
 	return L;
 }
 
@@ -860,7 +854,7 @@ int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float* positi
 		check_albedo(albedo);
 		if (!sun || !nerf) throw std::runtime_error("null argument");
 		const SunLight L = check_sun(sun, albedo);
-		check_sun_nerf(nerf);
+		if (nerf) check_desc(*nerf);
 		require_model(ctx, "the sun's shadow rays are traced through the model");
 		require_probe_model(ctx, "the sun's shadow rays");
 		const uint32_t K = check_sh_desc(n, desc);
@@ -998,7 +992,7 @@ int ngp_irradiance_volume_ratio(ngp_ctx* ctx, uint32_t n, const float* positions
 		require_volume(ctx);
 		require_reference(ctx);
 		if (!desc) throw std::runtime_error("null argument");
-		check_ambient_change_desc(*desc);
+		check_desc(*desc);
 		if (n == 0) return;
 		if (!positions || !normals || !out) throw std::runtime_error("null argument");
 		check_positions(n, positions);

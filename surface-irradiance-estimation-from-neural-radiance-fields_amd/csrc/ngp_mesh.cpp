@@ -369,17 +369,7 @@ int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* direc
 namespace ngp {
 void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 	peer->shade = primary->shade;
-	peer->sun_nerf_shadow = primary->sun_nerf_shadow; // each device traces the shadow rays of its own share
-	peer->sun_nerf_shadow_desc = primary->sun_nerf_shadow_desc;
-	peer->mesh_shadow_on_nerf = primary->mesh_shadow_on_nerf; // each device shadows its own share
-	peer->mesh_shadow_on_nerf_desc = primary->mesh_shadow_on_nerf_desc;
-	peer->sun_disk = primary->sun_disk; // each device spreads the shadow rays of its own share
-	peer->sun_disk_desc = primary->sun_disk_desc;
-	peer->ambient_change_on_nerf = primary->ambient_change_on_nerf; // each device scales its own share
-	peer->ambient_change_desc = primary->ambient_change_desc;
-	peer->mesh_reflection = primary->mesh_reflection; // each device traces the mirror rays of its own share
-	peer->mesh_reflection_desc = primary->mesh_reflection_desc;
-	peer->mesh_reflection_meshes = primary->mesh_reflection_meshes; // ... and shades the hits of its own share
+	peer->options = primary->options;
 	const bool meshes_changed = peer->synced_mesh_generation != primary->mesh_generation;
 	if (!meshes_changed && peer->synced_material_generation != primary->material_generation) { // the materials alone: the slots' copies and the table
 		for (size_t i = 0; i < peer->meshes.size(); ++i) {

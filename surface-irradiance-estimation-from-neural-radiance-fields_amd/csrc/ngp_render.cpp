@@ -188,8 +188,8 @@ void sun_disk_table(const ngp_sun_disk_desc& desc, const float* sun_dir, uint32_
 }
 SunDisk sun_disk_of(const ngp_ctx* ctx, uint32_t spp_index) {
 	SunDisk D{};
-	D.n_rays = ctx->sun_disk_desc.n_rays;
-	sun_disk_table(ctx->sun_disk_desc, ctx->shade.sun_dir, spp_index, D.d);
+	D.n_rays = ctx->options.sun_disk.desc.n_rays;
+	sun_disk_table(ctx->options.sun_disk.desc, ctx->shade.sun_dir, spp_index, D.d);
 	return D;
 }
 // NGP_SUN_DISK_LAYOUT=thread: one thread a pixel loops over its rays instead of the wave dealing them over its lanes (A/B runs,
@@ -273,112 +273,67 @@ void ensure_frame_buffers(ngp_ctx* ctx, size_t n_pixels) {
 	ctx->d_rgba.reset(n_pixels);
 }
 
-void FramePass::read_record(ngp_ctx* ctx, float* out, size_t n, const char* none) const {
-	require_device(ctx);
-	if (!out) throw std::runtime_error("null argument");
-	if (!ctx->n_calls || !hist[(ctx->n_calls - 1) % FRAME_HISTORY]) throw std::runtime_error(none);
-	if (n != n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(n_pixels) + " pixels on this device");
-	NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-	NGP_HIP_CHECK(hipMemcpy(out, record.get(), stride * n * sizeof(float4), hipMemcpyDeviceToHost));
-}
-void FramePass::read_ms(ngp_ctx* ctx, float* ms) const {
-	require_device(ctx);
-	if (!ms) throw std::runtime_error("null argument");
-	*ms = 0.f;
-	if (!ctx->n_calls) return;
-	const int slot = (int)((ctx->n_calls - 1) % FRAME_HISTORY);
-	if (!hist[slot]) return;
-	NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-	NGP_HIP_CHECK(hipEventElapsedTime(ms, ev0[slot], ev1[slot]));
-}
-
-// ---- the optional passes' buffers. Who owns what: the G-buffer and the shadow list are the sun shadow's, and a frame with mirror rays
-// fills them too; the scratch d_ms_nerf is the mesh shadow's, and a frame with the ambient change composites into it too.
-static void ensure_sun_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	if (!ctx->pass_sun_shadow.ensure(n_pixels)) return;
-	ctx->d_ss_gbuf.reset(), ctx->ss_rays.release(); // all go before the new ones come
-	ctx->d_ss_gbuf.reset(3 * n_pixels);
-	ctx->ss_rays.allocate(n_pixels);
-	ctx->pass_sun_shadow.grow(n_pixels);
-}
-static void ensure_mesh_reflection_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	ensure_sun_shadow_buffers(ctx, n_pixels);
-	if (!ctx->pass_mesh_reflection.ensure(n_pixels)) return;
-	ctx->mr_rays.release();
-	ctx->mr_rays.allocate(n_pixels);
-	ctx->pass_mesh_reflection.grow(n_pixels);
-}
-static void ensure_mesh_reflection_hit_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	if (!ctx->pass_mesh_reflection_hits.ensure(n_pixels)) return;
-	ctx->d_mr_hit_ids.reset();
-	ctx->d_mr_hit_ids.reset(n_pixels);
-	ctx->pass_mesh_reflection_hits.grow(n_pixels);
-}
-static void ensure_mesh_shadow_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	if (!ctx->pass_mesh_shadow.ensure(n_pixels)) return;
-	ctx->d_ms_nerf.reset(n_pixels);
-	ctx->pass_mesh_shadow.grow(n_pixels);
-}
-static void ensure_ambient_change_buffers(ngp_ctx* ctx, size_t n_pixels) {
-	ensure_mesh_shadow_buffers(ctx, n_pixels);
-	if (ctx->pass_ambient_change.ensure(n_pixels)) ctx->pass_ambient_change.grow(n_pixels);
-}
-
-// Which passes a frame runs. The four options apply to a hybrid frame -- Geometry mode, meshes and a model (always the general path) --
-// and all but the sun shadow to the four shade modes alone. Resolved once a call, with the options' refusals and buffers, before
-// anything is enqueued; all of a frame's work then goes onto its stream and nothing waits.
+// Which passes a frame runs. The options apply to a hybrid frame -- Geometry mode, meshes and a model (always the general path) -- and all
+// but the sun shadow to the four shade modes alone; the sun's disk and the materials need the meshes alone. Resolved once a call, with the
+// options' refusals and buffers, before anything is enqueued; all of a frame's work then goes onto its stream and nothing waits.
 struct FramePlan {
-	bool have_meshes = false;    // a Geometry frame with meshes: it has a mesh pass
-	bool sun_shadow = false;     // the NeRF in front of the frames' sun: the mesh pass is split around one ray-list trace per sample
-	bool reflection = false;     // the NeRF mirrored in the meshes: the split mesh pass with a ray list of its own
-	bool reflection_meshes = false; // ... and the meshes in it: the cut rays' hits are shaded between the list's fill and its prep
-	bool mesh_shadow = false;    // the meshes in front of the sun on the NeRF: one kernel behind the NeRF launch finishes its composite
-	bool ambient_change = false; // the meshes' change of the ambient light on the NeRF: normals at the owners' surface points, then g = E_after / E_before
-	bool sun_disk = false;       // the sun's disk: K shadow rays a pixel against all meshes on the G-buffer (meshes alone fill the shadow list without tracing it), and in the mesh shadow's kernel
-	bool materials = false;      // some mesh owns a material: the mesh pass's material instantiations run and leave the frame's id plane
-	bool split() const { return sun_shadow || reflection || sun_disk; }
-	bool scratch() const { return mesh_shadow || ambient_change; } // the NeRF launch composites into d_ms_nerf and a kernel behind it closes the frame
+	bool have_meshes = false; // a Geometry frame with meshes: it has a mesh pass
+	bool runs[N_FRAME_PASSES] = {};
+	bool operator[](FramePassId pass) const { return runs[pass]; }
+	// the mesh pass is split around its ray lists: G-buffer -> per list: prep -> trace -> deferred shade (the disk alone fills the shadow list without tracing it)
+	bool split() const { return runs[PASS_SUN_SHADOW] || runs[PASS_REFLECTION] || runs[PASS_SUN_DISK]; }
+	// the NeRF launch composites into the NeRF scratch and a kernel behind it closes the frame
+	bool scratch() const { return runs[PASS_MESH_SHADOW] || runs[PASS_AMBIENT_CHANGE]; }
 };
+
+// The one rule of the passes' buffers: nothing is allocated until a frame first needs it; a group grows when a frame has more pixels than it
+// holds; all of its buffers go before any new one comes (releasing device memory waits for the device: nothing goes under a frame in
+// flight); and its capacity is 0 from before the release until the last allocation has succeeded, so the next frame rebuilds a group
+// that an allocation failed in.
+template <typename Group>
+static void grow_scratch(Group& g, size_t n_pixels) {
+	if (n_pixels <= g.capacity) return;
+	g.capacity = 0;
+	g.release();
+	g.allocate(n_pixels);
+	g.capacity = n_pixels;
+}
+static void ensure_pass_buffers(ngp_ctx* ctx, const FramePlan& plan, size_t n_pixels) {
+	if (plan.split()) grow_scratch(ctx->gbuffer_scratch, n_pixels);
+	if (plan[PASS_REFLECTION]) grow_scratch(ctx->reflection_scratch, n_pixels);
+	if (plan[PASS_REFLECTION_HITS]) grow_scratch(ctx->reflection_hit_scratch, n_pixels);
+	if (plan.scratch()) grow_scratch(ctx->nerf_scratch, n_pixels);
+	for (int i = 0; i < N_FRAME_PASSES; ++i)
+		if (plan.runs[i]) grow_scratch(ctx->passes[i], n_pixels);
+}
+
 static FramePlan plan_frame(ngp_ctx* ctx, const ngp_render_opts& opts, size_t n_pixels) {
+	const FrameOptions& o = ctx->options;
 	FramePlan p;
 	p.have_meshes = opts.testbed_mode == NGP_MODE_GEOMETRY && !ctx->meshes.empty();
 	const bool hybrid = p.have_meshes && ctx->model_loaded;
 	const bool shade_mode = opts.render_mode == NGP_RENDER_SHADE || opts.render_mode == NGP_RENDER_SHADE_ENVMAP || opts.render_mode == NGP_RENDER_SHADE_GRID_ENVMAP ||
 	                        opts.render_mode == NGP_RENDER_SHADE_IRRADIANCE_VOLUME;
-	p.sun_shadow = ctx->sun_nerf_shadow && hybrid;
-	if (p.sun_shadow) {
-		require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
-		ensure_sun_shadow_buffers(ctx, n_pixels);
-	}
+	p.runs[PASS_SUN_SHADOW] = o.sun_nerf_shadow.on && hybrid;
 	// (strength 0 adds nothing: no trace is run and the frame takes the path it would take with the option off)
-	p.reflection = ctx->mesh_reflection && ctx->mesh_reflection_desc.strength > 0.0f && hybrid && shade_mode;
-	if (p.reflection) {
-		require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
-		ensure_mesh_reflection_buffers(ctx, n_pixels);
-	}
-	p.reflection_meshes = p.reflection && ctx->mesh_reflection_meshes;
-	if (p.reflection_meshes) ensure_mesh_reflection_hit_buffers(ctx, n_pixels);
-	p.mesh_shadow = ctx->mesh_shadow_on_nerf && hybrid && shade_mode;
-	if (p.mesh_shadow) ensure_mesh_shadow_buffers(ctx, n_pixels);
-	p.ambient_change = ctx->ambient_change_on_nerf && hybrid && shade_mode;
-	if (p.ambient_change) {
+	p.runs[PASS_REFLECTION] = o.mesh_reflection.on && o.mesh_reflection.desc.strength > 0.0f && hybrid && shade_mode;
+	p.runs[PASS_REFLECTION_HITS] = p[PASS_REFLECTION] && o.mesh_reflection_meshes;
+	p.runs[PASS_MESH_SHADOW] = o.mesh_shadow_on_nerf.on && hybrid && shade_mode;
+	p.runs[PASS_AMBIENT_CHANGE] = o.ambient_change_on_nerf.on && hybrid && shade_mode;
+	p.runs[PASS_SUN_DISK] = o.sun_disk.on && p.have_meshes;
+	p.runs[PASS_MESH_IDS] = p.have_meshes && ctx->n_own_materials > 0; // some mesh owns a material: the mesh pass's material instantiations run and leave the id plane
+
+	if (p[PASS_SUN_SHADOW]) require_probe_model(ctx, "sun_nerf_shadow frames (ngp_set_sun_nerf_shadow)");
+	if (p[PASS_REFLECTION]) require_probe_model(ctx, "mesh_reflection frames (ngp_set_mesh_reflection)");
+	if (p[PASS_AMBIENT_CHANGE]) {
 		if (!ctx->d_sh_volume) throw std::runtime_error("ambient_change_on_nerf frames need the irradiance volume: call ngp_compute_irradiance_volume or ngp_set_irradiance_volume first");
 		if (!ctx->d_sh_reference)
 			throw std::runtime_error("ambient_change_on_nerf frames need the reference irradiance volume: call ngp_compute_reference_irradiance_volume or ngp_set_reference_irradiance_volume first");
 		if (ctx->M.wide.width) throw std::runtime_error("ambient_change_on_nerf frames need a grid-encoded model (ngp_set_ambient_change_on_nerf)");
-		ensure_ambient_change_buffers(ctx, n_pixels);
 	}
-	p.sun_disk = ctx->sun_disk && p.have_meshes;
-	if (p.sun_disk) {
-		(void)sun_disk_of(ctx, 0); // (a sun direction without a length is refused here, ahead of the frame's work)
-		ensure_sun_shadow_buffers(ctx, n_pixels);
-		if (ctx->pass_sun_disk.ensure(n_pixels)) ctx->pass_sun_disk.grow(n_pixels);
-	}
-	p.materials = p.have_meshes && ctx->n_own_materials > 0;
-	if (p.materials && n_pixels > ctx->d_mesh_ids.size()) {
-		ctx->d_mesh_ids.reset();
-		ctx->d_mesh_ids.reset(n_pixels);
-	}
+	if (p[PASS_SUN_DISK]) (void)sun_disk_of(ctx, 0); // (a sun direction without a length is refused here, ahead of the frame's work)
+
+	ensure_pass_buffers(ctx, p, n_pixels);
 	return p;
 }
 
@@ -432,57 +387,57 @@ static void mesh_pass(const FrameCall& f, const ngp_render_opts& opts, const Mod
 	const bool visible = volume && ctx->d_sh_visibility; // the held distance maps weight the probes
 	const IrradianceVolumeVisible VV = visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
 	// with materials the kernels select own ? table[mesh] : ctx->shade per thread and write the id plane (entries no pixel owns stay -1)
-	const MeshMaterial* materials = f.plan.materials ? ctx->d_mesh_materials.get() : nullptr;
-	int32_t* ids = f.plan.materials ? ctx->d_mesh_ids.get() : nullptr;
+	const MeshMaterial* materials = f.plan[PASS_MESH_IDS] ? ctx->d_mesh_materials.get() : nullptr;
+	int32_t* ids = f.plan[PASS_MESH_IDS] ? (int32_t*)ctx->passes[PASS_MESH_IDS].record.get() : nullptr;
 	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh0[f.slot], f.stream)); // (ngp_get_mesh_pass_ms)
-	if (ids) NGP_HIP_CHECK(hipMemsetAsync(ids, 0xff, (size_t)f.L.n_pixels * sizeof(int32_t), f.stream));
+	if (ids) ctx->passes[PASS_MESH_IDS].clear(f.L.n_pixels, f.stream);
 	if (f.plan.split()) {
-		const RayList& ss = ctx->ss_rays;
-		trace_pixel_rays(f, M, ss, ctx->pass_sun_shadow, f.plan.sun_shadow, ctx->sun_nerf_shadow_desc.min_transmittance, last, [&] {
-			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(), ss.d.get(), ss.t.get(), ids, f.stream);
-			if (!f.plan.sun_disk) return;
-			const FramePass& disk = ctx->pass_sun_disk; // (the kernel writes its owners' records; the clear covers the others)
+		const FrameOptions& o = ctx->options;
+		const RayList& ss = ctx->gbuffer_scratch.rays;
+		float4* gbuf = ctx->gbuffer_scratch.gbuf.get();
+		trace_pixel_rays(f, M, ss, ctx->passes[PASS_SUN_SHADOW], f.plan[PASS_SUN_SHADOW], o.sun_nerf_shadow.desc.min_transmittance, last, [&] {
+			launch_mesh_gbuffer(ctx->mesh_scene, ctx->shade, C, f.L, F.depth_buffer, o.sun_nerf_shadow.desc.t_min, gbuf, ss.o.get(), ss.d.get(), ss.t.get(), ids, f.stream);
+			if (!f.plan[PASS_SUN_DISK]) return;
+			const FramePass& disk = ctx->passes[PASS_SUN_DISK]; // (the kernel writes its owners' records; the clear covers the others)
 			disk.clear(f.L.n_pixels, f.stream);
 			disk.begin(f.slot, f.stream, last);
-			launch_mesh_sun_disk(ctx->mesh_scene, C, f.L, sun_disk_of(ctx, C.spp), sun_disk_wave_layout(), ctx->sun_nerf_shadow_desc.t_min, ctx->d_ss_gbuf.get(), ss.o.get(),
-			                     ss.t.get(), disk.record.get(), f.stream);
+			launch_mesh_sun_disk(ctx->mesh_scene, C, f.L, sun_disk_of(ctx, C.spp), sun_disk_wave_layout(), o.sun_nerf_shadow.desc.t_min, gbuf, ss.o.get(), ss.t.get(), disk.f4(), f.stream);
 			disk.end(f.slot, f.stream, last);
 		}, [] {});
 		MeshReflectionList R{};
-		if (f.plan.reflection) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
-			const RayList& mr = ctx->mr_rays;
-			trace_pixel_rays(f, M, mr, ctx->pass_mesh_reflection, true, ctx->mesh_reflection_desc.min_transmittance, last, [&] {
-				launch_mesh_reflection_rays(ctx->mesh_scene, C, f.L, ctx->mesh_reflection_desc.t_min, ctx->d_ss_gbuf.get(), mr.o.get(), mr.d.get(), mr.t.get(),
-				                            f.plan.reflection_meshes ? ctx->d_mr_hit_ids.get() : nullptr, f.stream);
+		if (f.plan[PASS_REFLECTION]) { // the mirror rays: a list and a trace of their own behind the shadow rays', every ray traced on its own
+			const RayList& mr = ctx->reflection_scratch.rays;
+			const FramePass& hits = ctx->passes[PASS_REFLECTION_HITS];
+			int2* hit_ids = f.plan[PASS_REFLECTION_HITS] ? ctx->reflection_hit_scratch.ids.get() : nullptr;
+			trace_pixel_rays(f, M, mr, ctx->passes[PASS_REFLECTION], true, o.mesh_reflection.desc.min_transmittance, last, [&] {
+				launch_mesh_reflection_rays(ctx->mesh_scene, C, f.L, o.mesh_reflection.desc.t_min, gbuf, mr.o.get(), mr.d.get(), mr.t.get(), hit_ids, f.stream);
 			}, [&] {
-				if (!f.plan.reflection_meshes) return;
-				const FramePass& hits = ctx->pass_mesh_reflection_hits; // (the kernel writes every pixel it owns; the clear covers the others)
-				hits.clear(f.L.n_pixels, f.stream);
+				if (!hit_ids) return;
+				hits.clear(f.L.n_pixels, f.stream); // (the kernel writes every pixel it owns; the clear covers the others)
 				hits.begin(f.slot, f.stream, last);
-				launch_mesh_reflection_hit_shade(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, mr.o.get(), mr.d.get(), mr.t.get(),
-				                                 ctx->d_mr_hit_ids.get(), hits.record.get(), materials, f.stream);
+				launch_mesh_reflection_hit_shade(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, mr.o.get(), mr.d.get(), mr.t.get(), hit_ids,
+				                                 hits.f4(), materials, f.stream);
 				hits.end(f.slot, f.stream, last);
 			});
-			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->pass_mesh_reflection.record.get(), ctx->mesh_reflection_desc.strength,
-			                       f.plan.reflection_meshes ? ctx->pass_mesh_reflection_hits.record.get() : nullptr};
+			R = MeshReflectionList{mr.o.get(), mr.t.get(), mr.traced.get(), ctx->passes[PASS_REFLECTION].f4(), o.mesh_reflection.desc.strength, hit_ids ? hits.f4() : nullptr};
 		}
-		launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), ctx->d_ss_gbuf.get(), ss.o.get(), ss.t.get(),
-		                           f.plan.sun_shadow ? ss.traced.get() : nullptr, ctx->pass_sun_shadow.record.get(), R, materials, ids, f.stream);
+		launch_mesh_shade_deferred(ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), gbuf, ss.o.get(), ss.t.get(),
+		                           f.plan[PASS_SUN_SHADOW] ? ss.traced.get() : nullptr, ctx->passes[PASS_SUN_SHADOW].f4(), R, materials, ids, f.stream);
 	} else {
 		launch_render_mesh(ctx->mesh_scene, ctx->shade, I, volume ? &V : nullptr, visible ? &VV : nullptr, C, f.L, ctx->d_frame.get(), F.depth_buffer, materials, ids, f.stream);
 	}
 	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_mesh1[f.slot], f.stream));
 }
 
-// the NeRF launch of sample s: into the frame, or with plan.scratch() over zeros into d_ms_nerf, apart from the mesh pass's pixels (its depth
+// the NeRF launch of sample s: into the frame, or with plan.scratch() over zeros into the NeRF scratch, apart from the mesh pass's pixels (its depth
 // test and depth writes are every frame's)
 static void nerf_pass(const FrameCall& f, const ModelParams& M, const CameraParams& C, FrameParams& F, int s, bool last) {
 	ngp_ctx* ctx = f.ctx;
 	if (f.plan.scratch()) {
-		NGP_HIP_CHECK(hipMemsetAsync(ctx->d_ms_nerf.get(), 0, (size_t)f.L.n_pixels * sizeof(float4), f.stream));
-		if (f.plan.mesh_shadow) ctx->pass_mesh_shadow.clear(f.L.n_pixels, f.stream);
-		if (f.plan.ambient_change) ctx->pass_ambient_change.clear(f.L.n_pixels, f.stream);
-		F.frame_buffer = ctx->d_ms_nerf.get();
+		NGP_HIP_CHECK(hipMemsetAsync(ctx->nerf_scratch.nerf.get(), 0, (size_t)f.L.n_pixels * sizeof(float4), f.stream));
+		if (f.plan[PASS_MESH_SHADOW]) ctx->passes[PASS_MESH_SHADOW].clear(f.L.n_pixels, f.stream);
+		if (f.plan[PASS_AMBIENT_CHANGE]) ctx->passes[PASS_AMBIENT_CHANGE].clear(f.L.n_pixels, f.stream);
+		F.frame_buffer = ctx->nerf_scratch.nerf.get();
 	}
 	if (last) NGP_HIP_CHECK(hipEventRecord(ctx->ev_kern0[f.slot], f.stream));
 	if (ctx->model_loaded) ctx->last_render_kernel = launch_render_nerf(M, C, F, ctx->n_cus, f.stream); // persistent grid sized by the launcher
@@ -494,24 +449,25 @@ static void nerf_pass(const FrameCall& f, const ModelParams& M, const CameraPara
 // mesh pass's pixels, scaled where a mesh stands in front of the sun (or plain: f = 1, no traversal)
 static void closing_passes(const FrameCall& f, const ModelParams& M, const CameraParams& C, const FrameParams& F, bool last) {
 	ngp_ctx* ctx = f.ctx;
-	if (f.plan.ambient_change) {
-		const FramePass& pass = ctx->pass_ambient_change;
+	float4* nerf = ctx->nerf_scratch.nerf.get();
+	if (f.plan[PASS_AMBIENT_CHANGE]) {
+		const FramePass& pass = ctx->passes[PASS_AMBIENT_CHANGE];
+		const ngp_ambient_change_desc& d = ctx->options.ambient_change_on_nerf.desc;
 		pass.begin(f.slot, f.stream, last);
-		launch_nerf_surface_normals(M, C, f.L, F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.stream);
-		launch_nerf_ambient_ratio(sh_volume_of(ctx), sh_reference_of(ctx), f.L.n_pixels, ctx->d_ms_nerf.get(), pass.record.get(), ctx->ambient_change_desc.min_irradiance,
-		                          ctx->ambient_change_desc.max_gain, f.stream);
+		launch_nerf_surface_normals(M, C, f.L, F.depth_buffer, nerf, pass.f4(), f.stream);
+		launch_nerf_ambient_ratio(sh_volume_of(ctx), sh_reference_of(ctx), f.L.n_pixels, nerf, pass.f4(), d.min_irradiance, d.max_gain, f.stream);
 		pass.end(f.slot, f.stream, last);
-		if (!f.plan.mesh_shadow) launch_nerf_composite(C, ctx->d_frame.get(), ctx->d_ms_nerf.get(), f.L, f.stream);
+		if (!f.plan[PASS_MESH_SHADOW]) launch_nerf_composite(C, ctx->d_frame.get(), nerf, f.L, f.stream);
 	}
-	if (f.plan.mesh_shadow) {
-		const FramePass& pass = ctx->pass_mesh_shadow;
+	if (f.plan[PASS_MESH_SHADOW]) {
+		const FramePass& pass = ctx->passes[PASS_MESH_SHADOW];
+		const ngp_mesh_shadow_on_nerf_desc& d = ctx->options.mesh_shadow_on_nerf.desc;
 		pass.begin(f.slot, f.stream, last);
-		if (f.plan.sun_disk)
-			launch_nerf_mesh_soft_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L, sun_disk_of(ctx, C.spp),
-			                             sun_disk_wave_layout(), ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
+		if (f.plan[PASS_SUN_DISK])
+			launch_nerf_mesh_soft_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, nerf, pass.f4(), f.L, sun_disk_of(ctx, C.spp), sun_disk_wave_layout(),
+			                             d.strength, d.bias, f.stream);
 		else
-			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, ctx->d_ms_nerf.get(), pass.record.get(), f.L,
-			                        ctx->mesh_shadow_on_nerf_desc.strength, ctx->mesh_shadow_on_nerf_desc.bias, f.stream);
+			launch_nerf_mesh_shadow(ctx->mesh_scene, ctx->shade, M, C, ctx->d_frame.get(), F.depth_buffer, nerf, pass.f4(), f.L, d.strength, d.bias, f.stream);
 		pass.end(f.slot, f.stream, last);
 	}
 }
@@ -573,20 +529,61 @@ void render_frames(ngp_ctx* ctx, const ngp_camera& cam, const ngp_render_opts& o
 	ctx->last_stream = stream;
 	ctx->hist_n_rays[slot] = (uint64_t)F.n_local_tiles * 64u * (uint64_t)spp;
 	ctx->hist_mesh_pass[slot] = plan.have_meshes && !F.direct;
-	ctx->pass_sun_shadow.ran(slot, plan.sun_shadow, n_pixels);
-	ctx->pass_mesh_reflection.ran(slot, plan.reflection, n_pixels);
-	ctx->pass_mesh_reflection_hits.ran(slot, plan.reflection_meshes, n_pixels);
-	ctx->pass_mesh_shadow.ran(slot, plan.mesh_shadow, n_pixels);
-	ctx->pass_ambient_change.ran(slot, plan.ambient_change, n_pixels);
-	ctx->pass_sun_disk.ran(slot, plan.sun_disk, n_pixels);
-	ctx->hist_mesh_ids[slot] = plan.materials && !F.direct;
-	if (ctx->hist_mesh_ids[slot]) ctx->mesh_ids_n_pixels = n_pixels;
+	for (int i = 0; i < N_FRAME_PASSES; ++i) ctx->passes[i].ran(slot, plan.runs[i], n_pixels); // (a frame with a pass has meshes: never the direct path)
 	ctx->last_was_multi = false;
 	++ctx->n_calls;
 }
 } // namespace ngp
 
 // ================================================================================================== C ABI
+namespace {
+// ---- the bodies the frame options' entries share. An option's setter validates first: a refused call leaves the option as it was.
+template <typename Desc>
+int set_option(ngp_ctx* ctx, FrameOption<Desc> FrameOptions::*option, const Desc* desc) {
+	return guarded(ctx, [&] {
+		if (desc) check_desc(*desc);
+		ctx->options.*option = FrameOption<Desc>{desc != nullptr, desc ? *desc : Desc{}};
+	});
+}
+template <typename Desc>
+int get_option(ngp_ctx* ctx, FrameOption<Desc> FrameOptions::*option, Desc* out, int* enabled) {
+	return guarded(ctx, [&] {
+		if (!out || !enabled) throw std::runtime_error("null argument");
+		*out = (ctx->options.*option).desc;
+		*enabled = (ctx->options.*option).on ? 1 : 0;
+	});
+}
+// whether the context's last call was a frame that ran the pass
+bool ran_last(const ngp_ctx* ctx, FramePassId pass) { return ctx->n_calls && ctx->passes[pass].hist[(ctx->n_calls - 1) % FRAME_HISTORY]; }
+// the record the pass left in the last frame, n pixels of FRAME_PASSES[pass].bytes each
+int read_record(ngp_ctx* ctx, FramePassId pass, void* out, size_t n) {
+	return guarded(ctx, [&] {
+		const FramePass& p = ctx->passes[pass];
+		require_device(ctx);
+		if (!out) throw std::runtime_error("null argument");
+		if (!ran_last(ctx, pass)) throw std::runtime_error(p.info->none);
+		if (n != p.n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(p.n_pixels) + " pixels on this device");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipMemcpy(out, p.record.get(), p.info->bytes * n, hipMemcpyDeviceToHost));
+	});
+}
+// the pass's device time in the last frame's last sample; after a frame without the pass 0, or the record's refusal (FRAME_PASSES)
+int read_ms(ngp_ctx* ctx, FramePassId pass, float* ms) {
+	return guarded(ctx, [&] {
+		const FramePass& p = ctx->passes[pass];
+		require_device(ctx);
+		const bool ran = ran_last(ctx, pass);
+		if (!ran && p.info->ms == PassMs::refuses) throw std::runtime_error(p.info->none);
+		if (!ms) throw std::runtime_error("null argument");
+		*ms = 0.f;
+		if (!ran) return;
+		const int slot = (int)((ctx->n_calls - 1) % FRAME_HISTORY);
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		NGP_HIP_CHECK(hipEventElapsedTime(ms, p.ev0[slot], p.ev1[slot]));
+	});
+}
+} // namespace
+
 extern "C" {
 
 // ---- page-locked host images. Testbed::render_to_cpu returns a fresh numpy array per call (src/python_api.cu:124-202); a
@@ -730,168 +727,49 @@ int ngp_get_mesh_pass_ms(ngp_ctx* ctx, float* ms_out) {
 	});
 }
 
-int ngp_set_sun_nerf_shadow(ngp_ctx* ctx, const ngp_irradiance_sun_nerf_desc* nerf) {
-	return guarded(ctx, [&] {
-		check_sun_nerf(nerf);
-		ctx->sun_nerf_shadow = nerf != nullptr;
-		ctx->sun_nerf_shadow_desc = nerf ? *nerf : ngp_irradiance_sun_nerf_desc{};
-	});
-}
-
-int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int* enabled) {
-	return guarded(ctx, [&] {
-		if (!out || !enabled) throw std::runtime_error("null argument");
-		*out = ctx->sun_nerf_shadow_desc;
-		*enabled = ctx->sun_nerf_shadow ? 1 : 0;
-	});
-}
-
-int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc) {
-	return guarded(ctx, [&] {
-		if (desc) {
-			if (!std::isfinite(desc->strength) || desc->strength < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: strength must be finite and >= 0");
-			if (std::isnan(desc->min_transmittance)) throw std::runtime_error("invalid mesh reflection descriptor: min_transmittance is NaN");
-			if (!std::isfinite(desc->t_min) || desc->t_min < 0.0f) throw std::runtime_error("invalid mesh reflection descriptor: t_min must be finite and >= 0");
-		}
-		ctx->mesh_reflection = desc != nullptr;
-		ctx->mesh_reflection_desc = desc ? *desc : ngp_mesh_reflection_desc{};
-	});
-}
-
+// ---- the frame options' settings (FrameOptions, ngp_host.h)
+int ngp_set_sun_nerf_shadow(ngp_ctx* ctx, const ngp_irradiance_sun_nerf_desc* nerf) { return set_option(ctx, &FrameOptions::sun_nerf_shadow, nerf); }
+int ngp_get_sun_nerf_shadow(ngp_ctx* ctx, ngp_irradiance_sun_nerf_desc* out, int* enabled) { return get_option(ctx, &FrameOptions::sun_nerf_shadow, out, enabled); }
+int ngp_set_mesh_reflection(ngp_ctx* ctx, const ngp_mesh_reflection_desc* desc) { return set_option(ctx, &FrameOptions::mesh_reflection, desc); }
+int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* enabled) { return get_option(ctx, &FrameOptions::mesh_reflection, out, enabled); }
+int ngp_set_mesh_shadow_on_nerf(ngp_ctx* ctx, const ngp_mesh_shadow_on_nerf_desc* desc) { return set_option(ctx, &FrameOptions::mesh_shadow_on_nerf, desc); }
+int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_desc* out, int* enabled) { return get_option(ctx, &FrameOptions::mesh_shadow_on_nerf, out, enabled); }
+int ngp_set_ambient_change_on_nerf(ngp_ctx* ctx, const ngp_ambient_change_desc* desc) { return set_option(ctx, &FrameOptions::ambient_change_on_nerf, desc); }
+int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, int* enabled) { return get_option(ctx, &FrameOptions::ambient_change_on_nerf, out, enabled); }
+int ngp_set_sun_disk(ngp_ctx* ctx, const ngp_sun_disk_desc* desc) { return set_option(ctx, &FrameOptions::sun_disk, desc); }
+int ngp_get_sun_disk(ngp_ctx* ctx, ngp_sun_disk_desc* out, int* enabled) { return get_option(ctx, &FrameOptions::sun_disk, out, enabled); }
 int ngp_set_mesh_reflection_meshes(ngp_ctx* ctx, int on) {
-	return guarded(ctx, [&] { ctx->mesh_reflection_meshes = on != 0; });
+	return guarded(ctx, [&] { ctx->options.mesh_reflection_meshes = on != 0; });
 }
 int ngp_get_mesh_reflection_meshes(ngp_ctx* ctx, int* on) {
 	return guarded(ctx, [&] {
 		if (!on) throw std::runtime_error("null argument");
-		*on = ctx->mesh_reflection_meshes ? 1 : 0;
-	});
-}
-int ngp_get_mesh_reflection(ngp_ctx* ctx, ngp_mesh_reflection_desc* out, int* enabled) {
-	return guarded(ctx, [&] {
-		if (!out || !enabled) throw std::runtime_error("null argument");
-		*out = ctx->mesh_reflection_desc;
-		*enabled = ctx->mesh_reflection ? 1 : 0;
-	});
-}
-
-int ngp_set_mesh_shadow_on_nerf(ngp_ctx* ctx, const ngp_mesh_shadow_on_nerf_desc* desc) {
-	return guarded(ctx, [&] {
-		if (desc) {
-			if (!(desc->strength >= 0.0f && desc->strength <= 1.0f)) throw std::runtime_error("invalid mesh shadow descriptor: strength must lie in [0, 1]");
-			if (!std::isfinite(desc->bias) || desc->bias < 0.0f) throw std::runtime_error("invalid mesh shadow descriptor: bias must be finite and >= 0");
-		}
-		ctx->mesh_shadow_on_nerf = desc != nullptr;
-		ctx->mesh_shadow_on_nerf_desc = desc ? *desc : ngp_mesh_shadow_on_nerf_desc{};
-	});
-}
-
-int ngp_get_mesh_shadow_on_nerf(ngp_ctx* ctx, ngp_mesh_shadow_on_nerf_desc* out, int* enabled) {
-	return guarded(ctx, [&] {
-		if (!out || !enabled) throw std::runtime_error("null argument");
-		*out = ctx->mesh_shadow_on_nerf_desc;
-		*enabled = ctx->mesh_shadow_on_nerf ? 1 : 0;
-	});
-}
-
-int ngp_set_ambient_change_on_nerf(ngp_ctx* ctx, const ngp_ambient_change_desc* desc) {
-	return guarded(ctx, [&] {
-		if (desc) check_ambient_change_desc(*desc);
-		ctx->ambient_change_on_nerf = desc != nullptr;
-		ctx->ambient_change_desc = desc ? *desc : ngp_ambient_change_desc{};
-	});
-}
-
-int ngp_get_ambient_change_on_nerf(ngp_ctx* ctx, ngp_ambient_change_desc* out, int* enabled) {
-	return guarded(ctx, [&] {
-		if (!out || !enabled) throw std::runtime_error("null argument");
-		*out = ctx->ambient_change_desc;
-		*enabled = ctx->ambient_change_on_nerf ? 1 : 0;
-	});
-}
-
-int ngp_set_sun_disk(ngp_ctx* ctx, const ngp_sun_disk_desc* desc) {
-	return guarded(ctx, [&] {
-		if (desc) {
-			if (!std::isfinite(desc->angular_radius) || desc->angular_radius < 0.0f || desc->angular_radius > 0.5f)
-				throw std::runtime_error("invalid sun disk descriptor: angular_radius must be finite and lie in [0, 0.5] rad");
-			const uint32_t k = desc->n_rays;
-			if (!(k == 1 || k == 2 || k == 4 || k == 8 || k == 16)) throw std::runtime_error("invalid sun disk descriptor: n_rays must be 1, 2, 4, 8 or 16");
-		}
-		ctx->sun_disk = desc != nullptr;
-		ctx->sun_disk_desc = desc ? *desc : ngp_sun_disk_desc{};
-	});
-}
-
-int ngp_get_sun_disk(ngp_ctx* ctx, ngp_sun_disk_desc* out, int* enabled) {
-	return guarded(ctx, [&] {
-		if (!out || !enabled) throw std::runtime_error("null argument");
-		*out = ctx->sun_disk_desc;
-		*enabled = ctx->sun_disk ? 1 : 0;
+		*on = ctx->options.mesh_reflection_meshes ? 1 : 0;
 	});
 }
 
 int ngp_sun_disk_directions(ngp_ctx* ctx, const float* sun_dir, uint32_t spp_index, float* out) {
 	return guarded(ctx, [&] {
 		if (!sun_dir || !out) throw std::runtime_error("null argument");
-		if (!ctx->sun_disk) throw std::runtime_error("the sun has no disk: call ngp_set_sun_disk first");
-		sun_disk_table(ctx->sun_disk_desc, sun_dir, spp_index, out);
+		if (!ctx->options.sun_disk.on) throw std::runtime_error("the sun has no disk: call ngp_set_sun_disk first");
+		sun_disk_table(ctx->options.sun_disk.desc, sun_dir, spp_index, out);
 	});
 }
 
-// what the last frame's optional passes left (FramePass, ngp_host.h)
-int ngp_get_frame_sun_disk(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] { ctx->pass_sun_disk.read_record(ctx, out, n_pixels, "the last frame ran no sun disk pass (ngp_set_sun_disk)"); });
-}
-int ngp_get_frame_sun_disk_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!ctx->n_calls || !ctx->pass_sun_disk.hist[(ctx->n_calls - 1) % ngp_ctx::HISTORY]) throw std::runtime_error("the last frame ran no sun disk pass (ngp_set_sun_disk)");
-		ctx->pass_sun_disk.read_ms(ctx, ms);
-	});
-}
-int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] { ctx->pass_sun_shadow.read_record(ctx, out, n_pixels, "the last frame traced no sun shadow rays (ngp_set_sun_nerf_shadow)"); });
-}
-int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] { ctx->pass_sun_shadow.read_ms(ctx, ms); });
-}
-int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_record(ctx, out, n_pixels, "the last frame traced no reflection rays (ngp_set_mesh_reflection)"); });
-}
-int ngp_get_frame_mesh_reflection_hits(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		ctx->pass_mesh_reflection_hits.read_record(ctx, out, n_pixels, "the last frame shaded no reflection hits (ngp_set_mesh_reflection_meshes)");
-	});
-}
-int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] { ctx->pass_mesh_reflection_hits.read_ms(ctx, ms); });
-}
-int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] { ctx->pass_mesh_reflection.read_ms(ctx, ms); });
-}
-int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] { ctx->pass_mesh_shadow.read_record(ctx, out, n_pixels, "the last frame ran no mesh shadow pass (ngp_set_mesh_shadow_on_nerf)"); });
-}
-int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] { ctx->pass_mesh_shadow.read_ms(ctx, ms); });
-}
-int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) {
-	return guarded(ctx, [&] { ctx->pass_ambient_change.read_record(ctx, out, n_pixels, "the last frame ran no ambient change pass (ngp_set_ambient_change_on_nerf)"); });
-}
-int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms) {
-	return guarded(ctx, [&] { ctx->pass_ambient_change.read_ms(ctx, ms); });
-}
-int ngp_get_frame_mesh_ids(ngp_ctx* ctx, int32_t* out, size_t n_pixels) {
-	return guarded(ctx, [&] {
-		require_device(ctx);
-		if (!out) throw std::runtime_error("null argument");
-		if (!ctx->n_calls || !ctx->hist_mesh_ids[(ctx->n_calls - 1) % FRAME_HISTORY]) throw std::runtime_error("the last frame ran without mesh materials (ngp_set_mesh_material)");
-		if (n_pixels != ctx->mesh_ids_n_pixels) throw std::runtime_error("n_pixels: the last frame had " + std::to_string(ctx->mesh_ids_n_pixels) + " pixels on this device");
-		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
-		NGP_HIP_CHECK(hipMemcpy(out, ctx->d_mesh_ids.get(), n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
-	});
-}
+// ---- what the last frame's optional passes left (FRAME_PASSES, ngp_host.h)
+int ngp_get_frame_sun_disk(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_SUN_DISK, out, n_pixels); }
+int ngp_get_frame_sun_disk_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_SUN_DISK, ms); }
+int ngp_get_frame_sun_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_SUN_SHADOW, out, n_pixels); }
+int ngp_get_frame_sun_shadow_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_SUN_SHADOW, ms); }
+int ngp_get_frame_mesh_reflection(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_REFLECTION, out, n_pixels); }
+int ngp_get_frame_mesh_reflection_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_REFLECTION, ms); }
+int ngp_get_frame_mesh_reflection_hits(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_REFLECTION_HITS, out, n_pixels); }
+int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_REFLECTION_HITS, ms); }
+int ngp_get_frame_mesh_shadow(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_MESH_SHADOW, out, n_pixels); }
+int ngp_get_frame_mesh_shadow_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_MESH_SHADOW, ms); }
+int ngp_get_frame_ambient_change(ngp_ctx* ctx, float* out, size_t n_pixels) { return read_record(ctx, PASS_AMBIENT_CHANGE, out, n_pixels); }
+int ngp_get_frame_ambient_change_ms(ngp_ctx* ctx, float* ms) { return read_ms(ctx, PASS_AMBIENT_CHANGE, ms); }
+int ngp_get_frame_mesh_ids(ngp_ctx* ctx, int32_t* out, size_t n_pixels) { return read_record(ctx, PASS_MESH_IDS, out, n_pixels); }
 
 int ngp_get_render_stats(ngp_ctx* ctx, ngp_render_stats* out) {
 	return guarded(ctx, [&] {

@@ -148,6 +148,16 @@ class MeshReflectionDesc(C.Structure):
     _fields_ = [("strength", C.c_float), ("min_transmittance", C.c_float), ("t_min", C.c_float)]
 
 
+# the frame options with a descriptor, by the name in ngp_set_<name> / ngp_get_<name>: the struct and what True takes, field by field
+FRAME_OPTIONS = {
+    "sun_nerf_shadow": (IrradianceSunNerfDesc, dict(min_transmittance=0.01, t_min=0.0)),
+    "mesh_shadow_on_nerf": (MeshShadowOnNerfDesc, dict(strength=0.5, bias=1e-2)),
+    "ambient_change_on_nerf": (AmbientChangeDesc, dict(min_irradiance=1e-3, max_gain=4.0)),
+    "mesh_reflection": (MeshReflectionDesc, dict(strength=1.0, min_transmittance=0.01, t_min=0.0)),
+    "sun_disk": (SunDiskDesc, dict(angular_radius=SUN_ANGULAR_RADIUS, n_rays=16)),
+}
+
+
 SUN_RADIANCE = tuple(float(np.float32(c) / np.float32(255.0) * np.float32(4.0)) for c in (255.0, 225.0, 195.0))  # the frames' suncol
 
 
@@ -981,17 +991,44 @@ class Context:
         self._check(fn(self.h, C.byref(ms)))
         return ms.value
 
+    @staticmethod
+    def _option_desc(name, value, check=None):
+        """the descriptor of the frame option `name` (FRAME_OPTIONS) from what its setter takes: None for None and False, the defaults for
+        True, a dict over the defaults; check (optional) sees the values before they are converted"""
+        struct, defaults = FRAME_OPTIONS[name]
+        if value is None or value is False:
+            return None
+        if value is True:
+            value = {}
+        if not isinstance(value, dict) or set(value) - set(defaults):
+            keys = list(defaults)
+            raise ValueError("%s: True, False, None or a dict of %s and %s" % (name, ", ".join(keys[:-1]), keys[-1]))
+        values = dict(defaults, **value)
+        if check is not None:
+            check(values)
+        d = struct()
+        for k, v in values.items():
+            setattr(d, k, type(defaults[k])(v))
+        return d
+
+    def _set_option(self, name, d):
+        self._check(getattr(self.L, "ngp_set_" + name)(self.h, C.byref(d) if d is not None else None))
+
+    def _option_dict(self, name):
+        """None while the frame option `name` is off, else its descriptor as set, a dict in the fields' order"""
+        struct, defaults = FRAME_OPTIONS[name]
+        d, on = struct(), C.c_int(0)
+        self._check(getattr(self.L, "ngp_get_" + name)(self.h, C.byref(d), C.byref(on)))
+        return {k: getattr(d, k) for k in defaults} if on.value else None
+
     def set_sun_nerf_shadow(self, shadow=True):
         """the NeRF's density in front of the frames' sun on mesh pixels (Geometry frames with meshes and a model): None or False switches it
         off (the default), True takes min_transmittance 0.01 and t_min 0, a dict or a tuple gives min_transmittance and t_min"""
-        ns = self._sun_nerf_desc(shadow)
-        self._check(self.L.ngp_set_sun_nerf_shadow(self.h, C.byref(ns) if ns is not None else None))
+        self._set_option("sun_nerf_shadow", self._sun_nerf_desc(shadow))
 
     def sun_nerf_shadow(self):
         """None while the option is off, else dict(min_transmittance=, t_min=) as set"""
-        ns, on = IrradianceSunNerfDesc(), C.c_int(0)
-        self._check(self.L.ngp_get_sun_nerf_shadow(self.h, C.byref(ns), C.byref(on)))
-        return dict(min_transmittance=ns.min_transmittance, t_min=ns.t_min) if on.value else None
+        return self._option_dict("sun_nerf_shadow")
 
     def frame_sun_shadow(self, n_pixels):
         """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (q xyz, alpha_s) of its shadow ray through the
@@ -1005,22 +1042,11 @@ class Context:
     def set_mesh_shadow_on_nerf(self, shadow=True):
         """the meshes in front of the sun on the NeRF (Geometry frames with meshes and a model, the four shade modes): None or False switches
         it off (the default), True takes strength 0.5 and bias 1e-2, a dict gives strength and bias"""
-        if shadow is None or shadow is False:
-            self._check(self.L.ngp_set_mesh_shadow_on_nerf(self.h, None))
-            return
-        if shadow is True:
-            shadow = {}
-        if not isinstance(shadow, dict) or set(shadow) - {"strength", "bias"}:
-            raise ValueError("mesh_shadow_on_nerf: True, False, None or a dict of strength and bias")
-        d = MeshShadowOnNerfDesc()
-        d.strength, d.bias = float(shadow.get("strength", 0.5)), float(shadow.get("bias", 1e-2))
-        self._check(self.L.ngp_set_mesh_shadow_on_nerf(self.h, C.byref(d)))
+        self._set_option("mesh_shadow_on_nerf", self._option_desc("mesh_shadow_on_nerf", shadow))
 
     def mesh_shadow_on_nerf(self):
         """None while the option is off, else dict(strength=, bias=) as set"""
-        d, on = MeshShadowOnNerfDesc(), C.c_int(0)
-        self._check(self.L.ngp_get_mesh_shadow_on_nerf(self.h, C.byref(d), C.byref(on)))
-        return dict(strength=d.strength, bias=d.bias) if on.value else None
+        return self._option_dict("mesh_shadow_on_nerf")
 
     def frame_mesh_shadow(self, n_pixels):
         """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (p xyz, 2 blocked / 1 open) of the NeRF's
@@ -1032,31 +1058,15 @@ class Context:
         return self._frame_pass_ms(self.L.ngp_get_frame_mesh_shadow_ms)
 
     # ---------------------------------------------------------------- the meshes' change of the ambient light on the NeRF (include/ngp_hip.h, "ambient")
-    @staticmethod
-    def _ambient_desc(change):
-        if change is True:
-            change = {}
-        if not isinstance(change, dict) or set(change) - {"min_irradiance", "max_gain"}:
-            raise ValueError("ambient_change_on_nerf: True, False, None or a dict of min_irradiance and max_gain")
-        d = AmbientChangeDesc()
-        d.min_irradiance, d.max_gain = float(change.get("min_irradiance", 1e-3)), float(change.get("max_gain", 4.0))
-        return d
-
     def set_ambient_change_on_nerf(self, change=True):
         """scale every NeRF pixel that owns a surface point by E_after / E_before there (Geometry frames with meshes and a model, the four
         shade modes; needs the irradiance volume and the reference volume): None or False switches it off (the default), True takes
         min_irradiance 1e-3 and max_gain 4, a dict gives them"""
-        if change is None or change is False:
-            self._check(self.L.ngp_set_ambient_change_on_nerf(self.h, None))
-            return
-        d = self._ambient_desc(change)
-        self._check(self.L.ngp_set_ambient_change_on_nerf(self.h, C.byref(d)))
+        self._set_option("ambient_change_on_nerf", self._option_desc("ambient_change_on_nerf", change))
 
     def ambient_change_on_nerf(self):
         """None while the option is off, else dict(min_irradiance=, max_gain=) as set"""
-        d, on = AmbientChangeDesc(), C.c_int(0)
-        self._check(self.L.ngp_get_ambient_change_on_nerf(self.h, C.byref(d), C.byref(on)))
-        return dict(min_irradiance=d.min_irradiance, max_gain=d.max_gain) if on.value else None
+        return self._option_dict("ambient_change_on_nerf")
 
     def compute_reference_irradiance_volume(self, resolution, aabb, n_u=32, n_v=32, min_transmittance=0.01):
         """trace the reference volume, the scene before the meshes: V_0 over the lattice with the meshes occluding nothing, no bounces, no
@@ -1089,7 +1099,7 @@ class Context:
         n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         if p.shape != n.shape:
             raise ValueError("positions and normals: n x 3 each")
-        d = self._ambient_desc(dict(min_irradiance=min_irradiance, max_gain=max_gain))
+        d = self._option_desc("ambient_change_on_nerf", dict(min_irradiance=min_irradiance, max_gain=max_gain))
         out = np.zeros((p.shape[0], 4), np.float32)
         self._check(self.L.ngp_irradiance_volume_ratio(self.h, p.shape[0], _p(p), _p(n), C.byref(d), _p(out)))
         return out
@@ -1107,22 +1117,11 @@ class Context:
     def set_mesh_reflection(self, reflection=True):
         """one reflection ray a mesh pixel through the NeRF (Geometry frames with meshes and a model, the four shade modes): None or False
         switches it off (the default), True takes strength 1, min_transmittance 0.01 and t_min 0, a dict gives them"""
-        if reflection is None or reflection is False:
-            self._check(self.L.ngp_set_mesh_reflection(self.h, None))
-            return
-        if reflection is True:
-            reflection = {}
-        if not isinstance(reflection, dict) or set(reflection) - {"strength", "min_transmittance", "t_min"}:
-            raise ValueError("mesh_reflection: True, False, None or a dict of strength, min_transmittance and t_min")
-        d = MeshReflectionDesc()
-        d.strength, d.min_transmittance, d.t_min = float(reflection.get("strength", 1.0)), float(reflection.get("min_transmittance", 0.01)), float(reflection.get("t_min", 0.0))
-        self._check(self.L.ngp_set_mesh_reflection(self.h, C.byref(d)))
+        self._set_option("mesh_reflection", self._option_desc("mesh_reflection", reflection))
 
     def mesh_reflection(self):
         """None while the option is off, else dict(strength=, min_transmittance=, t_min=) as set"""
-        d, on = MeshReflectionDesc(), C.c_int(0)
-        self._check(self.L.ngp_get_mesh_reflection(self.h, C.byref(d), C.byref(on)))
-        return dict(strength=d.strength, min_transmittance=d.min_transmittance, t_min=d.t_min) if on.value else None
+        return self._option_dict("mesh_reflection")
 
     def frame_mesh_reflection(self, n_pixels):
         """(n_pixels, 12): per pixel of the last frame's last sample, in the frame's pixel order: q (3), t_hit, r (3) before the tracer
@@ -1158,25 +1157,15 @@ class Context:
         """the sun's disk (Geometry frames with meshes): K shadow rays a pixel over the disk against all meshes, on mesh pixels and, with
         set_mesh_shadow_on_nerf, on NeRF pixels. None or False switches it off (the default), True takes the real sun's 0.00465 rad and 16
         rays, a dict gives angular_radius and n_rays (1, 2, 4, 8 or 16)"""
-        if disk is None or disk is False:
-            self._check(self.L.ngp_set_sun_disk(self.h, None))
-            return
-        if disk is True:
-            disk = {}
-        if not isinstance(disk, dict) or set(disk) - {"angular_radius", "n_rays"}:
-            raise ValueError("sun_disk: True, False, None or a dict of angular_radius and n_rays")
-        n_rays = disk.get("n_rays", 16)
-        if int(n_rays) != n_rays or not 0 <= n_rays < 2 ** 32:
-            raise ValueError("sun_disk: n_rays must be 1, 2, 4, 8 or 16")
-        d = SunDiskDesc()
-        d.angular_radius, d.n_rays = float(disk.get("angular_radius", SUN_ANGULAR_RADIUS)), int(n_rays)
-        self._check(self.L.ngp_set_sun_disk(self.h, C.byref(d)))
+        def whole_n_rays(values):  # (before int() would round it or the struct's uint32 wrap it)
+            if int(values["n_rays"]) != values["n_rays"] or not 0 <= values["n_rays"] < 2 ** 32:
+                raise ValueError("sun_disk: n_rays must be 1, 2, 4, 8 or 16")
+
+        self._set_option("sun_disk", self._option_desc("sun_disk", disk, whole_n_rays))
 
     def sun_disk(self):
         """None while the option is off, else dict(angular_radius=, n_rays=) as set"""
-        d, on = SunDiskDesc(), C.c_int(0)
-        self._check(self.L.ngp_get_sun_disk(self.h, C.byref(d), C.byref(on)))
-        return dict(angular_radius=d.angular_radius, n_rays=d.n_rays) if on.value else None
+        return self._option_dict("sun_disk")
 
     def sun_disk_directions(self, sun_dir, spp_index=0):
         """(n_rays, 3) float32: the shadow directions the frame's sample of spp index `spp_index` uses under sun_dir (host arithmetic)"""
@@ -1191,15 +1180,11 @@ class Context:
     def frame_sun_disk(self, n_pixels):
         """(n_pixels, 4): per pixel of the last frame's last sample, in the frame's pixel order, (q xyz, 1 + the blocked rays' count) of the
         mesh pixel's disk; zeros where the pixel owns none. On a multi-device context the primary's tile-packed share."""
-        out = np.zeros((int(n_pixels), 4), np.float32)
-        self._check(self.L.ngp_get_frame_sun_disk(self.h, _p(out), int(n_pixels)))
-        return out
+        return self._frame_record(self.L.ngp_get_frame_sun_disk, n_pixels, 4)
 
     def frame_sun_disk_ms(self):
         """device time of the sun disk kernel in the last frame's last sample, ms; refused after a frame without it"""
-        ms = C.c_float(0)
-        self._check(self.L.ngp_get_frame_sun_disk_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._frame_pass_ms(self.L.ngp_get_frame_sun_disk_ms)
 
     def irradiance_sh_bounce(self, positions, albedo, n_u=32, n_v=32, alpha=None, visible=False, occlude_by_meshes=True, return_rays=False):
         """one bounce pass at the probes at `positions` from the held volume (visible: through its visible lookup): the records R (n, 28) the pass

@@ -211,6 +211,61 @@ def test_no_state_survives_a_frame(ctx, first, native, scene_unit):
         fresh.close()
 
 
+IDS_REFUSAL = "ran without mesh materials"
+# the passes' time getters, by the option that runs the pass; after a frame without the pass the disk's refuses like its record, the others give 0
+MS_GETTERS = (("frame_sun_shadow_ms", "sun"), ("frame_sun_disk_ms", "disk"), ("frame_mesh_reflection_ms", "refl"), ("frame_mesh_reflection_hits_ms", "hits"),
+              ("frame_mesh_shadow_ms", "shadow"), ("frame_ambient_change_ms", "ambient"))
+
+
+def test_buffers_grow_whichever_pass_comes_first(first, native, scene_unit):
+    """a fresh context whose first frames each need a shared buffer through the pass that never allocated it first elsewhere: the sun's disk
+    alone (the G-buffer and the shadow list with no sun-shadow record), the ambient change alone (the NeRF scratch with no mesh-shadow
+    record), materials alone (the id plane; every mesh owns a copy of the context's material, which changes no byte), then everything on at
+    120 x 88 and at 60 x 44. After each of the first three frames exactly the getters of the passes that did not run refuse, each with its
+    own text; the last frame's colour, depth and six records are the long-lived context's all-on frame as bytes, and its id plane is the
+    third frame's and has a mesh wherever a pixel owns a disk."""
+    c = _context(native, scene_unit)
+
+    def materials(on):
+        for i in range(c.n_meshes()):
+            c.set_mesh_material(i, {} if on else None)
+
+    def check_refusals(ran, ids):
+        for (name, option, floats, refusal), rec in zip(GETTERS, _records(c, W * H).values()):
+            if option in ran:
+                assert not isinstance(rec, str) and rec.shape == (W * H, floats), (ran, name)
+            else:
+                assert isinstance(rec, str) and refusal in rec, (ran, name, rec)
+        for name, option in MS_GETTERS:
+            if option in ran:
+                assert getattr(c, name)() >= 0.0, (ran, name)
+            elif option == "disk":
+                with pytest.raises(RuntimeError, match="ran no sun disk pass"):
+                    getattr(c, name)()
+            else:
+                assert getattr(c, name)() == 0.0, (ran, name)
+        if ids:
+            return c.frame_mesh_ids(W * H)
+        with pytest.raises(RuntimeError, match=IDS_REFUSAL):
+            c.frame_mesh_ids(W * H)
+
+    try:
+        for ran in (frozenset(("disk",)), frozenset(("ambient",))):
+            assert _equal(_shot(c, native, ran), first[ran]), fo.name(ran)
+            check_refusals(ran, False)
+        materials(True)
+        assert _equal(_shot(c, native, frozenset()), first[frozenset()])
+        ids = check_refusals(frozenset(), True)
+        _shot(c, native, fo.ALL, *fo.WALK_SIZES[1])
+        assert c.frame_mesh_ids(fo.WALK_SIZES[1][0] * fo.WALK_SIZES[1][1]).shape == (fo.WALK_SIZES[1][0] * fo.WALK_SIZES[1][1],)
+        assert _equal(_shot(c, native, fo.ALL), first[fo.ALL])
+        assert c.frame_mesh_ids(W * H).tobytes() == ids.tobytes()
+        owns_disk = first[fo.ALL]["records"]["frame_sun_disk"][:, 3] != 0
+        assert owns_disk.sum() > 500 and np.all(ids[owns_disk] >= 0) and np.all(ids >= -1) and np.all(ids < c.n_meshes())
+    finally:
+        c.close()
+
+
 # ------------------------------------------------------------------------------------------- against the composed reference
 def _trace(c, o, d, t, min_transmittance):
     return c.trace_nerf_rays(np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32), np.ascontiguousarray(t, np.float32), min_transmittance)[0]
