@@ -258,6 +258,11 @@ NGP_API int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out);
  * "_unit_plain_prof2", or "wide" (Frequency / Identity encodings). "" before the first frame and after a frame of meshes alone. The string
  * is static. Recorded on the host where the launch is chosen; tests use it to assert that a frame exercised the kernel they mean. */
 NGP_API const char* ngp_last_render_kernel(ngp_ctx* ctx);
+/* How many 8 x 8 camera tiles of the last ngp_render / ngp_render_device (summed over its samples per pixel; the primary's share) the
+ * unit render kernels dropped right after ray setup because no ray of the tile can meet an occupied cell (csrc/tile_probe.h). Such a tile
+ * shows the empty pixel it would have shown anyway: frames and ngp_render_stats do not depend on the cull. 0 after any other kernel and in
+ * a library built without the cull. Synchronises the stream. */
+NGP_API int ngp_get_culled_tiles(ngp_ctx* ctx, uint64_t* out);
 
 /* Scheduling of the persistent render kernel: knobs[0..n) = refill_min [16,64], skip_steps [1,64], go_min [1,64], max_stall [0,64],
  * samples a ray may emit per round while most of a wave's ray slots are live [1,8], at most once fewer are [1,8] (the reference's n_steps

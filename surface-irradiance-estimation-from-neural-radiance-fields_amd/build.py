@@ -22,6 +22,7 @@ LIB_CELLSTATS = os.path.join(HERE, "libngp_hip_cellstats.so")  # -DNGP_EXPERIMEN
 LIB_SUN_ANY_HIT = os.path.join(HERE, "libngp_hip_sun_any_hit.so")  # -DNGP_EXPERIMENT_SUN_ANY_HIT: the sun pass's shadow query as an unsorted traversal that ends at the first hit (tools/irradiance_bounce_rate.py --sun); experiment only
 LIB_NOCACHE = os.path.join(HERE, "libngp_hip_nocache.so")  # -DNGP_NO_CELL_CACHE: no render kernel keeps coarse hash-grid cells in LDS (A/B runs, tests/test_cell_cache_gpu.py)
 LIB_ROUND_V1 = os.path.join(HERE, "libngp_hip_round_v1.so")  # -DNGP_ROUND_V1: the render round outside the network as it was: Morton-ordered occupancy summaries, no block-linear block words, a finished ray normalised in the composite (tests/test_round_gpu.py, A/B runs)
+LIB_NOCULL = os.path.join(HERE, "libngp_hip_nocull.so")  # -DNGP_NO_TILE_CULL: the unit render kernels march every camera tile, as before the tile cull (A/B runs, tests/test_tile_cull_gpu.py)
 LIB_NETSEC_V1 = os.path.join(HERE, "libngp_hip_netsec_v1.so")  # -DNGP_NETSEC_V1: the render passes' network section as it was before it was trimmed (tests/test_netsec_gpu.py, A/B runs)
 
 
@@ -36,7 +37,7 @@ def needs_build(lib=LIB):
     return os.path.getmtime(inc) > t
 
 
-def build(force=False, verbose=False, legacy=False, nocache=False, cellstats=False, netsec_v1=False, round_v1=False, sun_any_hit=False):
+def build(force=False, verbose=False, legacy=False, nocache=False, cellstats=False, netsec_v1=False, round_v1=False, sun_any_hit=False, nocull=False):
     """The shipped library sums the grid encoding's corners as tvec-era tiny-cuda-nn does (`fma((T)weight, val, result)`),
     bit for bit the oracle's "fma" mode. legacy=True builds the variant with the older published sequence
     (`result[f] += (T)(weight * val[f])`, oracle mode "legacy"): tiny-cuda-nn is un-pinned in the reference, so both are
@@ -47,10 +48,11 @@ def build(force=False, verbose=False, legacy=False, nocache=False, cellstats=Fal
     order, the bitfield's block words read from the bitfield itself and a ray that ends by transmittance normalised inside the composite
     (csrc/occ_index.h, csrc/nerf_kernels.hip), as before the round outside the network was trimmed: the same bytes again. sun_any_hit=True
     builds it with the sun pass's shadow query as an any-hit traversal (csrc/mesh_kernels.hip, any_hit) instead of the closest hit: the same
-    records, for timing the early exit alone."""
-    if legacy + nocache + cellstats + netsec_v1 + round_v1 + sun_any_hit > 1:
+    records, for timing the early exit alone. nocull=True builds it with the unit render kernels' tile cull compiled off (csrc/nerf_kernels.hip, tile_cull): every camera
+    tile marches, as before the cull; frames and counters are the same bytes."""
+    if legacy + nocache + cellstats + netsec_v1 + round_v1 + sun_any_hit + nocull > 1:
         raise ValueError("one variant at a time")
-    lib = LIB_LEGACY if legacy else LIB_NOCACHE if nocache else LIB_CELLSTATS if cellstats else LIB_NETSEC_V1 if netsec_v1 else LIB_ROUND_V1 if round_v1 else LIB_SUN_ANY_HIT if sun_any_hit else LIB
+    lib = LIB_LEGACY if legacy else LIB_NOCACHE if nocache else LIB_CELLSTATS if cellstats else LIB_NETSEC_V1 if netsec_v1 else LIB_ROUND_V1 if round_v1 else LIB_SUN_ANY_HIT if sun_any_hit else LIB_NOCULL if nocull else LIB
     if not force and not needs_build(lib):
         return lib
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
@@ -60,7 +62,7 @@ def build(force=False, verbose=False, legacy=False, nocache=False, cellstats=Fal
     # link to a private name and rename: another process (a rank of the same job, a test worker) may be dlopen-ing the
     # library at this moment and must see either the old file or the complete new one
     tmp = "%s.%d.tmp" % (lib, os.getpid())
-    cmd = [hipcc()] + FLAGS + (["-DNGP_TCNN_LEGACY_ENCODE"] if legacy else []) + (["-DNGP_NO_CELL_CACHE"] if nocache else []) + (["-DNGP_EXPERIMENT_CELL_CACHE_STATS"] if cellstats else []) + (["-DNGP_NETSEC_V1"] if netsec_v1 else []) + (["-DNGP_ROUND_V1"] if round_v1 else []) + (["-DNGP_EXPERIMENT_SUN_ANY_HIT"] if sun_any_hit else []) + os.environ.get("NGP_BUILD_DEFINES", "").split() + ["-o", tmp] + srcs + ["-lz"]  # NGP_BUILD_DEFINES: experiments only
+    cmd = [hipcc()] + FLAGS + (["-DNGP_TCNN_LEGACY_ENCODE"] if legacy else []) + (["-DNGP_NO_CELL_CACHE"] if nocache else []) + (["-DNGP_EXPERIMENT_CELL_CACHE_STATS"] if cellstats else []) + (["-DNGP_NETSEC_V1"] if netsec_v1 else []) + (["-DNGP_ROUND_V1"] if round_v1 else []) + (["-DNGP_EXPERIMENT_SUN_ANY_HIT"] if sun_any_hit else []) + (["-DNGP_NO_TILE_CULL"] if nocull else []) + os.environ.get("NGP_BUILD_DEFINES", "").split() + ["-o", tmp] + srcs + ["-lz"]  # NGP_BUILD_DEFINES: experiments only
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -45,11 +45,20 @@ constexpr bool CELL_CACHE_BUILT = false;
 #else
 constexpr bool CELL_CACHE_BUILT = true;
 #endif
+// tile_cull: a wave that has taken a whole 8 x 8 tile asks, right after ray setup, whether any of its rays can meet an occupied cell
+// (tile_probe.h: ~128 points on the tile's central ray against a dilated occupancy table) and gives the tile back if none can: such rays
+// emit no sample, so all they do to the frame is the empty pixel written at setup. The unit kernels only (one cascade: the tables are
+// cascade 0's). -DNGP_NO_TILE_CULL (libngp_hip_nocull.so): off everywhere, for the A/B and the equality test
+#if defined(NGP_NO_TILE_CULL)
+constexpr bool TILE_CULL_BUILT = false;
+#else
+constexpr bool TILE_CULL_BUILT = true;
+#endif
 struct FusedGeneric {
-	static constexpr bool probe = false, unit = false, outside = true, plain = false, normals = false, cell_cache = false;
+	static constexpr bool probe = false, unit = false, outside = true, plain = false, normals = false, cell_cache = false, tile_cull = false;
 	static constexpr int prof = 0, mips = (int)NERF_CASCADES, rgb_mid = 1;
 };
-struct FusedUnit : FusedGeneric { static constexpr bool unit = true, cell_cache = CELL_CACHE_BUILT; static constexpr int mips = 1; };
+struct FusedUnit : FusedGeneric { static constexpr bool unit = true, cell_cache = CELL_CACHE_BUILT, tile_cull = TILE_CULL_BUILT; static constexpr int mips = 1; };
 struct FusedUnitPlain : FusedUnit { static constexpr bool plain = true; };
 struct FusedC5 : FusedGeneric { static constexpr bool outside = false; static constexpr int mips = 4; };
 struct FusedC5Plain : FusedC5 { static constexpr bool plain = true; };
@@ -67,6 +76,7 @@ template <class V>
 NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const FrameParams& F, const ProbeParams& P) {
 	constexpr bool PROBE = V::probe, UNIT = V::unit, OUTSIDE = V::outside, PLAIN = V::plain, NORMALS = V::normals, CELL_CACHE = V::cell_cache;
 	constexpr int PROF = V::prof, MIPS = V::mips, RGB_MID = V::rgb_mid;
+	constexpr bool TILE_CULL = V::tile_cull && UNIT && !PROBE;
 	const uint32_t max_cascade = UNIT ? 0u : M.max_cascade;
 	const float cone_angle = UNIT ? 0.0f : M.cone_angle;
 	const Stepping stepping = make_stepping(cone_angle); // (wave-uniform: the exponential stepping's constants, formed once)
@@ -160,6 +170,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 	uint32_t qsel = (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u; // HW_REG_XCC_ID[3:0]: the XCD this workgroup runs on
 	int stall = 0;
 	uint32_t n_alive_init = 0, n_hit = 0, n_samples = 0; // wave-uniform (ballot counts)
+	uint32_t n_culled = 0; // wave-uniform: tiles the probe gave back (tile_cull)
 	unsigned long long p_skip[3] = {0, 0, 0};
 	unsigned long long pt[4] = {0, 0, 0, 0}, p_iters = 0, p_passes = 0, p_rounds = 0, p_lane_steps = 0, t0 = 0, t1 = 0;
 
@@ -264,7 +275,33 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 				const uint32_t tile_local = strip >> 2, s4 = strip & 3u, i16 = r & 15u;
 				const uint32_t slot = ((s4 >> 1) * 4u + (i16 >> 2)) * 8u + (s4 & 1u) * 4u + (i16 & 3u);
 				const uint32_t tile = F.shard_index + F.shard_count * tile_local;
-				bool fresh = false;
+				bool fresh = false, setup = false; // setup: the lane took a pixel of the frame (its setup writes follow the tile probe)
+				// what a fresh pixel writes at ray setup. A kernel with the tile cull runs it behind the tile probe (whose table reads would
+				// otherwise wait for these stores), every other kernel right after init_ray, as ever.
+				auto setup_writes = [&]() {
+					if (PLAIN || !F.envmap) {
+						if (F.direct) { // CudaRenderBufferView::clear + the untouched pixel's trip through accumulate / tonemap
+							F.frame_buffer[ray.out] = empty_pixel;
+							F.depth_buffer[ray.out] = MAX_DEPTH;
+						} else if (F.depth_buffer[ray.out] < 0.01f) { // src/testbed_nerf.cu:1490-1493
+							F.depth_buffer[ray.out] = MAX_DEPTH;
+						}
+					} else { // frame_buffer[idx] = read_envmap(envmap, ray.d) for every valid ray (src/testbed_nerf.cu:1526-1528)
+						const bool valid = ray.d.x != 0.0f || ray.d.y != 0.0f || ray.d.z != 0.0f;
+						float env[4] = {0.f, 0.f, 0.f, 0.f};
+						if (valid) {
+							float d3[3] = {ray.d.x, ray.d.y, ray.d.z};
+							read_envmap(F.envmap, F.env_w, F.env_h, d3, env);
+						}
+						if (F.direct) {
+							F.frame_buffer[ray.out] = valid ? tonemap_pixel(F, bg_linear, env[0], env[1], env[2], env[3]) : empty_pixel;
+							F.depth_buffer[ray.out] = MAX_DEPTH;
+						} else {
+							if (valid) F.frame_buffer[ray.out] = make_float4(env[0], env[1], env[2], env[3]);
+							if (F.depth_buffer[ray.out] < 0.01f) F.depth_buffer[ray.out] = MAX_DEPTH;
+						}
+					}
+				};
 				if (PROBE) {
 					uint32_t q = tile * 64u + slot;
 					if (take && q < P.n_rays) {
@@ -277,35 +314,61 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 					if (x < (uint32_t)C.width && y < (uint32_t)C.height) {
 						init_ray<PLAIN>(M, C, x, y, ray);
 						if (F.packed) ray.out = tile_local * 64u + slot;
-						if (PLAIN || !F.envmap) {
-							if (F.direct) { // CudaRenderBufferView::clear + the untouched pixel's trip through accumulate / tonemap
-								F.frame_buffer[ray.out] = empty_pixel;
-								F.depth_buffer[ray.out] = MAX_DEPTH;
-							} else if (F.depth_buffer[ray.out] < 0.01f) { // src/testbed_nerf.cu:1490-1493
-								F.depth_buffer[ray.out] = MAX_DEPTH;
-							}
-						} else { // frame_buffer[idx] = read_envmap(envmap, ray.d) for every valid ray (src/testbed_nerf.cu:1526-1528)
-							const bool valid = ray.d.x != 0.0f || ray.d.y != 0.0f || ray.d.z != 0.0f;
-							float env[4] = {0.f, 0.f, 0.f, 0.f};
-							if (valid) {
-								float d3[3] = {ray.d.x, ray.d.y, ray.d.z};
-								read_envmap(F.envmap, F.env_w, F.env_h, d3, env);
-							}
-							if (F.direct) {
-								F.frame_buffer[ray.out] = valid ? tonemap_pixel(F, bg_linear, env[0], env[1], env[2], env[3]) : empty_pixel;
-								F.depth_buffer[ray.out] = MAX_DEPTH;
-							} else {
-								if (valid) F.frame_buffer[ray.out] = make_float4(env[0], env[1], env[2], env[3]);
-								if (F.depth_buffer[ray.out] < 0.01f) F.depth_buffer[ray.out] = MAX_DEPTH;
-							}
+						setup = true;
+						if (!TILE_CULL) {
+							setup_writes();
+							if (ray.alive) ray.t = advance_n_steps(ray.t, stepping, ld_random_val_dim0(C.spp, ray.idx * 786433u)); // :355
 						}
-						if (ray.alive) {
-							ray.t = advance_n_steps(ray.t, stepping, ld_random_val_dim0(C.spp, ray.idx * 786433u)); // :355
-							fresh = true;
+						fresh = ray.alive;
+					}
+				}
+				bool empty_tile = false;
+				if (TILE_CULL && got == 4u && n_dead == 64 && (first & 3u) == 0u) {
+					// ---- the wave holds one whole tile (lane = strip-major pixel) and nothing else: the tile probe (tile_probe.h, step for step
+					// tile_probe_host; votes instead of reductions, and its table reads go out ahead of the setup writes below, which a load
+					// would otherwise wait for). A tile that cannot emit a sample leaves nothing but those writes behind.
+					float tn = 0.f, tf = 0.f, Tn = 0.f, Tf = 0.f;
+					const bool in = fresh && tile_probe_ray_range(ray.o.x, ray.o.y, ray.o.z, ray.d.x, ray.d.y, ray.d.z, ray.t, tn, tf, Tn, Tf);
+					const unsigned long long in_mask = __ballot(in);
+					empty_tile = in_mask == 0ull;
+					if ((in_mask >> 15) & 1ull) { // lane 15: pixel (3, 3) of the tile, the axis
+						auto lane15 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 15)); };
+						const float ax = lane15(ray.o.x), ay = lane15(ray.o.y), az = lane15(ray.o.z), adx = lane15(ray.d.x), ady = lane15(ray.d.y), adz = lane15(ray.d.z);
+						Tn = lane15(Tn);
+						Tf = lane15(Tf);
+						float D = 1e30f; // a ray that crosses the cube where the axis ray is outside the padded one: no radius covers it
+						if (!in) D = 0.f;
+						else if (tn >= Tn && tf <= Tf) D = probe_max(tile_probe_dev_at(ray.o.x, ray.o.y, ray.o.z, ray.d.x, ray.d.y, ray.d.z, ax, ay, az, adx, ady, adz, Tn),
+						                                             tile_probe_dev_at(ray.o.x, ray.o.y, ray.o.z, ray.d.x, ray.d.y, ray.d.z, ax, ay, az, adx, ady, adz, Tf));
+						// tile_probe_plan of the largest D: r is monotone in D, so the rays vote
+						uint32_t n_mine = 0;
+						const uint32_t g_mine = tile_probe_plan(D, Tf - Tn, n_mine);
+						const uint32_t g = __any(g_mine == 0u) ? 0u : (__any(g_mine == 4u) ? 4u : 2u);
+						if (g != 0u) {
+							uint32_t n_g = 0; // (this ray's point count at the tile's granularity)
+							const float r64 = D + (Tf - Tn) * (0.5f / 64.0f) + TILE_PROBE_EPS;
+							n_g = r64 <= (float)g * TILE_PROBE_CELL ? 64u : 128u;
+							const uint32_t n_points = __any(n_g == 128u) ? 128u : 64u;
+							const uint32_t* near = M.coarse + COARSE_NEAR_OFFSET;
+							const float s = (Tf - Tn) / (float)n_points;
+							bool set = false;
+							for (uint32_t k = (uint32_t)lane; k < n_points; k += 64u) {
+								const float t = Tn + ((float)k + 0.5f) * s;
+								set = set || tile_probe_point_set(near, ax + adx * t, ay + ady * t, az + adz * t, g);
+							}
+							empty_tile = !__any(set);
 						}
 					}
 				}
+				if (TILE_CULL && setup) setup_writes();
+				if (empty_tile) {
+					ray.alive = false; // all 64 slots are free again; nothing was counted, nothing waits to be shaded
+					++n_culled;
+					if (PROF) { tr_info1 |= 16u << 24; tr_t[1] = stamp(); pt[0] += tr_t[1] - t0; trace_emit(1); }
+					continue; // straight back to the refill
+				}
 				if (fresh) {
+					if (TILE_CULL) ray.t = advance_n_steps(ray.t, stepping, ld_random_val_dim0(C.spp, ray.idx * 786433u)); // :355 (behind the probe, which wants the ray's start)
 					{ // K5c once per ray: the direction (and so its SH encoding) is constant along the ray
 						union { half_t h[16]; uint2 u[4]; } sh;
 						sh4_all((ray.d.x + 1.0f) * 0.5f, (ray.d.y + 1.0f) * 0.5f, (ray.d.z + 1.0f) * 0.5f, sh.h);
@@ -800,7 +863,7 @@ NGP_DEV void fused_body(const ModelParams& M, const CameraParams& C, const Frame
 		}
 	}
 #endif
-	finish_launch(F, lane, n_alive_init, n_hit, n_samples);
+	finish_launch<TILE_CULL>(F, lane, n_alive_init, n_hit, n_samples, n_culled);
 }
 
 // the camera kernels: name, waves per SIMD they are built for (= workgroups per CU: a workgroup has one wave on each SIMD), variant
@@ -1275,6 +1338,12 @@ __global__ void coarse16_occupancy_kernel(uint32_t* __restrict__ coarse) {
 	coarse[NERF_CASCADES * COARSE_WORDS_PER_MIP + w] = bits;
 }
 #endif
+// cascade 0's near-occupancy tables for the tile cull (tile_probe.h), behind everything else in `coarse`: one output word a thread
+__global__ void near_occupancy_kernel(const uint8_t* __restrict__ bitfield, uint32_t* __restrict__ coarse) {
+	const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+	if (w >= NEAR_WORDS) return;
+	coarse[COARSE_NEAR_OFFSET + w] = w < NEAR4_WORDS ? near_table_word(bitfield, 4u, w) : near_table_word(bitfield, 2u, w - NEAR4_WORDS);
+}
 
 __global__ void bitfield_max_pool_kernel(uint32_t n_elements, const uint8_t* __restrict__ prev_level, uint8_t* __restrict__ next_level) {
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1521,6 +1590,7 @@ void launch_coarse_occupancy(const uint8_t* bitfield, uint32_t* coarse, hipStrea
 	uint32_t n = NERF_CASCADES * COARSE_WORDS_PER_MIP;
 	hipLaunchKernelGGL(coarse_occupancy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, bitfield, coarse);
 	hipLaunchKernelGGL(coarse16_occupancy_kernel, dim3(1), dim3(128), 0, stream, coarse);
+	hipLaunchKernelGGL(near_occupancy_kernel, dim3((NEAR_WORDS + 255) / 256), dim3(256), 0, stream, bitfield, coarse);
 }
 // tile gather at the primary device of a multi-device context: pixel (x, y) lives in device (tile % n) 's block at
 // (tile / n) * 64 + slot -- the layout FrameParams::packed writes

@@ -554,7 +554,8 @@ struct ngp_ctx {
 	ngp::DevArray<float> d_depth;
 	ngp::DevArray<float4> d_accum;
 	ngp::DevArray<float4> d_rgba;
-	// a ring of per-call slots of 80 B: accumulators [alive, hit, samples], {tile queue, exited waves}, results [alive, hit, samples, device ticks], start stamp.
+	// a ring of per-call slots of 128 B, as 8-byte words: 0-2 accumulators [alive, hit, samples], 3 {tile queue, exited waves}, 4-7 results [alive, hit, samples, device ticks],
+	// 8 start stamp, 9-12 the eight XCD queues, 13 / 14 culled tiles: accumulator and result (results[RESULT_CULL_SUM], results[RESULT_CULLED]; ngp_get_culled_tiles), 15 free.
 	// Zeroed once; every launch's last wave leaves its slot's first four words zero again (nerf_kernels.hip fused_body)
 	static constexpr int HISTORY = ngp::FRAME_HISTORY;
 	static constexpr size_t SLOT_BYTES = 128;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bvh4_build.h"
+#include "tile_probe.h"
 
 namespace ngp {
 
@@ -96,7 +97,8 @@ struct ModelParams {
 	const uint4* wfrags;     // [N_FRAGS][64] x 8 fp16, MFMA A fragments in lane order
 	const uint8_t* bitfield; // 8 x 128^3 bits
 	const uint32_t* coarse;  // derived from the bitfield (occ_index.h): 8 x 32^3 bits, one per 4x4x4 block of cells that holds an occupied cell; 8 x 8^3 bits,
-	                         // one per 16^3 block; then (COARSE_SUMMARY_WORDS on, not with -DNGP_ROUND_V1) the bitfield's 8-byte block words in block-linear order
+	                         // one per 16^3 block; then (COARSE_SUMMARY_WORDS on, not with -DNGP_ROUND_V1) the bitfield's 8-byte block words in block-linear order;
+	                         // then (COARSE_NEAR_OFFSET on) cascade 0's near-occupancy tables for the tile cull (tile_probe.h)
 	LevelInfo levels[N_LEVELS];
 	float aabb_min[3], aabb_diag[3];
 	float raabb_min[3], raabb_max[3];
@@ -115,10 +117,11 @@ struct ModelParams {
 constexpr uint32_t COARSE_WORDS_PER_MIP = 32 * 32 * 32 / 32;
 constexpr uint32_t COARSE_SUMMARY_WORDS = NERF_CASCADES * COARSE_WORDS_PER_MIP + NERF_CASCADES * 16; // both summaries (an even count: what follows is 8-byte aligned)
 #ifdef NGP_ROUND_V1
-constexpr uint32_t COARSE_TOTAL_WORDS = COARSE_SUMMARY_WORDS;
+constexpr uint32_t COARSE_NEAR_OFFSET = COARSE_SUMMARY_WORDS;
 #else
-constexpr uint32_t COARSE_TOTAL_WORDS = COARSE_SUMMARY_WORDS + NERF_CASCADES * (NERF_GRID_N_CELLS / 64) * 2; // + 2 MB of block words
+constexpr uint32_t COARSE_NEAR_OFFSET = COARSE_SUMMARY_WORDS + NERF_CASCADES * (NERF_GRID_N_CELLS / 64) * 2; // + 2 MB of block words
 #endif
+constexpr uint32_t COARSE_TOTAL_WORDS = COARSE_NEAR_OFFSET + NEAR_WORDS; // + cascade 0's near-occupancy tables, near4 then near2 (tile_probe.h)
 
 struct CameraParams {
 	float m[12]; // column-major 4x3
@@ -146,6 +149,7 @@ struct FrameLayout {
 	int32_t packed;
 };
 
+constexpr int RESULT_CULL_SUM = 9, RESULT_CULLED = 10; // FrameParams::results of a camera frame: words 13 and 14 of the call's 16-word slot, behind the XCD queues (finish_launch)
 struct FrameParams {
 	float4* frame_buffer;
 	float* depth_buffer;

@@ -840,6 +840,21 @@ int ngp_set_schedule(ngp_ctx* ctx, const int32_t* knobs, int n) {
 
 const char* ngp_last_render_kernel(ngp_ctx* ctx) { return ctx ? ctx->last_render_kernel : ""; }
 
+int ngp_get_culled_tiles(ngp_ctx* ctx, uint64_t* out) {
+	return guarded(ctx, [&] {
+		if (!out) throw std::runtime_error("null argument");
+		if (!ctx->n_calls) throw std::runtime_error("nothing rendered yet");
+		NGP_HIP_CHECK(hipStreamSynchronize(ctx->last_stream));
+		*out = 0;
+		// only the unit kernels cull (nerf_kernels.hip tile_cull) and write the word: after any other kernel the slot holds an older frame's
+		if (strncmp(ctx->last_render_kernel, "render_nerf_fused_unit", 22) != 0) return;
+		const int slot = (int)((ctx->n_calls - 1) % ngp_ctx::HISTORY);
+		unsigned long long c = 0;
+		NGP_HIP_CHECK(hipMemcpy(&c, ctx->d_sync.get() + ngp_ctx::SLOT_BYTES * (size_t)slot + 32 + 8 * ngp::RESULT_CULLED, sizeof(c), hipMemcpyDeviceToHost));
+		*out = c;
+	});
+}
+
 int ngp_get_render_history(ngp_ctx* ctx, int n, ngp_render_stats* out) {
 	return guarded(ctx, [&] {
 		if (!out || n <= 0) throw std::runtime_error("invalid argument");

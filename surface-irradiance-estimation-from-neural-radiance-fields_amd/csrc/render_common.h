@@ -231,13 +231,21 @@ NGP_DEV unsigned long long stamp() {
 // reads and hands the accumulators, the tile queue and the exit count back as zeros: the slot's next launch needs no
 // memset (a dependent dispatch per frame behind a persistent kernel). Everything goes through device-scope atomics,
 // which execute at the memory side -- no cache holds a stale copy; the release orders this wave's adds before its exit.
-NGP_DEV void finish_launch(const FrameParams& F, int lane, uint32_t n_alive_init, uint32_t n_hit, uint32_t n_samples) {
+// CULLS (the kernels with the tile cull, whose results are a slot of ngp_ctx::bind_slot): the tiles the launch culled are summed in
+// results[RESULT_CULL_SUM] and moved to results[RESULT_CULLED] in the same way (ngp_get_culled_tiles; ngp_render_stats keeps its layout).
+template <bool CULLS = false>
+NGP_DEV void finish_launch(const FrameParams& F, int lane, uint32_t n_alive_init, uint32_t n_hit, uint32_t n_samples, uint32_t n_culled = 0) {
 	if (lane == 0) {
 		atomicAdd(&F.counters[0], (unsigned long long)n_alive_init);
 		atomicAdd(&F.counters[1], (unsigned long long)n_hit);
 		atomicAdd(&F.counters[2], (unsigned long long)n_samples);
+		if (CULLS && n_culled) atomicAdd(&F.results[RESULT_CULL_SUM], (unsigned long long)n_culled);
 		const uint32_t left = __hip_atomic_fetch_add(F.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
 		if (left + 1u == F.n_waves) {
+			if (CULLS) {
+				const unsigned long long total = atomicExch(&F.results[RESULT_CULL_SUM], 0ull);
+				F.results[RESULT_CULLED] = F.add_results ? F.results[RESULT_CULLED] + total : total;
+			}
 #pragma unroll
 			for (int k = 0; k < 3; ++k) {
 				const unsigned long long total = atomicExch(&F.counters[k], 0ull);

@@ -243,6 +243,8 @@ def load_library():
     L.ngp_set_schedule.argtypes = [vp, vp, ip]
     if hasattr(L, "ngp_last_render_kernel"):  # (an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
         L.ngp_last_render_kernel.argtypes = [vp]; L.ngp_last_render_kernel.restype = C.c_char_p
+    if hasattr(L, "ngp_get_culled_tiles"):  # (an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
+        L.ngp_get_culled_tiles.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "ngp_get_profile_trace"):  # (diagnostic entry; an older build loaded through NGP_HIP_LIBRARY for an A/B run lacks it)
         L.ngp_get_profile_trace.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.ngp_grid_encode.argtypes = [vp, C.c_uint32, vp, vp]
@@ -646,6 +648,12 @@ class Context:
     def last_render_kernel(self):
         """Name of the kernel the last frame ran ("render_nerf_fused_unit_plain", ..., "wide"; ngp_last_render_kernel)"""
         return self.L.ngp_last_render_kernel(self.h).decode()
+
+    def culled_tiles(self):
+        """8 x 8 camera tiles the last frame's unit render kernel dropped right after ray setup (ngp_get_culled_tiles; csrc/tile_probe.h)"""
+        n = C.c_uint64(0)
+        self._check(self.L.ngp_get_culled_tiles(self.h, C.byref(n)))
+        return int(n.value)
 
     def render_history(self, n):
         arr = (RenderStats * n)()

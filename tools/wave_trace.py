@@ -63,7 +63,7 @@ print(f"# {len(rows)} traced waves: arrival spread {a[:, 0].min():.1f} .. {a[:, 
       f"busy median {np.median(a[:, 4]):.1f} us max {a[:, 4].max():.1f} us | cycles/round median {np.median(a[:, 5]):.0f}")
 
 # ---- what a round costs, by kind
-kinds = {"network": [], "stall (waits for marching lanes / chain growth)": [], "march only (nothing ready)": []}
+kinds = {"network": [], "stall (waits for marching lanes / chain growth)": [], "march only (nothing ready)": [], "refill of a culled tile (tile_cull)": []}
 per_section = {k: [] for k in kinds}
 inner = []
 n_run_hist = np.zeros(65, np.int64)
@@ -74,7 +74,9 @@ for (i, *_rest) in rows:
         t1, t2, t3, t4 = r[j, 1], r[j, 2], r[j, 3], r[j, 4]
         n_ready, n_run, n_pass = r[j, 5] & 255, (r[j, 5] >> 8) & 255, (r[j, 5] >> 16) & 255
         nxt = (int(r[j + 1, 0]) - int(r[j, 0])) & 0xffffffff if j + 1 < n_it else t4
-        if t3 > t2:
+        if (r[j, 6] >> 24) & 16:  # the round ended at the refill: the tile it took was culled (the stamps after the refill repeat it)
+            kind = "refill of a culled tile (tile_cull)"
+        elif t3 > t2:
             kind = "network"
             n_run_hist[n_run] += 1
             inner.append(r[j, 8:15])
@@ -100,7 +102,7 @@ if level >= 2 and inner:
 # ---- the longest wave, round by round (first 24 rounds and the last 8)
 longest = max(rows, key=lambda r: r[3])[0]
 n_it = min(int(hd[longest, 4]), rec.shape[1])
-print(f"# longest traced wave ({n_it} rounds): round | cycles since its first round | refill march network composite | ready run passes stall | alive marching continuations | flags (1 queue empty, 4 retired, 8 refilled)")
+print(f"# longest traced wave ({n_it} rounds): round | cycles since its first round | refill march network composite | ready run passes stall | alive marching continuations | flags (1 queue empty, 4 retired, 8 refilled, 16 the tile was culled)")
 r = rec[longest, :n_it].astype(np.int64)
 for j in list(range(min(24, n_it))) + list(range(max(24, n_it - 8), n_it)):
     print(f"  {j:4d} | {(int(r[j, 0]) - int(r[0, 0])) & 0xffffffff:9d} | {r[j, 1]:6d} {r[j, 2] - r[j, 1]:6d} {r[j, 3] - r[j, 2]:6d} {r[j, 4] - r[j, 3]:6d} | {r[j, 5] & 255:3d} {(r[j, 5] >> 8) & 255:3d} {(r[j, 5] >> 16) & 255:2d} {(r[j, 5] >> 24) & 255:2d} | "
