@@ -559,7 +559,8 @@ NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const flo
  *   N = normalize(cross(b - a, c - a)) of the hit triangle, the normal ngp_trace_mesh_rays leaves; N_ff = N if N . w_k < 0, else -N.
  * Source: (E, W) = the lookup of V_{b-1} at (h, N_ff): ngp_irradiance_volume_at's, or, when the call is given a visibility descriptor,
  *   ngp_irradiance_volume_at_visible's with that lookup's own normal_bias and no other offset.
- * Radiance leaving the hit: M_ch = albedo_ch max(E_ch, 0) / pi; 0 where W = 0. The mesh is opaque and diffuse.
+ * Radiance leaving the hit: M_ch = albedo_ch max(E_ch, 0) / pi; 0 where W = 0. The mesh is opaque and diffuse. albedo: the call's, or the
+ *   hit mesh's own where it owns one ("mesh albedos", below).
  * Bounce radiance of the ray: B_k = (1 - alpha_k) M, alpha_k the alpha of the ray's NeRF trace (the rgba.w V_0 was projected from): the
  *   NeRF in front of the hit attenuates the bounce.
  * Records: R_b = the SH9 section's projection of B (the same order, the 4 pi / K scale, coefficients 0..26); V_b[j] = V_0[j] + R_b[j] in
@@ -574,7 +575,7 @@ NGP_API int ngp_irradiance_volume_at_visible(ngp_ctx* ctx, uint32_t n, const flo
  *   use_visible without visibility ("no irradiance visibility"); a non-finite alpha. */
 typedef struct ngp_irradiance_bounce_desc {
 	uint32_t n_bounces; /* N, at most 16 */
-	float albedo[3];    /* of every mesh, each channel in [0, 1] */
+	float albedo[3];    /* of every mesh without its own (ngp_set_mesh_albedo), each channel in [0, 1] */
 } ngp_irradiance_bounce_desc;
 /* V_N, kept like ngp_compute_irradiance_volume's result: on the primary device, the held visibility dropped. With `visibility` non-NULL
  * the distance maps of the new lattice are computed BEFORE the bounces, used by them, and left in the context as
@@ -601,7 +602,8 @@ NGP_API int ngp_get_irradiance_bounce_ms(ngp_ctx* ctx, float* ms);
  *   ray starts at q = h + shadow_bias N_ff (float32, every product rounded before its sum) and runs along s^; it is blocked when any
  *   triangle of ANY loaded mesh is hit at 0 <= t < 100 (the traversal's range, MAX_DIST); vis_k = 0 when blocked, else 1.
  *   B^sun_k,ch = (1 - alpha_k) ((albedo_ch radiance_ch) c_k / pi) vis_k in float32, alpha_k the alpha of the ray's NeRF trace, albedo
- *   ngp_irradiance_bounce_desc::albedo. The term does not depend on the volume: a hit among dead probes is lit like any other.
+ *   ngp_irradiance_bounce_desc::albedo, or the hit mesh's own where it owns one ("mesh albedos", below). The term does not depend on the
+ *   volume: a hit among dead probes is lit like any other.
  * Records: R_sun = the SH9 section's projection of B^sun (the same kernel, order and 4 pi / K scale); S[j] = V_0[j] + R_sun[j] in float32
  *   for j < 27; float 27 stays V_0's, so dead probes stay dead. S takes V_0's place in the bounce recurrence: V_b = S + R(V_{b-1}) with
  *   V_0 := S. With N = 0 the held volume is S, the sun's first bounce alone; with N passes sun light has bounced N + 1 times and NeRF
@@ -668,6 +670,34 @@ NGP_API int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float
                                            float* rays_out /* nullable, n K x 4 */, float* shadow_out /* nullable, n K x 4 */, float* sh_out /* n x 28 */);
 /* device time (HIP events) of the shadow rays' prep and trace in the last sun pass, ms, summed over its chunks; 0 after a pass without them */
 NGP_API int ngp_get_irradiance_sun_shadow_ms(ngp_ctx* ctx, float* ms);
+
+/* mesh albedos: a mesh may own an albedo for the SH9 volume's passes, three floats, each finite and in [0, 1]. The bounce passes and the
+ * sun pass use it where a probe ray's closest hit is on that mesh; a mesh without one uses the call's albedo, as every mesh does by default.
+ * The frames' mesh pass never reads it (a frame's colours come from ngp_geometry_opts and the materials).
+ *
+ * Resolution at call time: for mesh m, a_m = its own albedo if it owns one, else the call's. The call's albedo is
+ *   ngp_irradiance_bounce_desc::albedo for the volume entries (ngp_compute_irradiance_volume_bounced, _sunlit, _sunlit_shadowed) and the
+ *   albedo[3] argument of the stage entries (ngp_irradiance_sh_bounce, ngp_irradiance_sh_sun, ngp_irradiance_sh_sun_shadowed).
+ * Bounce: M_ch = a_m,ch max(E_ch, 0) / pi with m the mesh of the ray's closest hit; everything else of "bounces" is unchanged.
+ * Sun: the source of mesh m is fl(a_m,ch radiance_ch), formed on the host in float like the descriptor's; B^sun uses the source of the hit's mesh.
+ * Unchanged: geometry never depends on an albedo: t, N_ff, h, q, vis, the shadow-ray list, alpha_s and float 27 of a record.
+ * No-source rules, over the resolved albedos: no bounce pass runs when every mesh's a_m is black on every channel; no sun pass runs when no
+ *   mesh's source has a non-zero channel. A black call's albedo with one mesh owning a non-black one DOES run the passes. (The stage
+ *   entries always run their one pass, as before.)
+ * Lifetime: an albedo belongs to its mesh slot. ngp_clear_meshes and ngp_load_scene drop all of them; a mesh added by ngp_add_mesh or
+ *   ngp_load_mesh_file has none; ngp_set_geometry_opts and ngp_set_mesh_material never touch one. ngp_load_scene gives a "Mesh" entry that
+ *   carries "albedo": [r, g, b] that albedo. Both entries work on a host-only context.
+ * Refusals: a mesh index out of range; a channel that is not finite or outside [0, 1] ("mesh albedo must be finite and in [0, 1] on every
+ *   channel"); a per-mesh source that is not finite, like the descriptor's. A refusal leaves the state alone.
+ * Identities as bytes: while no mesh owns an albedo every call launches the kernels it launched before albedos existed and returns those
+ *   bytes; with every mesh owning the call's albedo the results are those bytes too.
+ * Determinism: no atomics; bit-identical from run to run and for any chunking. The device table (16 bytes a mesh) is built and uploaded once
+ *   per call, ahead of its passes, and freed behind the call's last synchronisation.
+ * Several devices: the volume is computed on the primary alone, so no table travels; the peers get the records.
+ * Stated limits: one albedo a mesh: no per-triangle albedo, no textures; the volume's bounce stays diffuse whatever the mesh's material. */
+NGP_API int ngp_set_mesh_albedo(ngp_ctx* ctx, int mesh, const float albedo[3] /* nullable: back to the call's */);
+/* out (nullable) receives the mesh's own albedo, zeros where it owns none; own (nullable) receives 1 or 0 */
+NGP_API int ngp_get_mesh_albedo(ngp_ctx* ctx, int mesh, float out[3], int* own);
 
 /* sun: the NeRF in front of the frames' sun. With the block above the ambient light under the captured object darkens; this option lets the
  * same density stand in front of the frames' own direct sun term on mesh pixels. Context state, set like the geometry options; off by
@@ -987,8 +1017,9 @@ NGP_API int ngp_get_frame_mesh_reflection_hits_ms(ngp_ctx* ctx, float* ms);
  * Determinism: no atomics; frames are bit-identical from run to run. The device table (64 bytes a mesh) is uploaded by ngp_set_mesh_material and
  *   by the calls that change the mesh list, never inside a frame: ngp_render_device stays asynchronous.
  * Several devices: the materials travel to the peers with the geometry; ngp_get_frame_mesh_ids reads the primary's share only.
- * Stated limits: the SH9 volume's bounce and sun passes keep one albedo for all meshes (ngp_irradiance_bounce_desc::albedo); no per-triangle
- *   or per-OBJ-group materials, no textures, no MTL files; the sun and up directions stay per context. */
+ * Stated limits: the SH9 volume's bounce and sun passes read no material: a mesh's albedo there is its own where it owns one
+ *   (ngp_set_mesh_albedo, "mesh albedos"), else the call's; no per-triangle or per-OBJ-group materials, no textures, no MTL files; the sun and
+ *   up directions stay per context. */
 typedef struct ngp_mesh_material {
 	float metallic, subsurface, specular, roughness, sheen, clearcoat, clearcoat_gloss;
 	float basecolor[3], ambientcolor[3];

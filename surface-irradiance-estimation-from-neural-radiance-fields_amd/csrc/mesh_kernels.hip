@@ -1042,18 +1042,32 @@ void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, cons
 // projection counts it. B = (1 - alpha) albedo max(E, 0) / pi with (E, W) the lookup A at the hit point o + t w and the hit triangle's
 // winding normal turned against the ray; 0 without a hit and where W = 0. alpha: the chunk's rays' NeRF alpha (nullptr: 0). The lookup's
 // accumulators are live behind the traversals only, as in render_mesh_fused.
-template <typename Lookup>
-__global__ void irradiance_bounce_rays_kernel(const MeshSceneParams S, const Lookup A, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
-                                              float albedo_r, float albedo_g, float albedo_b, const float* __restrict__ alpha, float4* __restrict__ rgba_out,
-                                              float2* __restrict__ t_out) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
+// where a hit's albedo (a bounce pass) or its sun source (a sun pass) comes from: the call's three scalars for every mesh, or one float4 of
+// the call's table of one entry a mesh (ngp_hip.h, "mesh albedos"). The table's entry is read where the values are first used, behind the
+// traversals: one 16-byte load a hit ray.
+struct CallColour {
+	f3 v;
+	NGP_DEV f3 operator()(int) const { return v; }
+};
+struct MeshColour {
+	const float4* __restrict__ table;
+	NGP_DEV f3 operator()(int mesh) const {
+		const float4 c = table[mesh];
+		return mk3(c.x, c.y, c.z);
+	}
+};
+
+// ray i of a chunk of whole probes in a bounce pass: B as the kernels below state it, albedo(mesh) the hit mesh's; returns t of the hit.
+// A by reference: by value the visible kernel's prologue came out in another order.
+template <typename Lookup, typename Albedo>
+NGP_DEV float bounce_ray(const MeshSceneParams S, const Lookup& A, int occlude, uint32_t n_u, uint32_t n_v, uint32_t i, const float* __restrict__ positions, const Albedo albedo,
+                         const float* __restrict__ alpha, f3& B) {
 	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
 	const f3 dir = sphere_dir(k, n_u, n_v);
 	const f3 org = ld3(positions + 3 * (size_t)pl);
 	int mesh = -1, tri_idx = -1;
 	const float t_max = occlude ? closest_hit(S, org, dir, &mesh, &tri_idx) : __builtin_huge_valf();
-	f3 B = mk3(0.f, 0.f, 0.f);
+	B = mk3(0.f, 0.f, 0.f);
 	if (mesh > -1) {
 		const Triangle& tri = S.meshes[mesh].tris[tri_idx];
 		const f3 a = ld3(tri.a);
@@ -1065,9 +1079,33 @@ __global__ void irradiance_bounce_rays_kernel(const MeshSceneParams S, const Loo
 		else irradiance_volume_lookup(A, h, nff, E, W);
 		if (W > 0.0f) {
 			const float through = 1.0f - (alpha ? alpha[i] : 0.0f);
-			B = mk3(through * (albedo_r * fmaxf(E[0], 0.0f) / PI_F), through * (albedo_g * fmaxf(E[1], 0.0f) / PI_F), through * (albedo_b * fmaxf(E[2], 0.0f) / PI_F));
+			const f3 al = albedo(mesh);
+			B = mk3(through * (al.x * fmaxf(E[0], 0.0f) / PI_F), through * (al.y * fmaxf(E[1], 0.0f) / PI_F), through * (al.z * fmaxf(E[2], 0.0f) / PI_F));
 		}
 	}
+	return t_max;
+}
+
+template <typename Lookup>
+__global__ void irradiance_bounce_rays_kernel(const MeshSceneParams S, const Lookup A, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
+                                              float albedo_r, float albedo_g, float albedo_b, const float* __restrict__ alpha, float4* __restrict__ rgba_out,
+                                              float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B;
+	const float t_max = bounce_ray(S, A, occlude, n_u, n_v, i, positions, CallColour{mk3(albedo_r, albedo_g, albedo_b)}, alpha, B);
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+}
+// the same pass with every mesh's own albedo: albedos[m] = (a_m rgb, unused), resolved by the host for the call (ngp_hip.h, "mesh albedos")
+template <typename Lookup>
+__global__ void irradiance_bounce_rays_mesh_albedo_kernel(const MeshSceneParams S, const Lookup A, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n,
+                                                          const float* __restrict__ positions, const float4* __restrict__ albedos, const float* __restrict__ alpha,
+                                                          float4* __restrict__ rgba_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B;
+	const float t_max = bounce_ray(S, A, occlude, n_u, n_v, i, positions, MeshColour{albedos}, alpha, B);
 	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
 	t_out[i] = make_float2(0.0f, t_max);
 }
@@ -1086,11 +1124,17 @@ __global__ void ray_alpha_kernel(uint32_t n, const float4* __restrict__ rgba, fl
 	if (i < n) alpha[i] = rgba[i].w;
 }
 
-// VV != nullptr: the lookup weighted by the probes' visibility, and V is not looked at
+// VV != nullptr: the lookup weighted by the probes' visibility, and V is not looked at. albedos != nullptr: the device table of one
+// float4 a mesh, and albedo is not looked at
 void launch_irradiance_bounce_rays(const MeshSceneParams& S, const IrradianceVolume& V, const IrradianceVolumeVisible* VV, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n,
-                                   const float* positions, const float* albedo, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
+                                   const float* positions, const float* albedo, const float4* albedos, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
 	if (!n) return;
 	const dim3 blocks((n + 127) / 128), threads(128);
+	if (albedos) {
+		if (VV) hipLaunchKernelGGL(irradiance_bounce_rays_mesh_albedo_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, S, *VV, occlude ? 1 : 0, n_u, n_v, n, positions, albedos, alpha, rgba, t);
+		else hipLaunchKernelGGL(irradiance_bounce_rays_mesh_albedo_kernel<IrradianceVolume>, blocks, threads, 0, stream, S, V, occlude ? 1 : 0, n_u, n_v, n, positions, albedos, alpha, rgba, t);
+		return;
+	}
 	if (VV) hipLaunchKernelGGL(irradiance_bounce_rays_kernel<IrradianceVolumeVisible>, blocks, threads, 0, stream, S, *VV, occlude ? 1 : 0, n_u, n_v, n, positions, albedo[0], albedo[1], albedo[2], alpha, rgba, t);
 	else hipLaunchKernelGGL(irradiance_bounce_rays_kernel<IrradianceVolume>, blocks, threads, 0, stream, S, V, occlude ? 1 : 0, n_u, n_v, n, positions, albedo[0], albedo[1], albedo[2], alpha, rgba, t);
 }
@@ -1152,7 +1196,9 @@ NGP_DEV bool any_hit(const MeshSceneParams S, f3 org, f3 dir) {
 // q = h + bias N_ff along sun; 0 without a hit and where c <= 0. Returns t of the primary hit (+inf without one). alpha: the chunk's rays'
 // NeRF alpha (nullptr: 0). No volume is read. lit: the ray has a hit, c > 0 and vis = 1, and q is that ray's lifted hit point (zeros
 // otherwise); a caller that drops both keeps the code it had before they were returned. S by value, as in closest_hit.
-NGP_DEV float sun_ray(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t i, const float* __restrict__ positions, f3 sun, float bias, f3 source,
+// source(mesh): albedo x radiance of the hit's mesh (CallColour: one for all; MeshColour: the call's table).
+template <typename Source>
+NGP_DEV float sun_ray(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t i, const float* __restrict__ positions, f3 sun, float bias, const Source source_of,
                       const float* __restrict__ alpha, f3& B, f3& q_out, bool& lit) {
 	const uint32_t K = n_u * n_v, pl = i / K, k = i - pl * K;
 	const f3 dir = sphere_dir(k, n_u, n_v);
@@ -1173,6 +1219,7 @@ NGP_DEV float sun_ray(const MeshSceneParams S, int occlude, uint32_t n_u, uint32
 			const f3 q = add3(h, scale3(nff, bias));
 			if (!any_hit(S, q, sun)) {
 				const float through = 1.0f - (alpha ? alpha[i] : 0.0f);
+				const f3 source = source_of(mesh);
 				B = mk3(through * (source.x * c / PI_F), through * (source.y * c / PI_F), through * (source.z * c / PI_F));
 				q_out = q;
 				lit = true;
@@ -1191,7 +1238,20 @@ __global__ void irradiance_sun_rays_kernel(const MeshSceneParams S, int occlude,
 	if (i >= n) return;
 	f3 B, q;
 	bool lit;
-	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, mk3(source_r, source_g, source_b), alpha, B, q, lit);
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, CallColour{mk3(source_r, source_g, source_b)}, alpha, B, q, lit);
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+}
+
+// the same pass with every mesh's own source: sources[m] = (fl(a_m radiance) rgb, unused), formed by the host for the call
+__global__ void irradiance_sun_rays_mesh_albedo_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
+                                                       float sun_x, float sun_y, float sun_z, float bias, const float4* __restrict__ sources, const float* __restrict__ alpha,
+                                                       float4* __restrict__ rgba_out, float2* __restrict__ t_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B, q;
+	bool lit;
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, MeshColour{sources}, alpha, B, q, lit);
 	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
 	t_out[i] = make_float2(0.0f, t_max);
 }
@@ -1210,7 +1270,24 @@ __global__ void irradiance_sun_shadow_rays_kernel(const MeshSceneParams S, int o
 	if (i >= n) return;
 	f3 B, q;
 	bool lit;
-	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, mk3(source_r, source_g, source_b), alpha, B, q, lit);
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, CallColour{mk3(source_r, source_g, source_b)}, alpha, B, q, lit);
+	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
+	t_out[i] = make_float2(0.0f, t_max);
+	o_out[3 * (size_t)i] = q.x; o_out[3 * (size_t)i + 1] = q.y; o_out[3 * (size_t)i + 2] = q.z;
+	d_out[3 * (size_t)i] = sun_x; d_out[3 * (size_t)i + 1] = sun_y; d_out[3 * (size_t)i + 2] = sun_z;
+	st_out[i] = lit ? make_float2(t_min, __builtin_huge_valf()) : make_float2(0.0f, 0.0f);
+}
+
+// the same generator with every mesh's own source (irradiance_sun_rays_mesh_albedo_kernel's table)
+__global__ void irradiance_sun_shadow_rays_mesh_albedo_kernel(const MeshSceneParams S, int occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* __restrict__ positions,
+                                                              float sun_x, float sun_y, float sun_z, float bias, const float4* __restrict__ sources,
+                                                              const float* __restrict__ alpha, float t_min, float4* __restrict__ rgba_out, float2* __restrict__ t_out,
+                                                              float* __restrict__ o_out, float* __restrict__ d_out, float2* __restrict__ st_out) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	f3 B, q;
+	bool lit;
+	const float t_max = sun_ray(S, occlude, n_u, n_v, i, positions, mk3(sun_x, sun_y, sun_z), bias, MeshColour{sources}, alpha, B, q, lit);
 	rgba_out[i] = make_float4(B.x, B.y, B.z, t_max);
 	t_out[i] = make_float2(0.0f, t_max);
 	o_out[3 * (size_t)i] = q.x; o_out[3 * (size_t)i + 1] = q.y; o_out[3 * (size_t)i + 2] = q.z;
@@ -1236,17 +1313,26 @@ __global__ void irradiance_sun_shadow_apply_kernel(uint32_t n, const float4* __r
 	if (shadow_out) shadow_out[i] = has ? make_float4(o[3 * (size_t)i], o[3 * (size_t)i + 1], o[3 * (size_t)i + 2], alpha_s) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// sun: the unit direction towards the sun; source: albedo x radiance per channel, as the host forms it in float
+// sun: the unit direction towards the sun; source: albedo x radiance per channel, as the host forms it in float. sources != nullptr: the
+// device table of one float4 a mesh, and source is not looked at
 void launch_irradiance_sun_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
-                                const float* source, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
-	if (n) hipLaunchKernelGGL(irradiance_sun_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias,
-	                          source[0], source[1], source[2], alpha, rgba, t);
+                                const float* source, const float4* sources, const float* alpha, float4* rgba, float2* t, hipStream_t stream) {
+	if (!n) return;
+	const dim3 blocks((n + 127) / 128), threads(128);
+	if (sources) hipLaunchKernelGGL(irradiance_sun_rays_mesh_albedo_kernel, blocks, threads, 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias, sources, alpha, rgba, t);
+	else hipLaunchKernelGGL(irradiance_sun_rays_kernel, blocks, threads, 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias,
+	                        source[0], source[1], source[2], alpha, rgba, t);
 }
 // the same pass with the shadow-ray list of its chunk: o, d (3 n floats each) and st (n) for launch_ray_list_prep and the ray-list tracer
 void launch_irradiance_sun_shadow_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
-                                       const float* source, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st, hipStream_t stream) {
-	if (n) hipLaunchKernelGGL(irradiance_sun_shadow_rays_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2],
-	                          bias, source[0], source[1], source[2], alpha, t_min, rgba, t, o, d, st);
+                                       const float* source, const float4* sources, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st,
+                                       hipStream_t stream) {
+	if (!n) return;
+	const dim3 blocks((n + 127) / 128), threads(128);
+	if (sources) hipLaunchKernelGGL(irradiance_sun_shadow_rays_mesh_albedo_kernel, blocks, threads, 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2], bias, sources, alpha,
+	                                t_min, rgba, t, o, d, st);
+	else hipLaunchKernelGGL(irradiance_sun_shadow_rays_kernel, blocks, threads, 0, stream, S, occlude ? 1 : 0, n_u, n_v, n, positions, sun[0], sun[1], sun[2],
+	                        bias, source[0], source[1], source[2], alpha, t_min, rgba, t, o, d, st);
 }
 void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const float* o, const float2* st, float4* rgba, float4* shadow_out, hipStream_t stream) {
 	if (n) hipLaunchKernelGGL(irradiance_sun_shadow_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, traced, o, st, rgba, shadow_out);

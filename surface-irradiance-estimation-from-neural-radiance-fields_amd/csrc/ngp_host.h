@@ -197,13 +197,13 @@ void launch_irradiance_volume_lookup(const IrradianceVolume& V, uint32_t n, cons
 void launch_irradiance_distance_reduce(uint32_t n_u, uint32_t n_v, uint32_t n_probes, uint32_t sharpness_log2, float D, const float2* t, float2* out, hipStream_t stream);
 void launch_irradiance_volume_lookup_visible(const IrradianceVolumeVisible& A, uint32_t n, const float* positions, const float* normals, float4* out, hipStream_t stream);
 void launch_irradiance_bounce_rays(const MeshSceneParams& S, const IrradianceVolume& V, const IrradianceVolumeVisible* VV, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n,
-                                   const float* positions, const float* albedo, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // VV: the visible lookup
+                                   const float* positions, const float* albedo, const float4* albedos, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // VV: the visible lookup; albedos (nullable): one float4 a mesh instead of albedo
 void launch_irradiance_volume_add(uint32_t n_float4, const float4* v0, const float4* r, float4* out, hipStream_t stream);
 void launch_ray_alpha(uint32_t n, const float4* rgba, float* alpha, hipStream_t stream);
 void launch_irradiance_sun_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
-                                const float* source, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // sun: unit; source: albedo x radiance
+                                const float* source, const float4* sources, const float* alpha, float4* rgba, float2* t, hipStream_t stream); // sun: unit; source: albedo x radiance; sources (nullable): one float4 a mesh instead
 void launch_irradiance_sun_shadow_rays(const MeshSceneParams& S, bool occlude, uint32_t n_u, uint32_t n_v, uint32_t n, const float* positions, const float* sun, float bias,
-                                       const float* source, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st, hipStream_t stream);
+                                       const float* source, const float4* sources, const float* alpha, float t_min, float4* rgba, float2* t, float* o, float* d, float2* st, hipStream_t stream);
 void launch_irradiance_sun_shadow_apply(uint32_t n, const float4* traced, const float* o, const float2* st, float4* rgba, float4* shadow_out, hipStream_t stream);
 
 // marching cubes, mc_kernels.hip (ngp_mc.cpp). Wide models evaluate the lattice in chunks of `chunk` points through the caller's
@@ -238,6 +238,8 @@ struct HostMesh { // MeshData (mesh.h:18-24) after load_mesh
 	float center[3];
 	ngp_mesh_material material{}; // its own material where own_material (ngp_set_mesh_material); a peer's copy follows the primary's
 	bool own_material = false;
+	float albedo[3] = {0.f, 0.f, 0.f}; // its own albedo in the SH9 volume's passes where own_albedo (ngp_set_mesh_albedo)
+	bool own_albedo = false;
 	DevArray<Triangle> d_tris; // (a peer's replica holds these alone: the host vectors stay empty, ngp_mesh.cpp sync_peer_geometry)
 	DevArray<TriangleBvhNode> d_nodes;
 };

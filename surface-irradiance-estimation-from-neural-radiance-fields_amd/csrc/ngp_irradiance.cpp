@@ -245,7 +245,7 @@ void check_albedo(const float* albedo) {
 
 // a sun descriptor as the passes use it: the unit direction (formed in double, rounded to float) and albedo x radiance per channel
 struct SunLight {
-	float dir[3], source[3], bias;
+	float dir[3], source[3], radiance[3], bias;
 	bool lit; // some channel of the source is not 0
 };
 SunLight check_sun(const ngp_irradiance_sun_desc* s, const float* albedo) {
@@ -257,6 +257,7 @@ SunLight check_sun(const ngp_irradiance_sun_desc* s, const float* albedo) {
 	const double x = s->direction[0], y = s->direction[1], z = s->direction[2], len = std::sqrt(x * x + y * y + z * z);
 	L.dir[0] = (float)(x / len); L.dir[1] = (float)(y / len); L.dir[2] = (float)(z / len);
 	for (int c = 0; c < 3; ++c) {
+		L.radiance[c] = s->radiance[c];
 		L.source[c] = albedo[c] * s->radiance[c];
 		if (!std::isfinite(L.source[c])) throw std::runtime_error("invalid irradiance sun descriptor: albedo x radiance is not finite");
 		L.lit = L.lit || L.source[c] != 0.0f;
@@ -274,6 +275,53 @@ SunLight check_sunlit(const ngp_irradiance_bounce_desc* bounce, const ngp_irradi
 	if (sun) L = check_sun(sun, bounce->albedo);
 	if (nerf) check_desc(*nerf); // (nullable: the meshes alone shadow the sun)
 	return L;
+}
+
+// ---- mesh albedos (contract: include/ngp_hip.h, "mesh albedos"): one call's table of one float4 a mesh, the resolved albedo a_m for the
+// bounce passes or the source fl(a_m radiance) for the sun pass. While no mesh owns an albedo there is no table, and the passes launch the
+// kernels that take the call's three scalars.
+struct MeshColours {
+	std::vector<float4> host; // empty: no mesh owns an albedo
+	DevArray<float4> dev;     // the host's entries once upload_colours ran; get() is nullptr without a table
+	bool any = false;         // some channel of some mesh's entry is not 0 (without a table: of the call's)
+};
+bool owns_albedo(const ngp_ctx* ctx) {
+	for (const HostMesh& m : ctx->meshes)
+		if (m.own_albedo) return true;
+	return false;
+}
+// a_m of every mesh for a call whose albedo is `albedo`
+void resolve_albedos(const ngp_ctx* ctx, const float* albedo, MeshColours& T) {
+	T.any = nonzero3(albedo);
+	if (!owns_albedo(ctx)) return;
+	T.any = false;
+	for (const HostMesh& m : ctx->meshes) {
+		const float* a = m.own_albedo ? m.albedo : albedo;
+		T.host.push_back(make_float4(a[0], a[1], a[2], 0.0f));
+		T.any = T.any || nonzero3(a);
+	}
+}
+// fl(a_m radiance) of every mesh, formed and checked as check_sun forms the call's
+void resolve_sources(const ngp_ctx* ctx, const float* albedo, const SunLight& sun, MeshColours& T) {
+	T.any = sun.lit;
+	if (!owns_albedo(ctx)) return;
+	T.any = false;
+	for (const HostMesh& m : ctx->meshes) {
+		const float* a = m.own_albedo ? m.albedo : albedo;
+		float src[3];
+		for (int c = 0; c < 3; ++c) {
+			src[c] = a[c] * sun.radiance[c];
+			if (!std::isfinite(src[c])) throw std::runtime_error("invalid irradiance sun descriptor: albedo x radiance is not finite");
+		}
+		T.host.push_back(make_float4(src[0], src[1], src[2], 0.0f));
+		T.any = T.any || nonzero3(src);
+	}
+}
+// the table onto the device, once a call, on the context's stream ahead of its passes; it goes with T, behind the call's last synchronisation
+void upload_colours(ngp_ctx* ctx, MeshColours& T) {
+	if (T.host.empty()) return;
+	T.dev.reset(T.host.size());
+	upload(ctx, T.dev.get(), T.host.data(), T.host.size() * sizeof(float4));
 }
 
 void require_volume(const ngp_ctx* ctx) {
@@ -494,18 +542,19 @@ void mesh_light_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp
 	NGP_HIP_CHECK(hipEventElapsedTime(ms, ev0, ev1));
 }
 // one bounce pass from the source volume V (VV non-null: through its visible lookup): the lookup at the rays' mesh hits. d_alpha: the
-// rays' NeRF alpha, n K floats on the device (nullable: 0).
-void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const float* albedo, const IrradianceVolume& V,
+// rays' NeRF alpha, n K floats on the device (nullable: 0). d_albedos: the call's table of the meshes' albedos (nullable: `albedo` for all).
+void bounce_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const float* albedo, const float4* d_albedos, const IrradianceVolume& V,
                  const IrradianceVolumeVisible* VV, const float* d_alpha, float* h_sh, float* h_rays, const float4* d_v0, float4* d_next) {
 	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
-		launch_irradiance_bounce_rays(ctx->mesh_scene, V, VV, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, albedo, d_alpha ? d_alpha + r0 : nullptr, rgba, t, ctx->stream);
+		launch_irradiance_bounce_rays(ctx->mesh_scene, V, VV, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, albedo, d_albedos, d_alpha ? d_alpha + r0 : nullptr, rgba, t, ctx->stream);
 	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_bounce_ms);
 }
-// the sun pass: the shadow query at the rays' mesh hits that face the sun; no volume is read. d_alpha as above.
-void sun_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun, const float* d_alpha, float* h_sh,
+// the sun pass: the shadow query at the rays' mesh hits that face the sun; no volume is read. d_alpha as above. d_sources: the call's table
+// of the meshes' sources (nullable: sun.source for all).
+void sun_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun, const float4* d_sources, const float* d_alpha, float* h_sh,
               float* h_rays, const float4* d_v0, float4* d_next) {
 	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
-		launch_irradiance_sun_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_alpha ? d_alpha + r0 : nullptr, rgba, t,
+		launch_irradiance_sun_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_sources, d_alpha ? d_alpha + r0 : nullptr, rgba, t,
 		                           ctx->stream);
 	}, h_sh, h_rays, d_v0, d_next, &ctx->sh_sun_ms);
 	ctx->sh_sun_shadow_ms = 0.f;
@@ -514,7 +563,7 @@ void sun_pass(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradi
 // the sun pass with the NeRF's density in front of the sun: per chunk the generator also leaves the shadow-ray list (one entry a probe ray,
 // dead where the sun lights nothing), the ray-list tracer walks it inside ONE tracer call, and the apply kernel scales B ahead of the
 // projection. h_shadow (host, n K x 4, nullable): (q, alpha_s) per ray. Needs a model (require_probe_model is the caller's).
-void sun_pass_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun,
+void sun_pass_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const ngp_irradiance_sh_desc* d, uint32_t K, const SunLight& sun, const float4* d_sources,
                        const ngp_irradiance_sun_nerf_desc& nerf, const float* d_alpha, float* h_sh, float* h_rays, float* h_shadow, const float4* d_v0, float4* d_next) {
 	const size_t cap = (size_t)std::min<uint64_t>((uint64_t)n * K, RAY_CHUNK); // (ProbeChunks' cap)
 	DevArray<float> o(3 * cap), dir(3 * cap);
@@ -523,7 +572,7 @@ void sun_pass_shadowed(ngp_ctx* ctx, uint32_t n, const float* positions, const n
 	std::vector<std::pair<Event, Event>> spans; // one chunk's prep and trace each
 	TracerCall tr(ctx, (uint64_t)n * K, nerf.min_transmittance);
 	mesh_light_pass(ctx, n, positions, d, K, [&](const float* pts, uint64_t r0, uint32_t m, float4* rgba, float2* t) {
-		launch_irradiance_sun_shadow_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_alpha ? d_alpha + r0 : nullptr,
+		launch_irradiance_sun_shadow_rays(ctx->mesh_scene, d->occlude_by_meshes != 0, d->n_u, d->n_v, m, pts, sun.dir, sun.bias, sun.source, d_sources, d_alpha ? d_alpha + r0 : nullptr,
 		                                  nerf.t_min, rgba, t, o.get(), dir.get(), st.get(), ctx->stream);
 		spans.emplace_back(new_event(), new_event());
 		NGP_HIP_CHECK(hipEventRecord(spans.back().first, ctx->stream));
@@ -554,11 +603,14 @@ void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const 
 	const uint32_t K_vis = visibility ? check_visibility_desc(probes, visibility, true) : 0;
 	const float D = visibility ? visibility_distance(visibility, *desc) : 0.0f;
 	const std::vector<float> positions = volume_positions(desc, probes);
-	// without a source (no pass asked for, a black albedo, nothing to hit) the records are V_0's own: no pass runs
+	// without a source (no pass asked for, every mesh's albedo black, nothing to hit) the records are V_0's own: no pass runs
 	const float* al = bounce ? bounce->albedo : nullptr;
+	MeshColours albedos, sources; // (the meshes' own albedos resolved against the call's; no tables while no mesh owns one)
+	if (al) resolve_albedos(ctx, al, albedos);
+	if (al && sun) resolve_sources(ctx, al, *sun, sources);
 	const bool hits = !ctx->meshes.empty() && desc->sh.occlude_by_meshes != 0;
-	const uint32_t n_bounces = al && (al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) && hits ? bounce->n_bounces : 0;
-	const bool sunlit = sun && sun->lit && hits; // (a black albedo leaves no channel of the source lit)
+	const uint32_t n_bounces = al && albedos.any && hits ? bounce->n_bounces : 0;
+	const bool sunlit = sun && sources.any && hits; // (black albedos leave no channel of any source lit)
 	DevArray<float4> traced(SH_FLOAT4 * (size_t)probes), lit(sunlit ? traced.size() : 0), even(n_bounces > 1 ? traced.size() : 0), odd(n_bounces > 0 ? traced.size() : 0);
 	DevArray<float> alpha(n_bounces || sunlit ? (size_t)probes * K : 0); // the whole volume's rays: the NeRF is traced once
 	// (alpha is empty without a pass: an empty DevArray's get() is nullptr, which is how trace_sh_probes and bounce_pass are told "none")
@@ -569,14 +621,16 @@ void compute_volume(ngp_ctx* ctx, const ngp_irradiance_volume_desc* desc, const 
 	A.maps = maps.get();
 	A.D = D;
 	A.normal_bias = visibility ? visibility->normal_bias : 0.0f;
-	if (sunlit && nerf) sun_pass_shadowed(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, *nerf, alpha.get(), nullptr, nullptr, nullptr, traced.get(), lit.get());
-	else if (sunlit) sun_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, alpha.get(), nullptr, nullptr, traced.get(), lit.get());
+	if (sunlit) upload_colours(ctx, sources);
+	if (n_bounces) upload_colours(ctx, albedos);
+	if (sunlit && nerf) sun_pass_shadowed(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, sources.dev.get(), *nerf, alpha.get(), nullptr, nullptr, nullptr, traced.get(), lit.get());
+	else if (sunlit) sun_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, *sun, sources.dev.get(), alpha.get(), nullptr, nullptr, traced.get(), lit.get());
 	DevArray<float4>& v0 = sunlit ? lit : traced; // what the passes add to: the sun's light bounces with the NeRF's
 	const float4* prev = v0.get();
 	for (uint32_t b = 1; b <= n_bounces; ++b) { // every probe of a pass reads the pass before it alone
 		float4* next = b % 2u ? odd.get() : even.get();
 		A.V = irradiance_volume_from(*desc, prev);
-		bounce_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, al, A.V, visibility ? &A : nullptr, alpha.get(), nullptr, nullptr, v0.get(), next);
+		bounce_pass(ctx, (uint32_t)probes, positions.data(), &desc->sh, K, al, albedos.dev.get(), A.V, visibility ? &A : nullptr, alpha.get(), nullptr, nullptr, v0.get(), next);
 		prev = next;
 	}
 	if (reference) return commit_reference(ctx, v0, *desc);
@@ -844,7 +898,10 @@ int ngp_irradiance_sh_sun(ngp_ctx* ctx, uint32_t n, const float* positions, cons
 				if (!std::isfinite(alpha[i])) throw std::runtime_error("alpha " + std::to_string(i) + " is not finite");
 		DevArray<float> d_alpha(alpha ? rays : 0);
 		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
-		sun_pass(ctx, n, positions, desc, K, L, d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+		MeshColours sources;
+		resolve_sources(ctx, albedo, L, sources);
+		upload_colours(ctx, sources);
+		sun_pass(ctx, n, positions, desc, K, L, sources.dev.get(), d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
 	});
 }
 
@@ -867,7 +924,10 @@ int ngp_irradiance_sh_sun_shadowed(ngp_ctx* ctx, uint32_t n, const float* positi
 				if (!std::isfinite(alpha[i])) throw std::runtime_error("alpha " + std::to_string(i) + " is not finite");
 		DevArray<float> d_alpha(alpha ? rays : 0);
 		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
-		sun_pass_shadowed(ctx, n, positions, desc, K, L, *nerf, d_alpha.get(), sh_out, rays_out, shadow_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+		MeshColours sources;
+		resolve_sources(ctx, albedo, L, sources);
+		upload_colours(ctx, sources);
+		sun_pass_shadowed(ctx, n, positions, desc, K, L, sources.dev.get(), *nerf, d_alpha.get(), sh_out, rays_out, shadow_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
 	});
 }
 
@@ -905,7 +965,10 @@ int ngp_irradiance_sh_bounce(ngp_ctx* ctx, uint32_t n, const float* positions, c
 		DevArray<float> d_alpha(alpha ? rays : 0);
 		if (alpha) upload(ctx, d_alpha.get(), alpha, rays * sizeof(float));
 		const IrradianceVolumeVisible A = use_visible ? sh_volume_visible_of(ctx) : IrradianceVolumeVisible{};
-		bounce_pass(ctx, n, positions, desc, K, albedo, sh_volume_of(ctx), use_visible ? &A : nullptr, d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
+		MeshColours albedos;
+		resolve_albedos(ctx, albedo, albedos);
+		upload_colours(ctx, albedos);
+		bounce_pass(ctx, n, positions, desc, K, albedo, albedos.dev.get(), sh_volume_of(ctx), use_visible ? &A : nullptr, d_alpha.get(), sh_out, rays_out, nullptr, nullptr); // (no alpha: d_alpha is empty, get() nullptr)
 	});
 }
 

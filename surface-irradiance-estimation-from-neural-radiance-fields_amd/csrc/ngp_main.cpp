@@ -75,7 +75,8 @@ void usage() {
 	std::cout << "ngp_hip_main [files...] [--scene PATH] [--snapshot|--load_snapshot PATH] [--width W] [--height H] [--spp N]\n"
 	             "             [--screenshot OUT.png] [--screenshot_transforms T.json --screenshot_dir DIR] [--render_mode Shade|ShadeEnvMap|ShadeGridEnvMap|ShadeIrradianceVolume|AO|Normals|Positions|Depth]\n"
 	             "             [--irradiance_volume_res N] [--irradiance_volume_visibility] [--irradiance_volume_bounces N] [--irradiance_volume_sun]\n"
-	             "             [--irradiance_volume_sun_nerf_shadow] [--sun_nerf_shadow [--sun_nerf_shadow_t_min X]]\n"
+	             "             [--irradiance_volume_sun_nerf_shadow] [--irradiance_volume_albedo_from_materials] [--save_irradiance_volume OUT.bin]\n"
+	             "             [--sun_nerf_shadow [--sun_nerf_shadow_t_min X]]\n"
 	             "             [--mesh_shadow_on_nerf [--mesh_shadow_on_nerf_strength X]] [--ambient_change_on_nerf]\n"
 	             "             [--sun_disk [--sun_disk_angular_radius X] [--sun_disk_rays K]]\n"
 	             "             [--mesh_reflection [--mesh_reflection_strength X] [--mesh_reflection_meshes]]\n"
@@ -92,6 +93,8 @@ int main(int argc, char** argv) {
 		std::string save_mesh;          // scripts/run.py --save_mesh, --marching_cubes_res (256), --marching_cubes_density_thresh (2.5)
 		int mc_res = 256;
 		float mc_thresh = 2.5f;
+		std::string save_volume; // the volume the context holds after the frames: its records, probes x 28 floats, raw
+		bool volume_albedo_from_materials = false;
 		std::string scene, snapshot, screenshot, shot_transforms, shot_dir, render_mode = "Shade", save_snapshot, network, video_path, video_output = "video_%04d.png";
 		int width = 1920, height = 1080, spp = 1, volume_res = 8, volume_bounces = 0, n_steps = -1, video_seconds = 1, video_fps = 60, video_spp = 8;
 		bool no_train = false, volume_visibility = false, volume_sun = false, volume_sun_nerf_shadow = false, sun_nerf_shadow = false, mesh_shadow_on_nerf = false, ambient_change_on_nerf = false, mesh_reflection = false, mesh_reflection_meshes = false;
@@ -120,6 +123,8 @@ int main(int argc, char** argv) {
 			else if (a == "--irradiance_volume_visibility") volume_visibility = true; // ... and its probes are weighted by their visibility
 			else if (a == "--irradiance_volume_bounces") volume_bounces = std::atoi(val().c_str()); // ... and it holds that many passes of light thrown back by the meshes
 			else if (a == "--irradiance_volume_sun_nerf_shadow") volume_sun_nerf_shadow = true; // ... with the NeRF's density in front of that sun (with --irradiance_volume_sun)
+			else if (a == "--irradiance_volume_albedo_from_materials") volume_albedo_from_materials = true; // ... and a mesh with a material and no "albedo" bounces light with its base colour squared
+			else if (a == "--save_irradiance_volume") save_volume = val(); // the records of the volume the frames used, as raw floats
 			else if (a == "--sun_nerf_shadow") sun_nerf_shadow = true; // Geometry frames: the NeRF's density shadows the frames' own sun on mesh pixels
 			else if (a == "--sun_nerf_shadow_t_min") sun_nerf_shadow_t_min = (float)std::atof(val().c_str()); // ... ignoring the NeRF within this distance of the surface
 			else if (a == "--sun_disk") sun_disk = true; // Geometry frames with meshes: the sun has a disk, soft mesh shadows on the meshes and (with --mesh_shadow_on_nerf) on the NeRF
@@ -158,6 +163,7 @@ int main(int argc, char** argv) {
 		testbed.m_irradiance_volume_visibility = volume_visibility;
 		testbed.m_irradiance_volume_sun = volume_sun;
 		testbed.m_irradiance_volume_sun_nerf_shadow = volume_sun_nerf_shadow;
+		testbed.m_irradiance_volume_albedo_from_materials = volume_albedo_from_materials;
 		testbed.m_sun_nerf_shadow = sun_nerf_shadow;
 		testbed.m_sun_nerf_shadow_t_min = sun_nerf_shadow_t_min;
 		testbed.m_mesh_shadow_on_nerf = mesh_shadow_on_nerf;
@@ -252,6 +258,15 @@ int main(int argc, char** argv) {
 			std::cerr << "wrote " << screenshot << "\n";
 		} else {
 			if (save_snapshot.empty() && video_path.empty() && save_mesh.empty()) std::cerr << "nothing to do: give --screenshot, --screenshot_transforms or --n_steps with --save_snapshot (this build has no window)\n";
+		}
+		if (!save_volume.empty()) {
+			std::array<uint32_t, 3> res{};
+			float box[6];
+			const std::vector<float> sh = testbed.get_irradiance_volume(res, box);
+			std::ofstream f(save_volume, std::ios::binary);
+			f.write((const char*)sh.data(), (std::streamsize)(sh.size() * sizeof(float)));
+			if (!f) throw std::runtime_error("cannot write " + save_volume);
+			std::cerr << "wrote " << save_volume << " (" << res[0] << " x " << res[1] << " x " << res[2] << " probes)\n";
 		}
 		return 0;
 	} catch (const std::exception& e) {

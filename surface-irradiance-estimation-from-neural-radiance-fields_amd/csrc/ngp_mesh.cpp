@@ -90,6 +90,26 @@ ngp_mesh_material parse_material(const mj::Value& v, const std::string& where) {
 	check_material(m, where);
 	return m;
 }
+// three channels of a mesh's albedo: each finite and in [0, 1]
+void check_mesh_albedo(const float* a, const std::string& where) {
+	for (int c = 0; c < 3; ++c)
+		if (!std::isfinite(a[c]) || a[c] < 0.0f || a[c] > 1.0f) throw std::runtime_error(where + "mesh albedo must be finite and in [0, 1] on every channel");
+}
+// what a scene file's "Mesh" entry carries beside its path: its material and its albedo, where it has them
+struct SceneEntryExtras {
+	bool own_material = false, own_albedo = false;
+	ngp_mesh_material material{};
+	float albedo[3] = {0.f, 0.f, 0.f};
+};
+// the "albedo" array of a scene file's "Mesh" entry
+void parse_albedo(const mj::Value& v, const std::string& where, float* out) {
+	if (!v.is_array() || v.size() != 3) throw std::runtime_error(where + "'albedo' must be an array of 3 numbers");
+	for (size_t i = 0; i < 3; ++i) {
+		if (!v.at(i).is_number()) throw std::runtime_error(where + "'albedo' must be an array of 3 numbers");
+		out[i] = (float)v.at(i).num();
+	}
+	check_mesh_albedo(out, where);
+}
 HostMesh& mesh_slot(ngp_ctx* ctx, int mesh) {
 	if (mesh < 0 || mesh >= (int)ctx->meshes.size())
 		throw std::runtime_error("mesh: index " + std::to_string(mesh) + " outside [0, " + std::to_string(ctx->meshes.size()) + ") (ngp_n_meshes)");
@@ -264,18 +284,26 @@ int ngp_load_scene(ngp_ctx* ctx, const char* json_path) {
 		if (!json.is_object() || json.size() == 0) throw std::runtime_error("Geometry file must contain an array of geometry metadata.");
 		const mj::Value& geometries = json.at("geometry");
 		const std::string base = parent_dir(json_path);
-		// the entries' materials are read and refused before the scene is touched
-		std::vector<std::pair<bool, ngp_mesh_material>> materials;
+		// the entries' materials and albedos are read and refused before the scene is touched
+		std::vector<SceneEntryExtras> extras;
 		for (const mj::Value& g : geometries.arr) {
 			const mj::Value* mat = g.is_object() ? g.find("material") : nullptr;
-			const std::string where = "geometry[" + std::to_string(materials.size()) + "]: ";
-			if (mat && g.contains("type") && g.at("type").is_string() && g.at("type").str() == "Nerf") throw std::runtime_error(where + "'material' applies to a 'Mesh' entry, not to 'Nerf'");
-			materials.emplace_back(mat != nullptr, mat ? parse_material(*mat, where) : ngp_mesh_material{});
+			const mj::Value* alb = g.is_object() ? g.find("albedo") : nullptr;
+			const std::string where = "geometry[" + std::to_string(extras.size()) + "]: ";
+			const bool nerf = g.contains("type") && g.at("type").is_string() && g.at("type").str() == "Nerf";
+			if (mat && nerf) throw std::runtime_error(where + "'material' applies to a 'Mesh' entry, not to 'Nerf'");
+			if (alb && nerf) throw std::runtime_error(where + "'albedo' applies to a 'Mesh' entry, not to 'Nerf'");
+			SceneEntryExtras e;
+			e.own_material = mat != nullptr;
+			if (mat) e.material = parse_material(*mat, where);
+			e.own_albedo = alb != nullptr;
+			if (alb) parse_albedo(*alb, where, e.albedo);
+			extras.push_back(e);
 		}
 		ctx->meshes.clear();
 		size_t entry = 0;
 		for (const mj::Value& g : geometries.arr) {
-			const std::pair<bool, ngp_mesh_material>& material = materials[entry++];
+			const SceneEntryExtras& e = extras[entry++];
 			std::string path = g.at("path").str();
 			if (!path.empty() && path[0] != '/') path = base + "/" + path;
 			const std::string& type = g.at("type").str();
@@ -283,8 +311,10 @@ int ngp_load_scene(ngp_ctx* ctx, const char* json_path) {
 			for (int i = 0; i < 3; ++i) center[i] = (float)g.at("center").at((size_t)i).num();
 			if (type == "Mesh") {
 				load_mesh_file_impl(ctx, path, center);
-				ctx->meshes.back().own_material = material.first;
-				ctx->meshes.back().material = material.second;
+				ctx->meshes.back().own_material = e.own_material;
+				ctx->meshes.back().material = e.material;
+				ctx->meshes.back().own_albedo = e.own_albedo;
+				memcpy(ctx->meshes.back().albedo, e.albedo, sizeof(e.albedo));
 			} else if (type == "Nerf") load_snapshot_path(ctx, path);
 			else throw std::runtime_error("Geometry type must be either 'Mesh' or 'Nerf'.");
 		}
@@ -345,6 +375,24 @@ int ngp_get_mesh_material(ngp_ctx* ctx, int mesh, ngp_mesh_material* out, int* o
 	});
 }
 
+// (no device state: the passes of the SH9 volume resolve a table per call, ngp_irradiance.cpp)
+int ngp_set_mesh_albedo(ngp_ctx* ctx, int mesh, const float* albedo) {
+	return guarded(ctx, [&] {
+		HostMesh& slot = mesh_slot(ctx, mesh);
+		if (albedo) check_mesh_albedo(albedo, "");
+		slot.own_albedo = albedo != nullptr;
+		for (int c = 0; c < 3; ++c) slot.albedo[c] = albedo ? albedo[c] : 0.0f;
+	});
+}
+
+int ngp_get_mesh_albedo(ngp_ctx* ctx, int mesh, float* out, int* own) {
+	return guarded(ctx, [&] {
+		const HostMesh& slot = mesh_slot(ctx, mesh);
+		if (own) *own = slot.own_albedo ? 1 : 0;
+		if (out) memcpy(out, slot.albedo, sizeof(slot.albedo)); // (zeros without one)
+	});
+}
+
 int ngp_trace_mesh_rays(ngp_ctx* ctx, uint32_t n, float* positions, float* directions) {
 	return guarded(ctx, [&] {
 		require_device(ctx);
@@ -390,6 +438,8 @@ void sync_peer_geometry(ngp_ctx* primary, ngp_ctx* peer) {
 			memcpy(c.center, m.center, sizeof(c.center));
 			c.material = m.material;
 			c.own_material = m.own_material;
+			memcpy(c.albedo, m.albedo, sizeof(c.albedo)); // (nothing on a peer reads it: the volume is computed on the primary)
+			c.own_albedo = m.own_albedo;
 			c.d_tris.upload(m.tris.data(), m.tris.size());
 			c.d_nodes.upload(m.nodes.data(), m.nodes.size());
 			peer->meshes.push_back(std::move(c));

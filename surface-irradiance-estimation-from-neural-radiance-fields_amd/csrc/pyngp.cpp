@@ -285,6 +285,16 @@ PYBIND11_MODULE(pyngp, m) {
 			if (!t.mesh_material(mesh, b)) return py::none();
 			return py::cast(b);
 		}, py::arg("mesh"), "The mesh's own material (a BRDFParams), or None where it is shaded with testbed.brdf.")
+		.def("set_mesh_albedo", &Testbed::set_mesh_albedo, py::arg("mesh"), py::arg("rgb"),
+		     "Give an inserted mesh its own albedo in the SH9 volume's bounce and sun passes (three channels in [0, 1]); a mesh without one uses the computation's. Kept across load_training_data.")
+		.def("clear_mesh_albedo", &Testbed::clear_mesh_albedo, py::arg("mesh"), "The mesh bounces light with the computation's albedo again.")
+		.def("mesh_albedo", [](Testbed& t, int mesh) -> py::object {
+			std::array<float, 3> a{};
+			if (!t.mesh_albedo(mesh, a)) return py::none();
+			return py::make_tuple(a[0], a[1], a[2]);
+		}, py::arg("mesh"), "The mesh's own albedo (r, g, b), or None where the volume's passes use the computation's.")
+		.def_readwrite("irradiance_volume_albedo_from_materials", &Testbed::m_irradiance_volume_albedo_from_materials,
+		               "the volumes computed here (compute_irradiance_volume, the default volume of a render) take the albedo of a mesh that owns a material and no albedo from that material: the base colour squared (default False)")
 		.def_readwrite("mesh_reflection_meshes", &Testbed::m_mesh_reflection_meshes,
 		               "with mesh_reflection: a mirror ray that a mesh cuts carries that mesh's own shade at the hit, behind the NeRF along the ray (default False)")
 		.def_readwrite("mesh_reflection_strength", &Testbed::m_mesh_reflection_strength, "with mesh_reflection: the factor on the reflected radiance (1)")

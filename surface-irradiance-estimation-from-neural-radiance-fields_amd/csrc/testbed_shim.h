@@ -101,6 +101,8 @@ public:
 			// ngp_load_scene drops every material and gives the entries that carry one the file's; what set_mesh_material gave a slot comes back over it
 			for (const auto& kv : m_mesh_materials)
 				if (kv.first < ngp_n_meshes(m_ctx)) apply_mesh_material(kv.first, kv.second);
+			for (const auto& kv : m_mesh_albedos) // (the albedos likewise)
+				if (kv.first < ngp_n_meshes(m_ctx)) check(ngp_set_mesh_albedo(m_ctx, kv.first, kv.second.data()));
 			sync_model_state();
 		} else {
 			check(ngp_load_training_data(m_ctx, path.c_str()));
@@ -585,9 +587,11 @@ public:
 		for (int a = 0; a < 3; ++a) { d.res[a] = res[a]; d.aabb_min[a] = box[a]; d.aabb_max[a] = box[3 + a]; }
 		d.sh = ngp_irradiance_sh_desc{n_u, n_v, nerf.render_min_transmittance, occlude_by_meshes ? 1 : 0};
 		if (bounces > 0 || sun) {
+			const MaterialAlbedos from_materials(this); // (m_irradiance_volume_albedo_from_materials: for this computation alone)
 			ngp_irradiance_bounce_desc b{};
 			b.n_bounces = bounces;
-			for (int c = 0; c < 3; ++c) b.albedo[c] = albedo3 ? albedo3[c] : std::min(std::max(brdf.basecolor[c] * brdf.basecolor[c], 0.0f), 1.0f);
+			const std::array<float, 3> base_albedo = material_albedo(brdf.basecolor.data());
+			for (int c = 0; c < 3; ++c) b.albedo[c] = albedo3 ? albedo3[c] : base_albedo[c];
 			const ngp_irradiance_visibility_desc v{16, 16, 5, 0.f, 0.f};
 			ngp_irradiance_sun_desc s{};
 			for (int c = 0; c < 3; ++c) { s.direction[c] = m_sun_dir[c]; s.radiance[c] = m_irradiance_volume_sun_radiance[c]; }
@@ -703,6 +707,52 @@ public:
 		check(ngp_set_mesh_material(m_ctx, mesh, &m));
 	}
 	std::map<int, BRDFParams> m_mesh_materials;
+	// ---- a mesh's own albedo in the SH9 volume's bounce and sun passes (ngp_set_mesh_albedo): kept per slot and restored after load_scene; a
+	// mesh without one bounces light with the computation's albedo
+	void set_mesh_albedo(int mesh, const std::array<float, 3>& rgb) {
+		check(ngp_set_mesh_albedo(m_ctx, mesh, rgb.data()));
+		m_mesh_albedos[mesh] = rgb;
+	}
+	void clear_mesh_albedo(int mesh) {
+		check(ngp_set_mesh_albedo(m_ctx, mesh, nullptr));
+		m_mesh_albedos.erase(mesh);
+	}
+	// false: the mesh owns none (a scene file's albedo counts as the mesh's own)
+	bool mesh_albedo(int mesh, std::array<float, 3>& out) {
+		int own = 0;
+		check(ngp_get_mesh_albedo(m_ctx, mesh, out.data(), &own));
+		return own != 0;
+	}
+	// what the volume's passes take from a material: the base colour squared per channel, clamped to [0, 1] (what the mesh pass hands the BRDF)
+	static std::array<float, 3> material_albedo(const float* basecolor) {
+		return {std::min(std::max(basecolor[0] * basecolor[0], 0.0f), 1.0f), std::min(std::max(basecolor[1] * basecolor[1], 0.0f), 1.0f),
+		        std::min(std::max(basecolor[2] * basecolor[2], 0.0f), 1.0f)};
+	}
+	// while one lives and m_irradiance_volume_albedo_from_materials is on: every mesh that owns a material and no albedo owns
+	// material_albedo of its material; they are cleared again when it goes
+	struct MaterialAlbedos {
+		Testbed* t;
+		std::vector<int> given;
+		explicit MaterialAlbedos(Testbed* t) : t(t) {
+			if (!t->m_irradiance_volume_albedo_from_materials) return;
+			for (int m = 0; m < ngp_n_meshes(t->m_ctx); ++m) {
+				ngp_mesh_material mat{};
+				int own_material = 0, own_albedo = 0;
+				t->check(ngp_get_mesh_material(t->m_ctx, m, &mat, &own_material));
+				t->check(ngp_get_mesh_albedo(t->m_ctx, m, nullptr, &own_albedo));
+				if (!own_material || own_albedo) continue;
+				t->check(ngp_set_mesh_albedo(t->m_ctx, m, material_albedo(mat.basecolor).data()));
+				given.push_back(m);
+			}
+		}
+		~MaterialAlbedos() {
+			for (int m : given) (void)ngp_set_mesh_albedo(t->m_ctx, m, nullptr);
+		}
+		MaterialAlbedos(const MaterialAlbedos&) = delete;
+		MaterialAlbedos& operator=(const MaterialAlbedos&) = delete;
+	};
+	std::map<int, std::array<float, 3>> m_mesh_albedos;
+	bool m_irradiance_volume_albedo_from_materials = false; // the volumes computed here take a mesh's albedo from its material where it owns one and no albedo
 
 	ngp_ctx* ctx() { return m_ctx; }
 

@@ -26,6 +26,13 @@ def header_exports():
 EXPORTS = header_exports()
 
 
+def material_albedo(material):
+    """the diffuse albedo the SH9 volume's passes take from a material (a dict of set_mesh_material's keys): the base colour squared per
+    channel, clamped to [0, 1], formed in float32 -- what the mesh pass hands the BRDF"""
+    base = np.asarray(material.get("basecolor", (0.8, 0.8, 0.8)), np.float32)
+    return tuple(float(x) for x in np.minimum(np.maximum(base * base, np.float32(0.0)), np.float32(1.0)))
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("n_levels", C.c_uint32), ("n_features_per_level", C.c_uint32), ("log2_hashmap_size", C.c_uint32), ("base_resolution", C.c_uint32),
@@ -269,6 +276,8 @@ def load_library():
     L.ngp_trace_mesh_rays.argtypes = [vp, C.c_uint32, vp, vp]
     L.ngp_set_mesh_material.argtypes = [vp, ip, C.POINTER(MeshMaterial)]
     L.ngp_get_mesh_material.argtypes = [vp, ip, C.POINTER(MeshMaterial), C.POINTER(C.c_int)]
+    L.ngp_set_mesh_albedo.argtypes = [vp, ip, C.POINTER(C.c_float * 3)]
+    L.ngp_get_mesh_albedo.argtypes = [vp, ip, C.POINTER(C.c_float * 3), C.POINTER(C.c_int)]
     L.ngp_get_frame_mesh_ids.argtypes = [vp, vp, C.c_size_t]
     L.ngp_compute_envmap.argtypes = [vp, C.POINTER(ProbeDesc), vp]
     L.ngp_get_envmap.argtypes = [vp, vp, vp, vp, vp]
@@ -728,6 +737,21 @@ class Context:
         if not own.value:
             return None
         return {k: (tuple(getattr(m, k)) if k in ("basecolor", "ambientcolor") else getattr(m, k)) for k in MATERIAL_DEFAULTS}
+
+    def set_mesh_albedo(self, mesh, rgb=None):
+        """give mesh its own albedo in the SH9 volume's bounce and sun passes: three channels in [0, 1] (one number: all three), or None: back
+        to the call's albedo"""
+        if rgb is None:
+            self._check(self.L.ngp_set_mesh_albedo(self.h, int(mesh), None))
+            return
+        a = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(rgb, np.float32), (3,))])
+        self._check(self.L.ngp_set_mesh_albedo(self.h, int(mesh), C.byref(a)))
+
+    def mesh_albedo(self, mesh):
+        """the mesh's own albedo as a tuple of three floats, or None where the volume's passes use the call's"""
+        a, own = (C.c_float * 3)(), C.c_int(0)
+        self._check(self.L.ngp_get_mesh_albedo(self.h, int(mesh), C.byref(a), C.byref(own)))
+        return tuple(a) if own.value else None
 
     def frame_mesh_ids(self, n_pixels):
         """(n_pixels,) int32: per pixel of the last frame's last sample, in the frame's pixel order, the mesh its primary ray hit, -1 for every

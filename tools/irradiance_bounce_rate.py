@@ -4,6 +4,7 @@ tools/mesh_shade_rate.py's scene with N = 0, 1, 2 and 4 bounce passes, and the d
     python tools/irradiance_bounce_rate.py [--res 16] [--k 32] [--repeat 3] [--out profiles/irradiance_bounce_rate.json]
     python tools/irradiance_bounce_rate.py --sun [--repeat 5] [--out profiles/irradiance_sun_rate.json]
     python tools/irradiance_bounce_rate.py --sun --nerf-shadow [--repeat 6] [--out profiles/irradiance_sun_shadow_rate.json]
+    python tools/irradiance_bounce_rate.py --mesh-albedos [--repeat 8] [--out profiles/irradiance_mesh_albedo_rate.json]
 
 The volume spans the box of the meshes (it overlaps the NeRF's unit cube), the meshes occlude, albedo 0.64. Wall times are
 medians over --repeat calls after a warm-up and include the host's share; the pass time is HIP events around the last pass's chunks in
@@ -18,7 +19,11 @@ instead of the shipped closest hit: what that early exit would buy. --lib PATH m
 
 --sun --nerf-shadow measures what the NeRF's density in front of the sun costs: the same volume with and without sun_nerf_shadow, every
 repeat listed, the shadow trace's own device time (ngp_get_irradiance_sun_shadow_ms) and its tracer statistics beside the V_0 trace's, and
-the share of the uncompacted shadow-ray list that is live (one stage pass at the volume's probes, outside the timing)."""
+the share of the uncompacted shadow-ray list that is live (one stage pass at the volume's probes, outside the timing).
+
+--mesh-albedos measures what the meshes' own albedos cost (ngp_set_mesh_albedo): the sunlit volume with N = 2 while no mesh owns an
+albedo and while every mesh owns one (0.64, so that both compute the same records), in alternating calls of one process: the device time of
+the sun pass and of the last bounce pass, and the wall time of the call, as medians with their p10 and p90."""
 import argparse
 import json
 import os
@@ -133,6 +138,46 @@ def main_sun_shadow(args):
         json.dump(out, f, indent=1)
 
 
+def main_mesh_albedos(args):
+    pkg("build").build()
+    native, synthetic = pkg("native"), pkg("synthetic")
+    ctx, box = load(native, synthetic)
+    res, k = (args.res,) * 3, args.k
+    sun = ((1.0, 1.0, 1.0), native.SUN_RADIANCE, 1e-3)
+    n_meshes = ctx.n_meshes()
+    out = {"how": "a sunlit volume with N = 2: HIP events around the chunks of the sun pass and of the last bounce pass, and the wall time of the call; none: no mesh owns an "
+                  "albedo (the kernels that take the call's three scalars); every: every mesh owns 0.64 (their per-mesh twins, one float4 of the call's table a hit ray); the "
+                  "two alternate call by call in one process after a warm-up call of each; medians with p10 and p90 over --repeat calls; one MI355X, one run",
+           "resolution": [args.res] * 3, "rays_per_probe": k * k, "rays": args.res ** 3 * k * k, "albedo": 0.64, "sun": [1, 1, 1], "n_bounces": 2, "meshes": n_meshes,
+           "none": {"sun_pass_ms": [], "bounce_pass_ms": [], "wall_ms": []}, "every": {"sun_pass_ms": [], "bounce_pass_ms": [], "wall_ms": []}}
+    records = {}
+    for i in range(args.repeat + 1):
+        for name in ("none", "every"):
+            for m in range(n_meshes):
+                ctx.set_mesh_albedo(m, 0.64 if name == "every" else None)
+            t0 = time.perf_counter()
+            ctx.compute_irradiance_volume(res, box, k, k, bounces=2, albedo=0.64, sun=sun)
+            wall = time.perf_counter() - t0
+            if not i:  # (the first call of each warms up)
+                continue
+            o = out[name]
+            o["sun_pass_ms"].append(round(ctx.irradiance_sun_ms(), 3))
+            o["bounce_pass_ms"].append(round(ctx.irradiance_bounce_ms(), 3))
+            o["wall_ms"].append(round(1e3 * wall, 2))
+            records[name] = ctx.get_irradiance_volume()[1].tobytes()
+    ctx.close()
+    out["same_records"] = records["none"] == records["every"]
+    out["summary"] = {}
+    for name in ("none", "every"):
+        out["summary"][name] = {key: {"median": round(float(np.median(v)), 3), "p10": round(float(np.percentile(v, 10)), 3), "p90": round(float(np.percentile(v, 90)), 3)}
+                                for key, v in out[name].items()}
+        print(f"{name:5s}: " + ", ".join(f"{key} {q['median']} ({q['p10']}-{q['p90']})" for key, q in out["summary"][name].items()), flush=True)
+    print(json.dumps(out))
+    path = args.out or os.path.join(ROOT, "profiles", "irradiance_mesh_albedo_rate.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main_sun(args):
     import subprocess
 
@@ -167,8 +212,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sun", action="store_true")
     ap.add_argument("--nerf-shadow", action="store_true", help="with --sun: what the NeRF's density in front of the sun costs")
+    ap.add_argument("--mesh-albedos", action="store_true", help="what the meshes' own albedos cost in a sunlit volume with N = 2")
     ap.add_argument("--lib", default=None)
     args = ap.parse_args()
+    if args.mesh_albedos:
+        return main_mesh_albedos(args)
     if args.sun:
         return main_sun(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "irradiance_bounce_rate.json")
