@@ -5,7 +5,8 @@ NerfNetwork::forward / backward_impl (include/neural-graphics-primitives/nerf_ne
 FullyFusedMLP and GridEncoding (un-vendored submodule: forward y = W x with ReLU hidden layers and no bias; trilinear
 hash-grid interpolation), and its Adam / Ema optimizers (optimizers/adam.h, ema.h). The reference computes in fp16 with
 fp16 gradient accumulation; this oracle keeps float64 throughout, so comparisons carry the fp16 tolerance written in the
-tests. `check_gradients` pins the analytic backward against central differences of the oracle's own forward.
+tests. `forward` / `backward` take `fp16=True` to round, and only round, what the device stores as halves: the distance
+between the two modes is what the tests budget for those roundings (tests/training_cases.py). `check_gradients` pins the analytic backward against central differences of the oracle's own forward.
 """
 import numpy as np
 
@@ -92,20 +93,40 @@ def sh4(dir01):
     return o
 
 
-def forward(params, enc, coords, keep=False):
-    """coords (n, 7): pos01, dt, dir01 -> network output (n, 4): rgb logits, density logit."""
+def _half(a):
+    """Round to fp16 and back: where the device (like the reference) stores a value as a half."""
+    return np.asarray(a, np.float64).astype(np.float16).astype(np.float64)
+
+
+def _keep64(a):
+    return a
+
+
+def forward(params, enc, coords, keep=False, fp16=False):
+    """coords (n, 7): pos01, dt, dir01 -> network output (n, 4): rgb logits, density logit.
+    fp16: round to half what the device holds as halves -- the encoded features (summed corner by corner in half, with
+    half weights, like tcnn's kernel_grid), every hidden activation and the rgb network's input. The matrix products
+    stay float64, so the mode isolates the storage roundings from the summation order."""
+    r = _half if fp16 else _keep64
     WD0, WD1, WR0, WR1, WR2, grid = split_params(params, enc)
     cs = corners(enc, coords[:, :3])
     F = enc["n_features_per_level"]
     x = np.zeros((coords.shape[0], enc["n_levels"] * F))
     for l, (idx, wt) in enumerate(cs):
-        x[:, l * F:(l + 1) * F] = np.einsum("nc,ncf->nf", wt, grid[idx])
+        if fp16:  # tcnn kernel_grid: result = fma((half)weight, value, result) in half, corner after corner
+            acc = np.zeros((coords.shape[0], F))
+            for c in range(8):
+                acc = _half(_half(wt[:, c])[:, None] * grid[idx[:, c]] + acc)
+            x[:, l * F:(l + 1) * F] = acc
+        else:
+            x[:, l * F:(l + 1) * F] = np.einsum("nc,ncf->nf", wt, grid[idx])
     a_d = x @ WD0.T
-    h_d = np.maximum(a_d, 0)
+    h_d = r(np.maximum(a_d, 0))
     dens = h_d @ WD1.T
-    rin = np.concatenate([dens, sh4(coords[:, 4:7])], axis=1)
-    h1 = np.maximum(rin @ WR0.T, 0)
-    h2 = np.maximum(h1 @ WR1.T, 0)
+    rin = r(np.concatenate([dens, sh4(coords[:, 4:7])], axis=1))
+    dens = rin[:, :16]
+    h1 = r(np.maximum(rin @ WR0.T, 0))
+    h2 = r(np.maximum(h1 @ WR1.T, 0))
     out = h2 @ WR2.T
     res = np.concatenate([out[:, :3], dens[:, :1]], axis=1)
     if keep:
@@ -113,26 +134,29 @@ def forward(params, enc, coords, keep=False):
     return res
 
 
-def backward(params, enc, coords, dloss):
-    """dL/d(every parameter), snapshot order, for dL/d(output) = dloss (n, 4) [rgb logits, density logit]."""
-    _, k = forward(params, enc, coords, keep=True)
+def backward(params, enc, coords, dloss, fp16=False):
+    """dL/d(every parameter), snapshot order, for dL/d(output) = dloss (n, 4) [rgb logits, density logit].
+    fp16: the forward's fp16 mode, and the back-propagated activations and the per-sample gradient handed to the grid
+    rounded to half as well; the weight and grid gradient sums stay float64."""
+    r = _half if fp16 else _keep64
+    _, k = forward(params, enc, coords, keep=True, fp16=fp16)
     WD0, WD1, WR0, WR1, WR2 = k["W"]
     n = coords.shape[0]
     dl = np.asarray(dloss, np.float64)
     dout = np.zeros((n, 16))
     dout[:, :3] = dl[:, :3]
     gWR2 = dout.T @ k["h2"]
-    dh2 = (dout @ WR2) * (k["h2"] > 0)
+    dh2 = r((dout @ WR2) * (k["h2"] > 0))
     gWR1 = dh2.T @ k["h1"]
-    dh1 = (dh2 @ WR1) * (k["h1"] > 0)
+    dh1 = r((dh2 @ WR1) * (k["h1"] > 0))
     gWR0 = dh1.T @ k["rin"]
     drin = dh1 @ WR0
-    ddens = drin[:, :16].copy()
-    ddens[:, 0] += dl[:, 3]
+    ddens = r(drin[:, :16]).copy()
+    ddens[:, 0] = r(ddens[:, 0] + dl[:, 3])  # add_density_gradient: half + half, rounded again
     gWD1 = ddens.T @ k["h_d"]
-    dhd = (ddens @ WD1) * (k["h_d"] > 0)
+    dhd = r((ddens @ WD1) * (k["h_d"] > 0))
     gWD0 = dhd.T @ k["x"]
-    dx = dhd @ WD0
+    dx = r(dhd @ WD0)
     F = enc["n_features_per_level"]
     ggrid = np.zeros((k["n_grid"], F))
     for l, (idx, wt) in enumerate(k["cs"]):

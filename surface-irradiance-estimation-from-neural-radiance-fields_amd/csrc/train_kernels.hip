@@ -939,7 +939,11 @@ __global__ void train_optimizer_kernel(const AdamParams A, float* __restrict__ w
 		weights[i] = float_to_half_bits(new_weight);
 	}
 	if (weights_ema) {
-		const float filtered = (ema_tmp[i] * A.ema_decay * A.ema_debias_old + half_bits_to_float(weights[i]) * (1.0f - A.ema_decay)) * A.ema_debias_new;
+		float filtered = (ema_tmp[i] * A.ema_decay * A.ema_debias_old + half_bits_to_float(weights[i]) * (1.0f - A.ema_decay)) * A.ema_debias_new;
+		// The half copy is the rounding of the fp32 value that ema_tmp keeps (tcnn: weights_ema[i] = (T)filtered). Left alone, the compiler folds
+		// the last multiply into the conversion (v_fma_mixlo_f16: one rounding of the exact product), and the two views of the Ema differ by a
+		// half ulp at every tie, 2^-13 of the entries.
+		asm volatile("" : "+v"(filtered));
 		ema_tmp[i] = filtered;
 		weights_ema[i] = float_to_half_bits(filtered);
 	}

@@ -7,15 +7,14 @@ import numpy as np
 import pytest
 
 from conftest import pkg, psnr
+from training_cases import FOV, H, POSES, TARGET, W
+from training_cases import check_batch_against_oracle as _check_batch_against_oracle
+from training_cases import ctx_with_data as _ctx_with_data
+from training_cases import srgb_bytes as _srgb_bytes
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle"))
 
 pytestmark = pytest.mark.gpu
-
-W = H = 96
-FOV = 0.6911
-POSES = [(0, 30), (45, 20), (90, 40), (135, 10), (180, 30), (225, 50), (270, 25), (315, 35)]
-TARGET = 1 << 17
 
 
 def _make_dataset(tmp_dir, native, scene_mod, scene, aabb_scale=1, radius=4.03):
@@ -39,32 +38,6 @@ def dataset(tmp_path_factory, native, scene_mod, scene_unit):
 def dataset_big(tmp_path_factory, native, scene_mod, scene_big):
     """aabb_scale 4: three cascades, exponential stepping (cone angle 1/256), cameras inside the training box."""
     return _make_dataset(tmp_path_factory.mktemp("ds4"), native, scene_mod, scene_big, aabb_scale=4, radius=3.0)
-
-
-def _ctx_with_data(native, dataset, byte_images=False):
-    ctx = native.Context(0)
-    ctx.load_training_data(dataset["path"])
-    for i, im in enumerate(dataset["images"]):
-        if byte_images:
-            ctx.set_training_image(i, _srgb_bytes(im))
-        else:
-            ctx.set_training_image(i, im)
-    return ctx
-
-
-def _oracle_views(ctx, dataset):
-    views = []
-    for i, im in enumerate(dataset["images"]):
-        v = ctx.training_view(i)
-        views.append({"pixels": im, "xform": v["matrix"], "focal": tuple(v["focal_length"]), "principal": tuple(v["principal_point"])})
-    return views
-
-
-def _srgb_bytes(im):
-    a = np.clip(im[..., 3:4], 1e-6, 1.0)
-    rgb = np.clip(im[..., :3] / a, 0, 1)
-    srgb = np.where(rgb <= 0.0031308, 12.92 * rgb, 1.055 * rgb ** (1 / 2.4) - 0.055)
-    return (np.concatenate([srgb, im[..., 3:4]], -1) * 255 + 0.5).astype(np.uint8)
 
 
 def _write_png(path, rgba, filter_type=0):
@@ -189,84 +162,6 @@ def test_png_images_decode_to_the_same_batch(native, oracle, dataset, scene_unit
     ctx.load_training_data(path)
     assert ctx.load_training_images() == len(pixels) - 1
     ctx.close()
-
-
-def _check_batch_against_oracle(ctx, oracle, view_pixels, scene_unit, coord_tol=2e-6, same_frac=0.985, count_tol=2e-4, opts=None):
-    import oracle as O
-
-    dataset = {"images": view_pixels}
-    ctx.set_model(scene_unit)
-    if opts:
-        ctx.set_training_opts(**opts)
-    b = ctx.train_prepare_batch(TARGET)
-    n_rays = b["n_rays"]
-    assert n_rays == 4096
-    m = oracle.make_model(scene_unit)
-    images = oracle.make_train_images(_oracle_views(ctx, dataset))
-    o = O.TrainOpts()
-    o.n_rays, o.n_images, o.rng = n_rays, len(POSES), oracle.train_rng(1337, 0)
-    o.snap_to_pixel_centers, o.random_bg_color, o.linear_colors, o.color_space, o.loss_type = 1, 1, 0, 1, 4
-    o.near_distance, o.loss_scale, o.density_grid_mean = 0.1, 128.0, float(scene_unit["density_grid_mean"])
-    for k, v in (opts or {}).items():
-        if k == "background_color":
-            o.background = (O.C.c_float * 3)(*v)
-        else:
-            setattr(o, k, v)
-    gen = oracle.train_generate_samples(m, images, o, TARGET * 16)
-    # --- generate_training_samples_nerf: the same rays survive with the same number of steps
-    n_kept = int(b["counters"][1])
-    kept = b["ray_indices"][:n_kept]
-    assert len(set(kept.tolist())) == n_kept
-    ref_kept = set(np.flatnonzero(gen["numsteps"]).tolist())
-    if count_tol <= 2e-4:
-        assert set(kept.tolist()) == ref_kept
-    else:  # libm vs device exp / log in the stepping can move a ray's first or last step across a cell wall
-        assert len(set(kept.tolist()) ^ ref_kept) <= 0.005 * len(ref_kept)
-    assert abs(int(b["counters"][0]) - int(gen["total"])) <= count_tol * gen["total"]
-    # --- compute_loss_kernel_train_nerf on the oracle's own network output
-    net = oracle.network(m, gen["coords"][: gen["total"], :3], gen["coords"][: gen["total"], 4:7])
-    ls = oracle.train_loss(m, images, o, gen, net)
-    n_compacted = int(b["counters"][2])
-    assert n_compacted < TARGET and abs(n_compacted - int(ls["compacted_numsteps"].sum())) <= max(2e-3, 2 * count_tol) * n_compacted
-    same, checked, worst_coord, dl_err, dl_ref, loss_got, loss_ref, shifted = 0, 0, 0.0, [], [], [], [], 0
-    scale = n_compacted / TARGET
-    for r in range(n_kept):
-        i = int(kept[r])
-        if i not in ref_kept:
-            continue
-        cn, cb = int(b["numsteps"][r, 0]), int(b["numsteps"][r, 1])
-        ob, on = int(gen["base"][i]), int(ls["compacted_numsteps"][i])
-        if cn != on:
-            continue
-        same += 1
-        got_c, ref_c = b["coords"][cb:cb + cn], gen["coords"][ob:ob + cn]
-        ray_coord = float(np.abs(got_c - ref_c).max()) if cn else 0.0
-        if ray_coord > coord_tol and count_tol > 2e-4:
-            shifted += 1  # a position on a cell wall taken on one side and not on the other: the rest of the ray is shifted by one
-            continue
-        worst_coord = max(worst_coord, ray_coord)
-        loss_got.append(float(b["loss"][r]))
-        loss_ref.append(float(ls["loss"][i]))
-        # fill_rollover_and_rescale: sample at compacted index c carries 1 + copies * n / target
-        copies = (TARGET - 1 - np.arange(cb, cb + cn)) // n_compacted
-        ref_d = ls["dloss"][ob:ob + cn].astype(np.float32)
-        ref_d = ref_d + copies[:, None] * (ref_d * np.float32(scale)).astype(np.float16).astype(np.float32)
-        dl_err.append(np.abs(b["dloss"][cb:cb + cn].astype(np.float32) - ref_d).reshape(-1))
-        dl_ref.append(np.abs(ref_d).reshape(-1))
-        checked += cn
-    assert same >= same_frac * n_kept and checked > 20000
-    assert worst_coord <= coord_tol and shifted <= 0.005 * n_kept
-    # per-ray losses (already divided by n_rays): the two sides evaluate the network with fp16 outputs that differ by ulps
-    loss_got, loss_ref = np.array(loss_got), np.array(loss_ref)
-    lerr = np.abs(loss_got - loss_ref)
-    # (the model IS the ground truth here, so the losses are the fp16 noise floor: compared in sum and with a loose per-ray bound)
-    loose = count_tol > 2e-4
-    assert np.median(lerr / np.maximum(loss_ref, 1e-12)) < (3e-2 if loose else 1e-2) and lerr.sum() < (3e-2 if loose else 1e-2) * loss_ref.sum()
-    assert np.all(lerr <= 0.25 * loss_ref + 1e-7)  # positions, dt, directions: the same arithmetic up to the device's division / exp
-    dl_err, dl_ref = np.concatenate(dl_err), np.concatenate(dl_ref)
-    # the network outputs differ by fp16 ulps (test_network_outputs); gradients inherit that through sigmoid' / exp
-    assert np.sum(dl_err) <= (0.03 if loose else 0.02) * np.sum(dl_ref) and np.quantile(dl_err, 0.999) <= 0.05 * dl_ref.max()
-    oracle.release(m)
 
 
 def _split(g):
